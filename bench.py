@@ -18,9 +18,16 @@ counts (RCCL; the rows of `--counts-batch` passes, written by the scatter launch
 Default = weak scaling (10 M meshlets per GPU); `--total-meshlets T` = strong scaling (the T-meshlet pool split over the
 ranks; `--gpus 8 --total-meshlets 100000000` is BASELINE config 5).
 
-Prints ONE JSON line (rank 0):  metric/value/unit as in BASELINE.json + "roofline" (dominant kernel) + "cpu_baseline"
-(the CPU oracle timed on this host's cores; a reported baseline, not a target) + "parity" (every rank's visible-ID list of the
-benchmarked pass against the CPU oracle on its shard, outside the timed region; a difference on any rank is a non-zero exit).
+Prints ONE JSON line (rank 0):  metric/value/unit/ms_per_step as in BASELINE.json.  A plain run does only that: set-up, warm-up,
+the `--steps` timed passes, the line.  `--full` adds the side measurements and checks, each outside the timed region: "roofline"
+(dominant kernel, a second loop with HIP events) + "throughput_overlapped" + "cpu_baseline" (the CPU oracle timed on this host's
+cores; a reported baseline, not a target) + "parity" (every rank's visible-ID list of the benchmarked pass against the CPU oracle
+on its shard; a difference on any rank is a non-zero exit) + "contract_chain" + "frame".
+
+`--dump-outputs DIR` writes what the last timed pass left for its caller, as float64 .npy files (exact for 32-bit words):
+visible_ids.npy (the visible-ID list; above DUMP_MAX_IDS entries a sample at fixed, seeded positions) and count.npy (the
+four count words); with N > 1 each rank writes its own, suffixed _rank<r>, and counts_reduced_rank<r>.npy (the all-reduced
+counts of that pass).  The inputs are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -34,6 +41,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
+DUMP_MAX_IDS = 4 << 20  # --dump-outputs: at most 32 MiB of float64 IDs per rank
 
 
 def parse():
@@ -67,6 +75,11 @@ def parse():
                                                    "indices (shard.to_global_ids), as ids_<rank>.npy — tests/test_distributed_gpu.py concatenates them")
     ap.add_argument("--explicit-reset", action="store_true",
                     help="reference contract: zero the count word with a separate launch (nv_reset_count) instead of NV_OPT_FUSED_COUNT_RESET")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements and checks: roofline (profiled loop), throughput_overlapped, cpu_baseline "
+                         "+ parity against the CPU oracle, contract_chain, frame (--no-cpu-baseline / --no-contract-chain / --no-frame / "
+                         "--overlap-streams 0 leave parts out)")
+    ap.add_argument("--dump-outputs", default="", help="directory: write what the last timed pass computed (visible-ID list, count words) as float64 .npy files")
     return ap.parse_args()
 
 
@@ -176,7 +189,7 @@ def main():
     count4 = synth.count4_for(n_cmd)
 
     S = max(1, args.streams)
-    OS = max(0, args.overlap_streams) if not sharded else 0
+    OS = max(0, args.overlap_streams) if args.full and not sharded else 0
     ctxs = [P.Context(local_rank) for _ in range(max(S, OS, 1))]
     ctx = ctxs[0]
     for c in ctxs[1:]:
@@ -259,76 +272,80 @@ def main():
     # this is the list the oracle check further down holds
     timed_visible = visible_by_stream[s_last]
     timed_ids = cibs[s_last][:min(timed_visible, L.CLUSTER_LIMIT)].cpu().numpy().view(np.uint32).copy()
+    visible, visible_ids = timed_visible, timed_ids
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, visible_ids, ccbs[s_last], last_counts if sharded else None, rank if world > 1 else None)
+    if args.dump_ids:
+        np.save(os.path.join(args.dump_ids, "ids_%d.npy" % rank), shard.to_global_ids(visible_ids, cmd_b))
 
-    # ---- roofline leg: the same passes again with the library's HIP events bracketing each kernel on the launch stream
-    # (nv_profile_*), one pass after the other on ONE stream — the mode `value` is measured in when --streams is 1.  It is a
-    # separate loop because an event record is itself a barrier packet: three records per pass cost ~10 us per pass.
-    single = shard.CountsReducer(ctx, dev, B, force_collective=args.force_sharded)
-    serial_calls = [ctx.bind_clustercull(None, cd, 0, dcbs[c], dccb, db, mlb, None, None, cib, ccb) for c in range(copies)]
+    # ---- --full only: the side legs below, the side fields and checks further down.  A plain run goes from the timed region to the line.
+    overlapped = None
+    if args.full:
+        # ---- roofline leg: the same passes again with the library's HIP events bracketing each kernel on the launch stream
+        # (nv_profile_*), one pass after the other on ONE stream — the mode `value` is measured in when --streams is 1.  It is a
+        # separate loop because an event record is itself a barrier packet: three records per pass cost ~10 us per pass.
+        single = shard.CountsReducer(ctx, dev, B, force_collective=args.force_sharded)
+        serial_calls = [ctx.bind_clustercull(None, cd, 0, dcbs[c], dccb, db, mlb, None, None, cib, ccb) for c in range(copies)]
 
-    def serial_step(i):
-        if args.explicit_reset:
-            ctx.reset_count(ccb)
-        single.before_pass(i)
-        serial_calls[i % copies]()
-        single.after_pass(i)
+        def serial_step(i):
+            if args.explicit_reset:
+                ctx.reset_count(ccb)
+            single.before_pass(i)
+            serial_calls[i % copies]()
+            single.after_pass(i)
 
-    n_prof = max(args.steps, 100)  # (a short run still averages the kernels over 100 launches)
-    serial = None
-    if S > 1:  # the timed region overlapped passes: also report what one pass after the other takes
-        for i in range(5):
-            serial_step(i)
-        single.drain(5)
-        torch.cuda.synchronize()
-        t2 = time.perf_counter()
+        n_prof = max(args.steps, 100)  # (a short run still averages the kernels over 100 launches)
+        serial = None
+        if S > 1:  # the timed region overlapped passes: also report what one pass after the other takes
+            for i in range(5):
+                serial_step(i)
+            single.drain(5)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            for i in range(n_prof):
+                serial_step(i)
+            single.drain(n_prof)
+            torch.cuda.synchronize()
+            serial = (time.perf_counter() - t2) / n_prof
+        ctx.profile_variants()  # (reset: the counts below are the profiled loop's)
+        ctx.profile(True)
+        t1 = time.perf_counter()
         for i in range(n_prof):
             serial_step(i)
         single.drain(n_prof)
         torch.cuda.synchronize()
-        serial = (time.perf_counter() - t2) / n_prof
-    ctx.profile_variants()  # (reset: the counts below are the profiled loop's)
-    ctx.profile(True)
-    t1 = time.perf_counter()
-    for i in range(n_prof):
-        serial_step(i)
-    single.drain(n_prof)
-    torch.cuda.synchronize()
-    profiled = time.perf_counter() - t1
-    prof = ctx.profile_read()
-    variants = ctx.profile_variants()  # which kernel form the host's per-launch choices resolved to in the timed launches
-    ctx.profile(False)
-    ctx.status()
+        profiled = time.perf_counter() - t1
+        prof = ctx.profile_read()
+        variants = ctx.profile_variants()  # which kernel form the host's per-launch choices resolved to in the timed launches
+        ctx.profile(False)
+        ctx.status()
 
-    # the profiled loop's last pass ran the same code on the same pool (the rotated copies hold the same records): its list must be the timed loop's,
-    # which is the one checked against the oracle below
-    profiled_visible = int(ccb[0].item())
-    profiled_ids = cib[:min(profiled_visible, L.CLUSTER_LIMIT)].cpu().numpy().view(np.uint32)
-    if profiled_visible != timed_visible or profiled_ids.tobytes() != timed_ids.tobytes():
-        raise SystemExit("rank %d: the profiled loop's visible-ID list differs from the timed loop's (%d against %d IDs)" % (rank, profiled_visible, timed_visible))
-    visible, visible_ids = timed_visible, timed_ids
-    if args.dump_ids:
-        np.save(os.path.join(args.dump_ids, "ids_%d.npy" % rank), shard.to_global_ids(visible_ids, cmd_b))
+        # the profiled loop's last pass ran the same code on the same pool (the rotated copies hold the same records): its list must be the timed loop's,
+        # which is the one checked against the oracle below
+        profiled_visible = int(ccb[0].item())
+        profiled_ids = cib[:min(profiled_visible, L.CLUSTER_LIMIT)].cpu().numpy().view(np.uint32)
+        if profiled_visible != timed_visible or profiled_ids.tobytes() != timed_ids.tobytes():
+            raise SystemExit("rank %d: the profiled loop's visible-ID list differs from the timed loop's (%d against %d IDs)" % (rank, profiled_visible, timed_visible))
 
-    # ---- side leg (N = 1): independent passes in flight on `--overlap-streams` streams, contexts sharing one scene mirror, the
-    # scatter launch with 8 waves per workgroup.  A throughput figure for multi-view callers; never `value`.
-    overlapped = None
-    if OS > 1:
-        for c in ctxs[:OS]:
-            c.set_option(P.NV_OPT_SCATTER_WAVES, 8)
-        ocalls = [[ctxs[s].bind_clustercull(extra_streams[s], cd, 0, dcbs[c], dccb, db, mlb, None, None, cibs[s], ccbs[s]) for c in range(copies)] for s in range(OS)]
-        for i in range(max(OS * 2, 6)):
-            ocalls[i % OS][i % copies]()
-        torch.cuda.synchronize()
-        t3 = time.perf_counter()
-        for i in range(n_prof):
-            ocalls[i % OS][i % copies]()
-        torch.cuda.synchronize()
-        o_step = (time.perf_counter() - t3) / n_prof
-        overlapped = {"value": n_meshlets / o_step, "unit": "meshlets/s", "ms_per_step": o_step * 1e3, "streams": OS, "scatter_waves_per_workgroup": 8,
-                      "what": "%d independent passes in flight (contexts on %d HIP streams sharing one scene mirror): the scatter launch of one pass overlaps "
-                              "the next pass's cull launch; a frame's dependent passes cannot do this" % (OS, OS)}
-        for c in ctxs[:OS]:
-            c.set_option(P.NV_OPT_SCATTER_WAVES, scatter_waves)
+        # ---- side leg (N = 1): independent passes in flight on `--overlap-streams` streams, contexts sharing one scene mirror, the
+        # scatter launch with 8 waves per workgroup.  A throughput figure for multi-view callers; never `value`.
+        if OS > 1:
+            for c in ctxs[:OS]:
+                c.set_option(P.NV_OPT_SCATTER_WAVES, 8)
+            ocalls = [[ctxs[s].bind_clustercull(extra_streams[s], cd, 0, dcbs[c], dccb, db, mlb, None, None, cibs[s], ccbs[s]) for c in range(copies)] for s in range(OS)]
+            for i in range(max(OS * 2, 6)):
+                ocalls[i % OS][i % copies]()
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            for i in range(n_prof):
+                ocalls[i % OS][i % copies]()
+            torch.cuda.synchronize()
+            o_step = (time.perf_counter() - t3) / n_prof
+            overlapped = {"value": n_meshlets / o_step, "unit": "meshlets/s", "ms_per_step": o_step * 1e3, "streams": OS, "scatter_waves_per_workgroup": 8,
+                          "what": "%d independent passes in flight (contexts on %d HIP streams sharing one scene mirror): the scatter launch of one pass overlaps "
+                                  "the next pass's cull launch; a frame's dependent passes cannot do this" % (OS, OS)}
+            for c in ctxs[:OS]:
+                c.set_option(P.NV_OPT_SCATTER_WAVES, scatter_waves)
 
     if sharded:
         t = torch.tensor([elapsed, collective_wait], dtype=torch.float64, device=dev)
@@ -336,22 +353,23 @@ def main():
         elapsed, collective_wait = float(t[0].item()), float(t[1].item())
     total_visible = int(last_counts[2].item())
 
-    cull_ms, cull_n = prof["cluster_cull"]
-    scat_ms, scat_n = prof["cluster_scatter"]
-    kernel_avg_s = max(cull_ms / max(1, cull_n) * 1e-3, 1e-9)      # dominant kernel: cluster_mask_kernel
-    scatter_avg_s = scat_ms / max(1, scat_n) * 1e-3
-
-    # algorithmic bytes.  Whole pass: 12 cull bytes per meshlet + (20 + 48) per command + 4 per survivor
-    # + 4.  The dominant kernel moves the first two terms plus its 8-byte ballot per command; the survivors' 4 bytes
-    # belong to the scatter kernel.
-    per_meshlet = 24 if args.aos else 12
-    pass_bytes = n_meshlets * per_meshlet + n_cmd * 68 + visible * 4 + 4
-    algo_bytes = n_meshlets * per_meshlet + n_cmd * 68 + n_cmd * 8
-    achieved = algo_bytes / kernel_avg_s / 1e9
     step_s = elapsed / args.steps
-    single_s = step_s if S == 1 else serial
+    if args.full:
+        cull_ms, cull_n = prof["cluster_cull"]
+        scat_ms, scat_n = prof["cluster_scatter"]
+        kernel_avg_s = max(cull_ms / max(1, cull_n) * 1e-3, 1e-9)      # dominant kernel: cluster_mask_kernel
+        scatter_avg_s = scat_ms / max(1, scat_n) * 1e-3
 
-    traffic, traffic_note = pmc_traffic(n_meshlets, args)
+        # algorithmic bytes.  Whole pass: 12 cull bytes per meshlet + (20 + 48) per command + 4 per survivor
+        # + 4.  The dominant kernel moves the first two terms plus its 8-byte ballot per command; the survivors' 4 bytes
+        # belong to the scatter kernel.
+        per_meshlet = 24 if args.aos else 12
+        pass_bytes = n_meshlets * per_meshlet + n_cmd * 68 + visible * 4 + 4
+        algo_bytes = n_meshlets * per_meshlet + n_cmd * 68 + n_cmd * 8
+        achieved = algo_bytes / kernel_avg_s / 1e9
+        single_s = step_s if S == 1 else serial
+
+        traffic, traffic_note = pmc_traffic(n_meshlets, args)
 
     if rank == 0:
         if args.total_meshlets:
@@ -381,26 +399,27 @@ def main():
                        "visible_rank0": visible, "visible_per_stream": visible_by_stream, "visible_total": total_visible, "sharding": "commands x%d" % world,
                        "counts_allreduce": ("none (N=1)" if not sharded else "one async all-reduce of [%d, 3] int64 per %d passes, rows written by the scatter launch" % (B, B))},
             "collective_wait_ms": collective_wait * 1e3,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_measured_in_run": False, "traffic_source": traffic_note,
-                         "kernel": "cluster_mask_kernel", "kernel_avg_us": kernel_avg_s * 1e6, "timed_in": "one pass after the other on one stream (HIP events on the launch stream)",
-                         "algorithmic_bytes": algo_bytes, "launches_timed": cull_n, "kernel_variants": variants,
-                         "scatter_kernel_avg_us": scatter_avg_s * 1e6, "ms_per_step_with_events": profiled / n_prof * 1e3,
-                         "pass_algorithmic_bytes": pass_bytes,
-                         # the whole pass (cull + scatter launches) against the roofline, one pass after the other, un-instrumented
-                         "ms_per_pass_single_stream": single_s * 1e3,
-                         "pass_frac": pass_bytes / single_s / 1e9 / HBM_PEAK_GBS},
-            "throughput_overlapped": overlapped,
-            "library": niagara_amd.SO_PATH,
         }
-        if S == 1 and kernel_avg_s > step_s * 1.02:
+        if args.full:
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": traffic, "traffic_measured_in_run": False, "traffic_source": traffic_note,
+                               "kernel": "cluster_mask_kernel", "kernel_avg_us": kernel_avg_s * 1e6, "timed_in": "one pass after the other on one stream (HIP events on the launch stream)",
+                               "algorithmic_bytes": algo_bytes, "launches_timed": cull_n, "kernel_variants": variants,
+                               "scatter_kernel_avg_us": scatter_avg_s * 1e6, "ms_per_step_with_events": profiled / n_prof * 1e3,
+                               "pass_algorithmic_bytes": pass_bytes,
+                               # the whole pass (cull + scatter launches) against the roofline, one pass after the other, un-instrumented
+                               "ms_per_pass_single_stream": single_s * 1e3,
+                               "pass_frac": pass_bytes / single_s / 1e9 / HBM_PEAK_GBS}
+            out["throughput_overlapped"] = overlapped
+        out["library"] = niagara_amd.SO_PATH
+        if args.full and S == 1 and kernel_avg_s > step_s * 1.02:
             out["note"] = "inconsistent: the dominant kernel's event time exceeds ms_per_step"
 
     # ---- parity + CPU baseline, outside every timed region.  Every rank holds its visible-ID list of the last profiled pass against
     # the CPU oracle on ITS shard (same inputs, same command range); the line says "bit-identical" only if all ranks agree.  The timed
     # CPU baseline runs on rank 0's host cores after the other ranks' checks have finished (they share the host): at N = 1 over the
     # whole batch, at N > 1 over rank 0's shard — a bounded sample of the same workload, reported as a rate.
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         ok, detail = True, ""
         if sharded:
             try:  # (a rank that fails INSIDE the check must still reach the all-reduce: the others would wait for it until the rendezvous times out)
@@ -421,16 +440,16 @@ def main():
             out["parity"] = "bit-identical"
             out["parity_checked"] = ("visible-ID list and count of the TIMED loop's last pass (and, identical to it, the profiled loop's) against the CPU oracle: " +
                                      ("the whole batch" if not sharded else "every rank on its own shard, %d of %d ranks agree" % (world, world)))
-    elif rank == 0:
+    elif rank == 0 and args.full:
         out["parity"] = "not checked (--no-cpu-baseline)"
     # ---- side field (N = 1): BASELINE.json configs[2] as literally worded — "cone + frustum cull + LOD select" — i.e. the reference's
     # chain drawcull<0,1> (LOD select) -> tasksubmit -> clustercull<0> -> clustersubmit (src/niagara.cpp:1530-1611), timed in this
     # process after everything above, with its own parity check of every buffer of the chain.  Never `value`.
-    if rank == 0 and not sharded and not args.no_cpu_baseline and not args.no_contract_chain:
+    if rank == 0 and not sharded and args.full and not args.no_cpu_baseline and not args.no_contract_chain:
         out["contract_chain"] = contract_chain(local_rank)
     # ---- side field (N = 1): niagara's dependent FRAME at BASELINE scale (src/niagara.cpp:1765-1788: early cull -> pyramid -> late cull, 1 M draws, ~10 M
     # meshlets per cluster pass, 4096^2 depth), the production-shaped figure, timed by this process and held against the CPU oracle.  Never `value`.
-    if rank == 0 and not sharded and not args.no_cpu_baseline and not args.no_frame:
+    if rank == 0 and not sharded and args.full and not args.no_cpu_baseline and not args.no_frame:
         for c in ctxs:  # (the main leg's contexts and their scratch are done)
             c.close()
         ctxs = []
@@ -442,6 +461,20 @@ def main():
         c.close()
     if sharded:
         dist.destroy_process_group()
+
+
+def dump_outputs(directory, ids, count_words, reduced_counts=None, rank=None):
+    """--dump-outputs: what the last timed pass left for its caller, as float64 (exact for 32-bit words): the visible-ID list and the four count
+    words, and with N > 1 (`rank` given, the files carry it) the all-reduced counts of that pass.  A list longer than DUMP_MAX_IDS is written as
+    a sample at fixed positions (seed 0, the list's length), so that two builds with the same list write the same file."""
+    os.makedirs(directory, exist_ok=True)
+    sfx = "" if rank is None else "_rank%d" % rank
+    if len(ids) > DUMP_MAX_IDS:
+        ids = ids[np.sort(np.random.default_rng(0).choice(len(ids), DUMP_MAX_IDS, replace=False))]
+    np.save(os.path.join(directory, "visible_ids%s.npy" % sfx), ids.astype(np.float64))
+    np.save(os.path.join(directory, "count%s.npy" % sfx), count_words.cpu().numpy().view(np.uint32).astype(np.float64))
+    if reduced_counts is not None:
+        np.save(os.path.join(directory, "counts_reduced%s.npy" % sfx), reduced_counts.cpu().numpy().astype(np.float64))
 
 
 def frame_field(device_index, iters):

@@ -89,7 +89,32 @@ def task_fixture():
                                                                      int(out["late1_counts"].sum())))
 
 
+def kitten_fixture(obj):
+    """tests/golden/mesh/kitten.npz: the reference's data/kitten.obj as arrays (the text file is too large to commit): positions and normals as
+    float32 exactly as float() + np.float32 parse them, and every face corner as 0-based (position, normal) indices, three corners per triangle
+
+        python tests/golden/generate.py --kitten <reference>/data/kitten.obj"""
+    pos, nrm, corners = [], [], []
+    for line in open(obj):
+        if line.startswith("v "):
+            pos.append([float(x) for x in line.split()[1:4]])
+        elif line.startswith("vn "):
+            nrm.append([float(x) for x in line.split()[1:4]])
+        elif line.startswith("f "):
+            toks = line.split()[1:]
+            assert len(toks) == 3, line
+            for tok in toks:
+                a, _, n = tok.split("/")
+                corners.append((int(a) - 1, int(n) - 1))
+    path = os.path.join(HERE, "mesh", "kitten.npz")
+    np.savez_compressed(path, positions=np.array(pos, np.float32), normals=np.array(nrm, np.float32), corners=np.array(corners, np.uint16))
+    print("%-28s %6d bytes, %d vertices, %d triangles" % ("mesh/kitten.npz", os.path.getsize(path), len(pos), len(corners) // 3))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "--kitten":
+        kitten_fixture(sys.argv[2])
+        raise SystemExit(0)
     main()
     mesh_fixture()
     task_fixture()

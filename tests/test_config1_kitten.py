@@ -2,9 +2,9 @@
 
 The mesh bounds follow src/scene.cpp:207-220 (mean of the de-quantised fp16 positions of the unique vertices, max
 distance).  meshoptimizer's vertex reordering is not vendored, so the unique vertices are taken in first-appearance
-order; the float32 mean is order-sensitive only in its last bits.  kitten.obj itself stays in the reference tree: where
-it is mounted the bounds are recomputed and compared with the committed tests/golden/kitten_bounds.json, elsewhere the
-JSON is used.
+order; the float32 mean is order-sensitive only in its last bits.  kitten.obj is too large to commit: its positions,
+normals and face corners are stored as tests/golden/mesh/kitten.npz (tests/golden/generate.py --kitten), from which the bounds
+are recomputed and compared with the committed tests/golden/kitten_bounds.json.
 """
 import json
 import os
@@ -17,47 +17,39 @@ from niagara_amd import host
 from niagara_amd import layouts as L
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-OBJ = "/root/reference/data/kitten.obj"
+NPZ = os.path.join(HERE, "golden", "mesh", "kitten.npz")
 JSON = os.path.join(HERE, "golden", "kitten_bounds.json")
 
 
-def bounds_from_obj(path):
-    pos, nrm, corners = [], [], []
-    for line in open(path):
-        if line.startswith("v "):
-            pos.append([float(x) for x in line.split()[1:4]])
-        elif line.startswith("vn "):
-            nrm.append([float(x) for x in line.split()[1:4]])
-        elif line.startswith("f "):
-            for tok in line.split()[1:]:
-                a, _, n = tok.split("/")
-                corners.append((int(a) - 1, int(n) - 1))
-    pos, nrm = np.array(pos, np.float32), np.array(nrm, np.float32)
-    c = np.array(corners)
+def load_kitten():
+    """kitten.obj as arrays: positions, normals (float32) and the (position, normal) index of every face corner, three per triangle"""
+    k = np.load(NPZ)
+    return k["positions"], k["normals"], k["corners"].astype(np.int64)
+
+
+def bounds_from_kitten():
+    pos, nrm, c = load_kitten()
     half = pos[c[:, 0]].astype(np.float16)                       # src/scene.cpp:149-151
     q = np.rint(nrm[c[:, 1]] * 511).astype(np.int32) + 511       # src/scene.cpp:153-155
     key = np.concatenate([half.view(np.uint16).astype(np.int64), q.astype(np.int64)], axis=1)
     _, first = np.unique(key, axis=0, return_index=True)
     uniq = half[np.sort(first)].astype(np.float32)               # src/scene.cpp:193-198
     center, radius = host.mesh_bounds(uniq)                      # src/scene.cpp:207-220 through the C ABI (nv_mesh_bounds)
-    return dict(vertices=int(len(pos)), triangles=int(len(corners) // 3), unique_vertices=int(len(uniq)),
+    return dict(vertices=int(len(pos)), triangles=int(len(c) // 3), unique_vertices=int(len(uniq)),
                 center=[float(x) for x in center], radius=float(radius))
 
 
 def kitten_bounds():
-    if os.path.exists(OBJ):
-        b = bounds_from_obj(OBJ)
-        if not os.path.exists(JSON):
-            json.dump(b, open(JSON, "w"), indent=1)
-        ref = json.load(open(JSON))
-        assert b["vertices"] == ref["vertices"] == 14472 and b["triangles"] == ref["triangles"] == 28944
-        assert np.allclose(b["center"], ref["center"], atol=1e-6) and abs(b["radius"] - ref["radius"]) < 1e-6
-    return json.load(open(JSON))
+    b = bounds_from_kitten()
+    ref = json.load(open(JSON))
+    assert b["vertices"] == ref["vertices"] == 14472 and b["triangles"] == ref["triangles"] == 28944
+    assert np.allclose(b["center"], ref["center"], atol=1e-6) and abs(b["radius"] - ref["radius"]) < 1e-6
+    return ref
 
 
 def test_mesh_bounds_equal_the_reference_statements():
     """nv_mesh_bounds == src/scene.cpp:207-220 compiled verbatim (oracle/_ref), bit for bit: random clouds of every size
-    class (the fp32 sum is order- and size-sensitive), values that cancel, and the kitten where the reference tree is mounted"""
+    class (the fp32 sum is order- and size-sensitive), values that cancel, and the kitten"""
     import oracle.ref as R
     if not R.available():
         pytest.skip("oracle/_ref not built")
@@ -66,9 +58,7 @@ def test_mesh_bounds_equal_the_reference_statements():
               [(1, 1, 0), (2, 1, 5), (3, 1e-3, 0), (17, 10, -3), (1000, 1, 100), (14856, 0.3, 0), (200000, 50, 1e4), (65536, 1e-6, 1)]]
     clouds.append(np.array([[1e8, -1e8, 1], [-1e8, 1e8, 1], [1, 1, 1]], np.float32))
     clouds.append(rng.normal(0, 1, (5000, 3)).astype(np.float16).astype(np.float32))  # de-quantised halves, like the real input
-    if os.path.exists(OBJ):
-        pos = np.array([[float(x) for x in l.split()[1:4]] for l in open(OBJ) if l.startswith("v ")], np.float32)
-        clouds.append(pos.astype(np.float16).astype(np.float32))
+    clouds.append(load_kitten()[0].astype(np.float16).astype(np.float32))
     for pos in clouds:
         c, r = host.mesh_bounds(pos)
         cr, rr = R.mesh_bounds(pos)

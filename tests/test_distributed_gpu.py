@@ -39,7 +39,7 @@ def test_bench_two_ranks_on_one_device(batch, streams, total):
     out = None
     for attempt in range(2):  # (a rendezvous that never completes — seen once on the GPU box — gets one more try on a fresh port)
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
-               str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--shared-device", "--steps", str(steps), "--warmup", "3",
+               str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--shared-device", "--steps", str(steps), "--warmup", "3",
                "--counts-batch", str(batch), "--streams", str(streams), "--draws", str(draws_per_rank)] + (["--total-meshlets", str(total), "--cpu-seconds", "0.2"] if total else ["--no-cpu-baseline"])
         try:
             out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=180, cwd=ROOT)
@@ -85,7 +85,7 @@ def test_bench_forced_sharded_over_rccl(batch, streams, launcher):
     import bench
     from niagara_amd import synth
     draws, cpd, steps = 3000, 10, 19  # (19: a partial last batch for every batch size but 1)
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-sharded", "--backend", "nccl", "--steps", str(steps), "--warmup", "3", "--counts-batch", str(batch),
+    tail = [os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--force-sharded", "--backend", "nccl", "--steps", str(steps), "--warmup", "3", "--counts-batch", str(batch),
             "--streams", str(streams), "--draws", str(draws), "--cpu-seconds", "0.2"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     if launcher == "run":
@@ -125,7 +125,7 @@ def test_config5_eight_ranks_100m_meshlets(tmp_path):
     world, total, cpd = 8, 100_000_000, 10
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     # (no launcher in front — bench.py starts its own eight ranks, as the driver's `python3 bench.py --gpus N ...` needs)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--shared-device", "--steps", "3", "--warmup", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--backend", "gloo", "--shared-device", "--steps", "3", "--warmup", "2",
            "--total-meshlets", str(total), "--copies", "2", "--cpu-seconds", "0.5", "--dump-ids", str(tmp_path)]
     env = {k: v for k, v in env.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
@@ -156,7 +156,7 @@ def test_bench_launches_its_own_ranks():
     """VERDICT r5 item 1, the exact command of its `Done`: `python3 bench.py --gpus 2 --backend gloo --shared-device --steps 5 --warmup 2` with NO launcher
     and no rendezvous variables in the environment: rc 0, one JSON line for two ranks, parity on both shards"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--shared-device", "--steps", "5", "--warmup", "2"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--shared-device", "--steps", "5", "--warmup", "2"],
                          env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -168,9 +168,9 @@ def test_bench_launches_its_own_ranks():
 
 
 def test_bench_driver_command_carries_frame_and_contract_rooflines():
-    """the driver's N = 1 command as it is run at round end: the line carries the headline's roofline + cpu_baseline, `contract_chain` with its own roofline
+    """the driver's N = 1 command with --full: the line carries the headline's roofline + cpu_baseline, `contract_chain` with its own roofline
      and the dependent `frame` at BASELINE scale with its HBM fraction, per-launch times and parity (item 6a)"""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"], capture_output=True, text=True, timeout=1500, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "20", "--warmup", "5"], capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -192,7 +192,7 @@ def test_bench_single_gpu_line_is_one_regime():
     """the default line's value / ms_per_step are one pass after the other on one stream, the dominant kernel's
     event time fits inside a step, and the several-passes-in-flight figure is a side field"""
     sys.path.insert(0, ROOT)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--draws", "6000", "--cpu-seconds", "0.2", "--no-frame"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "30", "--warmup", "5", "--draws", "6000", "--cpu-seconds", "0.2", "--no-frame"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -202,6 +202,36 @@ def test_bench_single_gpu_line_is_one_regime():
     assert rec["throughput_overlapped"]["streams"] == 3 and rec["throughput_overlapped"]["value"] > 0
     assert rec["cpu_baseline"]["visible_list"].startswith("bit-identical") and rec["config"]["visible_total"] == rec["config"]["visible_rank0"]
     assert rec["parity"] == "bit-identical"
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run (no --full): exactly `--steps` timed passes, the headline fields and none of the side fields, and --dump-outputs writes the last timed
+    pass's visible-ID list and count words as float64 — the list is the CPU oracle's for the same seeded inputs"""
+    import argparse
+    import oracle
+    sys.path.insert(0, ROOT)
+    import bench
+    from niagara_amd import synth
+    draws, cpd, steps = 6000, 10, 7
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2", "--draws", str(draws),
+                          "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "meshlets culled+compacted /sec" and rec["unit"] == "meshlets/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+    assert rec["steps"] == steps and rec["warmup"] == 2 and rec["ms_per_step"] > 0
+    assert abs(rec["value"] - rec["config"]["meshlets_total"] / (rec["ms_per_step"] * 1e-3)) < 1e-6 * rec["value"]
+    assert not set(rec) & {"roofline", "throughput_overlapped", "cpu_baseline", "parity", "contract_chain", "frame"}
+    ids, count = np.load(tmp_path / "out" / "visible_ids.npy"), np.load(tmp_path / "out" / "count.npy")
+    assert ids.dtype == np.float64 and count.dtype == np.float64 and count.shape == (4,)
+    assert int(count[0]) == len(ids) == rec["config"]["visible_rank0"] > 0
+    args = argparse.Namespace(draws=draws, commands_per_draw=cpd, total_meshlets=0)
+    d, meshlets, cd, (b, e), _ = bench.make_inputs(args, 0, 1)
+    commands = bench.make_commands(b, e, cpd)
+    cib, cc4 = np.zeros(len(commands) * 64, np.uint32), np.zeros(4, np.uint32)
+    oracle.clustercull(cd, 0, commands, synth.count4_for(e - b), d, meshlets, None, None, cib, cc4, threads=oracle.max_threads())
+    assert int(cc4[0]) == len(ids) and (ids == cib[:len(ids)].astype(np.float64)).all()
 
 
 def _worker(rank, world, port, out_dir):

@@ -9,6 +9,8 @@ library is pinned here:
   * GPU suite: the HIP kernel equals the oracle bit for bit (random payloads, coherent geometry, degenerate triangles,
     empty meshlets, both reference widths), and a scene whose bounds were generated on the GPU goes through
     drawcull -> clustercull identically to the oracle."""
+import os
+
 import numpy as np
 import pytest
 
@@ -215,23 +217,16 @@ def test_scene_with_gpu_generated_bounds_through_the_passes():
         ctx.close()
 
 
-KITTEN = "/root/reference/data/kitten.obj"
+KITTEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mesh", "kitten.npz")
 
 
-@pytest.mark.skipif(not __import__("os").path.exists(KITTEN), reason="the reference tree (data/kitten.obj) is not mounted here")
 def test_kitten_meshlets_through_the_cluster_cull():
-    """niagara's own asset.  kitten.obj (read where the reference tree is mounted, never copied) is cut into
+    """niagara's own asset.  kitten.obj (stored as arrays in tests/golden/mesh/kitten.npz) is cut into
     meshlets in face order, the bounds come from orc_meshlet_bounds, and 600 instances go through the oracle's cluster cull:
     every meshlet the cull drops has no front-facing triangle inside the frustum (per-triangle ground truth in fp64), and
-    sphere / cone contain the geometry.  The GPU suite generates the same bounds with nv_meshlet_bounds on the torus; the
-    asset itself does not travel to the GPU box."""
-    pos, faces = [], []
-    for line in open(KITTEN):
-        if line.startswith("v "):
-            pos.append([float(x) for x in line.split()[1:4]])
-        elif line.startswith("f "):
-            faces.append([int(t.split("/")[0]) - 1 for t in line.split()[1:4]])
-    pos, faces = np.array(pos, np.float32), np.array(faces, np.int64)
+    sphere / cone contain the geometry.  The GPU suite generates the same bounds with nv_meshlet_bounds on the torus."""
+    k = np.load(KITTEN)
+    pos, faces = k["positions"], k["corners"][:, 0].astype(np.int64).reshape(-1, 3)
     assert len(pos) == 14472 and len(faces) == 28944
     # spatially coherent order (the clusterizer's job): sort faces by the Morton code of their centroid
     cen = pos[faces].mean(axis=1)

@@ -11,7 +11,7 @@ done
 shift $((OPTIND - 1))
 for round in $(seq $rounds); do
 for so in "$@"; do for m in $modes; do for b in $blocks; do
-  NV_DEBUG_MODE=$m NV_CC_BLOCKS_PER_CU=$b NV_LIBRARY_PATH=$PWD/$so timeout 100 python bench.py --steps $steps --no-cpu-baseline 2>&1 | tail -1 | python -c "
+  NV_DEBUG_MODE=$m NV_CC_BLOCKS_PER_CU=$b NV_LIBRARY_PATH=$PWD/$so timeout 100 python bench.py --full --steps $steps --no-cpu-baseline 2>&1 | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('$so', 'mode', $m, 'wg/CU', $b, 'round', $round, '| G/s', round(d['value']/1e9,1), 'step_us', round(d['ms_per_step']*1e3,2), 'cull_us', round(r['kernel_avg_us'],2), 'scatter_us', round(r['scatter_kernel_avg_us'],2), 'frac', round(r['frac'],3), 'visible', d['config']['visible_total'])"

@@ -19,7 +19,7 @@ else
   cd $R
   for rep in 1 2; do
     for lib in libniagara_vis.so libniagara_vis_fs8.so libniagara_vis_fs16.so libniagara_vis_fv8.so libniagara_vis_fv16.so libniagara_vis_fps200.so libniagara_vis_fpv100.so; do
-      NV_LIBRARY_PATH=niagara_amd/$lib timeout 200 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --overlap-streams 0 2>/dev/null | python3 -c "
+      NV_LIBRARY_PATH=niagara_amd/$lib timeout 200 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --overlap-streams 0 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); r=d['roofline']; print('%-26s' % '$lib', 'pass us %.2f' % (d['ms_per_step']*1e3), 'cull us %.2f' % r['kernel_avg_us'], 'scatter us %.2f' % r['scatter_kernel_avg_us'], 'visible', d['config']['visible_total'])"
     done

@@ -8,7 +8,7 @@ out=$R/gpurun_out/refresh_$tag; mkdir -p $out
 cd $R
 bash tools/pmc_traffic.sh $tag > $out/pmc_traffic.log 2>&1
 cp gpurun_out/pmct_$tag/pmc_traffic_summary.json $out/pmc_traffic.json && cp $out/pmc_traffic.json profiles/${tag}_pmc_traffic.json
-python bench.py 2> $out/bench_default.err | tail -1 > $out/bench_default.json
+python bench.py --full 2> $out/bench_default.err | tail -1 > $out/bench_default.json
 (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -f csv -d $out/kt -- python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline > $out/kt.log 2>&1)
 python tools/bench_configs.py --iters 100 2> $out/bench_configs.err | grep "^{" > $out/bench_configs.jsonl
 tail -c 600 $out/bench_default.json; echo; wc -l $out/bench_configs.jsonl

@@ -7,8 +7,8 @@ tag=${1:-r05}
 out=$R/gpurun_out/final_$tag; mkdir -p $out
 bash tools/pmc_traffic.sh $tag > $out/pmc_traffic.log 2>&1
 cp gpurun_out/pmct_$tag/pmc_traffic_summary.json $out/pmc_traffic.json && cp $out/pmc_traffic.json profiles/${tag}_pmc_traffic.json
-python bench.py 2> $out/bench_default.err | tail -1 > $out/bench_default.json
-for i in 1 2 3 4 5; do python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 >> $out/bench_20.jsonl; done
+python bench.py --full 2> $out/bench_default.err | tail -1 > $out/bench_default.json
+for i in 1 2 3 4 5; do python bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 >> $out/bench_20.jsonl; done
 bash tools/kt.sh ${tag}bench -- python bench.py --steps 100 --warmup 10 --no-cpu-baseline --overlap-streams 0 > $out/kt.txt 2>&1
 bash tools/pmc.sh ${tag}insts "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM SQ_ACTIVE_INST_VALU" -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --overlap-streams 0 > $out/pmc_insts.txt 2>&1
 python tools/bench_configs.py --iters 100 2> $out/bench_configs.err | grep "^{" > $out/bench_configs.jsonl
