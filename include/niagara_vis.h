@@ -256,6 +256,10 @@ int nv_profile_variants(nv_context* ctx, uint32_t out_count[NV_VARIANT_SLOTS]);
  * visibility words, 2 = always the visibility words first and then only the records of last frame's visible draws (the others leave
  * at drawcull.comp.glsl:66 whatever their record holds).  Speed only; the late pass decides every draw and reads every record. */
 #define NV_OPT_DRAW_RECORDS 8
+/* NV_OPT_RASTER_SMALL_LIMIT (default 16, 0 .. INT_MAX): nv_rasterdepth walks a triangle whose clipped bounding box holds at most this
+ * many pixel centres with one lane, a larger one with the whole wave (lane = pixel of an 8 x 8 stamp).  0 puts every triangle on the
+ * wave path, INT_MAX every triangle on the lane path.  Speed only: both paths write the same bits. */
+#define NV_OPT_RASTER_SMALL_LIMIT 9
 int nv_set_option(nv_context* ctx, int option, int value);
 
 /* ---- capacities ----
@@ -412,6 +416,28 @@ int nv_trianglecull(nv_context* ctx, void* stream, const NvGlobals* globals, con
                     const NvMeshDraw* d_draws, const NvMeshlet* d_meshlets, const uint32_t* d_meshletData,
                     const NvVertex* d_vertices, const uint32_t* d_clusterIndices, const uint32_t* d_clusterCount4,
                     NvTriangleMask* d_masks, uint32_t maskCapacity, uint64_t* d_totals3 /* clusters, triangles, kept */);
+
+/* ---- depth-only raster of the visible clusters ----
+ * The [raster] box of niagara's frame (src/niagara.cpp:1765-1788) for a part without a graphics pipeline.  Inputs are nv_trianglecull's;
+ * for every slot of the grid {cc4[1], cc4[2], cc4[3]} (index = x + 256 y + NV_CLUSTER_TILE z, ~0 = padding) the meshlet's vertices go to
+ * screen space with nv_trianglecull's arithmetic plus z = clip.z / clip.w, snap to 8 sub-pixel bits (X = rint(sx * 256),
+ * Y = height * 256 - rint(sy * 256): row 0 at the top, the reference's flipped viewport, src/niagara.cpp:1641) and every triangle
+ * i < min(triangleCount, 96) is rasterised at pixel centres with the top-left rule, unless
+ *   - an index byte is >= min(vertexCount, 64), or a vertex has !(clip.w > 0 && clip.z <= clip.w) (no near-plane clipping: such a
+ *     triangle writes nothing, which keeps the pyramid conservative), a non-finite screen position or |sx|, |sy| >= 2^21;
+ *   - its doubled area is 0, or it is a back face while globals->cullData.postPass == 0 (front = counter-clockwise in y-up space,
+ *     VK_CULL_MODE_BACK_BIT; postPass != 0 draws both faces; the post pass's depth bias is not modelled).
+ * Depth: fp32, interpolated in a fixed order from the exact int64 edge functions, clamped to [0, 1], written with an atomic max on its
+ * bits (reverse-Z, compare GREATER).  d_depth is width x height; the caller clears it (0 = far) before an early pass, not before a late
+ * one.  d_visibility (optional, width x height u64) receives the max of bits(z) << 32 | slot index << 7 | triangle: ties go to the larger ID.
+ * d_totals4 (optional, accumulated: zero it first): clusters, triangles (triangleCount as stored), triangles rasterised, samples covered.
+ * Every result is independent of the order of the GPU's work.  width and height must equal globals->screenWidth / screenHeight and lie in
+ * 1 .. 16384. */
+int nv_rasterdepth(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshTaskCommand* d_commands,
+                   const NvMeshDraw* d_draws, const NvMeshlet* d_meshlets, const uint32_t* d_meshletData,
+                   const NvVertex* d_vertices, const uint32_t* d_clusterIndices, const uint32_t* d_clusterCount4,
+                   float* d_depth, uint32_t width, uint32_t height,
+                   uint64_t* d_visibility /* optional, width*height */, uint64_t* d_totals4 /* optional */);
 
 /* depthreduce.comp.glsl:14-22 + the level loop at src/niagara.cpp:1703-1733.
  * d_depth is the width x height fp32 depth target (reverse-Z, far = 0). */

@@ -227,4 +227,23 @@ struct TriangleArgs
 	unsigned long long* __restrict__ partials; // library scratch: 3 counters per workgroup of the launch
 };
 
+// nv_rasterdepth (rasterdepth.hip)
+struct RasterArgs
+{
+	NvGlobals globals;
+	const NvMeshTaskCommand* __restrict__ commands;
+	const NvMeshDraw* __restrict__ draws;
+	const NvMeshlet* __restrict__ meshlets;
+	const uint32_t* __restrict__ meshletData;
+	const NvVertex* __restrict__ vertices;
+	const uint32_t* __restrict__ clusterIndices;
+	const uint32_t* __restrict__ cc4;
+	uint32_t* depth;                       // fp32 bits, width x height (atomic max)
+	unsigned long long* visibility;        // optional, width x height (atomic max)
+	uint32_t width, height;
+	uint32_t smallLimit;                   // NV_OPT_RASTER_SMALL_LIMIT: pixel centres in the box up to which a lane walks a triangle alone
+	unsigned long long* __restrict__ totals;   // optional
+	unsigned long long* __restrict__ partials; // library scratch: 4 counters per workgroup of the launch
+};
+
 } // namespace nv

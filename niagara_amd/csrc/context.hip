@@ -45,6 +45,7 @@ int launch_clustersubmit(hipStream_t, uint32_t* cc4, uint32_t* clusterIndices);
 int launch_pack_counts(hipStream_t, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*);
 int launch_depthreduce(hipStream_t, const float* depth, uint32_t w, uint32_t h, const NvPyramidDesc& pyr);
 int launch_trianglecull(hipStream_t, const TriangleArgs& a, uint32_t gridBlocks);
+int launch_rasterdepth(hipStream_t, const RasterArgs& a, uint32_t gridBlocks);
 int launch_meshlet_bounds(hipStream_t, const NvVertex* vertices, const uint32_t* data, NvMeshlet* meshlets, uint32_t count, float* out8, uint32_t gridBlocks);
 
 } // namespace nv
@@ -95,7 +96,7 @@ struct nv_context
 	uint8_t* drawResults;
 	size_t drawResultsCapacity;
 	nv::ClusterCounts* drawTileCounts;
-	unsigned long long* totalsPartials; // nv_trianglecull / nv_cluster_expand: per-workgroup partial totals (3 x u64 x grid)
+	unsigned long long* totalsPartials; // nv_trianglecull / nv_cluster_expand / nv_rasterdepth: per-workgroup partial totals (up to 4 x u64 x grid)
 	nv_scene* scene; // mirrors + registrations (shared between contexts by nv_share_scene)
 	// launch shape of the cull kernel (workgroups per CU) and the dealing's start-delay compensation in percent; constants
 	// in the product, environment-tunable (with the NV_DEBUG_MODE bit mask) only in the NV_EXPERIMENTS build
@@ -128,6 +129,7 @@ struct nv_context
 	float* timing; // NV_DEBUG_MODE bit 3: 8 x u64 stamps per wave of the last clustercull
 	size_t timingWaves; // its room, in waves
 	uint32_t variants[NV_VARIANT_SLOTS]; // nv_profile_variants: launches per kernel variant since the last read
+	uint32_t rasterSmallLimit; // NV_OPT_RASTER_SMALL_LIMIT
 };
 
 namespace
@@ -384,6 +386,7 @@ int nv_create(nv_context** out_ctx, int device)
 	ctx->dealScale = 100;
 	ctx->scatterTilesPerCU = 1;
 	ctx->scatterWaves = 16;
+	ctx->rasterSmallLimit = 16;
 	ctx->directPercent = 35; // measured crossover (config 3A geometry at several densities): ~36 % of the commands passing the filter
 	ctx->forceDirect = -1;
 	ctx->bitsBlocksPerCU = 4;
@@ -427,7 +430,7 @@ int nv_create(nv_context** out_ctx, int device)
 	    hipMemset(ctx->tileCounts, 0, sizeof(nv::ClusterCounts)) != hipSuccess ||
 	    scratch_alloc(&ctx->drawTileCounts, sizeof(nv::ClusterCounts)) != hipSuccess ||
 	    hipMemset(ctx->drawTileCounts, 0, sizeof(nv::ClusterCounts)) != hipSuccess || reserve_draw_results(ctx, 1u << 20) != NV_OK ||
-	    scratch_alloc(&ctx->totalsPartials, (size_t)persistent_grid(ctx, 8) * 3 * sizeof(unsigned long long)) != hipSuccess)
+	    scratch_alloc(&ctx->totalsPartials, (size_t)persistent_grid(ctx, 8) * 4 * sizeof(unsigned long long)) != hipSuccess)
 	{
 		nv_destroy(ctx);
 		return NV_ENOMEM;
@@ -526,6 +529,11 @@ int nv_set_option(nv_context* ctx, int option, int value)
 		if (value != 0 && value != 4 && value != 8)
 			return NV_EINVAL;
 		ctx->forceShallow = value == 0 ? -1 : (value == 4 ? 1 : 0);
+		return NV_OK;
+	case NV_OPT_RASTER_SMALL_LIMIT:
+		if (value < 0)
+			return NV_EINVAL;
+		ctx->rasterSmallLimit = (uint32_t)value;
 		return NV_OK;
 	case NV_OPT_CULL_WORKGROUPS_PER_CU:
 		if (value < 1 || value > 8)
@@ -1047,6 +1055,34 @@ int nv_trianglecull(nv_context* ctx, void* stream, const NvGlobals* globals, con
 	const uint32_t grid = persistent_grid(ctx, 8);
 	a.partials = ctx->totalsPartials;
 	return nv::launch_trianglecull((hipStream_t)stream, a, grid);
+}
+
+int nv_rasterdepth(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshTaskCommand* d_commands, const NvMeshDraw* d_draws,
+                   const NvMeshlet* d_meshlets, const uint32_t* d_meshletData, const NvVertex* d_vertices, const uint32_t* d_clusterIndices,
+                   const uint32_t* d_clusterCount4, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_visibility, uint64_t* d_totals4)
+{
+	if (!ctx || !globals || !d_commands || !d_draws || !d_meshlets || !d_meshletData || !d_vertices || !d_clusterIndices || !d_clusterCount4 ||
+	    !d_depth || width == 0 || height == 0 || width > 16384 || height > 16384 || globals->screenWidth != (float)width ||
+	    globals->screenHeight != (float)height)
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	nv::RasterArgs a;
+	a.globals = *globals;
+	a.commands = d_commands;
+	a.draws = d_draws;
+	a.meshlets = d_meshlets;
+	a.meshletData = d_meshletData;
+	a.vertices = d_vertices;
+	a.clusterIndices = d_clusterIndices;
+	a.cc4 = d_clusterCount4;
+	a.depth = reinterpret_cast<uint32_t*>(d_depth);
+	a.visibility = reinterpret_cast<unsigned long long*>(d_visibility);
+	a.width = width;
+	a.height = height;
+	a.smallLimit = ctx->rasterSmallLimit;
+	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
+	a.partials = ctx->totalsPartials;
+	return nv::launch_rasterdepth((hipStream_t)stream, a, persistent_grid(ctx, 8));
 }
 
 int nv_meshlet_bounds(nv_context* ctx, void* stream, const NvVertex* d_vertices, const uint32_t* d_meshletData, NvMeshlet* d_meshlets, uint32_t meshletCount,

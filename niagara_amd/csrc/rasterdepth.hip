@@ -1,0 +1,339 @@
+// rasterdepth.hip — depth-only rasteriser of the visible clusters for gfx950.
+//
+// Fills the [raster] box of niagara's frame (src/niagara.cpp:1765-1788) on a part without a graphics pipeline: for every slot of the
+// grid clustersubmit wrote, the meshlet's vertices go to screen space with nv_trianglecull's arithmetic, snap to 8 sub-pixel bits, and
+// every triangle that survives the rejection and facing rules is walked over the pixel centres it covers (top-left fill rule, exact
+// int64 edge functions).  The depth is interpolated in fp32 in a fixed order and written with an integer max on its bits (reverse-Z,
+// GREATER): the result does not depend on the order in which waves run.  The rule set is restated one sample at a time by
+// tests/raster_ref.c; both raster paths below must equal it bit for bit.
+//
+// Shape.  A persistent grid; a wave owns a contiguous run of slots and fetches their headers lane-parallel (lane = slot, as
+// trianglecull_kernel does), then takes the slots one after the other: lane = vertex for the vertex stage (snapped X, Y, z and a
+// reject bit into LDS), lane = triangle for the setup (two passes for 96 triangles).  A triangle whose clipped bounding box holds at
+// most `smallLimit` pixel centres is walked by its own lane right there; a larger one is queued in LDS and walked afterwards by the
+// whole wave, lane = pixel of an 8 x 8 stamp.  Before each atomic the lane loads the current value and skips the atomic when it would
+// not raise it (values only grow during a launch: a stale load costs an extra atomic, never a wrong result).
+#include "cullmath.h"
+#include "args.h"
+
+namespace nv
+{
+
+constexpr int RD_WAVES = 4;
+constexpr int RD_THREADS = RD_WAVES * 64;
+constexpr uint32_t RD_CHUNK = 64; // slots whose headers a wave fetches together (lane = slot)
+#ifndef RD_BLOCKS_PER_CU
+#define RD_BLOCKS_PER_CU 6 // <= 8: the partial totals are sized for 8 workgroups per CU (context.hip)
+#endif
+constexpr float RD_GUARD = 2097152.0f; // 2^21 pixels: every edge-function product stays below 2^62
+
+NV_DEV uint32_t rd_rl(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
+
+// the wave is the workgroup of the reference's mesh shader: its LDS accesses are ordered, the compiler is told so
+NV_DEV void rd_lds_order()
+{
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// a triangle ready to walk: corners with A > 0 (b and c swapped for a front face), top-left flags, 1 / A, pixel box (inclusive)
+struct RdTri
+{
+	int32_t ax, ay, bx, by, cx, cy;
+	float za, dzb, dzc, inv;
+	int32_t x0, x1, y0, y1;
+	uint32_t topLeft; // bit 0: a->b, bit 1: b->c, bit 2: c->a
+};
+
+NV_DEV int64_t rd_edge(int32_t px, int32_t py, int32_t qx, int32_t qy, int32_t sx, int32_t sy)
+{
+	// every difference is below 2^30 in magnitude (guard band, viewport <= 16384): 32 x 32 -> 64-bit products
+	return (int64_t)(qx - px) * (int64_t)(sy - py) - (int64_t)(qy - py) * (int64_t)(sx - px);
+}
+
+NV_DEV bool rd_top_left(int32_t px, int32_t py, int32_t qx, int32_t qy)
+{
+	const int32_t dx = qx - px, dy = qy - py;
+	return dy < 0 || (dy == 0 && dx > 0);
+}
+
+NV_DEV int32_t rd_floor256(int32_t v) { return v >> 8; } // arithmetic shift: floor(v / 256)
+
+// Setup of triangle (ia, ib, ic) from the slot's snapped vertices.  Returns false when it is not drawn (an index at or past the vertex
+// count, a rejected vertex, zero area, or a back face with back-face culling on); `tri` then is left undefined.
+NV_DEV bool rd_setup(const int4* vtx, uint32_t ia, uint32_t ib, uint32_t ic, uint32_t ve, bool bothFaces, int32_t W, int32_t H, RdTri& tri)
+{
+	if (ia >= ve || ib >= ve || ic >= ve)
+		return false;
+	int4 a = vtx[ia], b = vtx[ib], c = vtx[ic];
+	if ((a.w | b.w | c.w) != 0)
+		return false;
+	int64_t A = (int64_t)(b.x - a.x) * (int64_t)(c.y - a.y) - (int64_t)(b.y - a.y) * (int64_t)(c.x - a.x);
+	if (A == 0 || (A > 0 && !bothFaces))
+		return false;
+	if (A < 0) // front face (counter-clockwise in y-up space): wind it so that A > 0
+	{
+		const int4 s = b;
+		b = c, c = s, A = -A;
+	}
+	tri.ax = a.x, tri.ay = a.y, tri.bx = b.x, tri.by = b.y, tri.cx = c.x, tri.cy = c.y;
+	const float za = __int_as_float(a.z), zb = __int_as_float(b.z), zc = __int_as_float(c.z);
+	tri.za = za, tri.dzb = zb - za, tri.dzc = zc - za;
+	tri.inv = 1.0f / (float)A;
+	tri.topLeft = (rd_top_left(a.x, a.y, b.x, b.y) ? 1u : 0u) | (rd_top_left(b.x, b.y, c.x, c.y) ? 2u : 0u) | (rd_top_left(c.x, c.y, a.x, a.y) ? 4u : 0u);
+	const int32_t xmin = min(min(a.x, b.x), c.x), xmax = max(max(a.x, b.x), c.x);
+	const int32_t ymin = min(min(a.y, b.y), c.y), ymax = max(max(a.y, b.y), c.y);
+	// pixel centres x * 256 + 128 inside [xmin, xmax]; |X|, |Y| < 2^29 + 2^22: no overflow
+	tri.x0 = max(rd_floor256(xmin - 128 + 255), 0), tri.x1 = min(rd_floor256(xmax - 128), W - 1);
+	tri.y0 = max(rd_floor256(ymin - 128 + 255), 0), tri.y1 = min(rd_floor256(ymax - 128), H - 1);
+	return true;
+}
+
+// One pixel centre: coverage, depth, and the two atomics.  Returns whether the sample is covered.
+NV_DEV bool rd_sample(const RdTri& t, int32_t px, int32_t py, uint32_t W, uint32_t* __restrict__ depth, unsigned long long* __restrict__ vis, uint32_t id)
+{
+	const int32_t sx = px * 256 + 128, sy = py * 256 + 128;
+	const int64_t wa = rd_edge(t.bx, t.by, t.cx, t.cy, sx, sy);
+	const int64_t wb = rd_edge(t.cx, t.cy, t.ax, t.ay, sx, sy);
+	const int64_t wc = rd_edge(t.ax, t.ay, t.bx, t.by, sx, sy);
+	const bool covered = (wa > 0 || (wa == 0 && (t.topLeft & 2u))) && (wb > 0 || (wb == 0 && (t.topLeft & 4u))) && (wc > 0 || (wc == 0 && (t.topLeft & 1u)));
+	if (!covered)
+		return false;
+	float z = (t.za + ((float)wb * t.inv) * t.dzb) + ((float)wc * t.inv) * t.dzc;
+	z = z > 0.0f ? z : 0.0f; // (NaN -> 0)
+	z = z < 1.0f ? z : 1.0f;
+	const uint32_t bits = __float_as_uint(z);
+	const size_t at = (size_t)py * W + (size_t)px;
+	if (bits > depth[at])
+		atomicMax(depth + at, bits);
+	if (vis)
+	{
+		const unsigned long long v = (unsigned long long)bits << 32 | id;
+		if (v > vis[at])
+			atomicMax(vis + at, v);
+	}
+	return true;
+}
+
+__global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(RasterArgs a)
+{
+	__shared__ int4 s_vtx[RD_WAVES][64];      // per vertex of the current slot: X, Y, z bits, reject
+	__shared__ uint32_t s_queue[RD_WAVES][96]; // large triangles of the current slot: t | ia << 8 | ib << 16 | ic << 24 (after the swap)
+
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const uint32_t gx = a.cc4[1], gz = a.cc4[3];
+	const uint32_t slots = gx * a.cc4[2] * gz;
+	const uint32_t numWaves = gridDim.x * RD_WAVES;
+	const uint32_t w = blockIdx.x * RD_WAVES + wave;
+	const uint32_t per = (slots + numWaves - 1) / numWaves; // contiguous slots per wave
+	const uint32_t begin = w * per < slots ? w * per : slots;
+	const uint32_t end = begin + per < slots ? begin + per : slots;
+	const int32_t W = (int32_t)a.width, H = (int32_t)a.height;
+	const bool bothFaces = a.globals.cullData.postPass != 0;
+	const uint8_t* data8 = reinterpret_cast<const uint8_t*>(a.meshletData);
+	const uint16_t* data16 = reinterpret_cast<const uint16_t*>(a.meshletData);
+	int4* vtx = s_vtx[wave];
+	uint32_t* queue = s_queue[wave];
+
+	uint32_t clusters = 0, triangles = 0; // wave-uniform
+	uint32_t drawn = 0;                   // per lane
+	unsigned long long samples = 0;       // per lane
+
+	for (uint32_t chunk = begin; chunk < end; chunk += RD_CHUNK)
+	{
+		const uint32_t cnt = end - chunk < RD_CHUNK ? end - chunk : RD_CHUNK;
+		// lane = slot: grid position -> index (the mesh shader's x + 256 y + CLUSTER_TILE z) -> cluster index -> command -> headers
+		uint32_t hIndex = 0, hCi = ~0u, hDataOffset = 0, hBaseVertex = 0, hCounts = 0;
+		float4 hD0 = make_float4(0, 0, 0, 0), hD1 = make_float4(0, 0, 0, 1);
+		if (lane < cnt)
+		{
+			const uint32_t k = chunk + lane, x = k % gx, r = k / gx;
+			hIndex = x + (r / gz) * 256u + (r % gz) * NV_CLUSTER_TILE;
+			hCi = a.clusterIndices[hIndex];
+		}
+		if (hCi != ~0u)
+		{
+			const uint32_t* cmd = reinterpret_cast<const uint32_t*>(a.commands + (hCi & 0xffffffu));
+			const uint32_t drawId = cmd[0], taskOffset = cmd[1];
+			const uint32_t* mw = reinterpret_cast<const uint32_t*>(a.meshlets + taskOffset + (hCi >> 24));
+			hDataOffset = mw[3];
+			hBaseVertex = mw[4];
+			hCounts = mw[5] & 0xffffffu; // vertexCount | triangleCount << 8 | shortRefs << 16
+			const float4* dp = reinterpret_cast<const float4*>(a.draws + drawId);
+			hD0 = dp[0];
+			hD1 = dp[1];
+		}
+
+		for (uint32_t s = 0; s < cnt; ++s)
+		{
+			const uint32_t ci = rd_rl(hCi, s);
+			if (ci == ~0u)
+				continue;
+			const uint32_t index = rd_rl(hIndex, s);
+			const uint32_t dataOffset = rd_rl(hDataOffset, s), baseVertex = rd_rl(hBaseVertex, s), counts = rd_rl(hCounts, s);
+			const uint32_t vcRaw = counts & 0xffu, tcRaw = counts >> 8 & 0xffu, shortRefs = (counts >> 16 & 0xffu) == 1u;
+			const uint32_t ve = vcRaw < 64u ? vcRaw : 64u, te = tcRaw < 96u ? tcRaw : 96u;
+			const uint32_t indexOffset = dataOffset + (shortRefs ? (vcRaw + 1) / 2 : vcRaw);
+			clusters += 1;
+			triangles += tcRaw;
+
+			rd_lds_order(); // the previous slot's readers are done
+			// ---- vertex stage, lane = vertex (nv_trianglecull's arithmetic, src/shaders/meshlet.mesh.glsl:121-160)
+			const f3 q = { __uint_as_float(rd_rl(__float_as_uint(hD1.x), s)), __uint_as_float(rd_rl(__float_as_uint(hD1.y), s)),
+			               __uint_as_float(rd_rl(__float_as_uint(hD1.z), s)) };
+			const float qw = __uint_as_float(rd_rl(__float_as_uint(hD1.w), s)), scale = __uint_as_float(rd_rl(__float_as_uint(hD0.w), s));
+			const float px = __uint_as_float(rd_rl(__float_as_uint(hD0.x), s)), py = __uint_as_float(rd_rl(__float_as_uint(hD0.y), s));
+			const float pz = __uint_as_float(rd_rl(__float_as_uint(hD0.z), s));
+			if (lane < ve)
+			{
+				const uint32_t ref = shortRefs ? (uint32_t)data16[dataOffset * 2 + lane] : a.meshletData[dataOffset + lane];
+				const uint2 pv = *reinterpret_cast<const uint2*>(a.vertices + ref + baseVertex);
+				const f3 position = { half_bits_to_float(pv.x & 0xffffu), half_bits_to_float(pv.x >> 16), half_bits_to_float(pv.y & 0xffffu) };
+				const f3 rot = rotate_quat(position, q, qw);
+				const float wx = rot.x * scale + px, wy = rot.y * scale + py, wz = rot.z * scale + pz;
+				const float* V = a.globals.cullData.view;
+				const float* P = a.globals.projection;
+				float v4[4], clip[4];
+#pragma unroll
+				for (int r = 0; r < 4; ++r) // view * vec4(wpos, 1): c3 * 1.0f is c3 exactly
+					v4[r] = ((V[r] * wx + V[4 + r] * wy) + V[8 + r] * wz) + V[12 + r];
+#pragma unroll
+				for (int r = 0; r < 4; ++r)
+					clip[r] = ((P[r] * v4[0] + P[4 + r] * v4[1]) + P[8 + r] * v4[2]) + P[12 + r] * v4[3];
+				const float sx = ((clip[0] / clip[3]) * 0.5f + 0.5f) * a.globals.screenWidth;
+				const float sy = ((clip[1] / clip[3]) * 0.5f + 0.5f) * a.globals.screenHeight;
+				const float z = clip[2] / clip[3];
+				// behind or in front of the near plane (NaN included), non-finite, or outside the guard band: no triangle of it is drawn
+				const bool bad = !(clip[3] > 0.0f && clip[2] <= clip[3]) || !(__builtin_fabsf(sx) < RD_GUARD) || !(__builtin_fabsf(sy) < RD_GUARD);
+				const int32_t X = bad ? 0 : (int32_t)__builtin_rintf(sx * 256.0f);
+				const int32_t Y = bad ? 0 : H * 256 - (int32_t)__builtin_rintf(sy * 256.0f); // viewport flipped: row 0 at the top
+				vtx[lane] = make_int4(X, Y, __float_as_int(z), bad ? 1 : 0);
+			}
+			rd_lds_order();
+
+			// ---- triangle setup, lane = triangle; small ones are walked here by their own lane, large ones queued
+			uint32_t queued = 0; // wave-uniform
+			for (uint32_t tb = 0; tb < te; tb += 64)
+			{
+				const uint32_t t = tb + lane;
+				RdTri tri;
+				bool live = false, large = false;
+				uint32_t ia = 0, ib = 0, ic = 0;
+				if (t < te)
+				{
+					const uint32_t o = indexOffset * 4 + t * 3;
+					ia = data8[o], ib = data8[o + 1], ic = data8[o + 2];
+					live = rd_setup(vtx, ia, ib, ic, ve, bothFaces, W, H, tri);
+				}
+				if (live)
+				{
+					drawn += 1;
+					if (tri.x0 <= tri.x1 && tri.y0 <= tri.y1)
+					{
+						const uint32_t n = (uint32_t)(tri.x1 - tri.x0 + 1) * (uint32_t)(tri.y1 - tri.y0 + 1);
+						large = n > a.smallLimit;
+						if (!large)
+						{
+							const uint32_t id = index << 7 | t;
+							for (int32_t py = tri.y0; py <= tri.y1; ++py)
+								for (int32_t px = tri.x0; px <= tri.x1; ++px)
+									samples += rd_sample(tri, px, py, a.width, a.depth, a.visibility, id) ? 1u : 0u;
+						}
+					}
+				}
+				const uint64_t q = __ballot(large);
+				if (large)
+				{
+					// the raw index bytes: the wave reruns rd_setup on them (same inputs, same bits)
+					const uint32_t at = queued + (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(q >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)q, 0u));
+					queue[at] = t | ia << 8 | ib << 16 | ic << 24;
+				}
+				queued += (uint32_t)__builtin_popcountll(q);
+			}
+			rd_lds_order();
+
+			// ---- large triangles, the whole wave: lane = pixel of an 8 x 8 stamp
+			for (uint32_t k = 0; k < queued; ++k)
+			{
+				const uint32_t e = queue[k];
+				RdTri tri;
+				rd_setup(vtx, e >> 8 & 0xffu, e >> 16 & 0xffu, e >> 24, ve, bothFaces, W, H, tri); // (true: it was queued)
+				const uint32_t id = index << 7 | (e & 0xffu);
+				const uint32_t sw = (uint32_t)(tri.x1 - tri.x0) / 8u + 1u, sh = (uint32_t)(tri.y1 - tri.y0) / 8u + 1u;
+				const int32_t lx = (int32_t)(lane & 7u), ly = (int32_t)(lane >> 3);
+				for (uint32_t sy = 0; sy < sh; ++sy)
+				{
+					const int32_t py = tri.y0 + (int32_t)sy * 8 + ly;
+					for (uint32_t sx = 0; sx < sw; ++sx)
+					{
+						const int32_t px = tri.x0 + (int32_t)sx * 8 + lx;
+						if (px <= tri.x1 && py <= tri.y1)
+							samples += rd_sample(tri, px, py, a.width, a.depth, a.visibility, id) ? 1u : 0u;
+					}
+				}
+			}
+		}
+	}
+
+	// totals: per-workgroup partial sums, plain stores; rasterdepth_totals_kernel adds them up
+	__shared__ unsigned long long s_tot[RD_WAVES][4];
+	unsigned long long d = drawn, smp = samples;
+	for (int o = 32; o > 0; o >>= 1)
+	{
+		d += __shfl_xor(d, o, 64);
+		smp += __shfl_xor(smp, o, 64);
+	}
+	if (lane == 0)
+	{
+		s_tot[wave][0] = clusters;
+		s_tot[wave][1] = triangles;
+		s_tot[wave][2] = d;
+		s_tot[wave][3] = smp;
+	}
+	__syncthreads();
+	if (threadIdx.x < 4)
+	{
+		unsigned long long t = 0;
+#pragma unroll
+		for (int k = 0; k < RD_WAVES; ++k)
+			t += s_tot[k][threadIdx.x];
+		a.partials[(size_t)blockIdx.x * 4 + threadIdx.x] = t;
+	}
+}
+
+// adds the per-workgroup partial sums of a launch to the caller's four totals (one workgroup)
+__global__ __launch_bounds__(256) void rasterdepth_totals_kernel(const unsigned long long* __restrict__ partials, uint32_t blocks,
+                                                                 unsigned long long* __restrict__ totals)
+{
+	__shared__ unsigned long long s_part[4][4];
+	unsigned long long t[4] = { 0, 0, 0, 0 };
+	for (uint32_t i = threadIdx.x; i < blocks; i += 256)
+#pragma unroll
+		for (int k = 0; k < 4; ++k)
+			t[k] += partials[(size_t)i * 4 + k];
+#pragma unroll
+	for (int k = 0; k < 4; ++k)
+		for (int o = 32; o > 0; o >>= 1)
+			t[k] += __shfl_xor(t[k], o, 64);
+	if ((threadIdx.x & 63u) == 0)
+		for (int k = 0; k < 4; ++k)
+			s_part[threadIdx.x >> 6][k] = t[k];
+	__syncthreads();
+	if (threadIdx.x < 4)
+		totals[threadIdx.x] += s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
+}
+
+int launch_rasterdepth(hipStream_t stream, const RasterArgs& a, uint32_t gridBlocks)
+{
+	gridBlocks = gridBlocks / 8 * RD_BLOCKS_PER_CU; // the caller passes 8 workgroups per CU, the size of `partials`
+	hipLaunchKernelGGL(rasterdepth_kernel, dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
+	hipError_t e = hipGetLastError();
+	if (e != hipSuccess || !a.totals)
+		return (int)e;
+	hipLaunchKernelGGL(rasterdepth_totals_kernel, dim3(1), dim3(256), 0, stream, a.partials, gridBlocks, a.totals);
+	return (int)hipGetLastError();
+}
+
+} // namespace nv

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import host
+from . import synth
 from . import layouts as L
 from ._lib import NvError, PyramidDesc, check, lib
 
@@ -43,6 +44,7 @@ NV_OPT_CULL_FORM = 5
 NV_OPT_CULL_RING = 6
 NV_OPT_TASK_EMIT = 7
 NV_OPT_DRAW_RECORDS = 8
+NV_OPT_RASTER_SMALL_LIMIT = 9
 
 
 class Context:
@@ -165,6 +167,13 @@ class Context:
         check(lib.nv_trianglecull(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(dcb), _ptr(db), _ptr(mlb), _ptr(meshlet_data), _ptr(vertices),
                                   _ptr(cib), _ptr(ccb), _ptr(masks), capacity, _ptr(totals3)), "nv_trianglecull")
 
+    def rasterdepth(self, globals_, dcb, db, mlb, meshlet_data, vertices, cib, ccb, depth, width, height, visibility=None, totals4=None):
+        """depth-only raster of the clusters in cib / ccb into `depth` (fp32 width x height, reverse-Z, atomic max: the caller clears it);
+        visibility (optional, width x height u64): max of bits(z) << 32 | slot << 7 | triangle; totals4 (optional, accumulated):
+        clusters, triangles, triangles rasterised, samples covered"""
+        check(lib.nv_rasterdepth(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(dcb), _ptr(db), _ptr(mlb), _ptr(meshlet_data), _ptr(vertices),
+                                 _ptr(cib), _ptr(ccb), _ptr(depth), int(width), int(height), _ptr(visibility), _ptr(totals4)), "nv_rasterdepth")
+
     def depthreduce(self, depth, width, height, pyramid):
         check(lib.nv_depthreduce(self.h, _stream(), _ptr(depth), width, height, C.byref(pyramid)), "nv_depthreduce")
 
@@ -200,7 +209,8 @@ class DepthPyramid:
 class VisibilityPipeline:
     """niagara's GPU-driven visibility front-end for one scene on one device."""
 
-    def __init__(self, meshes, meshlets, draws, depth_size, ctx=None, task_capacity=None, cluster_capacity=None, use_soa=True, fused=False):
+    def __init__(self, meshes, meshlets, draws, depth_size, ctx=None, task_capacity=None, cluster_capacity=None, use_soa=True, fused=False,
+                 meshlet_data=None, vertices=None):
         self.ctx = ctx or Context()
         # fused=True: the passes absorb the count-word resets and the tasksubmit / clustersubmit fix-ups (same buffer
         # contents, four launches less per phase); fused=False issues the reference's dispatch sequence one to one
@@ -242,6 +252,12 @@ class VisibilityPipeline:
             self.ctx.upload_meshlets(self.mlb, self.meshlet_count)
         if use_soa and self.draw_count:
             self.ctx.upload_draws(self.db, self.draw_count, self.mb)
+        # geometry (meshlet payloads + vertices, src/scene.cpp:24-47): with it the pipeline rasterises its own depth target
+        self.mdb = self.vb = self.depth = None
+        if meshlet_data is not None and vertices is not None:
+            self.mdb = to_device(meshlet_data, dev) if len(meshlet_data) else torch.zeros(4, dtype=torch.uint8, device=dev)
+            self.vb = to_device(vertices, dev) if len(vertices) else torch.zeros(L.VERTEX.itemsize, dtype=torch.uint8, device=dev)
+            self.depth = torch.zeros((self.depth_h, self.depth_w), dtype=torch.float32, device=dev)
 
     # src/niagara.cpp:1530-1574
     def cull(self, cull_data, late, task=True, post_pass=0):
@@ -267,6 +283,33 @@ class VisibilityPipeline:
     # src/niagara.cpp:1703-1733
     def build_pyramid(self, depth):
         self.ctx.depthreduce(depth, self.depth_w, self.depth_h, self.pyramid.desc)
+
+    def render_depth(self, cull_data, late, post_pass=0, visibility=None, totals4=None):
+        """the raster of render() (src/niagara.cpp:1582-1611): the clusters of the last render_clusters into self.depth.  The early pass
+        clears the target first (LOAD_OP_CLEAR, depthClear = 0), the late and post passes load it"""
+        if self.depth is None:
+            raise NvError("render_depth needs the scene's geometry: VisibilityPipeline(..., meshlet_data=, vertices=)")
+        if not late:
+            self.depth.zero_()
+        pass_data = cull_data.copy()
+        pass_data["postPass"] = post_pass
+        g = synth.make_globals(pass_data, (self.depth_w, self.depth_h))
+        self.ctx.rasterdepth(g, self.dcb, self.db, self.mlb, self.mdb, self.vb, self.cib, self.ccb, self.depth, self.depth_w, self.depth_h,
+                             visibility, totals4)
+
+    def frame(self, cull_data, post_pass=False, on_phase=None):
+        """one frame of src/niagara.cpp:1765-1788 with the raster in place of the graphics passes: early cull -> clusters -> raster ->
+        pyramid -> late cull -> clusters -> raster (-> post cull -> clusters -> raster).  on_phase(name) is called after each phase's
+        raster ("early", "late", "post")"""
+        phases = [("early", False, 0), ("late", True, 0)] + ([("post", True, 1)] if post_pass else [])
+        for name, late, pp in phases:
+            if name == "late":
+                self.build_pyramid(self.depth)
+            self.cull(cull_data, late=late, task=True, post_pass=pp)
+            self.render_clusters(cull_data, late=late, post_pass=pp)
+            self.render_depth(cull_data, late=late, post_pass=pp)
+            if on_phase is not None:
+                on_phase(name)
 
     def visible_clusters(self):
         n = int(self.ccb[0].item())

@@ -156,3 +156,119 @@ def make_geometry(meshlets, seed=5, vertices_per_mesh=4096):
     meshlets["baseVertex"] = base
     meshlets["shortRefs"] = short
     return data, vertices
+
+
+def _grid_meshlets(nx, ny, block):
+    """a plane of nx x ny quads over [-1, 1]^2 at z = 0, facing +z (counter-clockwise seen from +z), cut into meshlets of block x block
+    quads: ((block + 1)^2 <= 64 vertices, 2 block^2 <= 96 triangles).  Returns (positions (n, 3), [(vertex ids, triangles (t, 3) local)])"""
+    xs, ys = np.linspace(-1, 1, nx + 1, dtype=np.float32), np.linspace(-1, 1, ny + 1, dtype=np.float32)
+    vid = lambda i, j: j * (nx + 1) + i
+    pos = np.array([(xs[i], ys[j], 0.0) for j in range(ny + 1) for i in range(nx + 1)], np.float32)
+    out = []
+    for bj in range(0, ny, block):
+        for bi in range(0, nx, block):
+            tris = []
+            for j in range(bj, min(bj + block, ny)):
+                for i in range(bi, min(bi + block, nx)):
+                    a, b, c, d = vid(i, j), vid(i + 1, j), vid(i + 1, j + 1), vid(i, j + 1)
+                    tris += [(a, b, c), (a, c, d)]
+            out.append(tris)
+    return pos, out
+
+
+def _box_faces(n):
+    """a closed cube [-1, 1]^3, every face n x n quads, outward faces counter-clockwise: (positions, [triangles]) as one meshlet"""
+    pos, (tris,) = _grid_meshlets(n, n, n)
+    faces = [np.eye(3, dtype=np.float32)[[0, 1, 2]],  # +z: x, y, normal
+             np.array([[-1, 0, 0], [0, 1, 0], [0, 0, -1]], np.float32),  # -z
+             np.array([[0, 0, -1], [0, 1, 0], [1, 0, 0]], np.float32),   # +x
+             np.array([[0, 0, 1], [0, 1, 0], [-1, 0, 0]], np.float32),   # -x
+             np.array([[1, 0, 0], [0, 0, -1], [0, 1, 0]], np.float32),   # +y
+             np.array([[1, 0, 0], [0, 0, 1], [0, -1, 0]], np.float32)]   # -y
+    allpos, alltris = [], []
+    for k, m in enumerate(faces):
+        p = pos[:, :1] * m[0] + pos[:, 1:2] * m[1] + m[2]  # u, v in the face plane, pushed out along its normal
+        alltris += [(a + k * len(pos), b + k * len(pos), c + k * len(pos)) for a, b, c in tris]
+        allpos.append(p)
+    return np.concatenate(allpos).astype(np.float32), [alltris]
+
+
+def occluder_scene(viewport=(320, 192), wall_distance=20.0, wall_half=12.0, hidden=8, beside=4, box_scale=1.0, hidden_spread=4.0,
+                   seed=6, meshlet_bounds=None):
+    """A controlled scene with real surfaces for the closed occlusion loop: a wall (a tessellated grid, 24 x 24 quads in meshlets of
+    6 x 6) facing the camera at `wall_distance`, `hidden` closed boxes behind it within +-`hidden_spread` of its centre line (their
+    HiZ footprints lie well inside the wall) and `beside` boxes to its left and right that it does not cover.  The camera is
+    niagara's default (origin, looking down -z).  Meshlet bounds are the library's algorithm: `meshlet_bounds(vertices, data, meshlets)`
+    fills them in place (oracle.meshlet_bounds), or, when None, Context.meshlet_bounds on the current device.
+    Returns a dict of meshes, meshlets, draws, meshlet data, vertices, cull data, viewport and the draw ids of each group."""
+    rng = np.random.default_rng(seed)
+    wall_pos, wall_tris = _grid_meshlets(24, 24, 6)
+    box_pos, box_tris = _box_faces(2)
+    meshes = np.zeros(2, dtype=L.MESH)
+    meshlet_list, words, vertices = [], [], []
+    vbase = 0
+    for mi, (pos, groups, short) in enumerate(((wall_pos, wall_tris, 0), (box_pos, box_tris, 1))):
+        h = pos.astype(np.float16)
+        v = np.zeros(len(pos), dtype=L.VERTEX)
+        v["vx"], v["vy"], v["vz"] = (h[:, k].view(np.uint16) for k in range(3))
+        vertices.append(v)
+        center, radius = host.mesh_bounds(h.astype(np.float32))
+        meshes[mi]["center"], meshes[mi]["radius"] = center, radius
+        meshes[mi]["vertexOffset"], meshes[mi]["vertexCount"] = vbase, len(pos)
+        meshes[mi]["lodCount"] = 1
+        lod = meshes[mi]["lods"][0]
+        lod["meshletOffset"], lod["meshletCount"], lod["indexCount"] = len(meshlet_list), len(groups), 3 * sum(len(g) for g in groups)
+        for tris in groups:
+            t = np.asarray(tris, np.uint32)
+            used = np.unique(t)
+            local = np.searchsorted(used, t).astype(np.uint8)
+            assert len(used) <= 64 and len(t) <= 96
+            m = np.zeros(1, dtype=L.MESHLET)
+            m["dataOffset"] = sum(len(w) for w in words)
+            m["baseVertex"] = vbase
+            m["vertexCount"], m["triangleCount"], m["shortRefs"] = len(used), len(t), short
+            refs = used.astype(np.uint16 if short else np.uint32)
+            if short and len(refs) % 2:
+                refs = np.append(refs, np.uint16(0))
+            idx = local.reshape(-1)
+            idx = np.append(idx, np.zeros((-len(idx)) % 4, np.uint8))
+            words.append(np.concatenate([refs.view(np.uint32), idx.view(np.uint32)]))
+            meshlet_list.append(m)
+        vbase += len(pos)
+    meshlets = np.concatenate(meshlet_list)
+    data = np.concatenate(words + [np.zeros(4, np.uint32)]).astype(np.uint32)
+    vertices = np.concatenate(vertices)
+    if meshlet_bounds is None:
+        from . import pipeline as P
+        import torch
+        ctx = P.Context()
+        try:
+            mlb = P.to_device(meshlets, ctx.device)
+            ctx.meshlet_bounds(P.to_device(vertices, ctx.device), P.to_device(data, ctx.device), mlb, len(meshlets))
+            ctx.status()
+            meshlets = P.from_device(mlb, L.MESHLET).copy()
+        finally:
+            ctx.close()
+        del torch
+    else:
+        meshlet_bounds(vertices, data, meshlets)
+
+    n = 1 + hidden + beside
+    draws = np.zeros(n, dtype=L.MESHDRAW)
+    draws["orientation"] = (0.0, 0.0, 0.0, 1.0)
+    draws[0]["position"], draws[0]["scale"], draws[0]["meshIndex"] = (0.0, 0.0, -wall_distance), wall_half, 0
+    for i in range(1, n):
+        draws[i]["meshIndex"], draws[i]["scale"] = 1, box_scale
+        d = rng.uniform(1.5, 2.0) * wall_distance
+        if i <= hidden:
+            x, y = rng.uniform(-hidden_spread, hidden_spread, 2)
+        else:
+            side = 1.0 if (i - hidden) % 2 else -1.0
+            x, y = side * rng.uniform(1.3, 1.6) * wall_half * d / wall_distance, rng.uniform(-hidden_spread, hidden_spread)
+        draws[i]["position"] = (x, y, -d)
+    slots, _ = host.assign_visibility_offsets(draws, meshes)
+    pw, ph = host.previous_pow2(viewport[0]), host.previous_pow2(viewport[1])
+    cd = host.build_cull_data(viewport=viewport, pyramid=(pw, ph), draw_count=n, cullingEnabled=1, lodEnabled=1, occlusionEnabled=1,
+                              clusterOcclusionEnabled=1, clusterBackfaceEnabled=1)
+    return dict(meshes=meshes, meshlets=meshlets, draws=draws, data=data, vertices=vertices, cull=cd, viewport=viewport, slots=slots,
+                wall=[0], hidden=list(range(1, 1 + hidden)), beside=list(range(1 + hidden, n)))
