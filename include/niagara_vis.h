@@ -267,7 +267,8 @@ int nv_set_option(nv_context* ctx, int option, int value);
  * HIP graph (stream capture) with growing arguments.  nv_create sizes the library's scratch for 1 M draws and
  * NV_TASK_WGLIMIT task commands (the size niagara allocates dcb for, src/niagara.cpp:1070); nv_reserve raises the
  * per-draw scratch to maxDraws before the first pass over that many (it may synchronise the device: call it at scene
- * load, next to createBuffer(dvb), src/niagara.cpp:1060).  nv_drawcull over more draws than were reserved returns
+ * load, next to createBuffer(dvb), src/niagara.cpp:1060); per draw that is about 17 B for nv_drawcull and 4 B for nv_rasterdepth_indexed (+ 20 KiB
+ * fixed).  nv_drawcull or nv_rasterdepth_indexed over more draws than were reserved returns
  * NV_ENOMEM and enqueues nothing.  maxCommands is accepted for symmetry; values above NV_TASK_WGLIMIT buy nothing (the
  * passes clamp there like the shaders do). */
 int nv_reserve(nv_context* ctx, uint32_t maxDraws, uint32_t maxCommands);
@@ -438,6 +439,27 @@ int nv_rasterdepth(nv_context* ctx, void* stream, const NvGlobals* globals, cons
                    const NvVertex* d_vertices, const uint32_t* d_clusterIndices, const uint32_t* d_clusterCount4,
                    float* d_depth, uint32_t width, uint32_t height,
                    uint64_t* d_visibility /* optional, width*height */, uint64_t* d_totals4 /* optional */);
+
+/* ---- depth-only raster of the indexed draws ----
+ * The classic branch of niagara's render() (src/niagara.cpp:1680-1694: vkCmdDrawIndexedIndirectCount(dcb, dccb, maxDrawCount) through
+ * mesh.vert.glsl:39-63) on a part without a graphics pipeline: the MeshDrawCommands nv_drawcull(task = 0) writes (drawcull.comp.glsl:141-151).
+ * Commands i < min(d_count[0], drawCount) are read on the device, like the indirect count; command i is skipped when its instanceCount is 0
+ * or its drawId >= drawCount (instanceCount > 1 writes the same depth as 1; firstInstance is not read).  Its triangle t < indexCount / 3
+ * (remainder indices are ignored) has the corners d_indices[firstIndex + 3t + k] + vertexOffset (mod 2^32, the index arithmetic in 64 bits)
+ * under the transform d_draws[drawId]; the triangle is skipped, and not counted as rasterised, when an index position is >= indexCapacity or
+ * a corner is >= vertexCapacity (0xFFFFFFFF included: there is no primitive restart), so every load stays inside the caller's buffers.
+ * Everything else is nv_rasterdepth's rule set, unchanged — the vertex stage, the snap, the near-plane / non-finite / guard-band rejection,
+ * facing by globals->cullData.postPass, top-left coverage, the fixed-order fp32 depth and the atomic max — so the same triangle under the same
+ * draw writes the same bits through either entry point.  No visibility buffer (a 32-bit ID cannot name both a draw and a triangle).
+ * d_totals4 (optional, accumulated: zero it first): commands drawn, triangles (sum of their indexCount / 3), triangles rasterised, samples
+ * covered.  d_draws holds drawCount records and d_commands up to drawCount commands; a zero capacity is allowed (nothing is read then).
+ * Scratch: 4 B per command slot (drawCount) + 20 KiB, sized by nv_create for 1 M and by nv_reserve(maxDraws); a larger drawCount returns
+ * NV_ENOMEM.  width and height must equal globals->screenWidth / screenHeight and lie in 1 .. 16384. */
+int nv_rasterdepth_indexed(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshDrawCommand* d_commands,
+                           const uint32_t* d_count /* dccb: word 0 */, const NvMeshDraw* d_draws,
+                           uint32_t drawCount /* = maxDrawCount, src/niagara.cpp:1693 */, const uint32_t* d_indices, uint32_t indexCapacity,
+                           const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width, uint32_t height,
+                           uint64_t* d_totals4 /* optional */);
 
 /* depthreduce.comp.glsl:14-22 + the level loop at src/niagara.cpp:1703-1733.
  * d_depth is the width x height fp32 depth target (reverse-Z, far = 0). */

@@ -71,6 +71,7 @@ _SIGS = {
     "nv_cluster_expand": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "nv_trianglecull": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "nv_rasterdepth": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "nv_rasterdepth_indexed": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp]),
     "nv_depthreduce": (_i, [_vp, _vp, _vp, _u32, _u32, C.POINTER(PyramidDesc)]),
     "nv_previous_pow2": (_u32, [_u32]),
     "nv_division_magic": (_u32, [_u32]),

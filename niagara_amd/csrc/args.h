@@ -246,4 +246,29 @@ struct RasterArgs
 	unsigned long long* __restrict__ partials; // library scratch: 4 counters per workgroup of the launch
 };
 
+// nv_rasterdepth_indexed (rasterindexed.hip)
+struct RasterIndexedArgs
+{
+	NvGlobals globals;
+	const NvMeshDrawCommand* __restrict__ commands;
+	const uint32_t* __restrict__ count; // dccb word 0
+	const NvMeshDraw* __restrict__ draws;
+	uint32_t drawCount;                 // maxDrawCount: commands [0, min(count, drawCount)), transforms [0, drawCount)
+	const uint32_t* __restrict__ indices;
+	uint32_t indexCapacity;
+	const NvVertex* __restrict__ vertices;
+	uint32_t vertexCapacity;
+	uint32_t* depth;                    // fp32 bits, width x height (atomic max)
+	uint32_t width, height;
+	uint32_t smallLimit;                // NV_OPT_RASTER_SMALL_LIMIT
+	// library scratch (context.hip, nv_reserve): per command the end of its chunks within its count workgroup's range, per count workgroup its
+	// chunk sum (the exclusive prefix after the scan launch; [scanBlocks] = the total) and {commands drawn, triangles}
+	uint32_t* __restrict__ chunkEnds;
+	uint32_t* __restrict__ blockChunks;
+	unsigned long long* __restrict__ blockTotals;
+	uint32_t scanBlocks, perBlock;      // workgroups of the count launch, commands per workgroup
+	unsigned long long* __restrict__ totals;   // optional
+	unsigned long long* __restrict__ partials; // library scratch: 4 counters per workgroup of the raster launch
+};
+
 } // namespace nv

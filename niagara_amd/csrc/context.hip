@@ -46,6 +46,8 @@ int launch_pack_counts(hipStream_t, const uint32_t*, const uint32_t*, const uint
 int launch_depthreduce(hipStream_t, const float* depth, uint32_t w, uint32_t h, const NvPyramidDesc& pyr);
 int launch_trianglecull(hipStream_t, const TriangleArgs& a, uint32_t gridBlocks);
 int launch_rasterdepth(hipStream_t, const RasterArgs& a, uint32_t gridBlocks);
+int launch_rasterindexed(hipStream_t, RasterIndexedArgs a, void* scratch, uint32_t gridBlocks);
+size_t rasterindexed_scratch_bytes(uint32_t drawCount);
 int launch_meshlet_bounds(hipStream_t, const NvVertex* vertices, const uint32_t* data, NvMeshlet* meshlets, uint32_t count, float* out8, uint32_t gridBlocks);
 
 } // namespace nv
@@ -96,7 +98,10 @@ struct nv_context
 	uint8_t* drawResults;
 	size_t drawResultsCapacity;
 	nv::ClusterCounts* drawTileCounts;
-	unsigned long long* totalsPartials; // nv_trianglecull / nv_cluster_expand / nv_rasterdepth: per-workgroup partial totals (up to 4 x u64 x grid)
+	unsigned long long* totalsPartials; // nv_trianglecull / nv_cluster_expand / nv_rasterdepth(_indexed): per-workgroup partial totals (up to 4 x u64 x grid)
+	// nv_rasterdepth_indexed: per-command chunk prefixes + the count launch's per-workgroup sums (rasterindexed.hip), sized like drawResults
+	void* rasterScratch;
+	uint32_t rasterScratchDraws;
 	nv_scene* scene; // mirrors + registrations (shared between contexts by nv_share_scene)
 	// launch shape of the cull kernel (workgroups per CU) and the dealing's start-delay compensation in percent; constants
 	// in the product, environment-tunable (with the NV_DEBUG_MODE bit mask) only in the NV_EXPERIMENTS build
@@ -271,6 +276,28 @@ int reserve_draw_results(nv_context* ctx, uint32_t drawCount)
 	return NV_OK;
 }
 
+// nv_rasterdepth_indexed's scratch: one word per command slot (maxDrawCount) and a fixed part; sized by nv_create and nv_reserve only, like
+// the result bytes above
+int reserve_raster_scratch(nv_context* ctx, uint32_t drawCount)
+{
+	if (ctx->rasterScratch && drawCount <= ctx->rasterScratchDraws)
+		return NV_OK;
+	hipError_t e = hipDeviceSynchronize(); // a raster still in flight on any stream may be reading the old scratch
+	if (e != hipSuccess)
+		return (int)e;
+	if (ctx->rasterScratch)
+		scratch_free(ctx->rasterScratch);
+	ctx->rasterScratch = nullptr;
+	ctx->rasterScratchDraws = 0;
+	const uint32_t cap = drawCount < (1u << 20) ? (1u << 20) : drawCount;
+	char* p = nullptr;
+	if (scratch_alloc(&p, nv::rasterindexed_scratch_bytes(cap)) != hipSuccess)
+		return NV_ENOMEM;
+	ctx->rasterScratch = p;
+	ctx->rasterScratchDraws = cap;
+	return NV_OK;
+}
+
 nv_scene* scene_new(int device)
 {
 	nv_scene* sc = new (std::nothrow) nv_scene();
@@ -430,6 +457,7 @@ int nv_create(nv_context** out_ctx, int device)
 	    hipMemset(ctx->tileCounts, 0, sizeof(nv::ClusterCounts)) != hipSuccess ||
 	    scratch_alloc(&ctx->drawTileCounts, sizeof(nv::ClusterCounts)) != hipSuccess ||
 	    hipMemset(ctx->drawTileCounts, 0, sizeof(nv::ClusterCounts)) != hipSuccess || reserve_draw_results(ctx, 1u << 20) != NV_OK ||
+	    reserve_raster_scratch(ctx, 1u << 20) != NV_OK ||
 	    scratch_alloc(&ctx->totalsPartials, (size_t)persistent_grid(ctx, 8) * 4 * sizeof(unsigned long long)) != hipSuccess)
 	{
 		nv_destroy(ctx);
@@ -469,6 +497,8 @@ void nv_destroy(nv_context* ctx)
 		scratch_free(ctx->drawTileCounts);
 	if (ctx->totalsPartials)
 		scratch_free(ctx->totalsPartials);
+	if (ctx->rasterScratch)
+		scratch_free(ctx->rasterScratch);
 	if (ctx->masks)
 		scratch_free(ctx->masks);
 	if (ctx->tileCounts)
@@ -551,7 +581,8 @@ int nv_reserve(nv_context* ctx, uint32_t maxDraws, uint32_t maxCommands)
 		return NV_EINVAL;
 	(void)maxCommands; // the per-command scratch (ballots, survivor lists) is sized for NV_TASK_WGLIMIT by nv_create: the passes never process more
 	DeviceGuard guard(ctx->device);
-	return reserve_draw_results(ctx, maxDraws);
+	const int rc = reserve_draw_results(ctx, maxDraws);
+	return rc ? rc : reserve_raster_scratch(ctx, maxDraws);
 }
 
 int nv_share_scene(nv_context* dst, nv_context* src)
@@ -1083,6 +1114,36 @@ int nv_rasterdepth(nv_context* ctx, void* stream, const NvGlobals* globals, cons
 	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
 	a.partials = ctx->totalsPartials;
 	return nv::launch_rasterdepth((hipStream_t)stream, a, persistent_grid(ctx, 8));
+}
+
+int nv_rasterdepth_indexed(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshDrawCommand* d_commands, const uint32_t* d_count,
+                           const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices, uint32_t indexCapacity,
+                           const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_totals4)
+{
+	if (!ctx || !globals || !d_commands || !d_count || !d_draws || !d_indices || !d_vertices || !d_depth || width == 0 || height == 0 ||
+	    width > 16384 || height > 16384 || globals->screenWidth != (float)width || globals->screenHeight != (float)height)
+		return NV_EINVAL;
+	if (drawCount > ctx->rasterScratchDraws)
+		return NV_ENOMEM; // nv_reserve(ctx, maxDraws, ...) first: a pass never allocates
+	DeviceGuard guard(ctx->device);
+	nv::RasterIndexedArgs a;
+	memset(&a, 0, sizeof(a));
+	a.globals = *globals;
+	a.commands = d_commands;
+	a.count = d_count;
+	a.draws = d_draws;
+	a.drawCount = drawCount;
+	a.indices = d_indices;
+	a.indexCapacity = indexCapacity;
+	a.vertices = d_vertices;
+	a.vertexCapacity = vertexCapacity;
+	a.depth = reinterpret_cast<uint32_t*>(d_depth);
+	a.width = width;
+	a.height = height;
+	a.smallLimit = ctx->rasterSmallLimit;
+	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
+	a.partials = ctx->totalsPartials;
+	return nv::launch_rasterindexed((hipStream_t)stream, a, ctx->rasterScratch, persistent_grid(ctx, 8));
 }
 
 int nv_meshlet_bounds(nv_context* ctx, void* stream, const NvVertex* d_vertices, const uint32_t* d_meshletData, NvMeshlet* d_meshlets, uint32_t meshletCount,

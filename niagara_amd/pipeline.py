@@ -174,6 +174,15 @@ class Context:
         check(lib.nv_rasterdepth(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(dcb), _ptr(db), _ptr(mlb), _ptr(meshlet_data), _ptr(vertices),
                                  _ptr(cib), _ptr(ccb), _ptr(depth), int(width), int(height), _ptr(visibility), _ptr(totals4)), "nv_rasterdepth")
 
+    def rasterdepth_indexed(self, globals_, dcb, dccb, db, draw_count, ib, index_capacity, vertices, vertex_capacity, depth, width, height,
+                            totals4=None):
+        """depth-only raster of the indexed draws dcb[0, min(dccb[0], draw_count)) (vkCmdDrawIndexedIndirectCount with maxDrawCount = draw_count)
+        into `depth` (fp32 width x height, reverse-Z, atomic max: the caller clears it); ib holds index_capacity u32 indices, vertices
+        vertex_capacity records; totals4 (optional, accumulated): commands drawn, triangles, triangles rasterised, samples covered"""
+        check(lib.nv_rasterdepth_indexed(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(dcb), _ptr(dccb), _ptr(db), int(draw_count), _ptr(ib),
+                                         int(index_capacity), _ptr(vertices), int(vertex_capacity), _ptr(depth), int(width), int(height), _ptr(totals4)),
+              "nv_rasterdepth_indexed")
+
     def depthreduce(self, depth, width, height, pyramid):
         check(lib.nv_depthreduce(self.h, _stream(), _ptr(depth), width, height, C.byref(pyramid)), "nv_depthreduce")
 
@@ -210,7 +219,7 @@ class VisibilityPipeline:
     """niagara's GPU-driven visibility front-end for one scene on one device."""
 
     def __init__(self, meshes, meshlets, draws, depth_size, ctx=None, task_capacity=None, cluster_capacity=None, use_soa=True, fused=False,
-                 meshlet_data=None, vertices=None):
+                 meshlet_data=None, vertices=None, indices=None):
         self.ctx = ctx or Context()
         # fused=True: the passes absorb the count-word resets and the tasksubmit / clustersubmit fix-ups (same buffer
         # contents, four launches less per phase); fused=False issues the reference's dispatch sequence one to one
@@ -240,7 +249,12 @@ class VisibilityPipeline:
         if tcap < min(worst_tasks, L.TASK_WGLIMIT) or ccap < min(worst_meshlets, L.CLUSTER_LIMIT):
             raise NvError("task_capacity %d / cluster_capacity %d cannot hold what this scene can emit (%d task commands, %d meshlets): the passes "
                           "drop output only at the reference's limits, never at a smaller buffer's end" % (tcap, ccap, worst_tasks, worst_meshlets))
-        self.dcb = torch.zeros(tcap * L.TASKCMD.itemsize + 64 * L.TASKCMD.itemsize, dtype=torch.uint8, device=dev)
+        dcb_bytes = tcap * L.TASKCMD.itemsize + 64 * L.TASKCMD.itemsize
+        if indices is not None:  # the classic path (frame(task=False)) also writes one MeshDrawCommand per draw into dcb
+            dcb_bytes = max(dcb_bytes, max(1, self.draw_count) * L.DRAWCMD.itemsize)
+            whole = L.TASKCMD.itemsize * L.DRAWCMD.itemsize  # a whole number of records of either kind (from_device views it as both)
+            dcb_bytes = (dcb_bytes + whole - 1) // whole * whole
+        self.dcb = torch.zeros(dcb_bytes, dtype=torch.uint8, device=dev)
         self.dccb = torch.zeros(4, dtype=torch.int32, device=dev)
         self.cib = torch.zeros(ccap + 256, dtype=torch.int32, device=dev)
         self.ccb = torch.zeros(4, dtype=torch.int32, device=dev)
@@ -252,12 +266,20 @@ class VisibilityPipeline:
             self.ctx.upload_meshlets(self.mlb, self.meshlet_count)
         if use_soa and self.draw_count:
             self.ctx.upload_draws(self.db, self.draw_count, self.mb)
-        # geometry (meshlet payloads + vertices, src/scene.cpp:24-47): with it the pipeline rasterises its own depth target
-        self.mdb = self.vb = self.depth = None
-        if meshlet_data is not None and vertices is not None:
-            self.mdb = to_device(meshlet_data, dev) if len(meshlet_data) else torch.zeros(4, dtype=torch.uint8, device=dev)
+        # geometry (meshlet payloads and / or the index buffer ib, + vertices, src/scene.cpp:24-47): with it the pipeline rasterises its own
+        # depth target, through the clusters (meshlet_data) or through the indexed draws of the classic path (indices)
+        self.mdb = self.vb = self.ib = self.depth = None
+        self.index_count = self.vertex_count = 0
+        if vertices is not None and (meshlet_data is not None or indices is not None):
             self.vb = to_device(vertices, dev) if len(vertices) else torch.zeros(L.VERTEX.itemsize, dtype=torch.uint8, device=dev)
+            self.vertex_count = len(vertices)
             self.depth = torch.zeros((self.depth_h, self.depth_w), dtype=torch.float32, device=dev)
+            if meshlet_data is not None:
+                self.mdb = to_device(meshlet_data, dev) if len(meshlet_data) else torch.zeros(4, dtype=torch.uint8, device=dev)
+            if indices is not None:
+                ind = np.ascontiguousarray(indices, np.uint32)
+                self.ib = to_device(ind, dev) if len(ind) else torch.zeros(4, dtype=torch.uint8, device=dev)
+                self.index_count = len(ind)
 
     # src/niagara.cpp:1530-1574
     def cull(self, cull_data, late, task=True, post_pass=0):
@@ -287,7 +309,7 @@ class VisibilityPipeline:
     def render_depth(self, cull_data, late, post_pass=0, visibility=None, totals4=None):
         """the raster of render() (src/niagara.cpp:1582-1611): the clusters of the last render_clusters into self.depth.  The early pass
         clears the target first (LOAD_OP_CLEAR, depthClear = 0), the late and post passes load it"""
-        if self.depth is None:
+        if self.mdb is None:
             raise NvError("render_depth needs the scene's geometry: VisibilityPipeline(..., meshlet_data=, vertices=)")
         if not late:
             self.depth.zero_()
@@ -297,17 +319,37 @@ class VisibilityPipeline:
         self.ctx.rasterdepth(g, self.dcb, self.db, self.mlb, self.mdb, self.vb, self.cib, self.ccb, self.depth, self.depth_w, self.depth_h,
                              visibility, totals4)
 
-    def frame(self, cull_data, post_pass=False, on_phase=None):
+    def render_draws(self, cull_data, late, post_pass=0, totals4=None):
+        """the classic branch of render() (src/niagara.cpp:1680-1694): the MeshDrawCommands of the last cull(task=False) drawn from ib into
+        self.depth.  The early pass clears the target first, the late and post passes load it"""
+        if self.ib is None:
+            raise NvError("render_draws needs the index buffer: VisibilityPipeline(..., indices=, vertices=)")
+        if not late:
+            self.depth.zero_()
+        pass_data = cull_data.copy()
+        pass_data["postPass"] = post_pass
+        g = synth.make_globals(pass_data, (self.depth_w, self.depth_h))
+        self.ctx.rasterdepth_indexed(g, self.dcb, self.dccb, self.db, self.draw_count, self.ib, self.index_count, self.vb, self.vertex_count,
+                                     self.depth, self.depth_w, self.depth_h, totals4)
+
+    def frame(self, cull_data, post_pass=False, on_phase=None, task=True):
         """one frame of src/niagara.cpp:1765-1788 with the raster in place of the graphics passes: early cull -> clusters -> raster ->
-        pyramid -> late cull -> clusters -> raster (-> post cull -> clusters -> raster).  on_phase(name) is called after each phase's
-        raster ("early", "late", "post")"""
+        pyramid -> late cull -> clusters -> raster (-> post cull -> clusters -> raster).  task=False runs the classic path instead (no mesh
+        shading): every cull writes MeshDrawCommands, render_draws rasterises them, and clusterOcclusionEnabled is 0 (src/niagara.cpp:1516).
+        on_phase(name) is called after each phase's raster ("early", "late", "post")"""
+        if not task:
+            cull_data = cull_data.copy()
+            cull_data["clusterOcclusionEnabled"] = 0
         phases = [("early", False, 0), ("late", True, 0)] + ([("post", True, 1)] if post_pass else [])
         for name, late, pp in phases:
             if name == "late":
                 self.build_pyramid(self.depth)
-            self.cull(cull_data, late=late, task=True, post_pass=pp)
-            self.render_clusters(cull_data, late=late, post_pass=pp)
-            self.render_depth(cull_data, late=late, post_pass=pp)
+            self.cull(cull_data, late=late, task=task, post_pass=pp)
+            if task:
+                self.render_clusters(cull_data, late=late, post_pass=pp)
+                self.render_depth(cull_data, late=late, post_pass=pp)
+            else:
+                self.render_draws(cull_data, late=late, post_pass=pp)
             if on_phase is not None:
                 on_phase(name)
 

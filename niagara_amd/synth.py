@@ -272,3 +272,37 @@ def occluder_scene(viewport=(320, 192), wall_distance=20.0, wall_half=12.0, hidd
                               clusterOcclusionEnabled=1, clusterBackfaceEnabled=1)
     return dict(meshes=meshes, meshlets=meshlets, draws=draws, data=data, vertices=vertices, cull=cd, viewport=viewport, slots=slots,
                 wall=[0], hidden=list(range(1, 1 + hidden)), beside=list(range(1 + hidden, n)))
+
+
+def indexed_geometry(meshes, meshlets, data):
+    """The index buffer of niagara's classic path recovered from the meshlet payloads: every LOD's meshlets decoded in order into mesh-local
+    vertex ids (reference + baseVertex - the mesh's vertexOffset, as drawcull's MeshDrawCommand adds vertexOffset back) and laid back to back.
+    Triangles whose index byte is past min(vertexCount, 64) are left out (the cluster path skips them).  Returns (indices u32[], a copy of
+    `meshes` with each LOD's indexOffset / indexCount set)."""
+    meshes = meshes.copy()
+    d16, d8 = data.view(np.uint16), data.view(np.uint8)
+    out, at = [], 0
+    for mi in range(len(meshes)):
+        base = int(meshes[mi]["vertexOffset"])
+        for l in range(int(meshes[mi]["lodCount"])):
+            first, count = int(meshes["lods"]["meshletOffset"][mi, l]), int(meshes["lods"]["meshletCount"][mi, l])
+            for k in range(first, first + count):
+                m = meshlets[k]
+                vc, tc, off, short = int(m["vertexCount"]), min(int(m["triangleCount"]), 96), int(m["dataOffset"]), m["shortRefs"] == 1
+                refs = (d16[off * 2:off * 2 + vc] if short else data[off:off + vc]).astype(np.int64) + int(m["baseVertex"]) - base
+                io = (off + ((vc + 1) // 2 if short else vc)) * 4
+                idx = d8[io:io + 3 * tc].reshape(-1, 3).astype(np.int64)
+                out.append(refs[idx[(idx < min(vc, 64)).all(axis=1)]].reshape(-1))
+            n = sum(len(t) for t in out) - at
+            meshes["lods"]["indexOffset"][mi, l], meshes["lods"]["indexCount"][mi, l] = at, n
+            at += n
+    indices = np.concatenate(out).astype(np.uint32) if out else np.zeros(0, np.uint32)
+    return indices, meshes
+
+
+def occluder_scene_indexed(**kw):
+    """occluder_scene(**kw) for the classic path: the same scene plus its index buffer ("indices") and the meshes with their LODs' index
+    ranges set (indexed_geometry)"""
+    s = occluder_scene(**kw)
+    indices, meshes = indexed_geometry(s["meshes"], s["meshlets"], s["data"])
+    return dict(s, meshes=meshes, indices=indices)

@@ -2,8 +2,11 @@
 config_n4: every meshlet of a 2048-draw pool once, 1920 x 1080) at several NV_OPT_RASTER_SMALL_LIMIT values, by HIP events around each
 launch, with its totals and the split of the rasterised triangles between the lane and the wave path; and the closed-loop frame of
 synth.occluder_scene (VisibilityPipeline.frame) against the same frame reduced from synthetic depth (synth.make_depth).
+--only indexed: nv_rasterdepth_indexed on the kitten x 1024 draws at 1024 x 768, the same kitten geometry meshletised
+(tests/meshlet_builder.py) through nv_rasterdepth on the same context, one 120 k-triangle draw, and the classic closed-loop frame
+(VisibilityPipeline.frame(task=False)) on synth.occluder_scene_indexed.
 
-    python tools/bench_raster.py [--iters N] [--only raster|loop] [--limits 0,16,...]
+    python tools/bench_raster.py [--iters N] [--only raster|loop|indexed] [--limits 0,16,...]
 Kernel-trace times: rocprofv3 --kernel-trace --stats -d OUT -o raster -- python tools/bench_raster.py --only raster
 Prints one JSON object."""
 import argparse
@@ -165,10 +168,128 @@ def bench_loop(iters):
     return out
 
 
+def _time(fn, iters, reset=None):
+    """median / min microseconds per call by HIP events (reset() before each call, outside the events)"""
+    for _ in range(3):
+        if reset:
+            reset()
+        fn()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+    for e0, e1 in ev:
+        if reset:
+            reset()
+        e0.record()
+        fn()
+        e1.record()
+    torch.cuda.synchronize()
+    us = sorted(e0.elapsed_time(e1) * 1e3 for e0, e1 in ev)
+    return us[len(us) // 2], us[0]
+
+
+def _rates(med, tot):
+    return dict(us_median=med, triangles_per_s=tot[1] / (med * 1e-6), rasterised_per_s=tot[2] / (med * 1e-6), samples_per_s=tot[3] / (med * 1e-6),
+                totals=dict(first=tot[0], triangles=tot[1], rasterised=tot[2], samples=tot[3]))
+
+
+def bench_indexed(iters):
+    import meshlet_builder
+    import raster_indexed_ref as RI
+    ctx = P.Context()
+    dev = ctx.device
+    out = {}
+    # kitten x 1024 (BASELINE config 1's draws), every draw one command
+    w, h = 1024, 768
+    vertices, indices, positions = RI.kitten_geometry()
+    n = 1024
+    draws = host.synth_draws(n, 1, 300.0)
+    cd = host.build_cull_data(draw_count=n, viewport=(w, h), cullingEnabled=1)
+    g = synth.make_globals(cd, (w, h))
+    cmds = RI.commands_for([(0, len(indices))] * n)
+    dcb, db, ib, vb = P.to_device(cmds, dev), P.to_device(draws, dev), P.to_device(indices, dev), P.to_device(vertices, dev)
+    dccb = P.to_device(np.array([n, 0, 0, 0], np.uint32), dev)
+    depth = torch.zeros((h, w), dtype=torch.float32, device=dev)
+    totals = torch.zeros(4, dtype=torch.int64, device=dev)
+
+    def indexed():
+        ctx.rasterdepth_indexed(g, dcb, dccb, db, n, ib, len(indices), vb, len(vertices), depth, w, h)
+
+    med, mn = _time(indexed, iters, depth.zero_)
+    depth.zero_()
+    ctx.rasterdepth_indexed(g, dcb, dccb, db, n, ib, len(indices), vb, len(vertices), depth, w, h, totals)
+    out["kitten_x1024"] = dict(_rates(med, [int(x) for x in totals.cpu().numpy()]), us_min=mn, viewport=[w, h])
+    d_indexed = depth.cpu().numpy().copy()
+    # the same triangles through the cluster path
+    meshlets, data, mvert = meshlet_builder.build_meshlets(positions, indices.reshape(-1, 3).astype(np.int64))
+    k = len(meshlets)
+    per = (k + 63) // 64
+    tc = np.zeros(n * per, dtype=L.TASKCMD)
+    ids = []
+    for d in range(n):
+        for c in range(per):
+            i = d * per + c
+            tc[i]["drawId"], tc[i]["taskOffset"], tc[i]["taskCount"] = d, c * 64, min(64, k - c * 64)
+            ids += [i | j << 24 for j in range(int(tc[i]["taskCount"]))]
+    cc4_h = np.array([len(ids), 0, 0, 0], np.uint32)
+    cib_h = np.concatenate([np.array(ids, np.uint32), np.zeros(512, np.uint32)])
+    oracle.clustersubmit(cc4_h, cib_h)
+    t = [P.to_device(a, dev) for a in (tc, draws, meshlets, data, mvert, cib_h, cc4_h)]
+
+    def cluster():
+        ctx.rasterdepth(g, *t, depth, w, h)
+
+    med, mn = _time(cluster, iters, depth.zero_)
+    depth.zero_()
+    totals.zero_()
+    ctx.rasterdepth(g, *t, depth, w, h, None, totals)
+    out["kitten_x1024_cluster_path"] = dict(_rates(med, [int(x) for x in totals.cpu().numpy()]), us_min=mn, meshlets_per_draw=k,
+                                            same_depth_bits=bool(depth.cpu().numpy().tobytes() == d_indexed.tobytes()))
+    # one 120 k-triangle draw (the balance case)
+    xs, ys = np.linspace(-6, 6, 301), np.linspace(-4, 4, 201)
+    pos = np.array([(x, y, 0.0) for y in ys for x in xs], np.float32)
+    i, j = np.meshgrid(np.arange(300), np.arange(200))
+    a = (j * 301 + i).reshape(-1)
+    big = np.stack([np.stack([a, a + 1, a + 302], 1), np.stack([a, a + 302, a + 301], 1)], 1).reshape(-1).astype(np.uint32)
+    bv = np.zeros(len(pos), dtype=L.VERTEX)
+    hp = pos.astype(np.float16)
+    bv["vx"], bv["vy"], bv["vz"] = (hp[:, c].view(np.uint16) for c in range(3))
+    bd = np.zeros(1, dtype=L.MESHDRAW)
+    bd["position"], bd["scale"], bd["orientation"] = (0.3, -0.2, -5.0), 1.0, (0, 0, 0, 1)
+    b_dcb, b_db, b_ib, b_vb = P.to_device(RI.commands_for([(0, len(big))]), dev), P.to_device(bd, dev), P.to_device(big, dev), P.to_device(bv, dev)
+    b_dccb = P.to_device(np.array([1, 0, 0, 0], np.uint32), dev)
+
+    def one():
+        ctx.rasterdepth_indexed(g, b_dcb, b_dccb, b_db, 1, b_ib, len(big), b_vb, len(bv), depth, w, h)
+
+    med, mn = _time(one, iters, depth.zero_)
+    depth.zero_()
+    totals.zero_()
+    ctx.rasterdepth_indexed(g, b_dcb, b_dccb, b_db, 1, b_ib, len(big), b_vb, len(bv), depth, w, h, totals)
+    out["one_draw_120k"] = dict(_rates(med, [int(x) for x in totals.cpu().numpy()]), us_min=mn)
+    ctx.close()
+    # the classic closed loop
+    s = synth.occluder_scene_indexed(meshlet_bounds=oracle.meshlet_bounds)
+    for task in (False, True):
+        pipe = P.VisibilityPipeline(s["meshes"], s["meshlets"], s["draws"], s["viewport"], task_capacity=4096, cluster_capacity=4096 * 64, fused=True,
+                                    meshlet_data=s["data"], vertices=s["vertices"], indices=s["indices"])
+        for _ in range(4):
+            pipe.frame(s["cull"], task=task)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            pipe.frame(s["cull"], task=task)
+        torch.cuda.synchronize()
+        us = (time.perf_counter() - t0) / iters * 1e6
+        dvb = pipe.dvb.cpu().numpy()
+        out["loop_classic" if not task else "loop_cluster"] = dict(frame_us=us, draws=len(s["draws"]), hidden_boxes_visible=int(dvb[s["hidden"]].sum()),
+                                                                   visible_draws=int(dvb.sum()))
+        pipe.ctx.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--only", choices=("raster", "loop"), default=None)
+    ap.add_argument("--only", choices=("raster", "loop", "indexed"), default=None)
     ap.add_argument("--limits", default="0,4,9,16,32,64,%d" % INT_MAX)
     ap.add_argument("--no-split", action="store_true")
     a = ap.parse_args()
@@ -179,6 +300,8 @@ def main():
         ctx.close()
     if a.only in (None, "loop"):
         res["loop"] = bench_loop(a.iters)
+    if a.only in (None, "indexed"):
+        res["indexed"] = bench_indexed(a.iters)
     print(json.dumps(res))
 
 
