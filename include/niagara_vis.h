@@ -294,6 +294,10 @@ int nv_share_scene(nv_context* dst, nv_context* src);
  * from — a pass that pairs new records with the old bounds is no longer conservative (only
  * the capacity-growth path synchronises the device by itself). */
 int nv_upload_meshlets(nv_context* ctx, void* stream, const NvMeshlet* d_meshlets, uint32_t meshletCount);
+/* Test-only accessor: copies the block table nv_upload_meshlets builds next to the mirror (one 16-B record per 64 meshlets of the
+ * mirror, the padding block included: {centre xyz as fp32, D | rho << 16 as fp16 bits}) to host memory, at most
+ * maxRecords of them; *out_records = the table's length (0 without a mirror).  Synchronises the device. */
+int nv_debug_block_table(nv_context* ctx, void* hostOut, uint32_t maxRecords, uint32_t* out_records);
 
 /* Upload hook next to uploadBuffer(mb) (src/niagara.cpp:1049): registers the Mesh table's pointer and size.  nv_drawcull
  * stages a registered table of <= 64 meshes in LDS (every draw reads its mesh's bounds, LOD errors and LOD range);

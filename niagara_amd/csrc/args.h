@@ -136,6 +136,8 @@ struct ClusterArgs
 	const uint2* __restrict__ soaBounds;
 	const uint32_t* __restrict__ soaCones;
 	const float* __restrict__ poolBounds; // {3 x the largest |centre component|, the largest |radius|} of the mirrored pool (nv_upload_meshlets); set whenever soaBounds is
+	const uint4* __restrict__ blockBounds; // one BlockRecord per 64 meshlets of the mirror (filtermath.h; nv_upload_meshlets); set whenever soaBounds is
+	uint32_t blockMeshlets;               // the mirrored meshlet count: a command whose range ends past it is not block-tested
 	uint32_t* __restrict__ mvb;
 	uint32_t* __restrict__ clusterIndices;
 	uint32_t* __restrict__ clusterCount4;

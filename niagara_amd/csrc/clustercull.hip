@@ -1213,6 +1213,7 @@ __global__ __launch_bounds__(CC_THREADS, 6) void cluster_mask_kernel(ClusterArgs
 		// behind them (counted), so the dependent chain is commands -> {draws, first bounds} instead of
 		// commands -> draws -> filters -> first bounds.
 		constexpr bool FOLD_A = !LATE; // (the late variants have no eight VGPRs to spare under the six-workgroup bound)
+		constexpr bool BLOCK = SOA && !LATE && !BITS && !DIRECT && !DEFER; // the filter form's block test (below gather_issue)
 		// (the folded rows evaluate cz f1 - |f0 cx| = cz f1 - |f0| |cx|, the reference cz f1 - |cx| f0: the same number only for f0, f2 >= 0.  A mirrored
 		// or flipped projection — a negative side-plane coefficient — therefore takes no filter at all in the folded variants: every valid command goes to pass B, whose
 		// certified test and reference arithmetic keep the coefficient's sign.  Written so that a NaN coefficient also fails it.)
@@ -1266,6 +1267,81 @@ __global__ __launch_bounds__(CC_THREADS, 6) void cluster_mask_kernel(ClusterArgs
 			if constexpr (PACK && !BITS)
 				packIncl = wave_scan_inclusive_u32(r.taskCount < 64u ? r.taskCount : 64u);
 			gather_issue();
+
+			// ---- the block test (BLOCK: the filter form of the early pass without visibility bits).  Each command's range touches one 64-meshlet
+			// block of the mirror (two when it is not aligned); the blocks' records (16 B each, filtermath.h block_record) come with the MeshDraw
+			// gather, and a command all of whose blocks are certainly outside one plane is finished here exactly as pass A would finish it — no
+			// candidate, ballot 0, not counted in passedFilter (block_outside implies certainly_outside<true> for every meshlet of the block).  The
+			// rest are moved to the front of the segment (lanes 0 .. cntA - 1, in order) and only they run pass A: the filter then reads 16-32 B per
+			// finished command instead of 512 B.  A command whose range ends past the mirror's meshlets is never finished here.
+			uint32_t cntA = cnt;          // pass A's commands: BLOCK, the ones the block test did not finish, moved to lanes 0 .. cntA - 1
+			bool kept = true;             // BLOCK: this lane's command is one of them
+			uint32_t keptRank = 0;        // its lane in the compacted segment
+			bool compacted = false;       // (uniform) the segment was permuted
+			if constexpr (BLOCK)
+			{
+				const bool inMirror = r.taskCount != 0u && r.taskOffset <= a.blockMeshlets && r.taskCount <= a.blockMeshlets - r.taskOffset;
+				const uint32_t blk0 = inMirror ? r.taskOffset >> 6 : 0u, blk1 = inMirror ? (r.taskOffset + r.taskCount - 1u) >> 6 : 0u;
+				u32x4 k0, k1;
+#ifdef NV_PLAIN_LOADS
+				k0 = reinterpret_cast<const u32x4*>(a.blockBounds)[blk0];
+				k1 = reinterpret_cast<const u32x4*>(a.blockBounds)[blk1];
+#else
+				asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %2, %4\n\tglobal_load_dwordx4 %1, %3, %4"
+				             : "=&v"(k0), "=&v"(k1)
+				             : "v"(blk0 * 16u), "v"(blk1 * 16u), "s"(a.blockBounds)
+				             : "memory");
+#endif
+				NV_COUNTED_WAIT("s_waitcnt vmcnt(%4) ; nv_ready %0 %1 %2 %3" : "+v"(g0), "+v"(g1), "+v"(k0), "+v"(k1) : "i"(0) : "memory"); // the gather and the blocks
+				gather_finish();
+				const float mz[3] = { r.f.m[6], r.f.m[7], r.f.m[8] };
+				const BlockPlanes planes = block_planes(r.fold, r.fold + 4, mz, a.cd.frustum[1], a.cd.frustum[3]);
+				const float thrBase = block_thr_base(r.f.tK, a.cd.znear, a.cd.zfar); // (tK = inf without the filter: nothing is finished)
+				const BlockRecord rec0 = { { __uint_as_float(k0.x), __uint_as_float(k0.y), __uint_as_float(k0.z) }, k0.w };
+				const BlockRecord rec1 = { { __uint_as_float(k1.x), __uint_as_float(k1.y), __uint_as_float(k1.z) }, k1.w };
+				const bool out0 = block_outside(r.fold, r.fold + 4, mz, r.f.b[2], planes, a.cd.frustum[1], a.cd.frustum[3], a.cd.znear, a.cd.zfar, r.f.scale, thrBase, rec0);
+				const bool out1 = block_outside(r.fold, r.fold + 4, mz, r.f.b[2], planes, a.cd.frustum[1], a.cd.frustum[3], a.cd.znear, a.cd.zfar, r.f.scale, thrBase, rec1);
+				kept = lane < cnt && myIdx < numCmds && r.taskCount != 0u && !(inMirror && out0 && out1);
+				const uint64_t keptM = __ballot(kept);
+				cntA = (uint32_t)__builtin_popcountll(keptM);
+				keptRank = __builtin_amdgcn_mbcnt_hi((uint32_t)(keptM >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)keptM, 0u));
+				compacted = keptM != (cntA >= 64u ? ~0ull : (1ull << cntA) - 1ull);
+				if (compacted)
+				{
+					// a permutation of the lanes: the kept commands to 0 .. cntA - 1, the others behind them (ds_permute_b32 pushes lane l's value to lane dst)
+					const int dst = (int)((kept ? keptRank : cntA + lane - keptRank) << 2);
+					auto push = [&](auto& v)
+					{
+						static_assert(sizeof(v) == 4, "one dword per lane");
+						int bits;
+						__builtin_memcpy(&bits, &v, 4);
+						bits = __builtin_amdgcn_ds_permute(dst, bits);
+						__builtin_memcpy(&v, &bits, 4);
+					};
+					push(r.drawId);
+					push(r.taskOffset);
+					push(r.taskCount);
+					push(r.lateDrawVisibility);
+					push(r.meshletVisibilityOffset);
+#pragma unroll
+					for (int i = 0; i < 9; ++i)
+						push(r.f.m[i]);
+#pragma unroll
+					for (int i = 0; i < 3; ++i)
+						push(r.f.b[i]);
+					push(r.f.aK);
+					push(r.f.bK);
+					push(r.f.aR);
+					push(r.f.tK);
+					push(r.f.scale);
+					push(r.f.coneK);
+#pragma unroll
+					for (int i = 0; i < 8; ++i)
+						push(r.fold[i]);
+				}
+				if (lane >= cntA) // empty commands behind the kept ones: pass A's loads for them re-read meshlet 0, their candidate masks are 0
+					r.taskCount = 0u;
+			}
 
 			// ---- pass A: stream the 8 bounds bytes of every command through the conservative frustum filter.
 			// Commands with no possible survivor are finished here (ballot 0); the rest are queued in candMask.
@@ -1409,16 +1485,19 @@ __global__ __launch_bounds__(CC_THREADS, 6) void cluster_mask_kernel(ClusterArgs
 				gather_finish();
 				candMask = __ballot(lane < cnt && myIdx < numCmds && r.taskCount != 0); // every valid command
 			}
-			else
+			else if (!BLOCK || cntA != 0u) // (BLOCK: a segment the block test finished entirely has no stream at all)
 			{
 				SlotA ring[CC_DA];
 #pragma unroll
 				for (int k = 0; k < CC_DA; ++k)
 					issueA(ring[k], k, (fullMask >> k & 1ull) != 0, 0); // lanes >= cnt hold an empty command (meshlet 0): redundant but unconditional, in-range loads
-				NV_COUNTED_WAIT("s_waitcnt vmcnt(%2) ; nv_ready %0 %1" : "+v"(g0), "+v"(g1) : "i"(CC_DA * (BITS_A ? 2 : 1)) : "memory"); // the gather
-				gather_finish();
+				if constexpr (!BLOCK) // (BLOCK: the gather has landed and the filters are derived, in front of the block test)
+				{
+					NV_COUNTED_WAIT("s_waitcnt vmcnt(%2) ; nv_ready %0 %1" : "+v"(g0), "+v"(g1) : "i"(CC_DA * (BITS_A ? 2 : 1)) : "memory"); // the gather
+					gather_finish();
+				}
 				NV_STAMP(2);
-				for (uint32_t i = 0; i < cnt; i += CC_DA)
+				for (uint32_t i = 0; i < cntA; i += CC_DA)
 				{
 					// The SIMD arbitrates oldest-first, which lets the oldest resident workgroup run ahead and leaves
 					// the youngest to finish alone at single-wave issue rate.  Rotating the priority, offset by the
@@ -1637,6 +1716,13 @@ __global__ __launch_bounds__(CC_THREADS, 6) void cluster_mask_kernel(ClusterArgs
 				for (int k = 0; k < DB; ++k)
 					ring_release(ring[k]);
 				}
+			}
+			if (BLOCK && compacted) // the ballots back to the commands' own lanes (ds_bpermute_b32 pulls from the kept command's compacted lane; the others: 0)
+			{
+				const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(keptRank << 2), (int)maskLo);
+				const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(keptRank << 2), (int)maskHi);
+				maskLo = kept ? lo : 0u;
+				maskHi = kept ? hi : 0u;
 			}
 		}
 		else
@@ -2962,6 +3048,19 @@ __global__ __launch_bounds__(256) void soa_split_kernel(const NvMeshlet* __restr
 	cones[i] = c;
 }
 
+// the block table (filtermath.h block_record): one thread per 64-meshlet block of the mirror, fp64, from the mirror's bounds; the blocks past
+// `count` (the padding block) hold no meshlet and never reject
+__global__ __launch_bounds__(256) void block_bounds_kernel(const uint2* __restrict__ bounds, uint32_t count, uint32_t blocks, uint4* __restrict__ out)
+{
+	const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+	if (b >= blocks)
+		return;
+	const uint32_t first = b * BLOCK_MESHLETS;
+	const uint32_t n = first < count ? (count - first < BLOCK_MESHLETS ? count - first : BLOCK_MESHLETS) : 0u;
+	const BlockRecord k = block_record(reinterpret_cast<const uint32_t*>(bounds + first), n);
+	out[b] = make_uint4(__float_as_uint(k.c[0]), __float_as_uint(k.c[1]), __float_as_uint(k.c[2]), k.dr);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // launchers (called from context.hip)
 
@@ -3160,9 +3259,12 @@ int launch_probe(hipStream_t stream, const ClusterArgs& a, bool soa, uint32_t gr
 }
 
 // poolWords: 2 x u32 scratch + 2 x float result (ClusterArgs::poolBounds points at the floats)
-int launch_soa_split(hipStream_t stream, const NvMeshlet* meshlets, uint32_t count, uint32_t padded, uint2* bounds, uint32_t* cones, uint32_t* poolWords)
+// blockTable: padded / 64 records (the block table, built from the mirror just written)
+int launch_soa_split(hipStream_t stream, const NvMeshlet* meshlets, uint32_t count, uint32_t padded, uint2* bounds, uint32_t* cones, uint32_t* poolWords, uint4* blockTable)
 {
 	hipLaunchKernelGGL(soa_split_kernel, dim3((padded + 255) / 256), dim3(256), 0, stream, meshlets, count, padded, bounds, cones);
+	const uint32_t nBlocks = padded / BLOCK_MESHLETS;
+	hipLaunchKernelGGL(block_bounds_kernel, dim3((nBlocks + 255) / 256), dim3(256), 0, stream, bounds, count, nBlocks, blockTable);
 	(void)hipMemsetAsync(poolWords, 0, 2 * sizeof(uint32_t), stream);
 	const uint32_t blocks = (count + 255) / 256 < 2048u ? ((count + 255) / 256 ? (count + 255) / 256 : 1u) : 2048u;
 	hipLaunchKernelGGL(pool_bounds_kernel, dim3(blocks), dim3(256), 0, stream, bounds, count, poolWords);

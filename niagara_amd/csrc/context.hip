@@ -33,7 +33,7 @@ size_t clustercull_list_bytes();
 uint32_t clustercull_list_stride();
 int launch_taskcull(hipStream_t, const ClusterArgs&, int late, bool soa, uint32_t gridBlocks);
 int launch_probe(hipStream_t, const ClusterArgs&, bool soa, uint32_t gridBlocks);
-int launch_soa_split(hipStream_t, const NvMeshlet*, uint32_t count, uint32_t padded, uint2* bounds, uint32_t* cones, uint32_t* poolWords);
+int launch_soa_split(hipStream_t, const NvMeshlet*, uint32_t count, uint32_t padded, uint2* bounds, uint32_t* cones, uint32_t* poolWords, uint4* blocks);
 int launch_drawcull(hipStream_t, const DrawArgs&, int late, int task);
 int launch_draw_split(hipStream_t, const NvMeshDraw*, const NvMesh*, uint32_t meshCount, uint32_t first, uint32_t count, float4* world, uint2* scaleMesh, uint32_t* postPass);
 size_t drawcull_result_bytes(uint32_t drawCount);
@@ -71,6 +71,7 @@ struct nv_scene
 	uint2* soaBounds;
 	uint32_t* soaCones;
 	uint32_t* poolWords; // 2 x u32 (largest |centre component| / |radius| as fp16 bits) + 2 x float {3 Vmax, Rmax}: clustercull.hip pool_bounds_kernel
+	uint4* blockBounds;  // one 16-B record per 64 meshlets of the mirror (soaCapacity / 64): filtermath.h block_record, clustercull.hip block_bounds_kernel
 	uint32_t soaCapacity;
 	// SoA mirror of the MeshDraw fields a draw decision reads (nv_upload_draws)
 	const NvMeshDraw* drawsFrom;
@@ -309,6 +310,7 @@ nv_scene* scene_new(int device)
 	sc->mirroredCount = 0;
 	sc->soaBounds = nullptr;
 	sc->soaCones = nullptr;
+	sc->blockBounds = nullptr;
 	sc->soaCapacity = 0;
 	sc->drawsFrom = nullptr;
 	sc->drawsMeshes = nullptr;
@@ -331,6 +333,8 @@ void scene_release(nv_scene* sc)
 		scratch_free(sc->soaBounds);
 	if (sc->soaCones)
 		scratch_free(sc->soaCones);
+	if (sc->blockBounds)
+		scratch_free(sc->blockBounds);
 	if (sc->poolWords)
 		scratch_free(sc->poolWords);
 	if (sc->soaWorld)
@@ -688,12 +692,16 @@ int nv_upload_meshlets(nv_context* ctx, void* stream, const NvMeshlet* d_meshlet
 			scratch_free(ctx->scene->soaBounds);
 		if (ctx->scene->soaCones)
 			scratch_free(ctx->scene->soaCones);
+		if (ctx->scene->blockBounds)
+			scratch_free(ctx->scene->blockBounds);
 		ctx->scene->soaBounds = nullptr;
 		ctx->scene->soaCones = nullptr;
+		ctx->scene->blockBounds = nullptr;
 		ctx->scene->soaCapacity = 0;
 		ctx->scene->mirroredFrom = nullptr;
 		if (scratch_alloc(&ctx->scene->soaBounds, (size_t)padded * sizeof(uint2)) != hipSuccess ||
-		    scratch_alloc(&ctx->scene->soaCones, (size_t)padded * sizeof(uint32_t)) != hipSuccess)
+		    scratch_alloc(&ctx->scene->soaCones, (size_t)padded * sizeof(uint32_t)) != hipSuccess ||
+		    scratch_alloc(&ctx->scene->blockBounds, (size_t)(padded / 64) * sizeof(uint4)) != hipSuccess)
 			return NV_ENOMEM;
 		ctx->scene->soaCapacity = padded;
 	}
@@ -702,12 +710,26 @@ int nv_upload_meshlets(nv_context* ctx, void* stream, const NvMeshlet* d_meshlet
 		ctx->scene->mirroredFrom = nullptr; // (no pool bounds: no SoA pass may name the old mirror either)
 		return NV_ENOMEM;
 	}
-	int rc = nv::launch_soa_split((hipStream_t)stream, d_meshlets, meshletCount, padded, ctx->scene->soaBounds, ctx->scene->soaCones, ctx->scene->poolWords);
+	int rc = nv::launch_soa_split((hipStream_t)stream, d_meshlets, meshletCount, padded, ctx->scene->soaBounds, ctx->scene->soaCones, ctx->scene->poolWords,
+	                              ctx->scene->blockBounds);
 	if (rc)
 		return rc;
 	ctx->scene->mirroredFrom = d_meshlets;
 	ctx->scene->mirroredCount = meshletCount;
 	return NV_OK;
+}
+
+int nv_debug_block_table(nv_context* ctx, void* hostOut, uint32_t maxRecords, uint32_t* out_records)
+{
+	if (!ctx || !out_records || (!hostOut && maxRecords))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	const uint32_t n = ctx->scene->mirroredFrom && ctx->scene->blockBounds ? (round_up(ctx->scene->mirroredCount, 64) + 64) / 64 : 0u;
+	*out_records = n;
+	hipError_t e = hipDeviceSynchronize();
+	if (e == hipSuccess && n && maxRecords)
+		e = hipMemcpy(hostOut, ctx->scene->blockBounds, (size_t)(n < maxRecords ? n : maxRecords) * sizeof(uint4), hipMemcpyDeviceToHost);
+	return (int)e;
 }
 
 int nv_upload_meshes(nv_context* ctx, void* stream, const NvMesh* d_meshes, uint32_t meshCount)
@@ -870,6 +892,8 @@ static int fill_cluster_args(nv_context* ctx, nv::ClusterArgs& a, const NvCullDa
 	a.soaBounds = soa ? ctx->scene->soaBounds : nullptr;
 	a.soaCones = soa ? ctx->scene->soaCones : nullptr;
 	a.poolBounds = soa ? reinterpret_cast<const float*>(ctx->scene->poolWords + 2) : nullptr;
+	a.blockBounds = soa ? ctx->scene->blockBounds : nullptr;
+	a.blockMeshlets = soa ? ctx->scene->mirroredCount : 0u;
 	a.mvb = d_meshletVisibility;
 	a.masks = ctx->masks;
 	a.candList = ctx->candList;

@@ -142,4 +142,157 @@ NV_FM FilterDraw filter_make(const float* V, float x, float y, float z, float w,
 	return f;
 }
 
+// ---- the 64-meshlet block bound (DESIGN.md §4.1 "block test")
+// nv_upload_meshlets keeps one record per 64-meshlet aligned range of the mirror (clustercull.hip block_bounds_kernel, built with block_record):
+// a centre C (fp32, inside the bounding box of the block's centres), D >= max_i ||v_i - C||_2 and rho >= max_i |r_i| (fp16 bits, rounded up), over
+// the decoded fp16 values of the block's meshlets.  A block with a non-finite centre or radius, or without meshlets, has D = rho = inf: the test
+// below never says "outside" for it.  block_outside is the filter form's test of a command against the blocks its range touches, evaluated on the
+// SAME fp32 values the filter loop uses for the draw (the folded side rows of SegmentRegs::fold, the z row of FilterDraw, tK).  It implies that
+// certainly_outside<true> holds for every meshlet of the block, and through it that the reference rejects every one of them (the proof is in
+// DESIGN.md §4.1; tests/test_block_cert.py checks it against this header):
+//   for a plane p with distance g_p (g1 = cz f1 - |cx'|, g2 = cz f3 - |cy'|, gn = cz - znear, gf = zfar - cz; cx', cy' the folded rows) and
+//   L_p = its Lipschitz constant in c (||x' row||_2 + |f1| ||z row||_2, ..., ||z row||_2):  g_p(v_i) <= g_p(C) + L_p D exactly, and the fp32
+//   evaluations at C and at v_i together err by < 32 u S (alpha vmax3 + beta) + 4 u (|znear| + |zfar|) — a sixth of tK >= 192 u S (alpha vmax3 + beta)
+//   plus 2^-20 (|znear| + |zfar|).
+//   So  g_p(C) + L_p D < -(|s| rho + 2 tK + 2^-20 (|znear| + |zfar|))  leaves g_p(v_i) < -(|s| r_i + tK) with room for every rounding.
+constexpr float BLOCK_L_UP = 1.0000152587890625f; // 1 + 2^-16: the fp32 2-norms of the rows (<= 5 roundings + a 1-ulp square root), rounded up
+constexpr float BLOCK_Z_U = 9.5367431640625e-7f;  // 2^-20: the roundings of cz - znear, zfar - cz relative to the planes themselves
+constexpr uint32_t BLOCK_MESHLETS = 64u;
+
+struct BlockRecord
+{
+	float c[3];
+	uint32_t dr; // D (fp16 bits, rounded up) | rho << 16 (fp16 bits)
+};
+
+// fp16 bits -> fp32, exact, on both sides (the host has no _Float16 in every compiler)
+NV_FM float fm_half_to_float(uint32_t h)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	_Float16 v;
+	unsigned short b = (unsigned short)h;
+	__builtin_memcpy(&v, &b, 2);
+	return (float)v;
+#else
+	const uint32_t s = (h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 1023u;
+	if (e == 0)
+	{
+		const float v = (float)m * 5.9604644775390625e-8f; // m 2^-24: exact
+		return s ? -v : v;
+	}
+	const uint32_t bits = s | (e == 31u ? 0x7f800000u | m << 13 : (e + 112u) << 23 | m << 13);
+	float v;
+	__builtin_memcpy(&v, &bits, 4);
+	return v;
+#endif
+}
+
+// the smallest fp16 >= x (x >= 0; NaN and x > 65504 give inf), as bits
+NV_FM uint32_t fm_half_up(double x)
+{
+	if (!(x <= 65504.0))
+		return 0x7c00u;
+	if (x <= 0.0)
+		return 0u;
+	if (x < 6.103515625e-05) // below 2^-14: subnormal steps of 2^-24 (1024 steps = the smallest normal's bits)
+		return (uint32_t)__builtin_ceil(x * 16777216.0);
+	int E = -14;
+	double p = 6.103515625e-05;
+	while (E < 15 && x >= 2.0 * p)
+	{
+		p *= 2.0;
+		++E;
+	}
+	const uint32_t q = (uint32_t)__builtin_ceil(x / p * 1024.0); // x / p in [1, 2): exact; q in [1024, 2048]
+	return ((uint32_t)(E + 15) << 10) + (q - 1024u);            // (q = 2048 carries into the exponent: 65504 < x is excluded above)
+}
+
+// the record of the n meshlets (bounds words {center.xy, center.z | radius << 16}) of one block; n = 0: never rejects
+NV_FM BlockRecord block_record(const uint32_t* words, uint32_t n)
+{
+	BlockRecord k = { { 0.0f, 0.0f, 0.0f }, 0x7c00u | 0x7c00u << 16 };
+	double lo[3] = { 0.0, 0.0, 0.0 }, hi[3] = { 0.0, 0.0, 0.0 };
+	uint32_t rho = 0;
+	for (uint32_t i = 0; i < n; ++i)
+	{
+		const uint32_t h[4] = { words[2 * i] & 0xffffu, words[2 * i] >> 16, words[2 * i + 1] & 0xffffu, words[2 * i + 1] >> 16 };
+		for (int j = 0; j < 4; ++j)
+			if ((h[j] & 0x7c00u) == 0x7c00u)
+				return k; // inf / NaN
+		for (int j = 0; j < 3; ++j)
+		{
+			const double v = (double)fm_half_to_float(h[j]);
+			lo[j] = i == 0 || v < lo[j] ? v : lo[j];
+			hi[j] = i == 0 || v > hi[j] ? v : hi[j];
+		}
+		rho = (h[3] & 0x7fffu) > rho ? (h[3] & 0x7fffu) : rho; // |r| in fp16 bits: ordered like the magnitudes
+	}
+	if (n == 0)
+		return k;
+	for (int j = 0; j < 3; ++j)
+		k.c[j] = (float)((lo[j] + hi[j]) * 0.5); // exact midpoint of two halfs, rounded to fp32: still inside [lo, hi]
+	double d2 = 0.0;
+	for (uint32_t i = 0; i < n; ++i)
+	{
+		double s = 0.0;
+		for (int j = 0; j < 3; ++j)
+		{
+			const double t = (double)fm_half_to_float(j < 2 ? (words[2 * i] >> (16 * j)) & 0xffffu : words[2 * i + 1] & 0xffffu) - (double)k.c[j];
+			s += t * t;
+		}
+		d2 = s > d2 ? s : d2;
+	}
+	// a handful of fp64 roundings (relative 2^-53 each) in d2 and its root: 1 + 2^-40 covers them, fm_half_up rounds the rest upward
+	k.dr = fm_half_up(__builtin_sqrt(d2) * (1.0 + 9.094947017729282e-13)) | rho << 16;
+	return k;
+}
+
+NV_FM float fm_sqrt(float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	return __builtin_amdgcn_sqrtf(x); // 1 ulp: BLOCK_L_UP covers it
+#else
+	return __builtin_sqrtf(x);
+#endif
+}
+
+// The per-draw part of the block test (lane-parallel once per segment): L1, L2, Lz of the planes, rounded up; fx, fy = the folded side rows
+// (f0 M_x | f0 b_x, f2 M_y | f2 b_y: SegmentRegs::fold), mz = the z row of M
+struct BlockPlanes
+{
+	float L1, L2, Lz;
+};
+
+NV_FM BlockPlanes block_planes(const float fx[4], const float fy[4], const float mz[3], float f1, float f3)
+{
+	const float lx = fm_sqrt(__builtin_fmaf(fx[0], fx[0], __builtin_fmaf(fx[1], fx[1], fx[2] * fx[2])));
+	const float ly = fm_sqrt(__builtin_fmaf(fy[0], fy[0], __builtin_fmaf(fy[1], fy[1], fy[2] * fy[2])));
+	const float lz = fm_sqrt(__builtin_fmaf(mz[0], mz[0], __builtin_fmaf(mz[1], mz[1], mz[2] * mz[2])));
+	BlockPlanes p;
+	p.L1 = __builtin_fmaf(__builtin_fabsf(f1), lz, lx) * BLOCK_L_UP;
+	p.L2 = __builtin_fmaf(__builtin_fabsf(f3), lz, ly) * BLOCK_L_UP;
+	p.Lz = lz * BLOCK_L_UP;
+	return p;
+}
+
+// true when every meshlet of the block is certainly outside one plane (see above).  thrBase = 2 tK + 2^-20 (|znear| + |zfar|) (block_thr_base).
+// Written with one comparison per plane: a NaN or inf anywhere (D = inf, tK = inf / NaN) makes every comparison false.
+NV_FM float block_thr_base(float tK, float znear, float zfar)
+{
+	return __builtin_fmaf(BLOCK_Z_U, __builtin_fabsf(znear) + __builtin_fabsf(zfar), 2.0f * tK);
+}
+
+NV_FM bool block_outside(const float fx[4], const float fy[4], const float mz[3], float bz, const BlockPlanes& p, float f1, float f3, float znear,
+                         float zfar, float scale, float thrBase, const BlockRecord& k)
+{
+	const float D = fm_half_to_float(k.dr & 0xffffu), rho = fm_half_to_float(k.dr >> 16);
+	const float cx = __builtin_fmaf(fx[0], k.c[0], __builtin_fmaf(fx[1], k.c[1], __builtin_fmaf(fx[2], k.c[2], fx[3])));
+	const float cy = __builtin_fmaf(fy[0], k.c[0], __builtin_fmaf(fy[1], k.c[1], __builtin_fmaf(fy[2], k.c[2], fy[3])));
+	const float cz = __builtin_fmaf(mz[0], k.c[0], __builtin_fmaf(mz[1], k.c[1], __builtin_fmaf(mz[2], k.c[2], bz)));
+	const float thr = -__builtin_fmaf(__builtin_fabsf(scale), rho, thrBase);
+	const float g1 = __builtin_fmaf(cz, f1, -__builtin_fabsf(cx)), g2 = __builtin_fmaf(cz, f3, -__builtin_fabsf(cy));
+	const float gn = cz - znear, gf = zfar - cz;
+	return (__builtin_fmaf(p.L1, D, g1) < thr) | (__builtin_fmaf(p.L2, D, g2) < thr) | (__builtin_fmaf(p.Lz, D, gn) < thr) | (__builtin_fmaf(p.Lz, D, gf) < thr);
+}
+
 } // namespace nv
