@@ -260,6 +260,18 @@ int nv_profile_variants(nv_context* ctx, uint32_t out_count[NV_VARIANT_SLOTS]);
  * many pixel centres with one lane, a larger one with the whole wave (lane = pixel of an 8 x 8 stamp).  0 puts every triangle on the
  * wave path, INT_MAX every triangle on the lane path.  Speed only: both paths write the same bits. */
 #define NV_OPT_RASTER_SMALL_LIMIT 9
+/* NV_OPT_RASTER_NEAR_CLIP (default 0; 0 / 1, anything else NV_EINVAL): 1 makes nv_rasterdepth and nv_rasterdepth_indexed clip a triangle
+ * that crosses the near plane instead of dropping it.  A triangle with one or two vertices that fail clip.w > 0 && clip.z <= clip.w is cut
+ * at d = clip.w - clip.z = 0 into one or two pieces (the fan of the Sutherland-Hodgman polygon over the edges v0->v1, v1->v2, v2->v0),
+ * provided all twelve clip components are finite and every failing vertex has d < 0; otherwise it is not drawn, as with 0.  A new vertex is
+ * computed from the edge's inside end I towards its outside end O whatever the edge's direction (t = dI / (dI - dO); x, y, w = I + t (O - I),
+ * fp32, no contraction), so two triangles sharing the edge get the same bits and a mesh stays watertight; its depth is exactly 1.  A new
+ * vertex with w <= 0, a non-finite screen position or one at or past 2^21 pixels rejects the whole triangle.  There is NO clipping
+ * against the guard band or the viewport: such a triangle still does not occlude, which is conservative.  Each piece is rasterised as a
+ * triangle of its own (facing by its own area, top-left rule: a sample of the polygon belongs to exactly one piece).  Totals word 2 then
+ * counts pieces; the visibility word of a piece carries the original triangle's id.  With 0 both entry points write the bits they
+ * wrote before the option existed.  Not speed only: with 1 more samples are written. */
+#define NV_OPT_RASTER_NEAR_CLIP 10
 int nv_set_option(nv_context* ctx, int option, int value);
 
 /* ---- capacities ----
@@ -428,14 +440,16 @@ int nv_trianglecull(nv_context* ctx, void* stream, const NvGlobals* globals, con
  * screen space with nv_trianglecull's arithmetic plus z = clip.z / clip.w, snap to 8 sub-pixel bits (X = rint(sx * 256),
  * Y = height * 256 - rint(sy * 256): row 0 at the top, the reference's flipped viewport, src/niagara.cpp:1641) and every triangle
  * i < min(triangleCount, 96) is rasterised at pixel centres with the top-left rule, unless
- *   - an index byte is >= min(vertexCount, 64), or a vertex has !(clip.w > 0 && clip.z <= clip.w) (no near-plane clipping: such a
- *     triangle writes nothing, which keeps the pyramid conservative), a non-finite screen position or |sx|, |sy| >= 2^21;
+ *   - an index byte is >= min(vertexCount, 64), or a vertex has !(clip.w > 0 && clip.z <= clip.w) (no near-plane clipping by default:
+ *     such a triangle writes nothing, which keeps the pyramid conservative; NV_OPT_RASTER_NEAR_CLIP 1 clips it into one or two pieces
+ *     instead, see the option), a non-finite screen position or |sx|, |sy| >= 2^21;
  *   - its doubled area is 0, or it is a back face while globals->cullData.postPass == 0 (front = counter-clockwise in y-up space,
  *     VK_CULL_MODE_BACK_BIT; postPass != 0 draws both faces; the post pass's depth bias is not modelled).
  * Depth: fp32, interpolated in a fixed order from the exact int64 edge functions, clamped to [0, 1], written with an atomic max on its
  * bits (reverse-Z, compare GREATER).  d_depth is width x height; the caller clears it (0 = far) before an early pass, not before a late
  * one.  d_visibility (optional, width x height u64) receives the max of bits(z) << 32 | slot index << 7 | triangle: ties go to the larger ID.
- * d_totals4 (optional, accumulated: zero it first): clusters, triangles (triangleCount as stored), triangles rasterised, samples covered.
+ * d_totals4 (optional, accumulated: zero it first): clusters, triangles (triangleCount as stored), triangles rasterised (with
+ * NV_OPT_RASTER_NEAR_CLIP 1: pieces rasterised; both pieces of a triangle write its id into d_visibility), samples covered.
  * Every result is independent of the order of the GPU's work.  width and height must equal globals->screenWidth / screenHeight and lie in
  * 1 .. 16384. */
 int nv_rasterdepth(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshTaskCommand* d_commands,
@@ -454,7 +468,8 @@ int nv_rasterdepth(nv_context* ctx, void* stream, const NvGlobals* globals, cons
  * a corner is >= vertexCapacity (0xFFFFFFFF included: there is no primitive restart), so every load stays inside the caller's buffers.
  * Everything else is nv_rasterdepth's rule set, unchanged — the vertex stage, the snap, the near-plane / non-finite / guard-band rejection,
  * facing by globals->cullData.postPass, top-left coverage, the fixed-order fp32 depth and the atomic max — so the same triangle under the same
- * draw writes the same bits through either entry point.  No visibility buffer (a 32-bit ID cannot name both a draw and a triangle).
+ * draw writes the same bits through either entry point, with NV_OPT_RASTER_NEAR_CLIP 1 as well (the same clip rule, totals word 2 then counts
+ * pieces).  No visibility buffer (a 32-bit ID cannot name both a draw and a triangle).
  * d_totals4 (optional, accumulated: zero it first): commands drawn, triangles (sum of their indexCount / 3), triangles rasterised, samples
  * covered.  d_draws holds drawCount records and d_commands up to drawCount commands; a zero capacity is allowed (nothing is read then).
  * Scratch: 4 B per command slot (drawCount) + 20 KiB, sized by nv_create for 1 M and by nv_reserve(maxDraws); a larger drawCount returns

@@ -45,8 +45,8 @@ int launch_clustersubmit(hipStream_t, uint32_t* cc4, uint32_t* clusterIndices);
 int launch_pack_counts(hipStream_t, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*);
 int launch_depthreduce(hipStream_t, const float* depth, uint32_t w, uint32_t h, const NvPyramidDesc& pyr);
 int launch_trianglecull(hipStream_t, const TriangleArgs& a, uint32_t gridBlocks);
-int launch_rasterdepth(hipStream_t, const RasterArgs& a, uint32_t gridBlocks);
-int launch_rasterindexed(hipStream_t, RasterIndexedArgs a, void* scratch, uint32_t gridBlocks);
+int launch_rasterdepth(hipStream_t, const RasterArgs& a, uint32_t gridBlocks, bool nearClip);
+int launch_rasterindexed(hipStream_t, RasterIndexedArgs a, void* scratch, uint32_t gridBlocks, bool nearClip);
 size_t rasterindexed_scratch_bytes(uint32_t drawCount);
 int launch_meshlet_bounds(hipStream_t, const NvVertex* vertices, const uint32_t* data, NvMeshlet* meshlets, uint32_t count, float* out8, uint32_t gridBlocks);
 
@@ -136,6 +136,7 @@ struct nv_context
 	size_t timingWaves; // its room, in waves
 	uint32_t variants[NV_VARIANT_SLOTS]; // nv_profile_variants: launches per kernel variant since the last read
 	uint32_t rasterSmallLimit; // NV_OPT_RASTER_SMALL_LIMIT
+	uint32_t rasterNearClip;   // NV_OPT_RASTER_NEAR_CLIP: 1 = the clipping instantiations of both depth rasterisers
 };
 
 namespace
@@ -418,6 +419,7 @@ int nv_create(nv_context** out_ctx, int device)
 	ctx->scatterTilesPerCU = 1;
 	ctx->scatterWaves = 16;
 	ctx->rasterSmallLimit = 16;
+	ctx->rasterNearClip = 0;
 	ctx->directPercent = 35; // measured crossover (config 3A geometry at several densities): ~36 % of the commands passing the filter
 	ctx->forceDirect = -1;
 	ctx->bitsBlocksPerCU = 4;
@@ -568,6 +570,11 @@ int nv_set_option(nv_context* ctx, int option, int value)
 		if (value < 0)
 			return NV_EINVAL;
 		ctx->rasterSmallLimit = (uint32_t)value;
+		return NV_OK;
+	case NV_OPT_RASTER_NEAR_CLIP:
+		if (value != 0 && value != 1)
+			return NV_EINVAL;
+		ctx->rasterNearClip = (uint32_t)value;
 		return NV_OK;
 	case NV_OPT_CULL_WORKGROUPS_PER_CU:
 		if (value < 1 || value > 8)
@@ -1137,7 +1144,7 @@ int nv_rasterdepth(nv_context* ctx, void* stream, const NvGlobals* globals, cons
 	a.smallLimit = ctx->rasterSmallLimit;
 	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
 	a.partials = ctx->totalsPartials;
-	return nv::launch_rasterdepth((hipStream_t)stream, a, persistent_grid(ctx, 8));
+	return nv::launch_rasterdepth((hipStream_t)stream, a, persistent_grid(ctx, 8), ctx->rasterNearClip != 0);
 }
 
 int nv_rasterdepth_indexed(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshDrawCommand* d_commands, const uint32_t* d_count,
@@ -1167,7 +1174,7 @@ int nv_rasterdepth_indexed(nv_context* ctx, void* stream, const NvGlobals* globa
 	a.smallLimit = ctx->rasterSmallLimit;
 	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
 	a.partials = ctx->totalsPartials;
-	return nv::launch_rasterindexed((hipStream_t)stream, a, ctx->rasterScratch, persistent_grid(ctx, 8));
+	return nv::launch_rasterindexed((hipStream_t)stream, a, ctx->rasterScratch, persistent_grid(ctx, 8), ctx->rasterNearClip != 0);
 }
 
 int nv_meshlet_bounds(nv_context* ctx, void* stream, const NvVertex* d_vertices, const uint32_t* d_meshletData, NvMeshlet* d_meshlets, uint32_t meshletCount,

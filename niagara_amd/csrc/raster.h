@@ -1,7 +1,8 @@
 // raster.h — the raster rules both depth rasterisers share: the vertex stage to snapped screen space, the triangle
 // setup (rejection, facing, top-left flags, pixel box) and the per-sample coverage / depth / atomic.  rasterdepth.hip (the cluster path) and
 // rasterindexed.hip (the indexed-draw path) use these statements and nothing else for what they write, so the same triangle under the same
-// draw writes the same bits through either path; tests/raster_ref.c restates them one sample at a time.
+// draw writes the same bits through either path; tests/raster_ref.c restates them one sample at a time.  With NV_OPT_RASTER_NEAR_CLIP both
+// kernels also share rd_clip, the near-plane rule (tests/raster_clip_ref.c).  There is no clipping against the guard band or the viewport.
 #pragma once
 
 #include "cullmath.h"
@@ -31,23 +32,28 @@ struct RdTri
 	uint32_t topLeft; // bit 0: a->b, bit 1: b->c, bit 2: c->a
 };
 
-// One vertex (the first 8 bytes of its record: fp16 x, y, z) under the draw {position, scale, orientation q.xyz, qw} to snapped screen
-// space: X, Y with 8 sub-pixel bits (row 0 at the top), the bits of z = clip.z / clip.w, and 1 in .w when no triangle of it is drawn.
+// One vertex (the first 8 bytes of its record: fp16 x, y, z) under the draw {position, scale, orientation q.xyz, qw} to clip space.
 // nv_trianglecull's arithmetic (src/shaders/meshlet.mesh.glsl:121-160; mesh.vert.glsl:41-57 computes the same).
-NV_DEV int4 rd_vertex(const NvGlobals& g, uint2 pv, f3 q, float qw, float scale, float px, float py, float pz, int32_t H)
+NV_DEV void rd_clip_position(const NvGlobals& g, uint2 pv, f3 q, float qw, float scale, float px, float py, float pz, float clip[4])
 {
 	const f3 position = { half_bits_to_float(pv.x & 0xffffu), half_bits_to_float(pv.x >> 16), half_bits_to_float(pv.y & 0xffffu) };
 	const f3 rot = rotate_quat(position, q, qw);
 	const float wx = rot.x * scale + px, wy = rot.y * scale + py, wz = rot.z * scale + pz;
 	const float* V = g.cullData.view;
 	const float* P = g.projection;
-	float v4[4], clip[4];
+	float v4[4];
 #pragma unroll
 	for (int r = 0; r < 4; ++r) // view * vec4(wpos, 1): c3 * 1.0f is c3 exactly
 		v4[r] = ((V[r] * wx + V[4 + r] * wy) + V[8 + r] * wz) + V[12 + r];
 #pragma unroll
 	for (int r = 0; r < 4; ++r)
 		clip[r] = ((P[r] * v4[0] + P[4 + r] * v4[1]) + P[8 + r] * v4[2]) + P[12 + r] * v4[3];
+}
+
+// A clip-space position to snapped screen space: X, Y with 8 sub-pixel bits (row 0 at the top), the bits of z = clip.z / clip.w, and 1 in
+// .w when no triangle of it is drawn.
+NV_DEV int4 rd_snap(const NvGlobals& g, const float clip[4], int32_t H)
+{
 	const float sx = ((clip[0] / clip[3]) * 0.5f + 0.5f) * g.screenWidth;
 	const float sy = ((clip[1] / clip[3]) * 0.5f + 0.5f) * g.screenHeight;
 	const float z = clip[2] / clip[3];
@@ -56,6 +62,98 @@ NV_DEV int4 rd_vertex(const NvGlobals& g, uint2 pv, f3 q, float qw, float scale,
 	const int32_t X = bad ? 0 : (int32_t)__builtin_rintf(sx * 256.0f);
 	const int32_t Y = bad ? 0 : H * 256 - (int32_t)__builtin_rintf(sy * 256.0f); // viewport flipped: row 0 at the top
 	return make_int4(X, Y, __float_as_int(z), bad ? 1 : 0);
+}
+
+// One vertex to snapped screen space (rd_clip_position, then rd_snap).
+NV_DEV int4 rd_vertex(const NvGlobals& g, uint2 pv, f3 q, float qw, float scale, float px, float py, float pz, int32_t H)
+{
+	float clip[4];
+	rd_clip_position(g, pv, q, qw, scale, px, py, pz, clip);
+	return rd_snap(g, clip, H);
+}
+
+// ---- near-plane clipping (NV_OPT_RASTER_NEAR_CLIP, DESIGN.md §4.10 "Near-plane clipping")
+constexpr int32_t RD_OUTSIDE = 2; // bit 1 of a snapped vertex's .w: the vertex fails clip.w > 0 && clip.z <= clip.w (then bit 0 is set as well)
+
+// rd_vertex for the clipping kernels: .w also carries RD_OUTSIDE, and `cv` receives what a crossing edge needs: clip x, y, w and
+// d = clip.w - clip.z, with NaN in place of d when one of the four clip components is not finite (d is NaN by itself only then).
+NV_DEV int4 rd_vertex_clip(const NvGlobals& g, uint2 pv, f3 q, float qw, float scale, float px, float py, float pz, int32_t H, float4& cv)
+{
+	float clip[4];
+	rd_clip_position(g, pv, q, qw, scale, px, py, pz, clip);
+	int4 s = rd_snap(g, clip, H);
+	const bool inside = clip[3] > 0.0f && clip[2] <= clip[3];
+	const bool finite = __builtin_fabsf(clip[0]) < __builtin_inff() && __builtin_fabsf(clip[1]) < __builtin_inff() &&
+	                    __builtin_fabsf(clip[2]) < __builtin_inff() && __builtin_fabsf(clip[3]) < __builtin_inff();
+	s.w |= inside ? 0 : RD_OUTSIDE;
+	cv = make_float4(clip[0], clip[1], clip[3], finite ? clip[3] - clip[2] : __builtin_nanf(""));
+	return s;
+}
+
+// c ? a : b per component: a conditional between two vector lvalues selects an address, and what it points to then lives in scratch memory
+NV_DEV int4 rd_sel(bool c, int4 a, int4 b) { return make_int4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w); }
+NV_DEV float4 rd_sel(bool c, float4 a, float4 b) { return make_float4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w); }
+
+// The vertex where the edge from the inside end `i` to the outside end `o` meets the near plane, snapped: always computed from the inside
+// end, so both triangles that share the edge get the same bits.  Its depth is 1 (it lies on the plane); .w = 1 when it is rejected.
+NV_DEV int4 rd_clip_vertex(const NvGlobals& g, float4 i, float4 o, int32_t H)
+{
+	const float t = i.w / (i.w - o.w);
+	const float x = i.x + t * (o.x - i.x), y = i.y + t * (o.y - i.y), w = i.z + t * (o.z - i.z);
+	const float sx = ((x / w) * 0.5f + 0.5f) * g.screenWidth;
+	const float sy = ((y / w) * 0.5f + 0.5f) * g.screenHeight;
+	const bool bad = !(w > 0.0f) || !(__builtin_fabsf(sx) < RD_GUARD) || !(__builtin_fabsf(sy) < RD_GUARD); // (NaN and infinity included)
+	const int32_t X = bad ? 0 : (int32_t)__builtin_rintf(sx * 256.0f);
+	const int32_t Y = bad ? 0 : H * 256 - (int32_t)__builtin_rintf(sy * 256.0f);
+	return make_int4(X, Y, __float_as_int(1.0f), bad ? 1 : 0);
+}
+
+// The triangle (s0, s1, s2) of rd_vertex_clip's results (c0, c1, c2 their clip records) against the near plane.  Returns the number of
+// pieces, 0-2, and the polygon p0..p3 in the triangle's winding: piece 0 is (p0, p1, p2), piece 1 is (p0, p2, p3).  Three inside vertices
+// give the triangle itself as piece 0.  The walk is Sutherland-Hodgman's over v0->v1, v1->v2, v2->v0 written out per case, with selects
+// instead of indexed arrays (which would live in scratch memory): with r the one outside vertex (or the one inside vertex), R0 = v[r],
+// R1 = v[r + 1], R2 = v[r + 2] and N1, N2 the two new vertices, the polygon is a rotation of (N1, R1, R2, N2) (or of (R0, N1, N2)).
+NV_DEV uint32_t rd_clip(const NvGlobals& g, int4 s0, int4 s1, int4 s2, float4 c0, float4 c1, float4 c2, int32_t H, int4& p0, int4& p1, int4& p2,
+                        int4& p3)
+{
+	const uint32_t out = (s0.w & RD_OUTSIDE ? 1u : 0u) | (s1.w & RD_OUTSIDE ? 2u : 0u) | (s2.w & RD_OUTSIDE ? 4u : 0u);
+	p0 = s0, p1 = s1, p2 = s2, p3 = s2;
+	if (out == 0u)
+		return 1u;
+	if (out == 7u)
+		return 0u;
+	// all twelve clip components finite, and every outside vertex strictly beyond the plane (a caller's projection may give w <= 0 with z <= w)
+	const bool ok = c0.w == c0.w && c1.w == c1.w && c2.w == c2.w && (!(out & 1u) || c0.w < 0.0f) && (!(out & 2u) || c1.w < 0.0f) &&
+	                (!(out & 4u) || c2.w < 0.0f);
+	if (!ok)
+		return 0u;
+	const bool one = (out & (out - 1u)) == 0u;          // one vertex outside: a quad; else one vertex inside: a triangle
+	const uint32_t sel = one ? out : out ^ 7u;          // the bit of vertex r
+	const uint32_t r = sel == 1u ? 0u : (sel == 2u ? 1u : 2u);
+	const bool r0 = r == 0u, r1 = r == 1u;
+	const int4 S0 = rd_sel(r0, s0, rd_sel(r1, s1, s2)), S1 = rd_sel(r0, s1, rd_sel(r1, s2, s0)), S2 = rd_sel(r0, s2, rd_sel(r1, s0, s1));
+	const float4 C0 = rd_sel(r0, c0, rd_sel(r1, c1, c2)), C1 = rd_sel(r0, c1, rd_sel(r1, c2, c0)), C2 = rd_sel(r0, c2, rd_sel(r1, c0, c1));
+	// one outside (R0): N1 on R1 -> R0, N2 on R2 -> R0.  One inside (R0): N1 on R0 -> R1, N2 on R0 -> R2.
+	const int4 N1 = rd_clip_vertex(g, rd_sel(one, C1, C0), rd_sel(one, C0, C1), H);
+	const int4 N2 = rd_clip_vertex(g, rd_sel(one, C2, C0), rd_sel(one, C0, C2), H);
+	if ((N1.w | N2.w) != 0) // a rejected new vertex rejects the whole triangle, never one piece alone
+		return 0u;
+	const int4 I0 = make_int4(S0.x, S0.y, S0.z, S0.w & 1), I1 = make_int4(S1.x, S1.y, S1.z, S1.w & 1), I2 = make_int4(S2.x, S2.y, S2.z, S2.w & 1);
+	if (one)
+	{
+		// (N1, R1, R2, N2) from the walk's first emitted vertex: r = 0 starts at N1, r = 1 at R2 (= v0), r = 2 at R1 (= v0)
+		p0 = rd_sel(r0, N1, rd_sel(r1, I2, I1));
+		p1 = rd_sel(r0, I1, rd_sel(r1, N2, I2));
+		p2 = rd_sel(r0, I2, rd_sel(r1, N1, N2));
+		p3 = rd_sel(r0, N2, rd_sel(r1, I1, N1));
+		return 2u;
+	}
+	// (R0, N1, N2): r = 0 starts at R0 (= v0), r = 1 and r = 2 at N2 (the crossing of the first edge that has one)
+	p0 = rd_sel(r0, I0, N2);
+	p1 = rd_sel(r0, N1, I0);
+	p2 = rd_sel(r0, N2, N1);
+	p3 = p2;
+	return 1u;
 }
 
 NV_DEV int64_t rd_edge(int32_t px, int32_t py, int32_t qx, int32_t qy, int32_t sx, int32_t sy)

@@ -13,6 +13,11 @@
 // most `smallLimit` pixel centres is walked by its own lane right there; a larger one is queued in LDS and walked afterwards by the
 // whole wave, lane = pixel of an 8 x 8 stamp.  Before each atomic the lane loads the current value and skips the atomic when it would
 // not raise it (values only grow during a launch: a stale load costs an extra atomic, never a wrong result).
+//
+// CLIP (NV_OPT_RASTER_NEAR_CLIP 1) is a second instantiation: the vertex stage also keeps each vertex's clip x, y, w and d = w - z in LDS, a
+// triangle that crosses the near plane becomes one or two pieces (raster.h: rd_clip), and each piece takes the road a triangle takes.  The
+// queue entry of a large piece carries the piece number; the wave runs rd_clip again on the same inputs (same bits).  CLIP = false is
+// the kernel without any of it.
 #include "raster.h"
 
 namespace nv
@@ -25,10 +30,13 @@ constexpr uint32_t RD_CHUNK = 64; // slots whose headers a wave fetches together
 #define RD_BLOCKS_PER_CU 6 // <= 8: the partial totals are sized for 8 workgroups per CU (context.hip)
 #endif
 
+template <bool CLIP>
 __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(RasterArgs a)
 {
-	__shared__ int4 s_vtx[RD_WAVES][64];      // per vertex of the current slot: X, Y, z bits, reject
-	__shared__ uint32_t s_queue[RD_WAVES][96]; // large triangles of the current slot: t | ia << 8 | ib << 16 | ic << 24 (after the swap)
+	constexpr uint32_t PIECES = CLIP ? 2u : 1u; // pieces of a triangle at most
+	__shared__ int4 s_vtx[RD_WAVES][64];       // per vertex of the current slot: X, Y, z bits, reject (CLIP: | RD_OUTSIDE)
+	__shared__ float4 s_clip[RD_WAVES][64];    // CLIP only: clip x, y, w and d = w - z (NaN: a non-finite component)
+	__shared__ uint32_t s_queue[RD_WAVES][96 * PIECES]; // large pieces of the current slot: t | piece << 7 | ia << 8 | ib << 16 | ic << 24
 
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -45,6 +53,9 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(RasterArgs a)
 	const uint16_t* data16 = reinterpret_cast<const uint16_t*>(a.meshletData);
 	int4* vtx = s_vtx[wave];
 	uint32_t* queue = s_queue[wave];
+	float4* cvx = nullptr;
+	if constexpr (CLIP)
+		cvx = s_clip[wave];
 
 	uint32_t clusters = 0, triangles = 0; // wave-uniform
 	uint32_t drawn = 0;                   // per lane
@@ -99,7 +110,14 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(RasterArgs a)
 			{
 				const uint32_t ref = shortRefs ? (uint32_t)data16[dataOffset * 2 + lane] : a.meshletData[dataOffset + lane];
 				const uint2 pv = *reinterpret_cast<const uint2*>(a.vertices + ref + baseVertex);
-				vtx[lane] = rd_vertex(a.globals, pv, q, qw, scale, px, py, pz, H);
+				if constexpr (CLIP)
+				{
+					float4 cv;
+					vtx[lane] = rd_vertex_clip(a.globals, pv, q, qw, scale, px, py, pz, H, cv);
+					cvx[lane] = cv;
+				}
+				else
+					vtx[lane] = rd_vertex(a.globals, pv, q, qw, scale, px, py, pz, H);
 			}
 			rd_lds_order();
 
@@ -107,40 +125,90 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(RasterArgs a)
 			uint32_t queued = 0; // wave-uniform
 			for (uint32_t tb = 0; tb < te; tb += 64)
 			{
-				const uint32_t t = tb + lane;
-				RdTri tri;
-				bool live = false, large = false;
-				uint32_t ia = 0, ib = 0, ic = 0;
-				if (t < te)
+				// The two branches repeat each other's text on purpose: written as one loop over pieces, the CLIP = false instantiation compiles to other
+				// code than the kernel had before the option (other registers, other schedule); kept apart, it is that kernel instruction for instruction.
+				if constexpr (!CLIP)
 				{
-					const uint32_t o = indexOffset * 4 + t * 3;
-					ia = data8[o], ib = data8[o + 1], ic = data8[o + 2];
-					live = rd_setup(vtx, ia, ib, ic, ve, bothFaces, W, H, tri);
-				}
-				if (live)
-				{
-					drawn += 1;
-					if (tri.x0 <= tri.x1 && tri.y0 <= tri.y1)
+					const uint32_t t = tb + lane;
+					RdTri tri;
+					bool live = false, large = false;
+					uint32_t ia = 0, ib = 0, ic = 0;
+					if (t < te)
 					{
-						const uint32_t n = (uint32_t)(tri.x1 - tri.x0 + 1) * (uint32_t)(tri.y1 - tri.y0 + 1);
-						large = n > a.smallLimit;
-						if (!large)
+						const uint32_t o = indexOffset * 4 + t * 3;
+						ia = data8[o], ib = data8[o + 1], ic = data8[o + 2];
+						live = rd_setup(vtx, ia, ib, ic, ve, bothFaces, W, H, tri);
+					}
+					if (live)
+					{
+						drawn += 1;
+						if (tri.x0 <= tri.x1 && tri.y0 <= tri.y1)
 						{
-							const uint32_t id = index << 7 | t;
-							for (int32_t py = tri.y0; py <= tri.y1; ++py)
-								for (int32_t px = tri.x0; px <= tri.x1; ++px)
-									samples += rd_sample(tri, px, py, a.width, a.depth, a.visibility, id) ? 1u : 0u;
+							const uint32_t n = (uint32_t)(tri.x1 - tri.x0 + 1) * (uint32_t)(tri.y1 - tri.y0 + 1);
+							large = n > a.smallLimit;
+							if (!large)
+							{
+								const uint32_t id = index << 7 | t;
+								for (int32_t py = tri.y0; py <= tri.y1; ++py)
+									for (int32_t px = tri.x0; px <= tri.x1; ++px)
+										samples += rd_sample(tri, px, py, a.width, a.depth, a.visibility, id) ? 1u : 0u;
+							}
 						}
 					}
+					const uint64_t q = __ballot(large);
+					if (large)
+					{
+						// the raw index bytes: the wave reruns rd_setup on them (same inputs, same bits)
+						const uint32_t at = queued + (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(q >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)q, 0u));
+						queue[at] = t | ia << 8 | ib << 16 | ic << 24;
+					}
+					queued += (uint32_t)__builtin_popcountll(q);
 				}
-				const uint64_t q = __ballot(large);
-				if (large)
+				else
 				{
-					// the raw index bytes: the wave reruns rd_setup on them (same inputs, same bits)
-					const uint32_t at = queued + (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(q >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)q, 0u));
-					queue[at] = t | ia << 8 | ib << 16 | ic << 24;
+					const uint32_t t = tb + lane;
+					uint32_t ia = 0, ib = 0, ic = 0, pieces = 0;
+					int4 p0 = make_int4(0, 0, 0, 1), p1 = p0, p2 = p0, p3 = p0;
+					if (t < te)
+					{
+						const uint32_t o = indexOffset * 4 + t * 3;
+						ia = data8[o], ib = data8[o + 1], ic = data8[o + 2];
+						if (ia < ve && ib < ve && ic < ve)
+							pieces = rd_clip(a.globals, vtx[ia], vtx[ib], vtx[ic], cvx[ia], cvx[ib], cvx[ic], H, p0, p1, p2, p3);
+					}
+					for (uint32_t p = 0; p < 2u; ++p)
+					{
+						if (!__ballot(p < pieces)) // (wave-uniform)
+							break;
+						RdTri tri;
+						bool large = false;
+						const bool live = p < pieces && rd_setup_corners(p0, rd_sel(p != 0u, p2, p1), rd_sel(p != 0u, p3, p2), bothFaces, W, H, tri);
+						if (live)
+						{
+							drawn += 1;
+							if (tri.x0 <= tri.x1 && tri.y0 <= tri.y1)
+							{
+								const uint32_t n = (uint32_t)(tri.x1 - tri.x0 + 1) * (uint32_t)(tri.y1 - tri.y0 + 1);
+								large = n > a.smallLimit;
+								if (!large)
+								{
+									const uint32_t id = index << 7 | t;
+									for (int32_t py = tri.y0; py <= tri.y1; ++py)
+										for (int32_t px = tri.x0; px <= tri.x1; ++px)
+											samples += rd_sample(tri, px, py, a.width, a.depth, a.visibility, id) ? 1u : 0u;
+								}
+							}
+						}
+						const uint64_t q = __ballot(large);
+						if (large)
+						{
+							// the raw index bytes: the wave reruns the setup on them (same inputs, same bits)
+							const uint32_t at = queued + (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(q >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)q, 0u));
+							queue[at] = t | p << 7 | ia << 8 | ib << 16 | ic << 24; // (t < 96; at < 96 * PIECES: each (t, p) once)
+						}
+						queued += (uint32_t)__builtin_popcountll(q);
+					}
 				}
-				queued += (uint32_t)__builtin_popcountll(q);
 			}
 			rd_lds_order();
 
@@ -149,8 +217,21 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(RasterArgs a)
 			{
 				const uint32_t e = queue[k];
 				RdTri tri;
-				rd_setup(vtx, e >> 8 & 0xffu, e >> 16 & 0xffu, e >> 24, ve, bothFaces, W, H, tri); // (true: it was queued)
-				const uint32_t id = index << 7 | (e & 0xffu);
+				uint32_t id;
+				if constexpr (CLIP)
+				{
+					const uint32_t ia = e >> 8 & 0xffu, ib = e >> 16 & 0xffu, ic = e >> 24; // (< ve: it was queued)
+					const bool second = (e & 0x80u) != 0u;
+					int4 p0, p1, p2, p3;
+					rd_clip(a.globals, vtx[ia], vtx[ib], vtx[ic], cvx[ia], cvx[ib], cvx[ic], H, p0, p1, p2, p3);
+					rd_setup_corners(p0, rd_sel(second, p2, p1), rd_sel(second, p3, p2), bothFaces, W, H, tri); // (true: it was queued)
+					id = index << 7 | (e & 0x7fu);
+				}
+				else
+				{
+					rd_setup(vtx, e >> 8 & 0xffu, e >> 16 & 0xffu, e >> 24, ve, bothFaces, W, H, tri); // (true: it was queued)
+					id = index << 7 | (e & 0xffu);
+				}
 				const uint32_t sw = (uint32_t)(tri.x1 - tri.x0) / 8u + 1u, sh = (uint32_t)(tri.y1 - tri.y0) / 8u + 1u;
 				const int32_t lx = (int32_t)(lane & 7u), ly = (int32_t)(lane >> 3);
 				for (uint32_t sy = 0; sy < sh; ++sy)
@@ -221,10 +302,13 @@ int launch_raster_totals(hipStream_t stream, const unsigned long long* partials,
 	return (int)hipGetLastError();
 }
 
-int launch_rasterdepth(hipStream_t stream, const RasterArgs& a, uint32_t gridBlocks)
+int launch_rasterdepth(hipStream_t stream, const RasterArgs& a, uint32_t gridBlocks, bool nearClip)
 {
 	gridBlocks = gridBlocks / 8 * RD_BLOCKS_PER_CU; // the caller passes 8 workgroups per CU, the size of `partials`
-	hipLaunchKernelGGL(rasterdepth_kernel, dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
+	if (nearClip)
+		hipLaunchKernelGGL(rasterdepth_kernel<true>, dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
+	else
+		hipLaunchKernelGGL(rasterdepth_kernel<false>, dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
 	hipError_t e = hipGetLastError();
 	if (e != hipSuccess || !a.totals)
 		return (int)e;

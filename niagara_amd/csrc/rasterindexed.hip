@@ -16,6 +16,9 @@
 //      64-wide search over those ends, and walks chunk after chunk with lane = triangle: 3 index loads, 3 corner transforms (no vertex
 //      cache), setup; a small triangle is walked by its own lane, a large one queued in LDS (its three snapped corners) and walked by
 //      the wave in 8 x 8 stamps, as in rasterdepth.hip.
+// CLIP (NV_OPT_RASTER_NEAR_CLIP 1) is a second instantiation of the raster kernel: the corners' clip coordinates stay in registers, a triangle
+// that crosses the near plane becomes one or two pieces (raster.h: rd_clip), and the chunk's first pieces, then its second pieces, take the
+// road the triangles take (the queue is drained after each, so it stays at 64 entries).  CLIP = false is the kernel without any of it.
 // Chunk positions are 32-bit and saturate: one launch draws at most 2^32 - 1 chunks (2.7e11 triangles); triangles past that are not drawn.
 #include "raster.h"
 
@@ -203,9 +206,10 @@ NV_DEV uint32_t ri_find(const RasterIndexedArgs& a, uint32_t k, uint32_t lo, uin
 	}
 }
 
+template <bool CLIP>
 __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(RasterIndexedArgs a)
 {
-	__shared__ int4 s_queue[RI_WAVES][RI_CHUNK][3]; // large triangles of the current chunk: their snapped corners
+	__shared__ int4 s_queue[RI_WAVES][RI_CHUNK][3]; // large pieces of the current chunk (one piece number at a time): their snapped corners
 
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -248,61 +252,138 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(RasterIndexed
 
 		// ---- lane = triangle: indices, corners (mesh.vert.glsl:41-57, per corner), setup; small ones walked here, large ones queued
 		const uint32_t t = (k - cmdBegin) * RI_CHUNK + lane; // (a command has < 2^26 chunks)
-		RdTri tri;
-		bool live = false, large = false;
-		int4 ca = make_int4(0, 0, 0, 1), cb = ca, cc = ca;
-		if (t < tris)
+		// The two branches repeat each other's text on purpose: written as one loop over pieces, the CLIP = false instantiation compiles to other
+		// code than the kernel had before the option (other registers, other schedule); kept apart, it is that kernel instruction for instruction.
+		if constexpr (!CLIP)
 		{
-			const unsigned long long at = (unsigned long long)firstIndex + 3ull * t; // at + 2 < indexCapacity (ri_triangles)
-			const uint32_t va = a.indices[at] + vertexOffset, vb = a.indices[at + 1] + vertexOffset, vc = a.indices[at + 2] + vertexOffset;
-			if (va < a.vertexCapacity && vb < a.vertexCapacity && vc < a.vertexCapacity) // (0xFFFFFFFF included: no primitive restart)
+			RdTri tri;
+			bool live = false, large = false;
+			int4 ca = make_int4(0, 0, 0, 1), cb = ca, cc = ca;
+			if (t < tris)
 			{
-				ca = rd_vertex(a.globals, *reinterpret_cast<const uint2*>(a.vertices + va), q, qw, scale, px, py, pz, H);
-				cb = rd_vertex(a.globals, *reinterpret_cast<const uint2*>(a.vertices + vb), q, qw, scale, px, py, pz, H);
-				cc = rd_vertex(a.globals, *reinterpret_cast<const uint2*>(a.vertices + vc), q, qw, scale, px, py, pz, H);
-				live = rd_setup_corners(ca, cb, cc, bothFaces, W, H, tri);
-			}
-		}
-		if (live)
-		{
-			drawn += 1;
-			if (tri.x0 <= tri.x1 && tri.y0 <= tri.y1)
-			{
-				const uint32_t boxPixels = (uint32_t)(tri.x1 - tri.x0 + 1) * (uint32_t)(tri.y1 - tri.y0 + 1);
-				large = boxPixels > a.smallLimit;
-				if (!large)
-					for (int32_t y = tri.y0; y <= tri.y1; ++y)
-						for (int32_t x = tri.x0; x <= tri.x1; ++x)
-							samples += rd_sample(tri, x, y, a.width, a.depth, nullptr, 0u) ? 1u : 0u;
-			}
-		}
-		const uint64_t qb = __ballot(large);
-		rd_lds_order(); // the previous chunk's queue readers are done
-		if (large)
-		{
-			const uint32_t slot = (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(qb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)qb, 0u));
-			queue[slot][0] = ca;
-			queue[slot][1] = cb;
-			queue[slot][2] = cc;
-		}
-		rd_lds_order();
-
-		// ---- large triangles, the whole wave: lane = pixel of an 8 x 8 stamp
-		const uint32_t queued = (uint32_t)__builtin_popcountll(qb);
-		for (uint32_t e = 0; e < queued; ++e)
-		{
-			RdTri tq;
-			rd_setup_corners(queue[e][0], queue[e][1], queue[e][2], bothFaces, W, H, tq); // (true: it was queued; same inputs, same bits)
-			const uint32_t sw = (uint32_t)(tq.x1 - tq.x0) / 8u + 1u, sh = (uint32_t)(tq.y1 - tq.y0) / 8u + 1u;
-			const int32_t lx = (int32_t)(lane & 7u), ly = (int32_t)(lane >> 3);
-			for (uint32_t sy = 0; sy < sh; ++sy)
-			{
-				const int32_t y = tq.y0 + (int32_t)sy * 8 + ly;
-				for (uint32_t sx = 0; sx < sw; ++sx)
+				const unsigned long long at = (unsigned long long)firstIndex + 3ull * t; // at + 2 < indexCapacity (ri_triangles)
+				const uint32_t va = a.indices[at] + vertexOffset, vb = a.indices[at + 1] + vertexOffset, vc = a.indices[at + 2] + vertexOffset;
+				if (va < a.vertexCapacity && vb < a.vertexCapacity && vc < a.vertexCapacity) // (0xFFFFFFFF included: no primitive restart)
 				{
-					const int32_t x = tq.x0 + (int32_t)sx * 8 + lx;
-					if (x <= tq.x1 && y <= tq.y1)
-						samples += rd_sample(tq, x, y, a.width, a.depth, nullptr, 0u) ? 1u : 0u;
+					ca = rd_vertex(a.globals, *reinterpret_cast<const uint2*>(a.vertices + va), q, qw, scale, px, py, pz, H);
+					cb = rd_vertex(a.globals, *reinterpret_cast<const uint2*>(a.vertices + vb), q, qw, scale, px, py, pz, H);
+					cc = rd_vertex(a.globals, *reinterpret_cast<const uint2*>(a.vertices + vc), q, qw, scale, px, py, pz, H);
+					live = rd_setup_corners(ca, cb, cc, bothFaces, W, H, tri);
+				}
+			}
+			if (live)
+			{
+				drawn += 1;
+				if (tri.x0 <= tri.x1 && tri.y0 <= tri.y1)
+				{
+					const uint32_t boxPixels = (uint32_t)(tri.x1 - tri.x0 + 1) * (uint32_t)(tri.y1 - tri.y0 + 1);
+					large = boxPixels > a.smallLimit;
+					if (!large)
+						for (int32_t y = tri.y0; y <= tri.y1; ++y)
+							for (int32_t x = tri.x0; x <= tri.x1; ++x)
+								samples += rd_sample(tri, x, y, a.width, a.depth, nullptr, 0u) ? 1u : 0u;
+				}
+			}
+			const uint64_t qb = __ballot(large);
+			rd_lds_order(); // the previous chunk's queue readers are done
+			if (large)
+			{
+				const uint32_t slot = (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(qb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)qb, 0u));
+				queue[slot][0] = ca;
+				queue[slot][1] = cb;
+				queue[slot][2] = cc;
+			}
+			rd_lds_order();
+
+			// ---- large triangles, the whole wave: lane = pixel of an 8 x 8 stamp
+			const uint32_t queued = (uint32_t)__builtin_popcountll(qb);
+			for (uint32_t e = 0; e < queued; ++e)
+			{
+				RdTri tq;
+				rd_setup_corners(queue[e][0], queue[e][1], queue[e][2], bothFaces, W, H, tq); // (true: it was queued; same inputs, same bits)
+				const uint32_t sw = (uint32_t)(tq.x1 - tq.x0) / 8u + 1u, sh = (uint32_t)(tq.y1 - tq.y0) / 8u + 1u;
+				const int32_t lx = (int32_t)(lane & 7u), ly = (int32_t)(lane >> 3);
+				for (uint32_t sy = 0; sy < sh; ++sy)
+				{
+					const int32_t y = tq.y0 + (int32_t)sy * 8 + ly;
+					for (uint32_t sx = 0; sx < sw; ++sx)
+					{
+						const int32_t x = tq.x0 + (int32_t)sx * 8 + lx;
+						if (x <= tq.x1 && y <= tq.y1)
+							samples += rd_sample(tq, x, y, a.width, a.depth, nullptr, 0u) ? 1u : 0u;
+					}
+				}
+			}
+		}
+		else
+		{
+			uint32_t pieces = 0;
+			int4 p0 = make_int4(0, 0, 0, 1), p1 = p0, p2 = p0, p3 = p0;
+			if (t < tris)
+			{
+				const unsigned long long at = (unsigned long long)firstIndex + 3ull * t; // at + 2 < indexCapacity (ri_triangles)
+				const uint32_t va = a.indices[at] + vertexOffset, vb = a.indices[at + 1] + vertexOffset, vc = a.indices[at + 2] + vertexOffset;
+				if (va < a.vertexCapacity && vb < a.vertexCapacity && vc < a.vertexCapacity) // (0xFFFFFFFF included: no primitive restart)
+				{
+					const uint2 ra = *reinterpret_cast<const uint2*>(a.vertices + va), rb = *reinterpret_cast<const uint2*>(a.vertices + vb);
+					const uint2 rc = *reinterpret_cast<const uint2*>(a.vertices + vc);
+					float4 ka, kb, kc;
+					const int4 ca = rd_vertex_clip(a.globals, ra, q, qw, scale, px, py, pz, H, ka);
+					const int4 cb = rd_vertex_clip(a.globals, rb, q, qw, scale, px, py, pz, H, kb);
+					const int4 cc = rd_vertex_clip(a.globals, rc, q, qw, scale, px, py, pz, H, kc);
+					pieces = rd_clip(a.globals, ca, cb, cc, ka, kb, kc, H, p0, p1, p2, p3);
+				}
+			}
+			for (uint32_t p = 0; p < 2u; ++p)
+			{
+				if (!__ballot(p < pieces)) // (wave-uniform)
+					break;
+				RdTri tri;
+				bool large = false;
+				const int4 cb = rd_sel(p != 0u, p2, p1), cc = rd_sel(p != 0u, p3, p2);
+				const bool live = p < pieces && rd_setup_corners(p0, cb, cc, bothFaces, W, H, tri);
+				if (live)
+				{
+					drawn += 1;
+					if (tri.x0 <= tri.x1 && tri.y0 <= tri.y1)
+					{
+						const uint32_t boxPixels = (uint32_t)(tri.x1 - tri.x0 + 1) * (uint32_t)(tri.y1 - tri.y0 + 1);
+						large = boxPixels > a.smallLimit;
+						if (!large)
+							for (int32_t y = tri.y0; y <= tri.y1; ++y)
+								for (int32_t x = tri.x0; x <= tri.x1; ++x)
+									samples += rd_sample(tri, x, y, a.width, a.depth, nullptr, 0u) ? 1u : 0u;
+					}
+				}
+				const uint64_t qb = __ballot(large);
+				rd_lds_order(); // the previous queue's readers are done
+				if (large)
+				{
+					const uint32_t slot = (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(qb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)qb, 0u));
+					queue[slot][0] = p0;
+					queue[slot][1] = cb;
+					queue[slot][2] = cc;
+				}
+				rd_lds_order();
+
+				// ---- large pieces, the whole wave: lane = pixel of an 8 x 8 stamp
+				const uint32_t queued = (uint32_t)__builtin_popcountll(qb);
+				for (uint32_t e = 0; e < queued; ++e)
+				{
+					RdTri tq;
+					rd_setup_corners(queue[e][0], queue[e][1], queue[e][2], bothFaces, W, H, tq); // (true: it was queued; same inputs, same bits)
+					const uint32_t sw = (uint32_t)(tq.x1 - tq.x0) / 8u + 1u, sh = (uint32_t)(tq.y1 - tq.y0) / 8u + 1u;
+					const int32_t lx = (int32_t)(lane & 7u), ly = (int32_t)(lane >> 3);
+					for (uint32_t sy = 0; sy < sh; ++sy)
+					{
+						const int32_t y = tq.y0 + (int32_t)sy * 8 + ly;
+						for (uint32_t sx = 0; sx < sw; ++sx)
+						{
+							const int32_t x = tq.x0 + (int32_t)sx * 8 + lx;
+							if (x <= tq.x1 && y <= tq.y1)
+								samples += rd_sample(tq, x, y, a.width, a.depth, nullptr, 0u) ? 1u : 0u;
+						}
+					}
 				}
 			}
 		}
@@ -333,7 +414,7 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(RasterIndexed
 	}
 }
 
-int launch_rasterindexed(hipStream_t stream, RasterIndexedArgs a, void* scratch, uint32_t gridBlocks)
+int launch_rasterindexed(hipStream_t stream, RasterIndexedArgs a, void* scratch, uint32_t gridBlocks, bool nearClip)
 {
 	a.blockTotals = static_cast<unsigned long long*>(scratch);
 	a.blockChunks = reinterpret_cast<uint32_t*>(a.blockTotals + RI_SCAN_BLOCKS * 2);
@@ -344,7 +425,10 @@ int launch_rasterindexed(hipStream_t stream, RasterIndexedArgs a, void* scratch,
 	hipLaunchKernelGGL(ri_count_kernel, dim3(a.scanBlocks), dim3(RI_THREADS), 0, stream, a);
 	hipLaunchKernelGGL(ri_scan_kernel, dim3(1), dim3(RI_THREADS), 0, stream, a);
 	gridBlocks = gridBlocks / 8 * RI_BLOCKS_PER_CU; // the caller passes 8 workgroups per CU, the size of `partials`
-	hipLaunchKernelGGL(rasterindexed_kernel, dim3(gridBlocks), dim3(RI_THREADS), 0, stream, a);
+	if (nearClip)
+		hipLaunchKernelGGL(rasterindexed_kernel<true>, dim3(gridBlocks), dim3(RI_THREADS), 0, stream, a);
+	else
+		hipLaunchKernelGGL(rasterindexed_kernel<false>, dim3(gridBlocks), dim3(RI_THREADS), 0, stream, a);
 	hipError_t e = hipGetLastError();
 	if (e != hipSuccess || !a.totals)
 		return (int)e;

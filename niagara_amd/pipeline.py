@@ -45,6 +45,7 @@ NV_OPT_CULL_RING = 6
 NV_OPT_TASK_EMIT = 7
 NV_OPT_DRAW_RECORDS = 8
 NV_OPT_RASTER_SMALL_LIMIT = 9
+NV_OPT_RASTER_NEAR_CLIP = 10
 
 
 class Context:
@@ -219,8 +220,12 @@ class VisibilityPipeline:
     """niagara's GPU-driven visibility front-end for one scene on one device."""
 
     def __init__(self, meshes, meshlets, draws, depth_size, ctx=None, task_capacity=None, cluster_capacity=None, use_soa=True, fused=False,
-                 meshlet_data=None, vertices=None, indices=None):
+                 meshlet_data=None, vertices=None, indices=None, near_clip=False):
         self.ctx = ctx or Context()
+        # near_clip=True: both depth rasterisers clip triangles at the near plane instead of dropping them (NV_OPT_RASTER_NEAR_CLIP), so
+        # that surfaces the camera stands on or next to occlude in frame()'s late passes
+        self.near_clip = bool(near_clip)
+        self.ctx.set_option(NV_OPT_RASTER_NEAR_CLIP, int(self.near_clip))
         # fused=True: the passes absorb the count-word resets and the tasksubmit / clustersubmit fix-ups (same buffer
         # contents, four launches less per phase); fused=False issues the reference's dispatch sequence one to one
         self.fused = bool(fused)

@@ -306,3 +306,93 @@ def occluder_scene_indexed(**kw):
     s = occluder_scene(**kw)
     indices, meshes = indexed_geometry(s["meshes"], s["meshlets"], s["data"])
     return dict(s, meshes=meshes, indices=indices)
+
+
+def _pack_meshes(parts, meshlet_bounds):
+    """(positions, [triangles per meshlet], shortRefs) per mesh -> (meshes, meshlets, meshlet data, vertices) with one LOD each, as
+    occluder_scene lays them out; meshlet bounds by `meshlet_bounds(vertices, data, meshlets)` (in place)"""
+    meshes = np.zeros(len(parts), dtype=L.MESH)
+    meshlet_list, words, vertices = [], [], []
+    vbase = 0
+    for mi, (pos, groups, short) in enumerate(parts):
+        h = pos.astype(np.float16)
+        v = np.zeros(len(pos), dtype=L.VERTEX)
+        v["vx"], v["vy"], v["vz"] = (h[:, k].view(np.uint16) for k in range(3))
+        vertices.append(v)
+        center, radius = host.mesh_bounds(h.astype(np.float32))
+        meshes[mi]["center"], meshes[mi]["radius"] = center, radius
+        meshes[mi]["vertexOffset"], meshes[mi]["vertexCount"] = vbase, len(pos)
+        meshes[mi]["lodCount"] = 1
+        lod = meshes[mi]["lods"][0]
+        lod["meshletOffset"], lod["meshletCount"], lod["indexCount"] = len(meshlet_list), len(groups), 3 * sum(len(g) for g in groups)
+        for tris in groups:
+            t = np.asarray(tris, np.uint32)
+            used = np.unique(t)
+            local = np.searchsorted(used, t).astype(np.uint8)
+            assert len(used) <= 64 and len(t) <= 96
+            m = np.zeros(1, dtype=L.MESHLET)
+            m["dataOffset"] = sum(len(w) for w in words)
+            m["baseVertex"] = vbase
+            m["vertexCount"], m["triangleCount"], m["shortRefs"] = len(used), len(t), short
+            refs = used.astype(np.uint16 if short else np.uint32)
+            if short and len(refs) % 2:
+                refs = np.append(refs, np.uint16(0))
+            idx = local.reshape(-1)
+            idx = np.append(idx, np.zeros((-len(idx)) % 4, np.uint8))
+            words.append(np.concatenate([refs.view(np.uint32), idx.view(np.uint32)]))
+            meshlet_list.append(m)
+        vbase += len(pos)
+    meshlets = np.concatenate(meshlet_list)
+    data = np.concatenate(words + [np.zeros(4, np.uint32)]).astype(np.uint32)
+    vertices = np.concatenate(vertices)
+    meshlet_bounds(vertices, data, meshlets)
+    return meshes, meshlets, data, vertices
+
+
+def interior_scene(viewport=(320, 192), half=30.0, eye_height=1.5, wall_x=1.5, below=4, behind=4, open_=4, box_scale=0.5, seed=7,
+                   meshlet_bounds=None):
+    """The camera inside the geometry, for the closed loop with near-plane clipping (NV_OPT_RASTER_NEAR_CLIP): niagara's default camera
+    (origin, looking down -z) stands `eye_height` above a floor and `wall_x` to the left of a wall.  Both are one coarse grid (4 x 4 quads in
+    meshlets of 2 x 2) of half-extent `half` centred under / beside the camera, so every triangle between the camera and 15 units ahead
+    crosses the near plane: without clipping only the far half of either surface is drawn.  `below` closed boxes lie 3.5 units under the
+    floor and `behind` as far behind the wall, 9 to 13 units ahead: inside the frustum, close enough that the undrawn part is what hides
+    them, and deep enough that the 2 x 2 pyramid texels of their test (up to twice the size of the sphere's box) still see only the surface
+    in front of them.  `open_` boxes stand on the open side.  `meshlet_bounds(vertices, data, meshlets)` fills the bounds in place (oracle.meshlet_bounds; required here: no device is
+    opened).  Returns occluder_scene's dict with the draw ids of "surfaces", "hidden" (below + behind) and "open"."""
+    if meshlet_bounds is None:
+        raise ValueError("interior_scene needs meshlet_bounds= (oracle.meshlet_bounds)")
+    rng = np.random.default_rng(seed)
+    grid_pos, grid_tris = _grid_meshlets(4, 4, 2)
+    box_pos, box_tris = _box_faces(2)
+    meshes, meshlets, data, vertices = _pack_meshes(((grid_pos, grid_tris, 0), (box_pos, box_tris, 1)), meshlet_bounds)
+    n = 2 + below + behind + open_
+    draws = np.zeros(n, dtype=L.MESHDRAW)
+    draws["orientation"] = (0.0, 0.0, 0.0, 1.0)
+    r = np.float32(np.sqrt(0.5))
+    # the grid faces +z: about x by -90 degrees it faces +y (the floor), about y by -90 degrees it faces -x (the wall, seen from the camera)
+    draws[0]["position"], draws[0]["scale"], draws[0]["orientation"] = (0.0, -eye_height, 0.0), half, (-r, 0.0, 0.0, r)
+    draws[1]["position"], draws[1]["scale"], draws[1]["orientation"] = (wall_x, 0.0, 0.0), half, (0.0, -r, 0.0, r)
+    for i in range(2, n):
+        draws[i]["meshIndex"], draws[i]["scale"] = 1, box_scale
+        z = -rng.uniform(9.0, 13.0)
+        if i < 2 + below:
+            pos = (rng.uniform(-3.0, 0.5), -eye_height - 3.5, z)
+        elif i < 2 + below + behind:
+            pos = (wall_x + 3.5, rng.uniform(0.5, 2.0), z)
+        else:
+            pos = (rng.uniform(-7.0, -1.0), rng.uniform(0.5, 2.0), z)
+        draws[i]["position"] = pos
+    slots, _ = host.assign_visibility_offsets(draws, meshes)
+    pw, ph = host.previous_pow2(viewport[0]), host.previous_pow2(viewport[1])
+    cd = host.build_cull_data(viewport=viewport, pyramid=(pw, ph), draw_count=n, cullingEnabled=1, lodEnabled=1, occlusionEnabled=1,
+                              clusterOcclusionEnabled=1, clusterBackfaceEnabled=1)
+    return dict(meshes=meshes, meshlets=meshlets, draws=draws, data=data, vertices=vertices, cull=cd, viewport=viewport, slots=slots,
+                surfaces=[0, 1], hidden=list(range(2, 2 + below + behind)), open=list(range(2 + below + behind, n)))
+
+
+def interior_scene_indexed(**kw):
+    """interior_scene(**kw) for the classic path: the same scene plus its index buffer ("indices") and the meshes with their LODs' index
+    ranges set (indexed_geometry)"""
+    s = interior_scene(**kw)
+    indices, meshes = indexed_geometry(s["meshes"], s["meshlets"], s["data"])
+    return dict(s, meshes=meshes, indices=indices)

@@ -5,8 +5,10 @@ synth.occluder_scene (VisibilityPipeline.frame) against the same frame reduced f
 --only indexed: nv_rasterdepth_indexed on the kitten x 1024 draws at 1024 x 768, the same kitten geometry meshletised
 (tests/meshlet_builder.py) through nv_rasterdepth on the same context, one 120 k-triangle draw, and the classic closed-loop frame
 (VisibilityPipeline.frame(task=False)) on synth.occluder_scene_indexed.
+--near-clip: the same workloads with NV_OPT_RASTER_NEAR_CLIP 1 (triangles crossing the near plane are clipped, not dropped).  --only loop also
+times synth.interior_scene (the camera inside the geometry) with and without clipping, whatever the switch.
 
-    python tools/bench_raster.py [--iters N] [--only raster|loop|indexed] [--limits 0,16,...]
+    python tools/bench_raster.py [--iters N] [--only raster|loop|indexed] [--limits 0,16,...] [--near-clip]
 Kernel-trace times: rocprofv3 --kernel-trace --stats -d OUT -o raster -- python tools/bench_raster.py --only raster
 Prints one JSON object."""
 import argparse
@@ -120,14 +122,40 @@ def _lists(pipe):
     return int(c4[0]), int(cc4[0])
 
 
-def bench_loop(iters):
+def bench_interior(iters):
+    """the closed-loop frame of synth.interior_scene with and without near-plane clipping, task and classic path: frame time, and what the late
+    pass rejects"""
+    s = synth.interior_scene_indexed(meshlet_bounds=oracle.meshlet_bounds)
+    out = {}
+    for task in (True, False):
+        for near_clip in (False, True):
+            pipe = P.VisibilityPipeline(s["meshes"], s["meshlets"], s["draws"], s["viewport"], task_capacity=4096, cluster_capacity=4096 * 64, fused=True,
+                                        meshlet_data=s["data"], vertices=s["vertices"], indices=s["indices"], near_clip=near_clip)
+            for _ in range(4):
+                pipe.frame(s["cull"], task=task)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                pipe.frame(s["cull"], task=task)
+            torch.cuda.synchronize()
+            us = (time.perf_counter() - t0) / iters * 1e6
+            dvb = pipe.dvb.cpu().numpy()
+            late = _lists(pipe)
+            out["%s_%s" % ("cluster" if task else "classic", "clip" if near_clip else "noclip")] = dict(
+                frame_us=us, draws=len(s["draws"]), draws_rejected=len(s["draws"]) - int(dvb.sum()), hidden_boxes_visible=int(dvb[s["hidden"]].sum()),
+                late_commands=late[0], late_meshlets=late[1] if task else None, depth_covered=float((pipe.depth > 0).float().mean().item()))
+            pipe.ctx.close()
+    return out
+
+
+def bench_loop(iters, near_clip=False):
     s = synth.occluder_scene(meshlet_bounds=oracle.meshlet_bounds)
     cd = s["cull"]
     w, h = s["viewport"]
     out = {}
     for mode in ("raster", "synthetic"):
         pipe = P.VisibilityPipeline(s["meshes"], s["meshlets"], s["draws"], s["viewport"], task_capacity=4096, cluster_capacity=4096 * 64, fused=True,
-                                    meshlet_data=s["data"], vertices=s["vertices"])
+                                    meshlet_data=s["data"], vertices=s["vertices"], near_clip=near_clip)
         synth_depth = torch.from_numpy(synth.make_depth(w, h)).to(pipe.ctx.device)
 
         def frame():
@@ -165,6 +193,7 @@ def bench_loop(iters):
                          late_commands=late[0], late_meshlets=late[1], visible_draws_after_late=visible,
                          draws_rejected=len(s["draws"]) - visible, hidden_boxes_visible=int(pipe.dvb.cpu().numpy()[s["hidden"]].sum()))
         pipe.ctx.close()
+    out["interior"] = bench_interior(iters)
     return out
 
 
@@ -191,10 +220,11 @@ def _rates(med, tot):
                 totals=dict(first=tot[0], triangles=tot[1], rasterised=tot[2], samples=tot[3]))
 
 
-def bench_indexed(iters):
+def bench_indexed(iters, near_clip=False):
     import meshlet_builder
     import raster_indexed_ref as RI
     ctx = P.Context()
+    ctx.set_option(P.NV_OPT_RASTER_NEAR_CLIP, int(near_clip))
     dev = ctx.device
     out = {}
     # kitten x 1024 (BASELINE config 1's draws), every draw one command
@@ -270,7 +300,7 @@ def bench_indexed(iters):
     s = synth.occluder_scene_indexed(meshlet_bounds=oracle.meshlet_bounds)
     for task in (False, True):
         pipe = P.VisibilityPipeline(s["meshes"], s["meshlets"], s["draws"], s["viewport"], task_capacity=4096, cluster_capacity=4096 * 64, fused=True,
-                                    meshlet_data=s["data"], vertices=s["vertices"], indices=s["indices"])
+                                    meshlet_data=s["data"], vertices=s["vertices"], indices=s["indices"], near_clip=near_clip)
         for _ in range(4):
             pipe.frame(s["cull"], task=task)
         torch.cuda.synchronize()
@@ -292,16 +322,18 @@ def main():
     ap.add_argument("--only", choices=("raster", "loop", "indexed"), default=None)
     ap.add_argument("--limits", default="0,4,9,16,32,64,%d" % INT_MAX)
     ap.add_argument("--no-split", action="store_true")
+    ap.add_argument("--near-clip", action="store_true", help="NV_OPT_RASTER_NEAR_CLIP 1 on every context")
     a = ap.parse_args()
-    res = {}
+    res = dict(near_clip=bool(a.near_clip))
     if a.only in (None, "raster"):
         ctx = P.Context()
+        ctx.set_option(P.NV_OPT_RASTER_NEAR_CLIP, int(a.near_clip))
         res["raster"] = bench_raster(ctx, a.iters, [int(x) for x in a.limits.split(",")], split=not a.no_split)
         ctx.close()
     if a.only in (None, "loop"):
-        res["loop"] = bench_loop(a.iters)
+        res["loop"] = bench_loop(a.iters, a.near_clip)
     if a.only in (None, "indexed"):
-        res["indexed"] = bench_indexed(a.iters)
+        res["indexed"] = bench_indexed(a.iters, a.near_clip)
     print(json.dumps(res))
 
 
