@@ -485,6 +485,21 @@ int nv_rasterdepth_indexed(nv_context* ctx, void* stream, const NvGlobals* globa
 int nv_depthreduce(nv_context* ctx, void* stream, const float* d_depth, uint32_t width, uint32_t height,
                    const NvPyramidDesc* pyramid);
 
+/* ---- depth composite of a sharded frame (the reference has one device and no such step) ----
+ * d_dst[i] = max(d_dst[i], d_srcs[0][i], ..., d_srcs[sources - 1][i]) for the width x height texels of tightly packed fp32 targets, the
+ * maximum taken on the BIT PATTERNS as unsigned 32-bit integers.  For the depth the rasterisers write (reverse-Z, [0, 1], far = 0) that is
+ * the maximum of the floats and the rule of their atomics, and it is exact, commutative and associative: shards that each rasterised a
+ * part of the draws composite to the bits one pass over all draws writes, in any order and grouping.  Nothing else is special-cased: -0.0,
+ * negative values and NaNs order by their bits (any pattern with the sign bit set is above every positive float, a NaN above infinity of
+ * its sign), denormals are kept as they are.
+ * d_srcs is a HOST array of `sources` device pointers (a pointer list, not base + stride: the targets of several contexts or a receive
+ * buffer are separate allocations); it is read during the call only.  Enqueues only (sources / 8 rounded up launches), so it can be
+ * captured.  NV_EINVAL: a NULL argument or list entry, sources == 0, width or height 0 or above 16384, a pointer that is not 4-byte
+ * aligned, a source equal to d_dst.  A source that overlaps d_dst partially is the caller's error; sources may repeat or overlap each
+ * other.  16-byte aligned pointers (any fresh allocation) take 16-byte loads and stores. */
+int nv_depth_merge(nv_context* ctx, void* stream, float* d_dst, const float* const* d_srcs, uint32_t sources, uint32_t width,
+                   uint32_t height);
+
 /* ---- host helpers mirroring src/niagara.cpp / src/resources.cpp (no device work) ---- */
 uint32_t nv_previous_pow2(uint32_t v);                        /* src/niagara.cpp:439-447 */
 uint32_t nv_image_mip_levels(uint32_t width, uint32_t height); /* src/resources.cpp:280-292 */

@@ -44,6 +44,7 @@ int launch_cluster_expand(hipStream_t, const NvMeshTaskCommand*, const NvMeshlet
 int launch_clustersubmit(hipStream_t, uint32_t* cc4, uint32_t* clusterIndices);
 int launch_pack_counts(hipStream_t, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*);
 int launch_depthreduce(hipStream_t, const float* depth, uint32_t w, uint32_t h, const NvPyramidDesc& pyr);
+int launch_depth_merge(hipStream_t, float* dst, const float* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks);
 int launch_trianglecull(hipStream_t, const TriangleArgs& a, uint32_t gridBlocks);
 int launch_rasterdepth(hipStream_t, const RasterArgs& a, uint32_t gridBlocks, bool nearClip);
 int launch_rasterindexed(hipStream_t, RasterIndexedArgs a, void* scratch, uint32_t gridBlocks, bool nearClip);
@@ -1202,6 +1203,18 @@ int nv_depthreduce(nv_context* ctx, void* stream, const float* d_depth, uint32_t
 	int rc = nv::launch_depthreduce((hipStream_t)stream, d_depth, width, height, *pyramid);
 	prof_push(ctx, NV_PROF_DEPTHREDUCE, e0, prof_mark(ctx, (hipStream_t)stream));
 	return rc;
+}
+
+int nv_depth_merge(nv_context* ctx, void* stream, float* d_dst, const float* const* d_srcs, uint32_t sources, uint32_t width, uint32_t height)
+{
+	if (!ctx || !d_dst || !d_srcs || sources == 0 || width == 0 || height == 0 || width > 16384 || height > 16384 ||
+	    (reinterpret_cast<uintptr_t>(d_dst) & 3u))
+		return NV_EINVAL;
+	for (uint32_t i = 0; i < sources; ++i)
+		if (!d_srcs[i] || d_srcs[i] == d_dst || (reinterpret_cast<uintptr_t>(d_srcs[i]) & 3u))
+			return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_depth_merge((hipStream_t)stream, d_dst, d_srcs, sources, width * height, persistent_grid(ctx, 8));
 }
 
 #ifdef NV_EXPERIMENTS

@@ -184,6 +184,12 @@ class Context:
                                          int(index_capacity), _ptr(vertices), int(vertex_capacity), _ptr(depth), int(width), int(height), _ptr(totals4)),
               "nv_rasterdepth_indexed")
 
+    def depth_merge(self, dst, srcs, width, height):
+        """dst = element-wise maximum of dst and every target of `srcs` on the bit patterns (nv_depth_merge): the depth composite of shards
+        that live on one device, and the fold of a received target into the local one"""
+        ptrs = (C.c_void_p * len(srcs))(*[None if t is None else t.data_ptr() for t in srcs])
+        check(lib.nv_depth_merge(self.h, _stream(), _ptr(dst), ptrs if len(srcs) else None, len(srcs), int(width), int(height)), "nv_depth_merge")
+
     def depthreduce(self, depth, width, height, pyramid):
         check(lib.nv_depthreduce(self.h, _stream(), _ptr(depth), width, height, C.byref(pyramid)), "nv_depthreduce")
 
@@ -220,8 +226,10 @@ class VisibilityPipeline:
     """niagara's GPU-driven visibility front-end for one scene on one device."""
 
     def __init__(self, meshes, meshlets, draws, depth_size, ctx=None, task_capacity=None, cluster_capacity=None, use_soa=True, fused=False,
-                 meshlet_data=None, vertices=None, indices=None, near_clip=False):
+                 meshlet_data=None, vertices=None, indices=None, near_clip=False, share=None):
         self.ctx = ctx or Context()
+        # share: a pipeline of the SAME scene on the same device whose scene buffers (meshes, meshlets, draws, geometry) and library
+        # mirrors this one uses instead of uploading its own (nv_share_scene); everything a pass writes stays this pipeline's own
         # near_clip=True: both depth rasterisers clip triangles at the near plane instead of dropping them (NV_OPT_RASTER_NEAR_CLIP), so
         # that surfaces the camera stands on or next to occlude in frame()'s late passes
         self.near_clip = bool(near_clip)
@@ -235,9 +243,12 @@ class VisibilityPipeline:
         self.mesh_count, self.meshlet_count, self.draw_count = len(meshes), len(meshlets), len(draws)
         self.draws_host = draws.copy()
         self.slots, self.post_mask = host.assign_visibility_offsets(self.draws_host, meshes)  # src/niagara.cpp:1002-1020
-        self.mb = to_device(meshes, dev)
-        self.mlb = to_device(meshlets, dev)
-        self.db = to_device(self.draws_host, dev)
+        if share is not None:
+            self.mb, self.mlb, self.db = share.mb, share.mlb, getattr(share, "db_all", share.db)
+        else:
+            self.mb = to_device(meshes, dev)
+            self.mlb = to_device(meshlets, dev)
+            self.db = to_device(self.draws_host, dev)
         self.dvb = torch.zeros(max(1, self.draw_count), dtype=torch.int32, device=dev)         # zeroed once (:1450-1457)
         self.mvb = torch.zeros(max(1, (self.slots + 31) // 32 + 2), dtype=torch.int32, device=dev)  # (:1459-1468)
         tcap = task_capacity or L.TASK_WGLIMIT
@@ -266,25 +277,32 @@ class VisibilityPipeline:
         self.depth_w, self.depth_h = depth_size
         self.pyramid = DepthPyramid(dev, *depth_size)
         self.ctx.reserve(self.draw_count, tcap)
-        self.ctx.upload_meshes(self.mb, self.mesh_count)
-        if use_soa and self.meshlet_count:
-            self.ctx.upload_meshlets(self.mlb, self.meshlet_count)
-        if use_soa and self.draw_count:
-            self.ctx.upload_draws(self.db, self.draw_count, self.mb)
+        if share is not None:
+            self.ctx.share_scene(share.ctx)
+        else:
+            self.ctx.upload_meshes(self.mb, self.mesh_count)
+            if use_soa and self.meshlet_count:
+                self.ctx.upload_meshlets(self.mlb, self.meshlet_count)
+            if use_soa and self.draw_count:
+                self.ctx.upload_draws(self.db, self.draw_count, self.mb)
         # geometry (meshlet payloads and / or the index buffer ib, + vertices, src/scene.cpp:24-47): with it the pipeline rasterises its own
         # depth target, through the clusters (meshlet_data) or through the indexed draws of the classic path (indices)
         self.mdb = self.vb = self.ib = self.depth = None
         self.index_count = self.vertex_count = 0
         if vertices is not None and (meshlet_data is not None or indices is not None):
-            self.vb = to_device(vertices, dev) if len(vertices) else torch.zeros(L.VERTEX.itemsize, dtype=torch.uint8, device=dev)
             self.vertex_count = len(vertices)
             self.depth = torch.zeros((self.depth_h, self.depth_w), dtype=torch.float32, device=dev)
-            if meshlet_data is not None:
-                self.mdb = to_device(meshlet_data, dev) if len(meshlet_data) else torch.zeros(4, dtype=torch.uint8, device=dev)
             if indices is not None:
-                ind = np.ascontiguousarray(indices, np.uint32)
-                self.ib = to_device(ind, dev) if len(ind) else torch.zeros(4, dtype=torch.uint8, device=dev)
-                self.index_count = len(ind)
+                self.index_count = len(indices)
+            if share is not None:
+                self.vb, self.mdb, self.ib = share.vb, share.mdb if meshlet_data is not None else None, share.ib if indices is not None else None
+            else:
+                self.vb = to_device(vertices, dev) if len(vertices) else torch.zeros(L.VERTEX.itemsize, dtype=torch.uint8, device=dev)
+                if meshlet_data is not None:
+                    self.mdb = to_device(meshlet_data, dev) if len(meshlet_data) else torch.zeros(4, dtype=torch.uint8, device=dev)
+                if indices is not None:
+                    ind = np.ascontiguousarray(indices, np.uint32)
+                    self.ib = to_device(ind, dev) if len(ind) else torch.zeros(4, dtype=torch.uint8, device=dev)
 
     # src/niagara.cpp:1530-1574
     def cull(self, cull_data, late, task=True, post_pass=0):
@@ -361,3 +379,164 @@ class VisibilityPipeline:
     def visible_clusters(self):
         n = int(self.ccb[0].item())
         return self.cib[:min(n, L.CLUSTER_LIMIT)].cpu().numpy().view(np.uint32), n
+
+
+class ShardedVisibilityPipeline(VisibilityPipeline):
+    """One rank's share of VisibilityPipeline.frame, sharded by a contiguous range of draws.
+
+    The scene is uploaded in full (draws replicated, no meshlet data exchanged); the passes run on d_draws + begin and
+    d_drawVisibility + begin with CullData.drawCount = end - begin, so the rank's commands carry rank-local drawIds, while
+    meshletVisibilityOffset stays the global prefix: the rank's full-size mvb only ever gets bits of its own draws.  After each phase's
+    raster the ranks' depth targets are composited (element-wise maximum, in place on every rank), so every rank builds the unsharded
+    frame's pyramid and takes the unsharded frame's decisions for its draws; shard.stitch_* reassemble the unsharded outputs.
+
+    Two deployments:
+      - one rank per process: ShardedVisibilityPipeline(..., rank=, world=, group=True or a process group); frame() composites with
+        shard.composite_depth (one all_reduce(MAX) per phase on the pass stream);
+      - several shards in one process on one device: ShardedVisibilityPipeline.local_shards(..., world=) returns a LocalShards, whose
+        pipelines share one upload (nv_share_scene) and composite with nv_depth_merge.
+
+    Equality with the unsharded frame holds while no rank, and not the unsharded frame, reaches NV_TASK_WGLIMIT / NV_CLUSTER_LIMIT (past
+    them each rank drops its own tail).  The visibility buffer of nv_rasterdepth is not composited (its slot index is rank-local)."""
+
+    def __init__(self, meshes, meshlets, draws, depth_size, rank=0, world=1, draw_range=None, weight="draws", group=None, **kw):
+        from . import shard
+        super().__init__(meshes, meshlets, draws, depth_size, **kw)
+        self.rank, self.world, self.group = int(rank), int(world), group
+        if draw_range is None:
+            if not 0 <= self.rank < self.world:
+                raise NvError("rank %d is not in [0, %d)" % (self.rank, self.world))
+            draw_range = shard.draw_ranges(self.draws_host, meshes, self.world, weight)[self.rank]
+        self.begin, self.end = int(draw_range[0]), int(draw_range[1])
+        if not 0 <= self.begin < self.end <= len(draws):
+            raise NvError("draw range [%d, %d) is empty or outside the scene's %d draws: use at most as many ranks as draws" %
+                          (self.begin, self.end, len(draws)))
+        if self.depth is None:
+            raise NvError("a sharded frame rasterises its own depth: ShardedVisibilityPipeline(..., vertices=, meshlet_data= and / or indices=)")
+        # the passes of the base class run on these: the rank's records inside the full buffers
+        self.total_draws = self.draw_count
+        self.db_all, self.dvb_all = self.db, self.dvb
+        self.db = self.db_all[self.begin * L.MESHDRAW.itemsize:]
+        self.dvb = self.dvb_all[self.begin:self.end]
+        self.draw_count = self.end - self.begin
+
+    @classmethod
+    def local_shards(cls, meshes, meshlets, draws, depth_size, world, weight="draws", ranges=None, **kw):
+        """`world` shards of one scene in this process on the current device: one upload, one context per shard (nv_share_scene)"""
+        from . import shard
+        draws = draws.copy()
+        host.assign_visibility_offsets(draws, meshes)
+        ranges = ranges or shard.draw_ranges(draws, meshes, world, weight)
+        pipes = []
+        try:
+            for r, rng in enumerate(ranges):
+                pipes.append(cls(meshes, meshlets, draws, depth_size, rank=r, world=len(ranges), draw_range=rng,
+                                 share=pipes[0] if pipes else None, **kw))
+        except Exception:
+            for p in pipes:
+                p.ctx.close()
+            raise
+        return LocalShards(pipes)
+
+    def _local(self, cull_data):
+        cd = cull_data.copy()
+        cd["drawCount"] = self.draw_count
+        return cd
+
+    def cull(self, cull_data, late, task=True, post_pass=0):
+        super().cull(self._local(cull_data), late, task, post_pass)
+
+    def render_clusters(self, cull_data, late, post_pass=0):
+        super().render_clusters(self._local(cull_data), late, post_pass)
+
+    def render_depth(self, cull_data, late, post_pass=0, visibility=None, totals4=None):
+        if visibility is not None:
+            raise NvError("a sharded frame has no visibility buffer: the slot index nv_rasterdepth writes is rank-local")
+        super().render_depth(self._local(cull_data), late, post_pass, None, totals4)
+
+    def render_draws(self, cull_data, late, post_pass=0, totals4=None):
+        super().render_draws(self._local(cull_data), late, post_pass, totals4)
+
+    PHASES = (("early", False, 0), ("late", True, 0), ("post", True, 1))
+
+    def phase(self, cull_data, name, task=True, totals4=None):
+        """one phase of frame() up to and including its raster; the composite is the caller's next step"""
+        late, pp = {n: (l, p) for n, l, p in self.PHASES}[name]
+        if not task:
+            cull_data = cull_data.copy()
+            cull_data["clusterOcclusionEnabled"] = 0
+        if name == "late":
+            self.build_pyramid(self.depth)
+        self.cull(cull_data, late=late, task=task, post_pass=pp)
+        if task:
+            self.render_clusters(cull_data, late=late, post_pass=pp)
+            self.render_depth(cull_data, late=late, post_pass=pp, totals4=totals4)
+        else:
+            self.render_draws(cull_data, late=late, post_pass=pp, totals4=totals4)
+
+    def composite(self):
+        """this rank's depth target := the maximum over the ranks of the group (a no-op without a group)"""
+        from . import shard
+        shard.composite_depth(self.depth, self.group)
+
+    def frame(self, cull_data, post_pass=False, on_phase=None, task=True, visibility=None, composite_last=True, on_raster=None):
+        """VisibilityPipeline.frame for this rank's draws, with the depth composite after each phase's raster.  on_raster(name) is called
+        between a phase's raster and its composite (the rank's own depth), on_phase(name) after the composite.  composite_last=False skips
+        the composite after the last phase: the rank's target then holds the earlier composites plus its own last raster"""
+        if visibility is not None:
+            raise NvError("a sharded frame has no visibility buffer: the slot index nv_rasterdepth writes is rank-local")
+        names = ["early", "late"] + (["post"] if post_pass else [])
+        for name in names:
+            self.phase(cull_data, name, task=task)
+            if on_raster is not None:
+                on_raster(name)
+            if composite_last or name != names[-1]:
+                self.composite()
+            if on_phase is not None:
+                on_phase(name)
+
+    def phase_counts(self, task=True):
+        """int64 device tensor {visible draws or task commands, task groups, visible meshlets} of the last phase (shard.allreduce_counts
+        sums it over the ranks)"""
+        out = torch.zeros(3, dtype=torch.int64, device=self.ctx.device)
+        self.ctx.pack_counts(self.dccb, None, self.ccb if task else None, out)
+        if task:
+            out[1] = (out[0] + 63) // 64
+        return out
+
+
+class LocalShards:
+    """The shards of ShardedVisibilityPipeline.local_shards: frame() runs every shard's phase on the current stream, then composites their
+    depth targets with nv_depth_merge (one launch folds all of them into the first shard's, which is then copied to the others), so that
+    afterwards every shard holds the full target, as after the all-reduce of the one-rank-per-process deployment"""
+
+    def __init__(self, pipes):
+        self.pipes = pipes
+        self.ranges = [(p.begin, p.end) for p in pipes]
+
+    def composite(self):
+        first, rest = self.pipes[0], self.pipes[1:]
+        if rest:
+            first.ctx.depth_merge(first.depth, [p.depth for p in rest], first.depth_w, first.depth_h)
+            for p in rest:
+                p.depth.copy_(first.depth)
+
+    def frame(self, cull_data, post_pass=False, on_phase=None, task=True, composite_last=True, on_raster=None):
+        names = ["early", "late"] + (["post"] if post_pass else [])
+        for name in names:
+            for p in self.pipes:
+                p.phase(cull_data, name, task=task)
+            if on_raster is not None:
+                on_raster(name)
+            if composite_last or name != names[-1]:
+                self.composite()
+            if on_phase is not None:
+                on_phase(name)
+
+    def status(self):
+        for p in self.pipes:
+            p.ctx.status()
+
+    def close(self):
+        for p in self.pipes:
+            p.ctx.close()

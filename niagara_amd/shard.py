@@ -2,6 +2,10 @@
 ranges per rank, no exchange of meshlet data; the only collective is one all-reduce (sum) of the visible counts per
 phase — RCCL over xGMI when the process group is "nccl", gloo in the CPU tests.
 
+A whole frame is sharded by contiguous ranges of DRAWS (pipeline.ShardedVisibilityPipeline): draw_ranges picks the
+ranges, composite_depth is the one exchange the closed loop adds (the element-wise maximum of the ranks' depth targets), and the
+stitch_* helpers put the ranks' outputs back together into the unsharded frame's, bit for bit.
+
 The reference has no multi-GPU path (one VkPhysicalDevice, src/device.cpp:190-248); this is the new part.
 """
 import numpy as np
@@ -33,6 +37,96 @@ def to_global_ids(local_ids, command_base):
     out = cmd.astype(np.uint32) | (local_ids & np.uint32(0xff000000))
     out[pad] = np.uint32(0xffffffff)
     return out
+
+
+def draw_weights(draws, meshes):
+    """per draw: the meshlet count of its mesh's largest LOD — what the draw costs the cluster passes at most"""
+    if not len(draws) or not len(meshes):
+        return np.zeros(len(draws), np.int64)
+    counts = meshes["lods"]["meshletCount"].astype(np.int64)
+    valid = np.arange(counts.shape[1])[None, :] < meshes["lodCount"][:, None]
+    per_mesh = np.where(valid, counts, 0).max(axis=1)
+    return per_mesh[np.minimum(draws["meshIndex"].astype(np.int64), len(meshes) - 1)]
+
+
+def draw_ranges(draws, meshes, world, weight="draws"):
+    """[(begin, end)] * world: contiguous ranges of draws in rank order that cover [0, len(draws)).
+
+    weight="draws": equal counts (nv_shard_range).  weight="meshlets": boundary k is the draw whose prefix of draw_weights is
+    nearest to k / world of the total, so every boundary is within half the heaviest draw's weight of the ideal split; equal
+    draw counts balance nothing when the meshes differ.  With at least `world` draws no range is empty (a boundary that would
+    coincide with its neighbour moves by one draw: an idle rank is worse than an uneven one); with fewer, some ranges are."""
+    n, world = len(draws), int(world)
+    if world < 1:
+        raise ValueError("world must be >= 1")
+    if weight == "draws":
+        return [tuple(host.shard_range(n, r, world)) for r in range(world)]
+    if weight != "meshlets":
+        raise ValueError("weight must be 'draws' or 'meshlets'")
+    prefix = np.concatenate([[0], np.cumsum(draw_weights(draws, meshes))]).astype(np.int64)
+    total = int(prefix[-1])
+    if total == 0:
+        return [tuple(host.shard_range(n, r, world)) for r in range(world)]
+    bounds = [0]
+    for k in range(1, world):
+        i = int(np.searchsorted(prefix * world, total * k))  # first prefix >= the ideal total * k / world (exact in integers)
+        if i > 0 and total * k - int(prefix[i - 1]) * world <= int(prefix[i]) * world - total * k:
+            i -= 1
+        if n >= world:
+            i = min(max(i, bounds[-1] + 1), n - (world - k))
+        bounds.append(max(i, bounds[-1]))
+    bounds.append(n)
+    return [(bounds[r], bounds[r + 1]) for r in range(world)]
+
+
+def composite_depth(depth, group=None):
+    """The depth composite of a sharded frame, in place on every rank: depth = element-wise maximum over the ranks of `group`
+    (a torch.distributed process group, or True for the default one).  It is one all_reduce(MAX) of the target viewed as int32: for
+    the values the rasterisers write (reverse-Z in [0, 1], never negative, never NaN) the signed maximum of the bits is the maximum
+    of the floats, exact and independent of the order of the ranks.  Runs on the caller's current stream (nccl / RCCL: on device
+    memory; gloo stages through the host), and returns when the collective is enqueued (nccl) or done (gloo).  group=None: nothing
+    to exchange, a no-op.  Shards of one process fold their targets with nv_depth_merge instead (Context.depth_merge)."""
+    if group is None:
+        return depth
+    import torch
+    import torch.distributed as dist
+    dist.all_reduce(depth.view(torch.int32), op=dist.ReduceOp.MAX, group=None if group is True else group)
+    return depth
+
+
+def to_global_draw_ids(commands, draw_base):
+    """a copy of a rank's MeshTaskCommands or MeshDrawCommands with the rank-local drawId rebased by the first draw the rank owns"""
+    out = np.array(commands, copy=True)
+    if len(out) and int(out["drawId"].max()) + int(draw_base) >= 1 << 32:
+        raise ValueError("global draw id does not fit 32 bits")
+    out["drawId"] += np.uint32(draw_base)
+    return out
+
+
+def stitch_commands(parts, ranges):
+    """parts[r]: the commands rank r appended (count4[0] of them, no tasksubmit padding); ranges: draw_ranges.  Returns the unsharded
+    pass's command list: append order is ascending draw index and the ranges are contiguous, so it is the concatenation in rank order"""
+    return np.concatenate([to_global_draw_ids(p, b) for p, (b, _) in zip(parts, ranges)])
+
+
+def stitch_cluster_ids(parts, command_counts):
+    """parts[r]: rank r's cluster indices (ccb[0] of them, or with clustersubmit's ~0 padding, which is dropped); command_counts[r]: the
+    commands rank r appended (dccb[0]).  The command id of rank r's entries is rebased by the commands of the ranks before it"""
+    out, base = [], 0
+    for ids, n in zip(parts, command_counts):
+        ids = np.asarray(ids, dtype=np.uint32)
+        out.append(to_global_ids(ids[ids != np.uint32(0xffffffff)], base))
+        base += int(n)
+    return np.concatenate(out) if out else np.zeros(0, np.uint32)
+
+
+def stitch_visibility(dvb_parts, mvb_parts):
+    """(dvb, mvb) of the unsharded frame: dvb_parts[r] is rank r's drawVisibility over ITS draws, concatenated; mvb_parts[r] is rank r's
+    full-size meshletVisibility, of which it only ever set bits of its own draws (meshletVisibilityOffset is the global prefix): OR"""
+    mvb = np.zeros_like(np.asarray(mvb_parts[0], dtype=np.uint32))
+    for m in mvb_parts:
+        mvb |= np.asarray(m, dtype=np.uint32)
+    return np.concatenate([np.asarray(d, dtype=np.uint32) for d in dvb_parts]), mvb
 
 
 class CountsReducer:
