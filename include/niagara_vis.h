@@ -272,6 +272,20 @@ int nv_profile_variants(nv_context* ctx, uint32_t out_count[NV_VARIANT_SLOTS]);
  * counts pieces; the visibility word of a piece carries the original triangle's id.  With 0 both entry points write the bits they
  * wrote before the option existed.  Not speed only: with 1 more samples are written. */
 #define NV_OPT_RASTER_NEAR_CLIP 10
+/* NV_OPT_RASTER_VISIBILITY_ID (default 0; 0 / 1, anything else NV_EINVAL): the form of the word nv_rasterdepth writes into d_visibility.
+ *   0 = bits(z) << 32 | slot << 7 | triangle, slot being the position in THIS launch's cluster list: a name that holds until the list is
+ *       overwritten, i.e. for one pass of one context.  The bits the entry point wrote before the option existed.
+ *   1 = the stable form, bits(z) << 34 | id34 with id34 = ((mvi << 7) | triangle) + 1 and mvi = command.meshletVisibilityOffset + lane,
+ *       the cluster's meshlet-visibility bit index (lane = the cluster-list entry >> 24).  mvi depends on the draw and its LOD only — not on
+ *       the pass, the list or, in a frame sharded by draws, the rank — so the early, late and post rasters of a frame can share one
+ *       target, the targets of several ranks composite with an unsigned 64-bit maximum (nv_visibility_merge), and
+ *       nv_visibility_resolve turns the word back into {draw, meshlet, triangle}.  z is clamped to [0, 1] with NaN -> 0 before it is
+ *       written, so bits(z) <= 0x3F800000 < 2^30 and the shift by 34 loses nothing; the order is depth first, id second, ties still go to
+ *       the larger id; 0 means "no sample" (hence the + 1).  A cluster with mvi >= 2^27 - 1 cannot be named in 34 bits: its samples write
+ *       depth as always and NO visibility word (dropping is conservative, as with the list limits).  With NV_OPT_RASTER_NEAR_CLIP 1 both
+ *       pieces of a triangle carry its id, as with 0.
+ * The depth target, the totals and a launch without d_visibility do not depend on the option. */
+#define NV_OPT_RASTER_VISIBILITY_ID 11
 int nv_set_option(nv_context* ctx, int option, int value);
 
 /* ---- capacities ----
@@ -447,7 +461,8 @@ int nv_trianglecull(nv_context* ctx, void* stream, const NvGlobals* globals, con
  *     VK_CULL_MODE_BACK_BIT; postPass != 0 draws both faces; the post pass's depth bias is not modelled).
  * Depth: fp32, interpolated in a fixed order from the exact int64 edge functions, clamped to [0, 1], written with an atomic max on its
  * bits (reverse-Z, compare GREATER).  d_depth is width x height; the caller clears it (0 = far) before an early pass, not before a late
- * one.  d_visibility (optional, width x height u64) receives the max of bits(z) << 32 | slot index << 7 | triangle: ties go to the larger ID.
+ * one.  d_visibility (optional, width x height u64) receives the max of bits(z) << 32 | slot index << 7 | triangle: ties go to the larger ID
+ * (NV_OPT_RASTER_VISIBILITY_ID 1: of the stable form bits(z) << 34 | ((mvi << 7 | triangle) + 1), which names the cluster for the whole frame).
  * d_totals4 (optional, accumulated: zero it first): clusters, triangles (triangleCount as stored), triangles rasterised (with
  * NV_OPT_RASTER_NEAR_CLIP 1: pieces rasterised; both pieces of a triangle write its id into d_visibility), samples covered.
  * Every result is independent of the order of the GPU's work.  width and height must equal globals->screenWidth / screenHeight and lie in
@@ -469,7 +484,8 @@ int nv_rasterdepth(nv_context* ctx, void* stream, const NvGlobals* globals, cons
  * Everything else is nv_rasterdepth's rule set, unchanged — the vertex stage, the snap, the near-plane / non-finite / guard-band rejection,
  * facing by globals->cullData.postPass, top-left coverage, the fixed-order fp32 depth and the atomic max — so the same triangle under the same
  * draw writes the same bits through either entry point, with NV_OPT_RASTER_NEAR_CLIP 1 as well (the same clip rule, totals word 2 then counts
- * pieces).  No visibility buffer (a 32-bit ID cannot name both a draw and a triangle).
+ * pieces).  No visibility buffer (neither a 32-bit nor the stable form's 34-bit ID can name both a draw and a triangle of an arbitrary
+ * indexed draw).
  * d_totals4 (optional, accumulated: zero it first): commands drawn, triangles (sum of their indexCount / 3), triangles rasterised, samples
  * covered.  d_draws holds drawCount records and d_commands up to drawCount commands; a zero capacity is allowed (nothing is read then).
  * Scratch: 4 B per command slot (drawCount) + 20 KiB, sized by nv_create for 1 M and by nv_reserve(maxDraws); a larger drawCount returns
@@ -499,6 +515,44 @@ int nv_depthreduce(nv_context* ctx, void* stream, const float* d_depth, uint32_t
  * other.  16-byte aligned pointers (any fresh allocation) take 16-byte loads and stores. */
 int nv_depth_merge(nv_context* ctx, void* stream, float* d_dst, const float* const* d_srcs, uint32_t sources, uint32_t width,
                    uint32_t height);
+
+/* ---- the stable-ID visibility buffer: composite and resolve (the reference reads its visibility in a fragment shader) ----
+ * nv_visibility_merge: d_dst[i] = max(d_dst[i], d_srcs[0][i], ..., d_srcs[sources - 1][i]) for width x height unsigned 64-bit words.  With
+ * NV_OPT_RASTER_VISIBILITY_ID 1 every shard of a frame writes the same word for the same sample, so the maximum over the shards' targets
+ * is, bit for bit, the target one pass over all draws leaves.  Arguments, NV_EINVAL rules and launch shape as nv_depth_merge (8-byte
+ * alignment required, 16-byte alignment takes 16-byte loads and stores; sources / 8 rounded up launches; enqueues only). */
+int nv_visibility_merge(nv_context* ctx, void* stream, uint64_t* d_dst, const uint64_t* const* d_srcs, uint32_t sources, uint32_t width,
+                        uint32_t height);
+
+/* One resolved pixel of nv_visibility_resolve.  No sample: {0xFFFFFFFF, 0, 0, 0}.  Unresolved: all four words 0xFFFFFFFF. */
+typedef struct NvVisRecord
+{
+	uint32_t drawId;       /* index into the d_draws the call was given (the full array: global ids in a sharded frame) */
+	uint32_t meshletIndex; /* index into the scene's meshlets */
+	uint32_t triangle;     /* < 96 */
+	uint32_t depthBits;    /* bits of the fp32 depth of the sample */
+} NvVisRecord;
+
+/* nv_visibility_resolve: per pixel with a non-zero stable-form word (NV_OPT_RASTER_VISIBILITY_ID 1) of the width x height target
+ *   mvi = (id34 - 1) >> 7, triangle = (id34 - 1) & 127, depthBits = word >> 34;
+ *   drawId = the largest d < drawCount with d_draws[d].meshletVisibilityOffset <= mvi (the offsets must be non-decreasing in d, as
+ *            nv_assign_visibility_offsets writes them; pass the FULL draw array, also on a rank of a sharded frame);
+ *   lod    = what nv_drawcull selects for that draw under `cull` (drawcull.comp.glsl:104-112; cull->view, lodTarget and lodEnabled are
+ *            read: pass the CullData of the frame that was rasterised);
+ *   meshletIndex = d_meshes[draw.meshIndex].lods[lod].meshletOffset + (mvi - draw.meshletVisibilityOffset).
+ * The pixel is UNRESOLVED — its record all ones, counted, nothing else written — when no draw has an offset <= mvi, draw.meshIndex >=
+ * meshCount, mvi - offset >= lods[lod].meshletCount, triangle >= 96 or id34 == 0.  Outputs, each optional:
+ *   d_records      width * height records (16-byte aligned);
+ *   d_meshletSeen  bit mvi set (atomic OR) for every resolved pixel, in nv_clustercull's d_meshletVisibility layout (the same size):
+ *                  the pixel-exact counterpart of that buffer; the caller clears it;
+ *   d_drawPixels   drawCount counters, d_drawPixels[drawId] += 1 per resolved pixel (accumulated: zero it first);
+ *   d_totals4      accumulated: covered pixels (non-zero words), unresolved pixels, 0, 0.
+ * Enqueues one launch (no allocation, no synchronisation: it can be captured).  NV_EINVAL: a NULL ctx, cull or d_visibility, width or
+ * height 0 or above 16384, d_draws NULL with drawCount > 0, d_meshes NULL with meshCount > 0, a misaligned pointer. */
+int nv_visibility_resolve(nv_context* ctx, void* stream, const NvCullData* cull, const uint64_t* d_visibility, uint32_t width, uint32_t height,
+                          const NvMeshDraw* d_draws, uint32_t drawCount, const NvMesh* d_meshes, uint32_t meshCount,
+                          NvVisRecord* d_records /* optional, width*height */, uint32_t* d_meshletSeen /* optional */,
+                          uint32_t* d_drawPixels /* optional, drawCount */, uint64_t* d_totals4 /* optional */);
 
 /* ---- host helpers mirroring src/niagara.cpp / src/resources.cpp (no device work) ---- */
 uint32_t nv_previous_pow2(uint32_t v);                        /* src/niagara.cpp:439-447 */
@@ -588,6 +642,7 @@ static_assert(offsetof(NvCullData, cullingEnabled) == 112 && offsetof(NvCullData
 static_assert(sizeof(NvVertex) == 16, "Vertex layout (src/shaders/mesh.h:3-9)");
 static_assert(sizeof(NvGlobals) == 224 && offsetof(NvGlobals, cullData) == 64 && offsetof(NvGlobals, screenWidth) == 208, "Globals layout (src/shaders/mesh.h:46-51)");
 static_assert(sizeof(NvTriangleMask) == 16, "one mask per grid slot");
+static_assert(sizeof(NvVisRecord) == 16, "one 16-byte store per pixel");
 static_assert(sizeof(NvSceneCacheInfo) == 208, "NvSceneCacheInfo is mirrored by niagara_amd/_lib.py");
 #endif
 

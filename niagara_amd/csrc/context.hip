@@ -46,7 +46,11 @@ int launch_pack_counts(hipStream_t, const uint32_t*, const uint32_t*, const uint
 int launch_depthreduce(hipStream_t, const float* depth, uint32_t w, uint32_t h, const NvPyramidDesc& pyr);
 int launch_depth_merge(hipStream_t, float* dst, const float* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks);
 int launch_trianglecull(hipStream_t, const TriangleArgs& a, uint32_t gridBlocks);
-int launch_rasterdepth(hipStream_t, const RasterArgs& a, uint32_t gridBlocks, bool nearClip);
+int launch_rasterdepth(hipStream_t, const RasterArgs& a, uint32_t gridBlocks, bool nearClip, bool stableIds);
+int launch_visibility_resolve(hipStream_t, const NvCullData& cd, const unsigned long long* visibility, uint32_t n, const NvMeshDraw* draws, uint32_t drawCount,
+                              const NvMesh* meshes, uint32_t meshCount, void* records, uint32_t* meshletSeen, uint32_t* drawPixels, unsigned long long* totals,
+                              uint32_t maxBlocks, bool perPixel);
+int launch_visibility_merge(hipStream_t, unsigned long long* dst, const unsigned long long* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks);
 int launch_rasterindexed(hipStream_t, RasterIndexedArgs a, void* scratch, uint32_t gridBlocks, bool nearClip);
 size_t rasterindexed_scratch_bytes(uint32_t drawCount);
 int launch_meshlet_bounds(hipStream_t, const NvVertex* vertices, const uint32_t* data, NvMeshlet* meshlets, uint32_t count, float* out8, uint32_t gridBlocks);
@@ -138,6 +142,8 @@ struct nv_context
 	uint32_t variants[NV_VARIANT_SLOTS]; // nv_profile_variants: launches per kernel variant since the last read
 	uint32_t rasterSmallLimit; // NV_OPT_RASTER_SMALL_LIMIT
 	uint32_t rasterNearClip;   // NV_OPT_RASTER_NEAR_CLIP: 1 = the clipping instantiations of both depth rasterisers
+	uint32_t rasterStableIds;  // NV_OPT_RASTER_VISIBILITY_ID: 1 = nv_rasterdepth writes the stable form of the visibility word
+	uint32_t resolvePerPixel;  // experiments: nv_visibility_resolve without the per-run de-duplication
 };
 
 namespace
@@ -421,6 +427,7 @@ int nv_create(nv_context** out_ctx, int device)
 	ctx->scatterWaves = 16;
 	ctx->rasterSmallLimit = 16;
 	ctx->rasterNearClip = 0;
+	ctx->rasterStableIds = 0;
 	ctx->directPercent = 35; // measured crossover (config 3A geometry at several densities): ~36 % of the commands passing the filter
 	ctx->forceDirect = -1;
 	ctx->bitsBlocksPerCU = 4;
@@ -432,6 +439,8 @@ int nv_create(nv_context** out_ctx, int device)
 	ctx->listSharers = 4;
 	ctx->listMinPer = 8;
 #ifdef NV_EXPERIMENTS
+	if (const char* v = getenv("NV_RESOLVE_PER_PIXEL"))
+		ctx->resolvePerPixel = (uint32_t)atoi(v);
 	if (const char* v = getenv("NV_DIRECT"))
 		ctx->forceDirect = atoi(v);
 	if (const char* v = getenv("NV_TASKCULL_ONE_LAUNCH"))
@@ -576,6 +585,11 @@ int nv_set_option(nv_context* ctx, int option, int value)
 		if (value != 0 && value != 1)
 			return NV_EINVAL;
 		ctx->rasterNearClip = (uint32_t)value;
+		return NV_OK;
+	case NV_OPT_RASTER_VISIBILITY_ID:
+		if (value != 0 && value != 1)
+			return NV_EINVAL;
+		ctx->rasterStableIds = (uint32_t)value;
 		return NV_OK;
 	case NV_OPT_CULL_WORKGROUPS_PER_CU:
 		if (value < 1 || value > 8)
@@ -1145,7 +1159,7 @@ int nv_rasterdepth(nv_context* ctx, void* stream, const NvGlobals* globals, cons
 	a.smallLimit = ctx->rasterSmallLimit;
 	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
 	a.partials = ctx->totalsPartials;
-	return nv::launch_rasterdepth((hipStream_t)stream, a, persistent_grid(ctx, 8), ctx->rasterNearClip != 0);
+	return nv::launch_rasterdepth((hipStream_t)stream, a, persistent_grid(ctx, 8), ctx->rasterNearClip != 0, ctx->rasterStableIds != 0);
 }
 
 int nv_rasterdepth_indexed(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshDrawCommand* d_commands, const uint32_t* d_count,
@@ -1215,6 +1229,33 @@ int nv_depth_merge(nv_context* ctx, void* stream, float* d_dst, const float* con
 			return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	return nv::launch_depth_merge((hipStream_t)stream, d_dst, d_srcs, sources, width * height, persistent_grid(ctx, 8));
+}
+
+int nv_visibility_resolve(nv_context* ctx, void* stream, const NvCullData* cull, const uint64_t* d_visibility, uint32_t width, uint32_t height,
+                          const NvMeshDraw* d_draws, uint32_t drawCount, const NvMesh* d_meshes, uint32_t meshCount, NvVisRecord* d_records,
+                          uint32_t* d_meshletSeen, uint32_t* d_drawPixels, uint64_t* d_totals4)
+{
+	if (!ctx || !cull || !d_visibility || width == 0 || height == 0 || width > 16384 || height > 16384 || (drawCount && !d_draws) ||
+	    (meshCount && !d_meshes) || (reinterpret_cast<uintptr_t>(d_visibility) & 7u) || (reinterpret_cast<uintptr_t>(d_records) & 15u) ||
+	    (reinterpret_cast<uintptr_t>(d_totals4) & 7u))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_visibility_resolve((hipStream_t)stream, *cull, reinterpret_cast<const unsigned long long*>(d_visibility), width * height, d_draws,
+	                                     drawCount, d_meshes, meshCount, d_records, d_meshletSeen, d_drawPixels,
+	                                     reinterpret_cast<unsigned long long*>(d_totals4), persistent_grid(ctx, 8), ctx->resolvePerPixel != 0);
+}
+
+int nv_visibility_merge(nv_context* ctx, void* stream, uint64_t* d_dst, const uint64_t* const* d_srcs, uint32_t sources, uint32_t width, uint32_t height)
+{
+	if (!ctx || !d_dst || !d_srcs || sources == 0 || width == 0 || height == 0 || width > 16384 || height > 16384 ||
+	    (reinterpret_cast<uintptr_t>(d_dst) & 7u))
+		return NV_EINVAL;
+	for (uint32_t i = 0; i < sources; ++i)
+		if (!d_srcs[i] || d_srcs[i] == d_dst || (reinterpret_cast<uintptr_t>(d_srcs[i]) & 7u))
+			return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_visibility_merge((hipStream_t)stream, reinterpret_cast<unsigned long long*>(d_dst),
+	                                   reinterpret_cast<const unsigned long long* const*>(d_srcs), sources, width * height, persistent_grid(ctx, 8));
 }
 
 #ifdef NV_EXPERIMENTS

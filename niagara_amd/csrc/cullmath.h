@@ -90,6 +90,26 @@ NV_DEV f3 sphere_center(const NvCullData& cd, f3 local, f3 q, float qw, float sc
 	return view_point(cd.view, w);
 }
 
+// drawcull.comp.glsl:104: the distance of a draw's view-space sphere, the input of its LOD threshold `distance * lodTarget / scale` (:105).
+// With lod_pick the one copy of the LOD select: drawcull.hip decides with it, visresolve.hip finds the decided LOD again with it.
+NV_DEV float lod_distance(f3 c, float radius) { return gl_max(length3(c) - radius, 0.0f); }
+
+// drawcull.comp.glsl:108-110: the last LOD i in [1, lodCount) with err[i] < threshold, else 0 (err[0] is not read).
+// "the last i in [1, lodCount) with err[i] < threshold" = the highest set bit of the comparisons' mask under the count's mask.  As the
+// loop reads (`if (i < lodCount && err[i] < threshold) lodIndex = i`) hipcc ANDs the two compares on the scalar unit into VCC and
+// selects on it — seven s_and_b64 vcc / v_cndmask pairs at ~23 cycles each on this chip (a VCC written by the scalar unit stalls the
+// vector instruction that reads it: tools/experiments/valu_classes.hip `vcc`) against three vector instructions per LOD here.
+NV_DEV uint32_t lod_pick(uint32_t lodCount, const float (&err)[NV_MAX_LODS], float threshold)
+{
+	uint32_t below = 1u; // bit 0: LOD 0 is always a candidate
+#pragma unroll
+	for (uint32_t i = 1; i < NV_MAX_LODS; ++i)
+		below |= err[i] < threshold ? 1u << i : 0u;
+	const uint32_t counted = lodCount < NV_MAX_LODS ? lodCount : NV_MAX_LODS; // (i < lodCount for every i of the loop once lodCount >= 8)
+	below &= (1u << counted) - 1u | 1u;
+	return 31u - (uint32_t)__builtin_clz(below);
+}
+
 // drawcull.comp.glsl:77-82 / clustercull.comp.glsl:103-108
 NV_DEV bool frustum_test(const NvCullData& cd, f3 c, float r)
 {

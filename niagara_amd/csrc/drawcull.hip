@@ -127,9 +127,9 @@ NV_DEV DrawResult decide_post(const DrawArgs& a, const DrawPre& pre, bool visibl
 		uint32_t lodIndex = 0;
 		if (cd.lodEnabled == 1 && !NV_DBG(a, 2u))
 		{
-			float distance = gl_max(length3(c) - radius, 0.0f);
+			float distance = lod_distance(c, radius);
 			float threshold = distance * cd.lodTarget / scale;
-			// drawcull.comp.glsl:108-110: the last LOD below the threshold.  All eight slots exist in the struct, so the
+			// drawcull.comp.glsl:108-110: the last LOD below the threshold (cullmath.h lod_pick).  All eight slots exist in the struct, so the
 			// errors are fetched together and the loop bound becomes part of the condition.
 			uint32_t lodCount;
 			float err[NV_MAX_LODS];
@@ -147,17 +147,7 @@ NV_DEV DrawResult decide_post(const DrawArgs& a, const DrawPre& pre, bool visibl
 				for (uint32_t i = 1; i < NV_MAX_LODS; ++i)
 					err[i] = *reinterpret_cast<const float*>(mesh + 48 + 20 * i + 16);
 			}
-			// "the last i in [1, lodCount) with err[i] < threshold" = the highest set bit of the comparisons' mask under the count's mask.  As the
-			// loop reads (`if (i < lodCount && err[i] < threshold) lodIndex = i`) hipcc ANDs the two compares on the scalar unit into VCC and
-			// selects on it — seven s_and_b64 vcc / v_cndmask pairs at ~23 cycles each on this chip (a VCC written by the scalar unit stalls the
-			// vector instruction that reads it: tools/experiments/valu_classes.hip `vcc`) against three vector instructions per LOD here.
-			uint32_t below = 1u; // bit 0: LOD 0 is always a candidate
-#pragma unroll
-			for (uint32_t i = 1; i < NV_MAX_LODS; ++i)
-				below |= err[i] < threshold ? 1u << i : 0u;
-			const uint32_t counted = lodCount < NV_MAX_LODS ? lodCount : NV_MAX_LODS; // (i < lodCount for every i of the loop once lodCount >= 8)
-			below &= (1u << counted) - 1u | 1u;
-			lodIndex = 31u - (uint32_t)__builtin_clz(below);
+			lodIndex = lod_pick(lodCount, err, threshold);
 		}
 		res.lodWord = lodIndex | 0x100u;
 		if (TASK)

@@ -205,8 +205,15 @@ NV_DEV bool rd_setup(const int4* vtx, uint32_t ia, uint32_t ib, uint32_t ic, uin
 	return rd_setup_corners(vtx[ia], vtx[ib], vtx[ic], bothFaces, W, H, tri);
 }
 
-// One pixel centre: coverage, depth, and the atomics (vis: optional).  Returns whether the sample is covered.
-NV_DEV bool rd_sample(const RdTri& t, int32_t px, int32_t py, uint32_t W, uint32_t* __restrict__ depth, unsigned long long* __restrict__ vis, uint32_t id)
+// The stable form of the visibility word (NV_OPT_RASTER_VISIBILITY_ID 1): bits(z) << 34 | id34, id34 = ((mvi << 7) | triangle) + 1.  rd_sample clamps
+// z to [0, 1] with NaN -> 0, so bits(z) <= 0x3F800000 < 2^30 and the shift loses nothing; mvi < RD_STABLE_MVI_END keeps id34 below 2^34.
+constexpr uint32_t RD_STABLE_SHIFT = 34;
+constexpr uint32_t RD_STABLE_MVI_END = (1u << 27) - 1u;
+
+// One pixel centre: coverage, depth, and the atomics (vis: optional).  Returns whether the sample is covered.  STABLE = false: the word is
+// bits(z) << 32 | id (ID = uint32_t, slot << 7 | triangle); STABLE = true: bits(z) << 34 | id (ID = 64 bits, id34).
+template <bool STABLE = false, class ID = uint32_t>
+NV_DEV bool rd_sample(const RdTri& t, int32_t px, int32_t py, uint32_t W, uint32_t* __restrict__ depth, unsigned long long* __restrict__ vis, ID id)
 {
 	const int32_t sx = px * 256 + 128, sy = py * 256 + 128;
 	const int64_t wa = rd_edge(t.bx, t.by, t.cx, t.cy, sx, sy);
@@ -224,7 +231,7 @@ NV_DEV bool rd_sample(const RdTri& t, int32_t px, int32_t py, uint32_t W, uint32
 		atomicMax(depth + at, bits);
 	if (vis)
 	{
-		const unsigned long long v = (unsigned long long)bits << 32 | id;
+		const unsigned long long v = (unsigned long long)bits << (STABLE ? RD_STABLE_SHIFT : 32u) | id;
 		if (v > vis[at])
 			atomicMax(vis + at, v);
 	}

@@ -18,6 +18,10 @@
 // triangle that crosses the near plane becomes one or two pieces (raster.h: rd_clip), and each piece takes the road a triangle takes.  The
 // queue entry of a large piece carries the piece number; the wave runs rd_clip again on the same inputs (same bits).  CLIP = false is
 // the kernel without any of it.
+//
+// STABLE (NV_OPT_RASTER_VISIBILITY_ID 1) changes the visibility word only: bits(z) << 34 | ((mvi << 7 | triangle) + 1) with mvi the cluster's
+// meshlet-visibility index, fetched with the slot's header, instead of bits(z) << 32 | slot << 7 | triangle.  STABLE = false is the kernel
+// without it, instruction for instruction.
 #include "raster.h"
 
 namespace nv
@@ -30,7 +34,17 @@ constexpr uint32_t RD_CHUNK = 64; // slots whose headers a wave fetches together
 #define RD_BLOCKS_PER_CU 6 // <= 8: the partial totals are sized for 8 workgroups per CU (context.hip)
 #endif
 
-template <bool CLIP>
+// the id of triangle t in the visibility word: slot << 7 | t, or the stable form's id34 (raster.h)
+template <bool STABLE>
+NV_DEV auto rd_id(uint32_t index, uint32_t mvi, uint32_t t)
+{
+	if constexpr (STABLE)
+		return ((unsigned long long)mvi << 7 | t) + 1ull;
+	else
+		return index << 7 | t;
+}
+
+template <bool CLIP, bool STABLE>
 __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(RasterArgs a)
 {
 	constexpr uint32_t PIECES = CLIP ? 2u : 1u; // pieces of a triangle at most
@@ -66,6 +80,7 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(RasterArgs a)
 		const uint32_t cnt = end - chunk < RD_CHUNK ? end - chunk : RD_CHUNK;
 		// lane = slot: grid position -> index (the mesh shader's x + 256 y + CLUSTER_TILE z) -> cluster index -> command -> headers
 		uint32_t hIndex = 0, hCi = ~0u, hDataOffset = 0, hBaseVertex = 0, hCounts = 0;
+		uint32_t hMvi = 0; // STABLE only: the cluster's meshlet-visibility index, command.meshletVisibilityOffset + lane (the bit nv_clustercull keeps for it)
 		float4 hD0 = make_float4(0, 0, 0, 0), hD1 = make_float4(0, 0, 0, 1);
 		if (lane < cnt)
 		{
@@ -81,6 +96,8 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(RasterArgs a)
 			hDataOffset = mw[3];
 			hBaseVertex = mw[4];
 			hCounts = mw[5] & 0xffffffu; // vertexCount | triangleCount << 8 | shortRefs << 16
+			if constexpr (STABLE)
+				hMvi = cmd[4] + (hCi >> 24);
 			const float4* dp = reinterpret_cast<const float4*>(a.draws + drawId);
 			hD0 = dp[0];
 			hD1 = dp[1];
@@ -98,6 +115,14 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(RasterArgs a)
 			const uint32_t indexOffset = dataOffset + (shortRefs ? (vcRaw + 1) / 2 : vcRaw);
 			clusters += 1;
 			triangles += tcRaw;
+			// STABLE: a cluster whose index does not fit the word's 27 bits writes depth and no visibility word
+			uint32_t mvi = 0;
+			unsigned long long* vis = a.visibility;
+			if constexpr (STABLE)
+			{
+				mvi = rd_rl(hMvi, s);
+				vis = mvi < RD_STABLE_MVI_END ? vis : nullptr;
+			}
 
 			rd_lds_order(); // the previous slot's readers are done
 			// ---- vertex stage, lane = vertex (nv_trianglecull's arithmetic, src/shaders/meshlet.mesh.glsl:121-160)
@@ -148,10 +173,10 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(RasterArgs a)
 							large = n > a.smallLimit;
 							if (!large)
 							{
-								const uint32_t id = index << 7 | t;
+								const auto id = rd_id<STABLE>(index, mvi, t);
 								for (int32_t py = tri.y0; py <= tri.y1; ++py)
 									for (int32_t px = tri.x0; px <= tri.x1; ++px)
-										samples += rd_sample(tri, px, py, a.width, a.depth, a.visibility, id) ? 1u : 0u;
+										samples += rd_sample<STABLE>(tri, px, py, a.width, a.depth, STABLE ? vis : a.visibility, id) ? 1u : 0u;
 							}
 						}
 					}
@@ -192,10 +217,10 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(RasterArgs a)
 								large = n > a.smallLimit;
 								if (!large)
 								{
-									const uint32_t id = index << 7 | t;
+									const auto id = rd_id<STABLE>(index, mvi, t);
 									for (int32_t py = tri.y0; py <= tri.y1; ++py)
 										for (int32_t px = tri.x0; px <= tri.x1; ++px)
-											samples += rd_sample(tri, px, py, a.width, a.depth, a.visibility, id) ? 1u : 0u;
+											samples += rd_sample<STABLE>(tri, px, py, a.width, a.depth, STABLE ? vis : a.visibility, id) ? 1u : 0u;
 								}
 							}
 						}
@@ -217,7 +242,7 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(RasterArgs a)
 			{
 				const uint32_t e = queue[k];
 				RdTri tri;
-				uint32_t id;
+				decltype(rd_id<STABLE>(0u, 0u, 0u)) id;
 				if constexpr (CLIP)
 				{
 					const uint32_t ia = e >> 8 & 0xffu, ib = e >> 16 & 0xffu, ic = e >> 24; // (< ve: it was queued)
@@ -225,12 +250,12 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(RasterArgs a)
 					int4 p0, p1, p2, p3;
 					rd_clip(a.globals, vtx[ia], vtx[ib], vtx[ic], cvx[ia], cvx[ib], cvx[ic], H, p0, p1, p2, p3);
 					rd_setup_corners(p0, rd_sel(second, p2, p1), rd_sel(second, p3, p2), bothFaces, W, H, tri); // (true: it was queued)
-					id = index << 7 | (e & 0x7fu);
+					id = rd_id<STABLE>(index, mvi, e & 0x7fu);
 				}
 				else
 				{
 					rd_setup(vtx, e >> 8 & 0xffu, e >> 16 & 0xffu, e >> 24, ve, bothFaces, W, H, tri); // (true: it was queued)
-					id = index << 7 | (e & 0xffu);
+					id = rd_id<STABLE>(index, mvi, e & 0xffu);
 				}
 				const uint32_t sw = (uint32_t)(tri.x1 - tri.x0) / 8u + 1u, sh = (uint32_t)(tri.y1 - tri.y0) / 8u + 1u;
 				const int32_t lx = (int32_t)(lane & 7u), ly = (int32_t)(lane >> 3);
@@ -241,7 +266,7 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(RasterArgs a)
 					{
 						const int32_t px = tri.x0 + (int32_t)sx * 8 + lx;
 						if (px <= tri.x1 && py <= tri.y1)
-							samples += rd_sample(tri, px, py, a.width, a.depth, a.visibility, id) ? 1u : 0u;
+							samples += rd_sample<STABLE>(tri, px, py, a.width, a.depth, STABLE ? vis : a.visibility, id) ? 1u : 0u;
 					}
 				}
 			}
@@ -302,13 +327,21 @@ int launch_raster_totals(hipStream_t stream, const unsigned long long* partials,
 	return (int)hipGetLastError();
 }
 
-int launch_rasterdepth(hipStream_t stream, const RasterArgs& a, uint32_t gridBlocks, bool nearClip)
+int launch_rasterdepth(hipStream_t stream, const RasterArgs& a, uint32_t gridBlocks, bool nearClip, bool stableIds)
 {
 	gridBlocks = gridBlocks / 8 * RD_BLOCKS_PER_CU; // the caller passes 8 workgroups per CU, the size of `partials`
-	if (nearClip)
-		hipLaunchKernelGGL(rasterdepth_kernel<true>, dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
+	// (the stable form differs only in the visibility word: without a visibility target the launch is the default kernel)
+	if (stableIds && a.visibility)
+	{
+		if (nearClip)
+			hipLaunchKernelGGL((rasterdepth_kernel<true, true>), dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
+		else
+			hipLaunchKernelGGL((rasterdepth_kernel<false, true>), dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
+	}
+	else if (nearClip)
+		hipLaunchKernelGGL((rasterdepth_kernel<true, false>), dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
 	else
-		hipLaunchKernelGGL(rasterdepth_kernel<false>, dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
+		hipLaunchKernelGGL((rasterdepth_kernel<false, false>), dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
 	hipError_t e = hipGetLastError();
 	if (e != hipSuccess || !a.totals)
 		return (int)e;

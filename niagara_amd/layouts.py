@@ -31,6 +31,10 @@ VERTEX = np.dtype([("vx", "<u2"), ("vy", "<u2"), ("vz", "<u2"), ("tp", "<u2"), (
 GLOBALS = np.dtype([("projection", "<f4", 16), ("cullData", CULLDATA), ("screenWidth", "<f4"), ("screenHeight", "<f4"), ("_pad", "<f4", 2)])  # mesh.h:46-51
 TRIMASK = np.dtype([("keep", "<u4", 3), ("counts", "<u4")])
 assert (VERTEX.itemsize, GLOBALS.itemsize, TRIMASK.itemsize) == (16, 224, 16)
+# NvVisRecord: one pixel of nv_visibility_resolve (no sample: drawId = 0xFFFFFFFF, the rest 0; unresolved: all ones)
+VISRECORD = np.dtype([("drawId", "<u4"), ("meshletIndex", "<u4"), ("triangle", "<u4"), ("depthBits", "<u4")])
+assert VISRECORD.itemsize == 16
+VIS_ID_BITS = 34  # the stable form of the visibility word: bits(z) << 34 | ((mvi << 7 | triangle) + 1)
 
 TASK_WGSIZE = 64
 TASK_WGLIMIT = 1 << 22

@@ -46,6 +46,7 @@ NV_OPT_TASK_EMIT = 7
 NV_OPT_DRAW_RECORDS = 8
 NV_OPT_RASTER_SMALL_LIMIT = 9
 NV_OPT_RASTER_NEAR_CLIP = 10
+NV_OPT_RASTER_VISIBILITY_ID = 11
 
 
 class Context:
@@ -170,7 +171,8 @@ class Context:
 
     def rasterdepth(self, globals_, dcb, db, mlb, meshlet_data, vertices, cib, ccb, depth, width, height, visibility=None, totals4=None):
         """depth-only raster of the clusters in cib / ccb into `depth` (fp32 width x height, reverse-Z, atomic max: the caller clears it);
-        visibility (optional, width x height u64): max of bits(z) << 32 | slot << 7 | triangle; totals4 (optional, accumulated):
+        visibility (optional, width x height u64): max of bits(z) << 32 | slot << 7 | triangle, or with NV_OPT_RASTER_VISIBILITY_ID 1 of the
+        stable form bits(z) << 34 | ((mvi << 7 | triangle) + 1); totals4 (optional, accumulated):
         clusters, triangles, triangles rasterised, samples covered"""
         check(lib.nv_rasterdepth(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(dcb), _ptr(db), _ptr(mlb), _ptr(meshlet_data), _ptr(vertices),
                                  _ptr(cib), _ptr(ccb), _ptr(depth), int(width), int(height), _ptr(visibility), _ptr(totals4)), "nv_rasterdepth")
@@ -189,6 +191,22 @@ class Context:
         that live on one device, and the fold of a received target into the local one"""
         ptrs = (C.c_void_p * len(srcs))(*[None if t is None else t.data_ptr() for t in srcs])
         check(lib.nv_depth_merge(self.h, _stream(), _ptr(dst), ptrs if len(srcs) else None, len(srcs), int(width), int(height)), "nv_depth_merge")
+
+    def visibility_merge(self, dst, srcs, width, height):
+        """dst = element-wise unsigned 64-bit maximum of dst and every visibility target of `srcs` (nv_visibility_merge): the composite of
+        stable-form visibility buffers of shards that live on one device"""
+        ptrs = (C.c_void_p * len(srcs))(*[None if t is None else t.data_ptr() for t in srcs])
+        check(lib.nv_visibility_merge(self.h, _stream(), _ptr(dst), ptrs if len(srcs) else None, len(srcs), int(width), int(height)), "nv_visibility_merge")
+
+    def visibility_resolve(self, cull, visibility, width, height, db, draw_count, mb, mesh_count, records=None, meshlet_seen=None, draw_pixels=None,
+                           totals4=None):
+        """the stable-form visibility buffer back to {draw, meshlet, triangle, depth bits} per pixel (nv_visibility_resolve).  db / mb: the FULL
+        draw array and the Mesh table; cull: the CullData of the frame that was rasterised (the LOD is selected again from it).  records
+        (width * height NvVisRecord), meshlet_seen (mvb layout, OR-ed), draw_pixels (draw_count u32, accumulated) and totals4 (u64:
+        covered, unresolved, 0, 0, accumulated) are each optional"""
+        check(lib.nv_visibility_resolve(self.h, _stream(), C.c_void_p(cull.ctypes.data), _ptr(visibility), int(width), int(height), _ptr(db),
+                                        int(draw_count), _ptr(mb), int(mesh_count), _ptr(records), _ptr(meshlet_seen), _ptr(draw_pixels),
+                                        _ptr(totals4)), "nv_visibility_resolve")
 
     def depthreduce(self, depth, width, height, pyramid):
         check(lib.nv_depthreduce(self.h, _stream(), _ptr(depth), width, height, C.byref(pyramid)), "nv_depthreduce")
@@ -226,7 +244,7 @@ class VisibilityPipeline:
     """niagara's GPU-driven visibility front-end for one scene on one device."""
 
     def __init__(self, meshes, meshlets, draws, depth_size, ctx=None, task_capacity=None, cluster_capacity=None, use_soa=True, fused=False,
-                 meshlet_data=None, vertices=None, indices=None, near_clip=False, share=None):
+                 meshlet_data=None, vertices=None, indices=None, near_clip=False, share=None, stable_ids=False):
         self.ctx = ctx or Context()
         # share: a pipeline of the SAME scene on the same device whose scene buffers (meshes, meshlets, draws, geometry) and library
         # mirrors this one uses instead of uploading its own (nv_share_scene); everything a pass writes stays this pipeline's own
@@ -234,6 +252,10 @@ class VisibilityPipeline:
         # that surfaces the camera stands on or next to occlude in frame()'s late passes
         self.near_clip = bool(near_clip)
         self.ctx.set_option(NV_OPT_RASTER_NEAR_CLIP, int(self.near_clip))
+        # stable_ids=True: nv_rasterdepth names a cluster in the visibility word by its meshlet-visibility index instead of its slot in the
+        # pass's list (NV_OPT_RASTER_VISIBILITY_ID), so that frame(visibility=) can keep one target over its passes and resolve() can read it
+        self.stable_ids = bool(stable_ids)
+        self.ctx.set_option(NV_OPT_RASTER_VISIBILITY_ID, int(self.stable_ids))
         # fused=True: the passes absorb the count-word resets and the tasksubmit / clustersubmit fix-ups (same buffer
         # contents, four launches less per phase); fused=False issues the reference's dispatch sequence one to one
         self.fused = bool(fused)
@@ -336,6 +358,8 @@ class VisibilityPipeline:
             raise NvError("render_depth needs the scene's geometry: VisibilityPipeline(..., meshlet_data=, vertices=)")
         if not late:
             self.depth.zero_()
+            if visibility is not None and self.stable_ids:  # one target for the frame: cleared with the depth, loaded by late / post
+                visibility.zero_()
         pass_data = cull_data.copy()
         pass_data["postPass"] = post_pass
         g = synth.make_globals(pass_data, (self.depth_w, self.depth_h))
@@ -355,11 +379,35 @@ class VisibilityPipeline:
         self.ctx.rasterdepth_indexed(g, self.dcb, self.dccb, self.db, self.draw_count, self.ib, self.index_count, self.vb, self.vertex_count,
                                      self.depth, self.depth_w, self.depth_h, totals4)
 
-    def frame(self, cull_data, post_pass=False, on_phase=None, task=True):
+    def new_visibility(self):
+        """a cleared visibility target of the depth target's size (u64 words, held as int64)"""
+        return torch.zeros((self.depth_h, self.depth_w), dtype=torch.int64, device=self.ctx.device)
+
+    def resolve(self, cull_data, visibility, records=True, meshlet_seen=True, draw_pixels=True):
+        """nv_visibility_resolve of a frame's stable-form visibility target under the frame's CullData: a dict with "records" (uint8 tensor,
+        height * width NvVisRecord), "meshlet_seen" (int32, mvb's size and layout), "draw_pixels" (int32 per draw of the whole scene) and
+        "totals" (int64: covered, unresolved, 0, 0); an output switched off is None.  Draw ids are the scene's, also on a shard"""
+        if not self.stable_ids:
+            raise NvError("resolve reads the stable form of the visibility word: VisibilityPipeline(..., stable_ids=True)")
+        dev = self.ctx.device
+        n_draws = getattr(self, "total_draws", self.draw_count)
+        out = dict(records=torch.zeros(self.depth_w * self.depth_h * L.VISRECORD.itemsize, dtype=torch.uint8, device=dev) if records else None,
+                   meshlet_seen=torch.zeros_like(self.mvb) if meshlet_seen else None,
+                   draw_pixels=torch.zeros(max(1, n_draws), dtype=torch.int32, device=dev) if draw_pixels else None,
+                   totals=torch.zeros(4, dtype=torch.int64, device=dev))
+        self.ctx.visibility_resolve(cull_data, visibility, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws, self.mb, self.mesh_count,
+                                    out["records"], out["meshlet_seen"], out["draw_pixels"], out["totals"])
+        return out
+
+    def frame(self, cull_data, post_pass=False, on_phase=None, task=True, visibility=None):
         """one frame of src/niagara.cpp:1765-1788 with the raster in place of the graphics passes: early cull -> clusters -> raster ->
         pyramid -> late cull -> clusters -> raster (-> post cull -> clusters -> raster).  task=False runs the classic path instead (no mesh
         shading): every cull writes MeshDrawCommands, render_draws rasterises them, and clusterOcclusionEnabled is 0 (src/niagara.cpp:1516).
-        on_phase(name) is called after each phase's raster ("early", "late", "post")"""
+        on_phase(name) is called after each phase's raster ("early", "late", "post").  visibility (stable_ids=True, task=True): a u64
+        target of the depth target's size that the three rasters share (cleared before the early one); resolve() reads it"""
+        if visibility is not None and not (self.stable_ids and task):
+            raise NvError("frame(visibility=) needs stable ids and the cluster path: VisibilityPipeline(..., stable_ids=True), task=True "
+                          "(the slot index of the default visibility word does not outlive a pass)")
         if not task:
             cull_data = cull_data.copy()
             cull_data["clusterOcclusionEnabled"] = 0
@@ -370,7 +418,7 @@ class VisibilityPipeline:
             self.cull(cull_data, late=late, task=task, post_pass=pp)
             if task:
                 self.render_clusters(cull_data, late=late, post_pass=pp)
-                self.render_depth(cull_data, late=late, post_pass=pp)
+                self.render_depth(cull_data, late=late, post_pass=pp, visibility=visibility)
             else:
                 self.render_draws(cull_data, late=late, post_pass=pp)
             if on_phase is not None:
@@ -397,7 +445,10 @@ class ShardedVisibilityPipeline(VisibilityPipeline):
         pipelines share one upload (nv_share_scene) and composite with nv_depth_merge.
 
     Equality with the unsharded frame holds while no rank, and not the unsharded frame, reaches NV_TASK_WGLIMIT / NV_CLUSTER_LIMIT (past
-    them each rank drops its own tail).  The visibility buffer of nv_rasterdepth is not composited (its slot index is rank-local)."""
+    them each rank drops its own tail).  With stable_ids=True frame(visibility=) also composites the visibility target (unsigned 64-bit
+    maximum: every rank writes the same word for the same sample, so the composite is the unsharded buffer) and resolve() on any rank
+    returns the unsharded frame's records with the scene's draw ids; without it the slot index of the word is rank-local and a
+    visibility target is refused."""
 
     def __init__(self, meshes, meshlets, draws, depth_size, rank=0, world=1, draw_range=None, weight="draws", group=None, **kw):
         from . import shard
@@ -450,17 +501,20 @@ class ShardedVisibilityPipeline(VisibilityPipeline):
         super().render_clusters(self._local(cull_data), late, post_pass)
 
     def render_depth(self, cull_data, late, post_pass=0, visibility=None, totals4=None):
-        if visibility is not None:
+        if visibility is not None and not self.stable_ids:
             raise NvError("a sharded frame has no visibility buffer: the slot index nv_rasterdepth writes is rank-local")
-        super().render_depth(self._local(cull_data), late, post_pass, None, totals4)
+        super().render_depth(self._local(cull_data), late, post_pass, visibility, totals4)
 
     def render_draws(self, cull_data, late, post_pass=0, totals4=None):
         super().render_draws(self._local(cull_data), late, post_pass, totals4)
 
     PHASES = (("early", False, 0), ("late", True, 0), ("post", True, 1))
 
-    def phase(self, cull_data, name, task=True, totals4=None):
+    def phase(self, cull_data, name, task=True, totals4=None, visibility=None):
         """one phase of frame() up to and including its raster; the composite is the caller's next step"""
+        if visibility is not None and not (self.stable_ids and task):
+            raise NvError("a sharded frame has no visibility buffer: the slot index nv_rasterdepth writes is rank-local "
+                          "(ShardedVisibilityPipeline(..., stable_ids=True) and task=True name clusters by a frame-stable id instead)")
         late, pp = {n: (l, p) for n, l, p in self.PHASES}[name]
         if not task:
             cull_data = cull_data.copy()
@@ -470,28 +524,37 @@ class ShardedVisibilityPipeline(VisibilityPipeline):
         self.cull(cull_data, late=late, task=task, post_pass=pp)
         if task:
             self.render_clusters(cull_data, late=late, post_pass=pp)
-            self.render_depth(cull_data, late=late, post_pass=pp, totals4=totals4)
+            self.render_depth(cull_data, late=late, post_pass=pp, totals4=totals4, visibility=visibility)
         else:
             self.render_draws(cull_data, late=late, post_pass=pp, totals4=totals4)
 
-    def composite(self):
-        """this rank's depth target := the maximum over the ranks of the group (a no-op without a group)"""
+    def composite(self, visibility=None):
+        """this rank's depth target (and stable-form visibility target) := the maximum over the ranks of the group (a no-op without a group)"""
         from . import shard
         shard.composite_depth(self.depth, self.group)
+        if visibility is not None:
+            shard.composite_visibility(visibility, self.group)
 
     def frame(self, cull_data, post_pass=False, on_phase=None, task=True, visibility=None, composite_last=True, on_raster=None):
         """VisibilityPipeline.frame for this rank's draws, with the depth composite after each phase's raster.  on_raster(name) is called
         between a phase's raster and its composite (the rank's own depth), on_phase(name) after the composite.  composite_last=False skips
         the composite after the last phase: the rank's target then holds the earlier composites plus its own last raster"""
-        if visibility is not None:
-            raise NvError("a sharded frame has no visibility buffer: the slot index nv_rasterdepth writes is rank-local")
+        if visibility is not None and not (self.stable_ids and task):
+            raise NvError("a sharded frame has no visibility buffer: the slot index nv_rasterdepth writes is rank-local "
+                          "(ShardedVisibilityPipeline(..., stable_ids=True) and task=True name clusters by a frame-stable id instead)")
         names = ["early", "late"] + (["post"] if post_pass else [])
         for name in names:
-            self.phase(cull_data, name, task=task)
+            self.phase(cull_data, name, task=task, visibility=visibility)
             if on_raster is not None:
                 on_raster(name)
             if composite_last or name != names[-1]:
-                self.composite()
+                # (the visibility target is only read after the frame: composited once, behind the last raster, would do as well; per
+                # phase it stays the unsharded frame's at every on_phase, like the depth).  Without a target the call is composite(), as
+                # before the argument existed: callers replace the method
+                if visibility is None:
+                    self.composite()
+                else:
+                    self.composite(visibility)
             if on_phase is not None:
                 on_phase(name)
 
@@ -514,22 +577,34 @@ class LocalShards:
         self.pipes = pipes
         self.ranges = [(p.begin, p.end) for p in pipes]
 
-    def composite(self):
+    def composite(self, visibility=None):
+        """visibility: one stable-form target per shard; folded with nv_visibility_merge like the depth targets"""
         first, rest = self.pipes[0], self.pipes[1:]
         if rest:
             first.ctx.depth_merge(first.depth, [p.depth for p in rest], first.depth_w, first.depth_h)
             for p in rest:
                 p.depth.copy_(first.depth)
+            if visibility is not None:
+                first.ctx.visibility_merge(visibility[0], list(visibility[1:]), first.depth_w, first.depth_h)
+                for v in visibility[1:]:
+                    v.copy_(visibility[0])
 
-    def frame(self, cull_data, post_pass=False, on_phase=None, task=True, composite_last=True, on_raster=None):
+    def new_visibility(self):
+        return [p.new_visibility() for p in self.pipes]
+
+    def frame(self, cull_data, post_pass=False, on_phase=None, task=True, composite_last=True, on_raster=None, visibility=None):
+        """visibility: a list with one u64 target per shard (new_visibility()); needs local_shards(..., stable_ids=True)"""
         names = ["early", "late"] + (["post"] if post_pass else [])
         for name in names:
-            for p in self.pipes:
-                p.phase(cull_data, name, task=task)
+            for k, p in enumerate(self.pipes):
+                p.phase(cull_data, name, task=task, visibility=None if visibility is None else visibility[k])
             if on_raster is not None:
                 on_raster(name)
             if composite_last or name != names[-1]:
-                self.composite()
+                if visibility is None:  # (composite() as before the argument existed: callers replace the method)
+                    self.composite()
+                else:
+                    self.composite(visibility)
             if on_phase is not None:
                 on_phase(name)
 

@@ -3,7 +3,8 @@ ranges per rank, no exchange of meshlet data; the only collective is one all-red
 phase — RCCL over xGMI when the process group is "nccl", gloo in the CPU tests.
 
 A whole frame is sharded by contiguous ranges of DRAWS (pipeline.ShardedVisibilityPipeline): draw_ranges picks the
-ranges, composite_depth is the one exchange the closed loop adds (the element-wise maximum of the ranks' depth targets), and the
+ranges, composite_depth is the one exchange the closed loop adds (the element-wise maximum of the ranks' depth targets;
+composite_visibility the same for the stable-ID visibility buffer), and the
 stitch_* helpers put the ranks' outputs back together into the unsharded frame's, bit for bit.
 
 The reference has no multi-GPU path (one VkPhysicalDevice, src/device.cpp:190-248); this is the new part.
@@ -92,6 +93,25 @@ def composite_depth(depth, group=None):
     import torch.distributed as dist
     dist.all_reduce(depth.view(torch.int32), op=dist.ReduceOp.MAX, group=None if group is True else group)
     return depth
+
+
+def composite_visibility(visibility, group=None):
+    """The composite of a sharded frame's stable-form visibility targets (NV_OPT_RASTER_VISIBILITY_ID 1), in place on every rank: the
+    element-wise UNSIGNED 64-bit maximum over the ranks of `group`, as one all_reduce(MAX).  Neither backend reduces unsigned 64-bit
+    integers, and bit 63 of a word can be set (bits(1.0) << 34 = 0x3F800000 << 34), so the signed maximum of the int64 view would order such
+    words below all others: the sign bit is flipped before and after (x ^ 1 << 63), which maps unsigned order onto signed order — an
+    order-preserving bijection, so max commutes with it.  `visibility` is an int64 (or uint64-viewed) tensor; group=None is a no-op.
+    Shards of one process fold their targets with nv_visibility_merge instead (Context.visibility_merge)."""
+    if group is None:
+        return visibility
+    import torch
+    import torch.distributed as dist
+    v = visibility.view(torch.int64)
+    sign = torch.tensor(-(1 << 63), dtype=torch.int64, device=v.device)
+    v.bitwise_xor_(sign)
+    dist.all_reduce(v, op=dist.ReduceOp.MAX, group=None if group is True else group)
+    v.bitwise_xor_(sign)
+    return visibility
 
 
 def to_global_draw_ids(commands, draw_base):

@@ -6,12 +6,14 @@
     python3 tools/sharded_frame.py --gpus 1 --force-collective                # one rank, the composite's all_reduce(MAX) over RCCL anyway
     python3 tools/sharded_frame.py --local-shards 8                           # 8 shards in ONE process, composite = nv_depth_merge
     python3 tools/sharded_frame.py --as-rank 0/8                              # one rank's share alone (no exchange): the per-rank frame cost
+    python3 tools/sharded_frame.py --local-shards 4 --visibility              # + the stable-ID visibility buffer, composited and resolved
 
 Like bench.py --gpus N it starts its own ranks under torch.distributed.run when no launcher did.  Prints ONE JSON line (rank 0): the
 per-phase counts of the last frame summed over the ranks, the frame time (MAX over the ranks; the shortest of three timed loops of
 --frames frames) and the time of one depth composite.  --dump DIR writes rank_<r>.npz per rank: for every frame f and phase p the
 commands, cluster ids, dvb (the rank's draws), mvb, counts and depth, and the pyramid per frame (the frames start from cleared
-visibility; nothing is timed then)."""
+visibility; nothing is timed then).  --visibility (cluster scenes) runs the frame with stable ids and a visibility target per rank,
+composited with the depth; the JSON line gains the resolve totals of the last frame and the dump "f<f>_visibility" and "f<f>_records"."""
 import argparse
 import json
 import os
@@ -44,6 +46,7 @@ def parse(argv=None):
     ap.add_argument("--unfused", action="store_true", help="the reference's dispatch sequence one to one (default: fused resets / submits)")
     ap.add_argument("--skip-last-composite", action="store_true")
     ap.add_argument("--dump", default="", help="directory for rank_<r>.npz")
+    ap.add_argument("--visibility", action="store_true", help="stable-ID visibility buffer: composited with the depth, resolved after the frame")
     return ap.parse_args(argv)
 
 
@@ -121,8 +124,10 @@ def main():
 
     s, task, near_clip = make_scene(args)
     geometry = dict(vertices=s["vertices"], meshlet_data=s["data"]) if task else dict(vertices=s["vertices"], indices=s["indices"])
+    if args.visibility and not task:
+        raise SystemExit("--visibility needs a cluster scene: the indexed path has no visibility buffer")
     kw = dict(task_capacity=4096 if len(s["draws"]) < 256 else None, cluster_capacity=4096 * 64 if len(s["draws"]) < 256 else None,
-              fused=not args.unfused, near_clip=near_clip, weight=args.weight, **geometry)
+              fused=not args.unfused, near_clip=near_clip, weight=args.weight, stable_ids=args.visibility, **geometry)
     shards = None
     if args.local_shards:
         shards = P.ShardedVisibilityPipeline.local_shards(s["meshes"], s["meshlets"], s["draws"], s["viewport"], args.local_shards, **kw)
@@ -135,6 +140,11 @@ def main():
     w, h = s["viewport"]
     names = ["early", "late"] + (["post"] if args.post else [])
     frame_kw = dict(post_pass=args.post, task=task, composite_last=not args.skip_last_composite)
+    vis = None
+    if args.visibility:
+        vis = shards.new_visibility() if shards else pipes[0].new_visibility()
+        frame_kw["visibility"] = vis
+    vis_of = (lambda k: vis[k]) if shards else (lambda k: vis)
 
     def counts_now():
         c = torch.stack([p.phase_counts(task) for p in pipes]).sum(0)
@@ -162,8 +172,11 @@ def main():
                     d[key + "mvb"] = p.mvb.cpu().numpy().view(np.uint32).copy()
                     d[key + "depth"] = p.depth.cpu().numpy().copy()
             runner.frame(s["cull"], on_phase=grab, **frame_kw)
-            for p, d in zip(pipes, dumps):
+            for k, (p, d) in enumerate(zip(pipes, dumps)):
                 d["f%d_pyramid" % f] = p.pyramid.data.cpu().numpy().copy()
+                if vis is not None:
+                    d["f%d_visibility" % f] = vis_of(k).cpu().numpy().view(np.uint64).copy()
+                    d["f%d_records" % f] = P.from_device(p.resolve(s["cull"], vis_of(k))["records"], L.VISRECORD).copy()
         for p, d in zip(pipes, dumps):
             np.savez(os.path.join(args.dump, "rank_%d.npz" % (p.rank if shards or args.as_rank else rank)), **d)
         result.update(frame_ms=None, composite_ms=None, timed=False)
@@ -193,6 +206,9 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         runner.frame(s["cull"], on_phase=lambda name: last_counts.__setitem__(name, counts_now()), **frame_kw)
         result.update(frame_ms=float(t[0]), composite_ms=float(t[1]), timed=True)
+    if vis is not None:  # every rank holds the frame's buffer after the composite: rank 0's resolve is the frame's
+        tot = pipes[0].resolve(s["cull"], vis_of(0), records=False)["totals"].cpu().numpy()
+        result.update(visibility=True, covered_pixels=int(tot[0]), unresolved_pixels=int(tot[1]), visibility_payload_bytes=w * h * 8)
     for p in pipes:
         p.ctx.status()
     result["counts"] = {n: [int(x) for x in last_counts[n]] for n in names}
