@@ -45,6 +45,9 @@ if not os.path.exists(SO_PATH):
 
 lib = C.CDLL(SO_PATH)
 
+# nv_profile_variants: the NV_VARIANT_* slots of include/niagara_vis.h in their order (NV_VARIANT_SLOTS names); pipeline.Context.VARIANTS is this tuple
+VARIANT_NAMES = ("cull_filter_ring4", "cull_filter_ring8", "cull_direct", "cull_lanes_bits", "cull_lanes", "cull_aos", "hiz_stage", "task_list", "task_per_draw", "cull_direct_packed")
+
 _vp, _u32, _i, _f = C.c_void_p, C.c_uint32, C.c_int, C.c_float
 _SIGS = {
     "nv_create": (_i, [C.POINTER(_vp), _i]),
@@ -56,7 +59,7 @@ _SIGS = {
     "nv_share_scene": (_i, [_vp, _vp]),
     "nv_profile_enable": (_i, [_vp, _i]),
     "nv_profile_read": (_i, [_vp, C.POINTER(C.c_float * 5), C.POINTER(C.c_uint32 * 5)]),
-    "nv_profile_variants": (_i, [_vp, C.POINTER(C.c_uint32 * 10)]),  # NV_VARIANT_SLOTS
+    "nv_profile_variants": (_i, [_vp, C.POINTER(C.c_uint32 * len(VARIANT_NAMES))]),
     "nv_upload_meshlets": (_i, [_vp, _vp, _vp, _u32]),
     "nv_debug_block_table": (_i, [_vp, _vp, _u32, C.POINTER(_u32)]),
     "nv_upload_meshes": (_i, [_vp, _vp, _vp, _u32]),

@@ -30,6 +30,7 @@
 #include "args.h"
 #include "filtermath.h"
 #include "dealing.h"
+#include "cullform.h"
 
 namespace nv
 {
@@ -345,9 +346,7 @@ constexpr uint32_t CC_CHUNK_LATE = NV_CC_CHUNK_LATE;
 // the one being filtered.  8 keep HBM saturated through the segment boundaries of a long stream (100 M meshlets: 198 us
 // vs 208 us with 4) and suit the late pass; for a pass of a few hundred thousand commands — one segment per wave — 4
 // measure 3 us faster (10 M meshlets: 27.8 vs 31 us): the queues stay shorter, so every dependent step of the later
-// workgroups' start-up chains is served sooner.  The host picks per launch from the command count of the PREVIOUS
-// clustercull (the kernel leaves it in a mapped host word; frame coherence; a wrong guess only costs speed).
-constexpr uint32_t CC_SHALLOW_COMMANDS = 500000;
+// workgroups' start-up chains is served sooner.  The host picks per launch (cullform.h CC_SHALLOW_COMMANDS).
 #ifndef NV_CC_DB
 #define NV_CC_DB 3
 #endif
@@ -3064,122 +3063,66 @@ __global__ __launch_bounds__(256) void block_bounds_kernel(const uint2* __restri
 // ---------------------------------------------------------------------------------------------------------------
 // launchers (called from context.hip)
 
-template <bool LATE, bool SOA, int DEPTH, bool DIRECT = false>
-static void launch_cc(hipStream_t stream, const ClusterArgs& a, uint32_t gridBlocks)
-{
-	dim3 grid(gridBlocks), block(CC_THREADS);
-	// the direct form's packed walk (windows of 64 valid meshlets instead of one command per iteration): early form without visibility bits, over the mirror
-	constexpr bool CAN_PACK = DIRECT && SOA && !LATE;
-	const bool pack = CAN_PACK && a.packDirect != 0;
-	if (!LATE && a.deferHiz)
-	{
-		if (pack)
-			hipLaunchKernelGGL((cluster_mask_kernel<false, SOA, false, DEPTH, DIRECT, true, CAN_PACK>), grid, block, 0, stream, a);
-		else
-			hipLaunchKernelGGL((cluster_mask_kernel<false, SOA, false, DEPTH, DIRECT, true>), grid, block, 0, stream, a);
-	}
-	else if (a.cd.clusterOcclusionEnabled == 1 && a.cd.postPass == 0)
-	{
-		if (pack && a.packBits != 0)
-			hipLaunchKernelGGL((cluster_mask_kernel<LATE, SOA, true, DEPTH, DIRECT, false, CAN_PACK>), grid, block, 0, stream, a);
-		else
-			hipLaunchKernelGGL((cluster_mask_kernel<LATE, SOA, true, DEPTH, DIRECT>), grid, block, 0, stream, a);
-	}
-	else if (pack)
-		hipLaunchKernelGGL((cluster_mask_kernel<LATE, SOA, false, DEPTH, DIRECT, false, CAN_PACK>), grid, block, 0, stream, a);
-	else
-		hipLaunchKernelGGL((cluster_mask_kernel<LATE, SOA, false, DEPTH, DIRECT>), grid, block, 0, stream, a);
-}
-
-// what launch_cluster_mask resolves (late, soa, direct) and the arguments to: the packed walk? (context.hip count_cull_variant)
-bool clustercull_takes_packed(const ClusterArgs& a, int late, bool soa, bool direct)
-{
-	return soa && direct && a.filterK > 0.0f && !late && a.packDirect != 0 && (a.deferHiz || a.packBits != 0 || !(a.cd.clusterOcclusionEnabled == 1 && a.cd.postPass == 0));
-}
-
-// any grid size (pure map); shallow = use the 4-deep filter ring (early pass over the SoA mirror only); direct = no filter
-// pass (SoA mirror only; the host's guess from the previous launch's statistic — a wrong guess only costs speed)
-// expectedCmds: the host's guess of the indirect command count (the previous launch's, or the explicit override): the dealing plan travels
-// with the arguments for it (dealing.h); 0 = no guess
-bool clustercull_takes_packed(const ClusterArgs& a, int late, bool soa, bool direct);
-
-int launch_cluster_mask(hipStream_t stream, const ClusterArgs& args, int late, bool soa, uint32_t maskBlocks, bool shallow, bool direct, uint32_t expectedCmds)
+// The cull launch: a flat dispatch from the form the host chose (cullform.h choose_cull_form — nothing is decided here) to the instantiation.  Any grid size
+// (pure map).  The dealing plan for form.expectedCmds travels with the arguments (dealing.h); 0 = no guess.
+#define CC_KEY(LATE, SOA, BITS, DEPTH, DIRECT, DEFER, PACK) ((LATE) | (SOA) << 1 | (BITS) << 2 | ((DEPTH) == 4) << 3 | (DIRECT) << 4 | (DEFER) << 5 | (PACK) << 6)
+#define CC_CASE(...) case CC_KEY(__VA_ARGS__): hipLaunchKernelGGL((cluster_mask_kernel<__VA_ARGS__>), grid, block, 0, stream, a); break;
+int launch_cluster_mask(hipStream_t stream, const ClusterArgs& args, const CullForm& form, uint32_t maskBlocks)
 {
 	ClusterArgs a = args;
 	// The dealing's delay compensation was calibrated on the filter form (a wave of config 3A lives ~11 us).  A wave of the packed walk lives 18-23 us and
 	// is bound by vector issue, so a later generation — the younger waves of every SIMD — falls behind by more than its start delay: the walk has a delay
 	// table of its own (dealing.h DEAL_PACKED_TABLE; round 6: 0 / 100 / 200 / 300 / 400 % of the filter form's — contract chain's cull launch 26.8 / 25.9 /
 	// 24.8 / 24.7 / 25.3 us — then the last generation's entry by the wave timeline)
-	if (clustercull_takes_packed(a, late, soa, direct))
+	if (form.packed)
 		a.dealScale += DEAL_PACKED_TABLE;
-	a.plan = deal_plan(expectedCmds, late ? CC_CHUNK_LATE : CC_CHUNK, !late, maskBlocks * CC_WAVES, a.cullWavesMagic, a.generations, a.genBlocks, maskBlocks, a.dealScale,
-	                   a.scatterTiles, a.tilesMagic);
-	if (expectedCmds == 0)
+	a.plan = deal_plan(form.expectedCmds, form.late ? CC_CHUNK_LATE : CC_CHUNK, !form.late, maskBlocks * CC_WAVES, a.cullWavesMagic, a.generations, a.genBlocks, maskBlocks,
+	                   a.dealScale, a.scatterTiles, a.tilesMagic);
+	if (form.expectedCmds == 0)
 		a.plan.flags = ~0u; // (no plan: an empty pass derives its own, which costs nothing)
-	if (soa && direct && a.filterK > 0.0f)
+	dim3 grid(maskBlocks), block(CC_THREADS);
+	switch (CC_KEY(form.late, form.soa, form.bits, form.depth, form.direct, form.defer, form.packed))
 	{
-		if (late)
-			launch_cc<true, true, 8, true>(stream, a, maskBlocks);
-		else
-			launch_cc<false, true, 8, true>(stream, a, maskBlocks);
-	}
-	else if (late)
-	{
-		// (the 4-deep ring measured slower for the late pass: 46.7 vs 42.9 us, config 4)
-		if (soa)
-			launch_cc<true, true, 8>(stream, a, maskBlocks);
-		else
-			launch_cc<true, false, 8>(stream, a, maskBlocks);
-	}
-	else
-	{
-		if (soa && shallow)
-			launch_cc<false, true, 4>(stream, a, maskBlocks);
-		else if (soa)
-			launch_cc<false, true, 8>(stream, a, maskBlocks);
-		else
-			launch_cc<false, false, 8>(stream, a, maskBlocks);
+		// <LATE, SOA, BITS, ring depth, DIRECT, DEFER, PACK>: the direct forms (over the mirror only), then the filter forms
+		CC_CASE(false, true, false, 8, true, true, false)
+		CC_CASE(true, true, true, 8, true, false, false) // (the three late forms WITH visibility bits are never chosen since the late pass with HiZ is two-stage)
+		CC_CASE(true, true, false, 8, true, false, false)
+		CC_CASE(false, true, false, 8, true, true, true)
+		CC_CASE(false, true, true, 8, true, false, true)
+		CC_CASE(false, true, true, 8, true, false, false)
+		CC_CASE(false, true, false, 8, true, false, true)
+		CC_CASE(false, true, false, 8, true, false, false)
+		CC_CASE(false, true, false, 8, false, true, false)
+		CC_CASE(true, true, true, 8, false, false, false)
+		CC_CASE(true, true, false, 8, false, false, false)
+		CC_CASE(false, false, false, 8, false, true, false)
+		CC_CASE(true, false, true, 8, false, false, false)
+		CC_CASE(true, false, false, 8, false, false, false)
+		CC_CASE(false, true, false, 4, false, true, false)
+		CC_CASE(false, true, true, 4, false, false, false)
+		CC_CASE(false, true, false, 4, false, false, false)
+		CC_CASE(false, true, true, 8, false, false, false)
+		CC_CASE(false, true, false, 8, false, false, false)
+		CC_CASE(false, false, true, 8, false, false, false)
+		CC_CASE(false, false, false, 8, false, false, false)
+	default:
+		return (int)hipErrorInvalidValue; // a form no instantiation exists for: choose_cull_form never answers one (tests/test_cull_form.py)
 	}
 	return (int)hipGetLastError();
 }
-
-bool clustercull_prefers_shallow(uint32_t previousCommandCount) { return previousCommandCount != 0 && previousCommandCount <= CC_SHALLOW_COMMANDS; }
-
-// the filter pass pays for itself while it finishes more than about half of the commands (measured: DESIGN.md §4.1)
-bool clustercull_prefers_direct(uint32_t previousCommandCount, uint32_t previousPassedFilter, uint32_t percent)
-{
-	return previousCommandCount != 0 && (uint64_t)previousPassedFilter * 100u > (uint64_t)previousCommandCount * percent;
-}
-
-// The filter form's time goes with the number of COMMANDS (its stream is bound by instruction issue: ~60 instructions per command whatever the command's
-// size), the packed direct walk's with the number of valid MESHLETS / 64.  Behind drawcull's LOD select a draw's meshlets end in a partial command — config
-// 3B at BASELINE scale: 250 k commands, 40 valid lanes on average — and the packed walk then wins even where the filter rejects nearly everything (22.5 against
-// 34 us there, a cache-resident pool; 3A's full commands streamed from HBM: filter 21 us, packed walk 32).  The pass's FILL — valid meshlets per command slot —
-// is ESTIMATED, at no cost to any kernel, from what the task pass that wrote the commands left for the host anyway (context.hip: emitting draws and commands,
-// hint words 2 and 3): every emitting draw ends in one command that is half full on average, fill ~ 1 - draws / (2 commands).  (Round 6 first MEASURED it — the
-// valid meshlets summed by the cull kernels, a second word beside the filter statistic, summed by the scatter launch: the scatter launch of the headline
-// pass took 5.09 instead of 4.71 us by kernel-trace, whichever part of the plumbing was taken out again; the estimate decides the same way on every config.)
-bool clustercull_prefers_packed(uint32_t taskCommands, uint32_t emittingDraws, uint32_t fillPercent)
-{
-	return taskCommands != 0 && emittingDraws != 0 && (uint64_t)(2u * (uint64_t)taskCommands - emittingDraws) * 100u < (uint64_t)taskCommands * 2u * fillPercent;
-}
+#undef CC_CASE
+#undef CC_KEY
 
 // early pass with visibility bits, dense form (one lane per set bit): any grid size (equal contiguous shares per block, grid-stride beyond CB_CMDS commands per block)
-template <bool SOA>
-static void launch_cb(hipStream_t stream, const ClusterArgs& a, uint32_t gridBlocks)
-{
-	// (the form without visibility bits — every valid cluster an entry, cluster_bits_kernel<SOA, false> — was the host's choice for a cache-resident pool in
-	// rounds 4-5; the direct form's packed walk took its place in round 6 and it is no longer instantiated)
-	dim3 grid(gridBlocks), block(CB_THREADS);
-	hipLaunchKernelGGL((cluster_bits_kernel<SOA, true>), grid, block, 0, stream, a);
-}
-
+// (the form without visibility bits — every valid cluster an entry, cluster_bits_kernel<SOA, false> — was the host's choice for a cache-resident pool in
+// rounds 4-5; the direct form's packed walk took its place in round 6 and it is no longer instantiated)
 int launch_cluster_bits(hipStream_t stream, const ClusterArgs& a, bool soa, uint32_t gridBlocks)
 {
+	dim3 grid(gridBlocks), block(CB_THREADS);
 	if (soa)
-		launch_cb<true>(stream, a, gridBlocks);
+		hipLaunchKernelGGL((cluster_bits_kernel<true, true>), grid, block, 0, stream, a);
 	else
-		launch_cb<false>(stream, a, gridBlocks);
+		hipLaunchKernelGGL((cluster_bits_kernel<false, true>), grid, block, 0, stream, a);
 	return (int)hipGetLastError();
 }
 

@@ -16,15 +16,12 @@
 #include "cullmath.h"
 #include "args.h"
 #include "filtermath.h"
+#include "cullform.h"
 
 namespace nv
 {
 
-int launch_cluster_mask(hipStream_t, const ClusterArgs&, int late, bool soa, uint32_t maskBlocks, bool shallow, bool direct, uint32_t expectedCmds);
-bool clustercull_prefers_shallow(uint32_t previousCommandCount);
-bool clustercull_prefers_direct(uint32_t previousCommandCount, uint32_t previousPassedFilter, uint32_t percent);
-bool clustercull_takes_packed(const ClusterArgs&, int late, bool soa, bool direct);
-bool clustercull_prefers_packed(uint32_t taskCommands, uint32_t emittingDraws, uint32_t fillPercent);
+int launch_cluster_mask(hipStream_t, const ClusterArgs&, const CullForm&, uint32_t maskBlocks);
 int launch_cluster_scatter(hipStream_t, const ClusterArgs&, uint32_t scatterBlocks, uint32_t waves);
 int launch_cluster_hiz(hipStream_t, const ClusterArgs&, bool soa, uint32_t gridBlocks);
 int launch_cluster_bits(hipStream_t, const ClusterArgs&, bool soa, uint32_t gridBlocks);
@@ -367,19 +364,38 @@ uint32_t persistent_grid(const nv_context* ctx, uint32_t blocksPerCU)
 	return (uint32_t)ctx->numCUs * blocksPerCU;
 }
 
-// nv_profile_variants: what launch_cluster_bits / launch_cluster_mask resolve the host's choices to (clustercull.hip)
-void count_cull_variant(nv_context* ctx, const nv::ClusterArgs& a, bool lanes, bool bits, bool late, bool shallow, bool direct)
+// The cull launch of nv_clustercull / nv_taskcull's early pass, in the form cullform.h choose_cull_form answers for the context, the pass's arguments and the mapped
+// hint words (each read once): the form's words into the arguments, the launch, nv_profile_variants' count.  The provenance of the command list is good for ONE
+// launch: a later list at the same address — a freed and reused buffer, a caller-built list — is not this context's drawcull output unless another
+// nv_drawcull(task) has written there since.
+nv::CullForm launch_cull(nv_context* ctx, hipStream_t s, nv::ClusterArgs& a, bool taskPayload, int late, const void* d_commands, int* rc)
 {
-	int v;
-	if (lanes)
-		v = bits ? NV_VARIANT_CULL_LANES_BITS : NV_VARIANT_CULL_LANES;
-	else if (!a.soaBounds)
-		v = NV_VARIANT_CULL_AOS;
-	else if (direct && a.filterK > 0.0f)
-		v = nv::clustercull_takes_packed(a, late, true, true) ? NV_VARIANT_CULL_DIRECT_PACKED : NV_VARIANT_CULL_DIRECT;
-	else
-		v = !late && shallow ? NV_VARIANT_CULL_FILTER_RING4 : NV_VARIANT_CULL_FILTER_RING8;
-	ctx->variants[v] += 1u;
+	nv::CullFormInputs in = {};
+	in.taskPayload = taskPayload;
+	in.late = late != 0;
+	in.clusterOcclusionEnabled = a.cd.clusterOcclusionEnabled;
+	in.postPass = a.cd.postPass;
+	in.soa = a.soaBounds != nullptr;
+	in.filterPositive = a.filterK > 0.0f;
+	in.forceDirect = ctx->forceDirect;
+	in.forceShallow = ctx->forceShallow;
+	in.directPercent = ctx->directPercent;
+	in.hints = ctx->hintHost != nullptr;
+	for (int i = 0; in.hints && i < 5; ++i)
+		in.hint[i] = ctx->hintHost[i];
+	in.ownTaskCommands = d_commands == ctx->taskCommandsFrom;
+	ctx->taskCommandsFrom = nullptr;
+	in.mirroredCount = ctx->scene->mirroredCount;
+	in.alwaysDeep = (ctx->debugMode & 65536u) != 0; // bit 16 (experiments)
+	in.commandCountOverride = a.commandCountOverride;
+	const nv::CullForm form = nv::choose_cull_form(in);
+	a.deferHiz = form.deferHiz;
+	a.packDirect = form.packDirect;
+	a.packBits = form.packBits;
+	ctx->variants[form.variant] += 1u;
+	*rc = form.lanes ? nv::launch_cluster_bits(s, a, form.soa, persistent_grid(ctx, ctx->bitsBlocksPerCU))
+	                 : nv::launch_cluster_mask(s, a, form, persistent_grid(ctx, ctx->ccBlocksPerCU));
+	return form;
 }
 
 } // namespace
@@ -961,8 +977,6 @@ int nv_clustercull(nv_context* ctx, void* stream, const NvCullData* cull, int la
 	a.clusterCount4 = d_clusterCount4;
 	a.fusedReset = ctx->fusedReset;
 	a.fusedSubmit = ctx->fusedSubmit;
-	a.packDirect = ctx->forceDirect != 3 ? 1u : 0u; // NV_OPT_CULL_FORM 4: one command per wave iteration also where the packed walk applies
-	a.packBits = ctx->forceDirect == 4 ? 1u : 0u;   // NV_OPT_CULL_FORM 5: the early pass with visibility bits as a packed walk too
 	a.countsSink = reinterpret_cast<unsigned long long*>(ctx->countsSink);
 #ifdef NV_EXPERIMENTS
 	a.debugMode = ctx->debugMode;
@@ -984,45 +998,7 @@ int nv_clustercull(nv_context* ctx, void* stream, const NvCullData* cull, int la
 	// two pure maps: the cull kernel also accumulates survivors per scatter tile, so no workgroup waits on another
 	hipStream_t s = (hipStream_t)stream;
 	hipEvent_t e0 = prof_mark(ctx, s);
-	bool shallow = ctx->hintHost && nv::clustercull_prefers_shallow(*ctx->hintHost) && !(ctx->debugMode & 65536u); // bit 16 (experiments): always deep
-	if (ctx->forceShallow >= 0)
-		shallow = ctx->forceShallow != 0;
-	// mapped host words the previous launches left: [0] command count, [1] commands their filter did not (or would not
-	// have) finished — possibly a launch or two behind, which only matters for speed
-	bool direct = ctx->hintHost && nv::clustercull_prefers_direct(ctx->hintHost[0], ctx->hintHost[1], ctx->directPercent);
-	if (!(ctx->hintHost && ctx->hintHost[0] != 0) && d_commands == ctx->taskCommandsFrom) // no statistic yet: by where the commands come from
-		direct = true;
-	// (the provenance is good for ONE cluster launch: a later list at the same address — a freed and reused buffer, a caller-built list — is not this
-	// context's drawcull output unless another nv_drawcull(task) has written there since)
-	const bool ownTaskCommands = d_commands == ctx->taskCommandsFrom;
-	ctx->taskCommandsFrom = nullptr;
-	// A pass of partial commands — what drawcull's LOD select leaves — takes the direct form's packed walk whatever the filter statistic says, where that form
-	// exists (early form without visibility bits, over the mirror): its fill is estimated from the emitting draws and commands the task pass that wrote the
-	// list left in hint words 2 and 3 (clustercull.hip clustercull_prefers_packed); a caller's own list has no such words and is taken as full.
-	const bool bits = cull->clusterOcclusionEnabled == 1 && cull->postPass == 0;
-	const bool twoStage = late && cull->clusterOcclusionEnabled == 1;
-	if (!direct && ownTaskCommands && ctx->hintHost && a.soaBounds && a.filterK > 0.0f && (twoStage || (!late && !bits)))
-	{
-		const bool poolInCache = (uint64_t)ctx->scene->mirroredCount * 12u <= (48ull << 20);
-		direct = nv::clustercull_prefers_packed(ctx->hintHost[3], ctx->hintHost[2], poolInCache ? 85u : 60u);
-	}
-	if (ctx->forceDirect >= 0)
-		direct = ctx->forceDirect != 0;
-	// Late pass with HiZ = three launches: the cull kernel in its early form (frustum + cone ballots), the occlusion probe
-	// with one lane per survivor (clustercull.hip cluster_hiz_kernel: visibility bits, skip, tile counts), the scatter.
-	a.deferHiz = twoStage ? 1u : 0u;
-	// Where the filter would not pay (direct), an EARLY pass with visibility bits tests one LANE per cluster that can be visible at all — per set bit —
-	// instead of one wave per command (clustercull.hip cluster_bits_kernel: 26 against 38-40 us at frame scale).  Without bits the direct form walks
-	// packed windows of 64 valid meshlets (cluster_mask_kernel PACK, round 6: the cluster pass behind drawcull's LOD select 24 us against 34 for the
-	// lane-per-valid-cluster form rounds 4-5 chose for a cache-resident pool, and 44 for one command per wave iteration); so does the late pass's first
-	// stage.  NV_OPT_CULL_FORM 3 keeps one wave per command with visibility bits, 4 one command per wave iteration throughout.
-	const bool laneForm = !late && direct && ctx->forceDirect < 2 && bits;
-	if (laneForm)
-		rc = nv::launch_cluster_bits(s, a, a.soaBounds != nullptr, persistent_grid(ctx, ctx->bitsBlocksPerCU));
-	else
-		rc = nv::launch_cluster_mask(s, a, twoStage ? 0 : late, a.soaBounds != nullptr, persistent_grid(ctx, ctx->ccBlocksPerCU), shallow, direct,
-		                             a.commandCountOverride ? a.commandCountOverride : (ctx->hintHost ? ctx->hintHost[0] : 0u));
-	count_cull_variant(ctx, a, laneForm, bits, late && !twoStage, shallow, direct); // (the two-stage late pass launches the early form)
+	const bool twoStage = launch_cull(ctx, s, a, false, late, d_commands, &rc).twoStage; // (late pass with HiZ: the occlusion stage follows)
 	ctx->variants[NV_VARIANT_HIZ_STAGE] += twoStage ? 1u : 0u;
 	hipEvent_t e1 = prof_mark(ctx, s);
 	hipEvent_t eh = e1;
@@ -1070,28 +1046,9 @@ int nv_taskcull(nv_context* ctx, void* stream, const NvCullData* cull, int late,
 		// sparse pass at 8 bytes per meshlet and finishes most commands in 23 instructions, where the one-command-per-wave kernel
 		// reads 12 and runs the reference's ~190 for every command (10 M meshlets: 38 us).  The cull kernel only snapshots the count
 		// word when the reset is not fused; there is no count word here.
-		hipStream_t s = (hipStream_t)stream;
 		a.fusedReset = 1u;
 		a.clusterCount4 = nullptr;
-		// mapped hint words: [4] = the command count of the previous nv_taskcull (ring depth); [0], [1] = command count and filter
-		// statistic of the previous nv_clustercull, a consistent pair (the payload form writes neither: no scatter launch follows it
-		// that would publish its statistic).  A context that only ever calls nv_taskcull stays on the filter form.
-		bool shallow = ctx->hintHost && nv::clustercull_prefers_shallow(ctx->hintHost[4]);
-		if (ctx->forceShallow >= 0)
-			shallow = ctx->forceShallow != 0;
-		bool direct = ctx->hintHost && nv::clustercull_prefers_direct(ctx->hintHost[0], ctx->hintHost[1], ctx->directPercent);
-		if (!(ctx->hintHost && ctx->hintHost[0] != 0) && d_commands == ctx->taskCommandsFrom) // (as in nv_clustercull)
-			direct = true;
-		ctx->taskCommandsFrom = nullptr;
-		if (ctx->forceDirect >= 0)
-			direct = ctx->forceDirect != 0;
-		const bool bitsForm = direct && ctx->forceDirect < 2 && cull->clusterOcclusionEnabled == 1 && cull->postPass == 0;
-		if (bitsForm)
-			rc = nv::launch_cluster_bits(s, a, a.soaBounds != nullptr, persistent_grid(ctx, ctx->bitsBlocksPerCU));
-		else
-			rc = nv::launch_cluster_mask(s, a, 0, a.soaBounds != nullptr, persistent_grid(ctx, ctx->ccBlocksPerCU), shallow, direct,
-			                             a.commandCountOverride ? a.commandCountOverride : (ctx->hintHost ? ctx->hintHost[4] : 0u));
-		count_cull_variant(ctx, a, bitsForm, cull->clusterOcclusionEnabled == 1 && cull->postPass == 0, false, shallow, direct);
+		(void)launch_cull(ctx, (hipStream_t)stream, a, true, 0, d_commands, &rc);
 		return rc;
 	}
 	return nv::launch_taskcull((hipStream_t)stream, a, late, a.soaBounds != nullptr, (uint32_t)ctx->numCUs * 8);

@@ -13,7 +13,7 @@ import torch
 from . import host
 from . import synth
 from . import layouts as L
-from ._lib import NvError, PyramidDesc, check, lib
+from ._lib import VARIANT_NAMES, NvError, PyramidDesc, check, lib
 
 
 def _ptr(t):
@@ -95,7 +95,7 @@ class Context:
         names = ("cluster_cull", "cluster_scatter", "drawcull", "depthreduce", "cluster_hiz")
         return {n: (float(ms[i]), int(cnt[i])) for i, n in enumerate(names)}
 
-    VARIANTS = ("cull_filter_ring4", "cull_filter_ring8", "cull_direct", "cull_lanes_bits", "cull_lanes", "cull_aos", "hiz_stage", "task_list", "task_per_draw", "cull_direct_packed")
+    VARIANTS = VARIANT_NAMES
 
     def profile_variants(self):
         """{variant: launches since the last call}: which kernel form the host's per-launch choices resolved to (non-zero entries only)"""
