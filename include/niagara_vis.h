@@ -554,6 +554,63 @@ int nv_visibility_resolve(nv_context* ctx, void* stream, const NvCullData* cull,
                           NvVisRecord* d_records /* optional, width*height */, uint32_t* d_meshletSeen /* optional */,
                           uint32_t* d_drawPixels /* optional, drawCount */, uint64_t* d_totals4 /* optional */);
 
+/* ---- the attribute pass of the visibility buffer (replaces the varyings of meshlet.mesh.glsl and mesh.frag.glsl) ---- */
+
+/* src/scene.h:25-37, src/shaders/mesh.h:80-90 (std430: the vec3 emissiveFactor is padded to 16 bytes); 64 B, align 16 */
+typedef struct NvMaterial
+{
+	uint32_t albedoTexture;
+	uint32_t normalTexture;
+	uint32_t specularTexture;
+	uint32_t emissiveTexture;
+	float diffuseFactor[4];
+	float specularFactor[4];
+	float emissiveFactor[3];
+	uint32_t padding;
+} NvMaterial;
+
+/* One pixel of nv_visibility_attributes: what mesh.frag.glsl:27-31 receives, plus the barycentrics.  No sample and invalid records: all
+ * zero except drawId = 0xFFFFFFFF. */
+typedef struct NvPixelAttributes
+{
+	float uv[2];
+	float bary[2];          /* lambda1, lambda2 (lambda0 belongs to the triangle's first index); not clamped */
+	float normal[3];        /* interpolated, not normalised */
+	uint32_t drawId;
+	float tangent[4];
+	float wpos[3];
+	uint32_t materialIndex; /* d_draws[drawId].materialIndex */
+} NvPixelAttributes;
+
+/* nv_visibility_attributes: per pixel of nv_visibility_resolve's records (width x height, the frame's `globals`: projection, cullData.view)
+ * the triangle's three vertices go through the mesh shader's vertex stage (meshlet.mesh.glsl:125-147: index and vertex fetch with shortRefs,
+ * position -> wpos -> clip with nv_rasterdepth's arithmetic, texcoord from fp16, unpackTBN, rotateQuat of normal and tangent), homogeneous
+ * barycentrics are taken at the pixel centre nx = ((px + 0.5) / width) 2 - 1, ny = 1 - ((py + 0.5) / height) 2 (row 0 at the top):
+ *   d_i = (x_i - nx w_i, y_i - ny w_i), b0 = d1 x d2, b1 = d2 x d0, b2 = d0 x d1, s = (b0 + b1) + b2, lambda_i = b_i / s
+ * (vertices with w <= 0 of a near-clipped triangle need no special case), and every varying is (l0 a0 + l1 a1) + l2 a2.  A pixel whose s is 0
+ * or whose lambdas are not all finite is DEGENERATE: lambda = (1, 0, 0), counted.  The lambdas are not clamped: the rasteriser covers by
+ * positions snapped to 1/256 pixel, so a lambda of a covered pixel can be slightly negative.  With d_materials the fragment stage
+ * (mesh.frag.glsl:57-89) is evaluated from the material's factors — the library samples no textures; a material with a texture index > 0 is
+ * shaded from its factors and its pixels are counted — and packed: d_gbuffer0 R8G8B8A8_UNORM {tosrgb(albedo).rgb, log2(1 + emissivef) / 5},
+ * d_gbuffer1 A2B10G10R10_UNORM_PACK32 {encodeOct(nrm) * 0.5 + 0.5 + deband * (0.5 / 1023), specgloss.a, 0} (src/niagara.cpp:634-637), UNORM =
+ * clamp to [0, 1] with NaN -> 0, times 2^bits - 1, rounded half to even.  The POST alpha discard (:88) is coverage and is not modelled.
+ * Every fp32 operation is one IEEE operation in a fixed order; pow and log2 (gbuffer0 only) are the device's.
+ * A record with drawId == 0xFFFFFFFF (no sample, unresolved) writes the no-sample attributes and 0 into both G-buffer words.  A record is
+ * INVALID — counted, written like no sample — when drawId >= drawCount, meshletIndex >= meshletCount, triangle >= min(triangleCount, 96), an
+ * index byte >= min(vertexCount, 64), an index byte or vertex reference lies past meshletDataWords, a resolved vertex index >= vertexCount,
+ * or (with d_materials) materialIndex >= materialCount: every load stays inside the caller's buffers, which need no padding.
+ * Outputs, each optional: d_attributes (width * height NvPixelAttributes, 16-byte aligned), d_gbuffer0 / d_gbuffer1 (width * height u32; either
+ * requires d_materials), d_totals4 (accumulated: pixels shaded, invalid records, degenerate pixels, pixels whose material names a texture; the
+ * last one stays 0 without d_materials).
+ * Enqueues one launch (no allocation, no synchronisation: it can be captured).  NV_EINVAL: a NULL ctx, globals or d_records, width or height 0
+ * or above 16384, or not globals->screenWidth / screenHeight, a NULL array with a non-zero count, a G-buffer output without d_materials, a
+ * misaligned pointer (16 bytes: records, attributes, draws, vertices, materials; 8: totals; 4: the rest). */
+int nv_visibility_attributes(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisRecord* d_records, uint32_t width, uint32_t height,
+                             const NvMeshDraw* d_draws, uint32_t drawCount, const NvMeshlet* d_meshlets, uint32_t meshletCount,
+                             const uint32_t* d_meshletData, uint32_t meshletDataWords, const NvVertex* d_vertices, uint32_t vertexCount,
+                             const NvMaterial* d_materials /* optional */, uint32_t materialCount, NvPixelAttributes* d_attributes /* optional */,
+                             uint32_t* d_gbuffer0 /* optional */, uint32_t* d_gbuffer1 /* optional */, uint64_t* d_totals4 /* optional */);
+
 /* ---- host helpers mirroring src/niagara.cpp / src/resources.cpp (no device work) ---- */
 uint32_t nv_previous_pow2(uint32_t v);                        /* src/niagara.cpp:439-447 */
 uint32_t nv_image_mip_levels(uint32_t width, uint32_t height); /* src/resources.cpp:280-292 */
@@ -643,6 +700,8 @@ static_assert(sizeof(NvVertex) == 16, "Vertex layout (src/shaders/mesh.h:3-9)");
 static_assert(sizeof(NvGlobals) == 224 && offsetof(NvGlobals, cullData) == 64 && offsetof(NvGlobals, screenWidth) == 208, "Globals layout (src/shaders/mesh.h:46-51)");
 static_assert(sizeof(NvTriangleMask) == 16, "one mask per grid slot");
 static_assert(sizeof(NvVisRecord) == 16, "one 16-byte store per pixel");
+static_assert(sizeof(NvMaterial) == 64 && offsetof(NvMaterial, diffuseFactor) == 16 && offsetof(NvMaterial, emissiveFactor) == 48, "Material layout (src/scene.h:25-37)");
+static_assert(sizeof(NvPixelAttributes) == 64 && offsetof(NvPixelAttributes, drawId) == 28 && offsetof(NvPixelAttributes, materialIndex) == 60, "four 16-byte stores per pixel");
 static_assert(sizeof(NvSceneCacheInfo) == 208, "NvSceneCacheInfo is mirrored by niagara_amd/_lib.py");
 #endif
 

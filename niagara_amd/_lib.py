@@ -80,6 +80,7 @@ _SIGS = {
     "nv_depth_merge": (_i, [_vp, _vp, _vp, C.POINTER(_vp), _u32, _u32, _u32]),
     "nv_visibility_merge": (_i, [_vp, _vp, _vp, C.POINTER(_vp), _u32, _u32, _u32]),
     "nv_visibility_resolve": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "nv_visibility_attributes": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
     "nv_previous_pow2": (_u32, [_u32]),
     "nv_division_magic": (_u32, [_u32]),
     "nv_image_mip_levels": (_u32, [_u32, _u32]),

@@ -47,6 +47,10 @@ int launch_rasterdepth(hipStream_t, const RasterArgs& a, uint32_t gridBlocks, bo
 int launch_visibility_resolve(hipStream_t, const NvCullData& cd, const unsigned long long* visibility, uint32_t n, const NvMeshDraw* draws, uint32_t drawCount,
                               const NvMesh* meshes, uint32_t meshCount, void* records, uint32_t* meshletSeen, uint32_t* drawPixels, unsigned long long* totals,
                               uint32_t maxBlocks, bool perPixel);
+int launch_visibility_attributes(hipStream_t, const NvGlobals& globals, const void* records, uint32_t width, uint32_t height, const NvMeshDraw* draws,
+                                 uint32_t drawCount, const NvMeshlet* meshlets, uint32_t meshletCount, const uint32_t* meshletData, uint32_t dataWords,
+                                 const NvVertex* vertices, uint32_t vertexCount, const NvMaterial* materials, uint32_t materialCount, void* attributes,
+                                 uint32_t* gbuffer0, uint32_t* gbuffer1, unsigned long long* totals, uint32_t maxBlocks, bool perPixel);
 int launch_visibility_merge(hipStream_t, unsigned long long* dst, const unsigned long long* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks);
 int launch_rasterindexed(hipStream_t, RasterIndexedArgs a, void* scratch, uint32_t gridBlocks, bool nearClip);
 size_t rasterindexed_scratch_bytes(uint32_t drawCount);
@@ -141,6 +145,7 @@ struct nv_context
 	uint32_t rasterNearClip;   // NV_OPT_RASTER_NEAR_CLIP: 1 = the clipping instantiations of both depth rasterisers
 	uint32_t rasterStableIds;  // NV_OPT_RASTER_VISIBILITY_ID: 1 = nv_rasterdepth writes the stable form of the visibility word
 	uint32_t resolvePerPixel;  // experiments: nv_visibility_resolve without the per-run de-duplication
+	uint32_t attributesPerPixel; // experiments: nv_visibility_attributes without the per-run set-up
 };
 
 namespace
@@ -457,6 +462,8 @@ int nv_create(nv_context** out_ctx, int device)
 #ifdef NV_EXPERIMENTS
 	if (const char* v = getenv("NV_RESOLVE_PER_PIXEL"))
 		ctx->resolvePerPixel = (uint32_t)atoi(v);
+	if (const char* v = getenv("NV_ATTRIBUTES_PER_PIXEL"))
+		ctx->attributesPerPixel = (uint32_t)atoi(v);
 	if (const char* v = getenv("NV_DIRECT"))
 		ctx->forceDirect = atoi(v);
 	if (const char* v = getenv("NV_TASKCULL_ONE_LAUNCH"))
@@ -1200,6 +1207,25 @@ int nv_visibility_resolve(nv_context* ctx, void* stream, const NvCullData* cull,
 	return nv::launch_visibility_resolve((hipStream_t)stream, *cull, reinterpret_cast<const unsigned long long*>(d_visibility), width * height, d_draws,
 	                                     drawCount, d_meshes, meshCount, d_records, d_meshletSeen, d_drawPixels,
 	                                     reinterpret_cast<unsigned long long*>(d_totals4), persistent_grid(ctx, 8), ctx->resolvePerPixel != 0);
+}
+
+int nv_visibility_attributes(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisRecord* d_records, uint32_t width, uint32_t height,
+                             const NvMeshDraw* d_draws, uint32_t drawCount, const NvMeshlet* d_meshlets, uint32_t meshletCount,
+                             const uint32_t* d_meshletData, uint32_t meshletDataWords, const NvVertex* d_vertices, uint32_t vertexCount,
+                             const NvMaterial* d_materials, uint32_t materialCount, NvPixelAttributes* d_attributes, uint32_t* d_gbuffer0,
+                             uint32_t* d_gbuffer1, uint64_t* d_totals4)
+{
+	const auto misaligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+	if (!ctx || !globals || !d_records || width == 0 || height == 0 || width > 16384 || height > 16384 || globals->screenWidth != (float)width ||
+	    globals->screenHeight != (float)height || (drawCount && !d_draws) || (meshletCount && !d_meshlets) || (meshletDataWords && !d_meshletData) ||
+	    (vertexCount && !d_vertices) || (materialCount && !d_materials) || ((d_gbuffer0 || d_gbuffer1) && !d_materials) || misaligned(d_records, 15u) ||
+	    misaligned(d_attributes, 15u) || misaligned(d_draws, 15u) || misaligned(d_vertices, 15u) || misaligned(d_materials, 15u) ||
+	    misaligned(d_totals4, 7u) || misaligned(d_meshlets, 3u) || misaligned(d_meshletData, 3u) || misaligned(d_gbuffer0, 3u) || misaligned(d_gbuffer1, 3u))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_visibility_attributes((hipStream_t)stream, *globals, d_records, width, height, d_draws, drawCount, d_meshlets, meshletCount, d_meshletData,
+	                                        meshletDataWords, d_vertices, vertexCount, d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1,
+	                                        reinterpret_cast<unsigned long long*>(d_totals4), persistent_grid(ctx, 8), ctx->attributesPerPixel != 0);
 }
 
 int nv_visibility_merge(nv_context* ctx, void* stream, uint64_t* d_dst, const uint64_t* const* d_srcs, uint32_t sources, uint32_t width, uint32_t height)

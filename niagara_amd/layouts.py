@@ -34,6 +34,13 @@ assert (VERTEX.itemsize, GLOBALS.itemsize, TRIMASK.itemsize) == (16, 224, 16)
 # NvVisRecord: one pixel of nv_visibility_resolve (no sample: drawId = 0xFFFFFFFF, the rest 0; unresolved: all ones)
 VISRECORD = np.dtype([("drawId", "<u4"), ("meshletIndex", "<u4"), ("triangle", "<u4"), ("depthBits", "<u4")])
 assert VISRECORD.itemsize == 16
+# NvMaterial (src/scene.h:25-37, src/shaders/mesh.h:80-90) and NvPixelAttributes, one pixel of nv_visibility_attributes (no sample and invalid
+# records: all zero except drawId = 0xFFFFFFFF)
+MATERIAL = np.dtype([("albedoTexture", "<u4"), ("normalTexture", "<u4"), ("specularTexture", "<u4"), ("emissiveTexture", "<u4"),
+                     ("diffuseFactor", "<f4", 4), ("specularFactor", "<f4", 4), ("emissiveFactor", "<f4", 3), ("padding", "<u4")])
+PIXELATTR = np.dtype([("uv", "<f4", 2), ("bary", "<f4", 2), ("normal", "<f4", 3), ("drawId", "<u4"), ("tangent", "<f4", 4), ("wpos", "<f4", 3),
+                      ("materialIndex", "<u4")])
+assert (MATERIAL.itemsize, PIXELATTR.itemsize) == (64, 64)
 VIS_ID_BITS = 34  # the stable form of the visibility word: bits(z) << 34 | ((mvi << 7 | triangle) + 1)
 
 TASK_WGSIZE = 64

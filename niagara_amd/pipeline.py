@@ -208,6 +208,17 @@ class Context:
                                         int(draw_count), _ptr(mb), int(mesh_count), _ptr(records), _ptr(meshlet_seen), _ptr(draw_pixels),
                                         _ptr(totals4)), "nv_visibility_resolve")
 
+    def visibility_attributes(self, globals_, records, width, height, db, draw_count, mlb, meshlet_count, meshlet_data, data_words, vertices,
+                              vertex_count, materials=None, material_count=0, attributes=None, gbuffer0=None, gbuffer1=None, totals4=None):
+        """the attribute pass over nv_visibility_resolve's records (nv_visibility_attributes): per pixel the varyings of the triangle it names
+        (attributes: width * height NvPixelAttributes) and, with a material table, the two G-buffer words (gbuffer0 R8G8B8A8_UNORM, gbuffer1
+        A2B10G10R10_UNORM_PACK32; width * height u32 each).  db: the FULL draw array; globals_: the frame's projection and view.  totals4 (u64,
+        accumulated): shaded, invalid, degenerate, pixels whose material names a texture.  Every output is optional"""
+        check(lib.nv_visibility_attributes(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(records), int(width), int(height), _ptr(db),
+                                           int(draw_count), _ptr(mlb), int(meshlet_count), _ptr(meshlet_data), int(data_words), _ptr(vertices),
+                                           int(vertex_count), _ptr(materials), int(material_count), _ptr(attributes), _ptr(gbuffer0), _ptr(gbuffer1),
+                                           _ptr(totals4)), "nv_visibility_attributes")
+
     def depthreduce(self, depth, width, height, pyramid):
         check(lib.nv_depthreduce(self.h, _stream(), _ptr(depth), width, height, C.byref(pyramid)), "nv_depthreduce")
 
@@ -397,6 +408,33 @@ class VisibilityPipeline:
                    totals=torch.zeros(4, dtype=torch.int64, device=dev))
         self.ctx.visibility_resolve(cull_data, visibility, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws, self.mb, self.mesh_count,
                                     out["records"], out["meshlet_seen"], out["draw_pixels"], out["totals"])
+        return out
+
+    def attributes(self, cull_data, records, materials=None, attributes=True, gbuffers=True):
+        """nv_visibility_attributes over resolve()'s "records" under the frame's CullData: a dict with "attributes" (uint8 tensor, height *
+        width NvPixelAttributes), "gbuffer0" / "gbuffer1" (int32, height x width; only with `materials`, a host array of layouts.MATERIAL or a
+        device tensor of them) and "totals" (int64: shaded, invalid, degenerate, textured); an output switched off is None.  The records are
+        global (the scene's draw ids), so this works unchanged on any rank of a sharded frame after the composite"""
+        if not self.stable_ids:
+            raise NvError("attributes reads resolve()'s records: VisibilityPipeline(..., stable_ids=True)")
+        if self.mdb is None:
+            raise NvError("attributes needs the scene's geometry: VisibilityPipeline(..., meshlet_data=, vertices=)")
+        dev = self.ctx.device
+        n = self.depth_w * self.depth_h
+        mat, n_mat = materials, 0
+        if materials is not None:
+            if isinstance(materials, np.ndarray):
+                mat = to_device(np.ascontiguousarray(materials, L.MATERIAL), dev)
+            n_mat = mat.numel() * mat.element_size() // L.MATERIAL.itemsize
+        out = dict(attributes=torch.zeros(n * L.PIXELATTR.itemsize, dtype=torch.uint8, device=dev) if attributes else None,
+                   gbuffer0=torch.zeros((self.depth_h, self.depth_w), dtype=torch.int32, device=dev) if gbuffers and mat is not None else None,
+                   gbuffer1=torch.zeros((self.depth_h, self.depth_w), dtype=torch.int32, device=dev) if gbuffers and mat is not None else None,
+                   totals=torch.zeros(4, dtype=torch.int64, device=dev))
+        g = synth.make_globals(cull_data, (self.depth_w, self.depth_h))
+        n_draws = getattr(self, "total_draws", self.draw_count)
+        self.ctx.visibility_attributes(g, records, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws, self.mlb, self.meshlet_count,
+                                       self.mdb, self.mdb.numel() * self.mdb.element_size() // 4, self.vb, self.vertex_count, mat, n_mat,
+                                       out["attributes"], out["gbuffer0"], out["gbuffer1"], out["totals"])
         return out
 
     def frame(self, cull_data, post_pass=False, on_phase=None, task=True, visibility=None):

@@ -13,7 +13,10 @@ per-phase counts of the last frame summed over the ranks, the frame time (MAX ov
 --frames frames) and the time of one depth composite.  --dump DIR writes rank_<r>.npz per rank: for every frame f and phase p the
 commands, cluster ids, dvb (the rank's draws), mvb, counts and depth, and the pyramid per frame (the frames start from cleared
 visibility; nothing is timed then).  --visibility (cluster scenes) runs the frame with stable ids and a visibility target per rank,
-composited with the depth; the JSON line gains the resolve totals of the last frame and the dump "f<f>_visibility" and "f<f>_records"."""
+composited with the depth; the JSON line gains the resolve totals of the last frame and the dump "f<f>_visibility" and "f<f>_records".
+--attributes (with --visibility) runs the attribute pass on every rank after the last frame (a fixed four-entry material table; the
+vertices' packed fields as the scene has them): the JSON line gains its totals and one digest of the outputs per rank of this process
+(equal digests: every rank shades the same frame), the dump attributes_<r>.npz."""
 import argparse
 import json
 import os
@@ -47,6 +50,7 @@ def parse(argv=None):
     ap.add_argument("--skip-last-composite", action="store_true")
     ap.add_argument("--dump", default="", help="directory for rank_<r>.npz")
     ap.add_argument("--visibility", action="store_true", help="stable-ID visibility buffer: composited with the depth, resolved after the frame")
+    ap.add_argument("--attributes", action="store_true", help="with --visibility: the attribute pass (nv_visibility_attributes) on every rank after the last frame")
     return ap.parse_args(argv)
 
 
@@ -126,6 +130,8 @@ def main():
     geometry = dict(vertices=s["vertices"], meshlet_data=s["data"]) if task else dict(vertices=s["vertices"], indices=s["indices"])
     if args.visibility and not task:
         raise SystemExit("--visibility needs a cluster scene: the indexed path has no visibility buffer")
+    if args.attributes and not args.visibility:
+        raise SystemExit("--attributes reads the resolved visibility buffer: add --visibility")
     kw = dict(task_capacity=4096 if len(s["draws"]) < 256 else None, cluster_capacity=4096 * 64 if len(s["draws"]) < 256 else None,
               fused=not args.unfused, near_clip=near_clip, weight=args.weight, stable_ids=args.visibility, **geometry)
     shards = None
@@ -209,6 +215,25 @@ def main():
     if vis is not None:  # every rank holds the frame's buffer after the composite: rank 0's resolve is the frame's
         tot = pipes[0].resolve(s["cull"], vis_of(0), records=False)["totals"].cpu().numpy()
         result.update(visibility=True, covered_pixels=int(tot[0]), unresolved_pixels=int(tot[1]), visibility_payload_bytes=w * h * 8)
+    if args.attributes:  # the records are global after the composite: every rank shades the whole frame, and all of them the same bytes
+        import hashlib
+        mats = np.zeros(4, L.MATERIAL)
+        mats["diffuseFactor"], mats["specularFactor"] = (0.8, 0.6, 0.4, 1.0), (0.5, 0.5, 0.5, 0.25)
+        mats["diffuseFactor"][:, 0] = np.linspace(0.2, 1.0, 4)
+        digests, tot = [], None
+        for k, p in enumerate(pipes):
+            out = p.attributes(s["cull"], p.resolve(s["cull"], vis_of(k))["records"], mats)
+            tot = out["totals"].cpu().numpy()
+            hsh = hashlib.sha256()
+            for name in ("attributes", "gbuffer0", "gbuffer1"):
+                hsh.update(out[name].cpu().numpy().tobytes())
+            digests.append(hsh.hexdigest()[:16])
+            if args.dump:
+                np.savez(os.path.join(args.dump, "attributes_%d.npz" % (p.rank if shards or args.as_rank else rank)),
+                         attributes=P.from_device(out["attributes"], L.PIXELATTR), gbuffer0=out["gbuffer0"].cpu().numpy().view(np.uint32),
+                         gbuffer1=out["gbuffer1"].cpu().numpy().view(np.uint32))
+        result.update(attributes=True, shaded_pixels=int(tot[0]), invalid_records=int(tot[1]), degenerate_pixels=int(tot[2]), attribute_digests=digests,
+                      attribute_payload_bytes=w * h * (L.PIXELATTR.itemsize + 8))
     for p in pipes:
         p.ctx.status()
     result["counts"] = {n: [int(x) for x in last_counts[n]] for n in names}
