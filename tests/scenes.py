@@ -39,6 +39,16 @@ def make_scene(seed=0, n_draws=300, n_meshes=3, lods=4, meshlets_lod0=150, scene
     return dict(meshes=meshes, meshlets=meshlets, draws=draws, slots=slots, post_mask=mask, cull=cd, depth=depth, viewport=viewport)
 
 
+MESH_TABLE_SEED = 418  # of the seeds 400-439 the one whose late pass rejects the most in-frustum draws (8-9) by occlusion
+
+
+def mesh_table_scene(n_meshes, seed=MESH_TABLE_SEED):
+    """The scene of tests/test_drawcull_mesh_table.py: 4097 draws (a partial 64-draw unit, several waves) over `n_meshes` meshes of
+    8 LODs (every word of a mesh's LOD table in use) and up to 3 task groups; the synthetic draws spread evenly over the table, so
+    its last entries are looked up as often as its first"""
+    return make_scene(seed=seed, n_draws=4097, n_meshes=n_meshes, lods=8, meshlets_lod0=150, post_pass_fraction=0.05)
+
+
 def task_capacity(scene):
     """upper bound on task commands any pass can emit for this scene (+64 for the tasksubmit padding)"""
     meshes, draws = scene["meshes"], scene["draws"]

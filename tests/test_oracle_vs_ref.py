@@ -192,6 +192,34 @@ def test_drawcull_flag_matrix(late, task):
             assert (dvb_o == dvb_r).all(), (flags, post)
 
 
+@pytest.mark.parametrize("late", [0, 1])
+@pytest.mark.parametrize("task", [0, 1])
+def test_drawcull_with_200_meshes(late, task):
+    """the scene of tests/test_drawcull_mesh_table.py at its largest table: "the GPU equals the oracle" at 200 meshes of 8 LODs rests on
+    an oracle that the tests above check with 3 meshes of 4"""
+    from scenes import mesh_table_scene
+    scene = mesh_table_scene(200)
+    rng = np.random.default_rng(200)
+    pyr_o, pyr_r = oracle.Pyramid(*scene["viewport"]), oracle.Pyramid(*scene["viewport"])
+    oracle.depthreduce(scene["depth"], pyr_o)
+    R.depthreduce(scene["depth"], pyr_r)
+    assert pyr_o.data.tobytes() == pyr_r.data.tobytes()
+    meshes_hit = set()
+    for flags in ((0, 1, 0, 0, 1), (1, 1, 1, 1, 1)):
+        cd = passes.set_flags(scene["cull"], flags)
+        for fraction in (1.0, 0.03):
+            for post in (0, 1):
+                dvb0 = (rng.random(len(scene["draws"])) < fraction).astype(np.uint32)
+                dvb_o, dvb_r = dvb0.copy(), dvb0.copy()
+                co, c4o = passes.run_drawcull(oracle, scene, cd, late, task, dvb_o, pyr_o, post)
+                cr, c4r = passes.run_drawcull(R, scene, cd, late, task, dvb_r, pyr_r, post)
+                assert c4o[0] == c4r[0], (flags, fraction, post)
+                assert co.tobytes() == cr.tobytes(), (flags, fraction, post)
+                assert (dvb_o == dvb_r).all(), (flags, fraction, post)
+                meshes_hit.update(scene["draws"]["meshIndex"][co["drawId"][:int(c4o[0])]].tolist())
+    assert {0, 63, 64, 199} <= meshes_hit and len(meshes_hit) >= 180
+
+
 def test_tasksubmit_and_clustersubmit_padding_and_clamps():
     for count in [0, 1, 63, 64, 65, 1000, 4095, 4096]:
         a, b = np.full(count + 80, 7, dtype=L.TASKCMD), np.full(count + 80, 7, dtype=L.TASKCMD)
