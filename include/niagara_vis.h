@@ -611,6 +611,55 @@ int nv_visibility_attributes(nv_context* ctx, void* stream, const NvGlobals* glo
                              const NvMaterial* d_materials /* optional */, uint32_t materialCount, NvPixelAttributes* d_attributes /* optional */,
                              uint32_t* d_gbuffer0 /* optional */, uint32_t* d_gbuffer1 /* optional */, uint64_t* d_totals4 /* optional */);
 
+/* ---- the shading end of the frame (replaces shadowfill.comp.glsl, shadowblur.comp.glsl and final.comp.glsl) ----
+ * Three of niagara's compute passes behind the G-buffer.  All images are linear buffers with row 0 at the top, as the raster target is:
+ *   depth               width * height fp32, the raster target as it stands: reverse-Z, 0 = no sample;
+ *   gbuffer0 / gbuffer1 width * height u32 as nv_visibility_attributes packs them: R8G8B8A8_UNORM, and A2B10G10R10_UNORM_PACK32 with R in bits 0-9;
+ *   shadow images       width * height u8 (VK_FORMAT_R8_UNORM, src/niagara.cpp:1328-1329), row pitch = width;
+ *   output colour       width * height u32 R8G8B8A8_UNORM, R in the low byte.  niagara writes the output in the swapchain's format
+ *                       (src/niagara.cpp:1864,1915 bind the swapchain image): a caller with a BGRA swapchain swizzles R and B.
+ * Rule set: every fp32 operation is one IEEE operation in the shader's order; max(a, b) = a < b ? b : a and min(a, b) =
+ * b < a ? b : a with the shader's argument order; UNORM fetch = code / (2^bits - 1); UNORM store = clamp to [0, 1] with NaN -> 0, times
+ * 2^bits - 1, round half to even; pow and exp2 are the device's.  A texelFetch / imageLoad OUTSIDE the image returns 0 and an imageStore
+ * outside it is dropped (Vulkan leaves both undefined without robust access; this is the library's defined semantic): every load stays
+ * inside the caller's buffers, which need no padding.
+ * Each entry point enqueues one launch (no allocation, no synchronisation: it can be captured).  NV_EINVAL: a NULL ctx or required pointer,
+ * width or height 0 or above 16384, a depth / G-buffer / colour pointer that is not 4-byte aligned, and what each entry point names. */
+
+/* src/niagara.cpp:280-290, final.comp.glsl:10-19; 112 B (104 used), align 16.  inverseViewProjection is column-major */
+typedef struct NvShadeData
+{
+	float cameraPosition[3];
+	float pad0;
+	float sunDirection[3];
+	int32_t shadowsEnabled;
+	float inverseViewProjection[16];
+	float imageSize[2];
+	float _pad[2];
+} NvShadeData;
+
+/* shadowfill.comp.glsl:17-46 over (width + 1) / 2 x height invocations (src/niagara.cpp:1797,1833), IN PLACE: invocation (x, y) owns the
+ * texel (2 x + (~(y ^ checkerboard) & 1), y) and replaces it by the depth-weighted mean of its four neighbours,
+ * dot(w, shadows) / (dot(w, 1) + 1e-2) with w = exp2(-abs(depths / depth - 1) * 20).  It reads texels of the other checkerboard parity only, so
+ * the update has no race; the texels of that other parity keep their bytes.  With an odd width the last invocation of a row can own x ==
+ * width: its store is dropped. */
+int nv_shadow_fill(nv_context* ctx, void* stream, uint8_t* d_shadow, const float* d_depth, uint32_t width, uint32_t height, int checkerboard);
+
+/* shadowblur.comp.glsl:24-64 with BLUR 1: a 21-tap depth-aware filter along one axis, direction 1 = horizontal, 0 = vertical
+ * (src/niagara.cpp:1847; anything else NV_EINVAL), znear as in NvCullData (the shader compares znear / depth, the view-space distance).
+ * exp2(-i * i / 50) is the shader's integer arithmetic: 1 for i = 1..7, 0.5 for 8 and 9, 0.25 for 10.  A tap outside the image has depth 0,
+ * distance +inf and therefore weight 0.  d_out == d_shadow is NV_EINVAL (partly overlapping images are the caller's error). */
+int nv_shadow_blur(nv_context* ctx, void* stream, uint8_t* d_out, const uint8_t* d_shadow, const float* d_depth, uint32_t width, uint32_t height,
+                   int direction, float znear);
+
+/* final.comp.glsl:37-80: the lit, tonemapped, debanded colour of every pixel from the two G-buffer words, the depth and (shadowsEnabled == 1)
+ * the shadow image; alpha is 255.  THE BLOOM TERM IS LEFT OUT: the result is exactly the shader's with an all-zero bloom image.  A sky pixel
+ * (depth 0) has wposh.w == 0 and a NaN view vector, as in the shader; tonemap's max(0, c - 0.004) turns it into 0.  gradientNoise takes the
+ * integer pixel position (no half-pixel offset, unlike mesh.frag.glsl).  NV_EINVAL also: shade->imageSize not (width, height); d_shadow NULL
+ * with shade->shadowsEnabled == 1 (with any other value the shadow image is never read and may be NULL). */
+int nv_shade_final(nv_context* ctx, void* stream, const NvShadeData* shade, const uint32_t* d_gbuffer0, const uint32_t* d_gbuffer1,
+                   const float* d_depth, const uint8_t* d_shadow /* optional */, uint32_t* d_color, uint32_t width, uint32_t height);
+
 /* ---- host helpers mirroring src/niagara.cpp / src/resources.cpp (no device work) ---- */
 uint32_t nv_previous_pow2(uint32_t v);                        /* src/niagara.cpp:439-447 */
 uint32_t nv_image_mip_levels(uint32_t width, uint32_t height); /* src/resources.cpp:280-292 */
@@ -625,6 +674,13 @@ int nv_build_cull_data(NvCullData* out, const float cameraPosition[3], const flo
                        float fovY, float znear, float drawDistance, uint32_t viewportWidth,
                        uint32_t viewportHeight, uint32_t pyramidWidth, uint32_t pyramidHeight,
                        uint32_t drawCount, int debugLodStep);
+/* src/niagara.cpp:1917-1922: the ShadeData of nv_shade_final from the frame's globals (projection, cullData.view): cameraPosition,
+ * sunDirection, shadowsEnabled, imageSize = (width, height) and inverseViewProjection = inverse(projection * view), the product and the
+ * inverse (adjugate / determinant) evaluated in fp64 from the fp32 entries and rounded once to fp32.  The reference uses glm's fp32 inverse,
+ * which is not vendored in its snapshot: the matrix is an INPUT of the pass, not part of its parity.  NV_EINVAL: a NULL pointer, width or
+ * height 0, a singular or non-finite product. */
+int nv_build_shade_data(NvShadeData* out, const NvGlobals* globals, const float cameraPosition[3], const float sunDirection[3],
+                        int shadowsEnabled, uint32_t width, uint32_t height);
 /* src/niagara.cpp:1002-1020: per-draw meshletVisibilityOffset prefix; returns the slot count
  * through out_slots (meshletVisibility bytes = (slots+31)/32*4) and the postPass mask. */
 int nv_assign_visibility_offsets(NvMeshDraw* draws, uint32_t drawCount, const NvMesh* meshes,
@@ -702,6 +758,8 @@ static_assert(sizeof(NvTriangleMask) == 16, "one mask per grid slot");
 static_assert(sizeof(NvVisRecord) == 16, "one 16-byte store per pixel");
 static_assert(sizeof(NvMaterial) == 64 && offsetof(NvMaterial, diffuseFactor) == 16 && offsetof(NvMaterial, emissiveFactor) == 48, "Material layout (src/scene.h:25-37)");
 static_assert(sizeof(NvPixelAttributes) == 64 && offsetof(NvPixelAttributes, drawId) == 28 && offsetof(NvPixelAttributes, materialIndex) == 60, "four 16-byte stores per pixel");
+static_assert(sizeof(NvShadeData) == 112 && offsetof(NvShadeData, sunDirection) == 16 && offsetof(NvShadeData, shadowsEnabled) == 28 &&
+              offsetof(NvShadeData, inverseViewProjection) == 32 && offsetof(NvShadeData, imageSize) == 96, "ShadeData layout (src/niagara.cpp:280-290)");
 static_assert(sizeof(NvSceneCacheInfo) == 208, "NvSceneCacheInfo is mirrored by niagara_amd/_lib.py");
 #endif
 

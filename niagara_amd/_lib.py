@@ -81,6 +81,10 @@ _SIGS = {
     "nv_visibility_merge": (_i, [_vp, _vp, _vp, C.POINTER(_vp), _u32, _u32, _u32]),
     "nv_visibility_resolve": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
     "nv_visibility_attributes": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "nv_shadow_fill": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _i]),
+    "nv_shadow_blur": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _i, _f]),
+    "nv_shade_final": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32]),
+    "nv_build_shade_data": (_i, [_vp, _vp, _vp, _vp, _i, _u32, _u32]),
     "nv_previous_pow2": (_u32, [_u32]),
     "nv_division_magic": (_u32, [_u32]),
     "nv_image_mip_levels": (_u32, [_u32, _u32]),

@@ -51,6 +51,10 @@ int launch_visibility_attributes(hipStream_t, const NvGlobals& globals, const vo
                                  uint32_t drawCount, const NvMeshlet* meshlets, uint32_t meshletCount, const uint32_t* meshletData, uint32_t dataWords,
                                  const NvVertex* vertices, uint32_t vertexCount, const NvMaterial* materials, uint32_t materialCount, void* attributes,
                                  uint32_t* gbuffer0, uint32_t* gbuffer1, unsigned long long* totals, uint32_t maxBlocks, bool perPixel);
+int launch_shadow_fill(hipStream_t, uint8_t* shadow, const float* depth, uint32_t width, uint32_t height, int checkerboard, uint32_t maxBlocks);
+int launch_shadow_blur(hipStream_t, uint8_t* out, const uint8_t* shadow, const float* depth, uint32_t width, uint32_t height, bool horizontal, float znear);
+int launch_shade_final(hipStream_t, const NvShadeData& sd, const uint32_t* gbuffer0, const uint32_t* gbuffer1, const float* depth, const uint8_t* shadow,
+                       uint32_t* color, uint32_t width, uint32_t height, uint32_t maxBlocks);
 int launch_visibility_merge(hipStream_t, unsigned long long* dst, const unsigned long long* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks);
 int launch_rasterindexed(hipStream_t, RasterIndexedArgs a, void* scratch, uint32_t gridBlocks, bool nearClip);
 size_t rasterindexed_scratch_bytes(uint32_t drawCount);
@@ -1226,6 +1230,39 @@ int nv_visibility_attributes(nv_context* ctx, void* stream, const NvGlobals* glo
 	return nv::launch_visibility_attributes((hipStream_t)stream, *globals, d_records, width, height, d_draws, drawCount, d_meshlets, meshletCount, d_meshletData,
 	                                        meshletDataWords, d_vertices, vertexCount, d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1,
 	                                        reinterpret_cast<unsigned long long*>(d_totals4), persistent_grid(ctx, 8), ctx->attributesPerPixel != 0);
+}
+
+// ---- the shading end of the frame (shade.hip)
+static bool shade_size_ok(uint32_t width, uint32_t height) { return width != 0 && height != 0 && width <= 16384 && height <= 16384; }
+
+int nv_shadow_fill(nv_context* ctx, void* stream, uint8_t* d_shadow, const float* d_depth, uint32_t width, uint32_t height, int checkerboard)
+{
+	if (!ctx || !d_shadow || !d_depth || !shade_size_ok(width, height) || (reinterpret_cast<uintptr_t>(d_depth) & 3u))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_shadow_fill((hipStream_t)stream, d_shadow, d_depth, width, height, checkerboard, persistent_grid(ctx, 8));
+}
+
+int nv_shadow_blur(nv_context* ctx, void* stream, uint8_t* d_out, const uint8_t* d_shadow, const float* d_depth, uint32_t width, uint32_t height,
+                   int direction, float znear)
+{
+	if (!ctx || !d_out || !d_shadow || !d_depth || d_out == d_shadow || !shade_size_ok(width, height) || (direction != 0 && direction != 1) ||
+	    (reinterpret_cast<uintptr_t>(d_depth) & 3u))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_shadow_blur((hipStream_t)stream, d_out, d_shadow, d_depth, width, height, direction == 1, znear);
+}
+
+int nv_shade_final(nv_context* ctx, void* stream, const NvShadeData* shade, const uint32_t* d_gbuffer0, const uint32_t* d_gbuffer1, const float* d_depth,
+                   const uint8_t* d_shadow, uint32_t* d_color, uint32_t width, uint32_t height)
+{
+	const auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
+	if (!ctx || !shade || !d_gbuffer0 || !d_gbuffer1 || !d_depth || !d_color || !shade_size_ok(width, height) || shade->imageSize[0] != (float)width ||
+	    shade->imageSize[1] != (float)height || (shade->shadowsEnabled == 1 && !d_shadow) || misaligned(d_gbuffer0) || misaligned(d_gbuffer1) ||
+	    misaligned(d_depth) || misaligned(d_color))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_shade_final((hipStream_t)stream, *shade, d_gbuffer0, d_gbuffer1, d_depth, d_shadow, d_color, width, height, persistent_grid(ctx, 8));
 }
 
 int nv_visibility_merge(nv_context* ctx, void* stream, uint64_t* d_dst, const uint64_t* const* d_srcs, uint32_t sources, uint32_t width, uint32_t height)

@@ -126,6 +126,64 @@ int nv_build_cull_data(NvCullData* out, const float cameraPosition[3], const flo
 	return NV_OK;
 }
 
+// src/niagara.cpp:1917-1922.  inverse(projection * view) in fp64 from the fp32 entries (the product's sums left to right, the inverse as adjugate /
+// determinant from the 2 x 2 minors of the row pairs), rounded once to fp32.  A structural zero of the product stays an exact zero: with niagara's
+// projection the w row of the result is (0, 0, 1 / znear, 0), so a sky pixel (depth 0) has wposh.w == 0 exactly, as in the shader.
+int nv_build_shade_data(NvShadeData* out, const NvGlobals* globals, const float cameraPosition[3], const float sunDirection[3], int shadowsEnabled,
+                        uint32_t width, uint32_t height)
+{
+	if (!out || !globals || !cameraPosition || !sunDirection || !width || !height)
+		return NV_EINVAL;
+	const float* P = globals->projection;
+	const float* V = globals->cullData.view;
+	double a[4][4]; // a[row][col] of projection * view (both column-major)
+	for (int r = 0; r < 4; ++r)
+		for (int c = 0; c < 4; ++c)
+			a[r][c] = (((double)P[r] * V[4 * c] + (double)P[4 + r] * V[4 * c + 1]) + (double)P[8 + r] * V[4 * c + 2]) + (double)P[12 + r] * V[4 * c + 3];
+	const double s0 = a[0][0] * a[1][1] - a[1][0] * a[0][1], s1 = a[0][0] * a[1][2] - a[1][0] * a[0][2], s2 = a[0][0] * a[1][3] - a[1][0] * a[0][3];
+	const double s3 = a[0][1] * a[1][2] - a[1][1] * a[0][2], s4 = a[0][1] * a[1][3] - a[1][1] * a[0][3], s5 = a[0][2] * a[1][3] - a[1][2] * a[0][3];
+	const double c5 = a[2][2] * a[3][3] - a[3][2] * a[2][3], c4 = a[2][1] * a[3][3] - a[3][1] * a[2][3], c3 = a[2][1] * a[3][2] - a[3][1] * a[2][2];
+	const double c2 = a[2][0] * a[3][3] - a[3][0] * a[2][3], c1 = a[2][0] * a[3][2] - a[3][0] * a[2][2], c0 = a[2][0] * a[3][1] - a[3][0] * a[2][1];
+	const double det = ((((s0 * c5 - s1 * c4) + s2 * c3) + s3 * c2) - s4 * c1) + s5 * c0;
+	if (!(fabs(det) > 0.0) || !(fabs(det) < INFINITY))
+		return NV_EINVAL;
+	double b[4][4]; // the adjugate, b[row][col]
+	b[0][0] = (a[1][1] * c5 - a[1][2] * c4) + a[1][3] * c3;
+	b[0][1] = (-a[0][1] * c5 + a[0][2] * c4) - a[0][3] * c3;
+	b[0][2] = (a[3][1] * s5 - a[3][2] * s4) + a[3][3] * s3;
+	b[0][3] = (-a[2][1] * s5 + a[2][2] * s4) - a[2][3] * s3;
+	b[1][0] = (-a[1][0] * c5 + a[1][2] * c2) - a[1][3] * c1;
+	b[1][1] = (a[0][0] * c5 - a[0][2] * c2) + a[0][3] * c1;
+	b[1][2] = (-a[3][0] * s5 + a[3][2] * s2) - a[3][3] * s1;
+	b[1][3] = (a[2][0] * s5 - a[2][2] * s2) + a[2][3] * s1;
+	b[2][0] = (a[1][0] * c4 - a[1][1] * c2) + a[1][3] * c0;
+	b[2][1] = (-a[0][0] * c4 + a[0][1] * c2) - a[0][3] * c0;
+	b[2][2] = (a[3][0] * s4 - a[3][1] * s2) + a[3][3] * s0;
+	b[2][3] = (-a[2][0] * s4 + a[2][1] * s2) - a[2][3] * s0;
+	b[3][0] = (-a[1][0] * c3 + a[1][1] * c1) - a[1][2] * c0;
+	b[3][1] = (a[0][0] * c3 - a[0][1] * c1) + a[0][2] * c0;
+	b[3][2] = (-a[3][0] * s3 + a[3][1] * s1) - a[3][2] * s0;
+	b[3][3] = (a[2][0] * s3 - a[2][1] * s1) + a[2][2] * s0;
+	memset(out, 0, sizeof(*out));
+	for (int r = 0; r < 4; ++r)
+		for (int c = 0; c < 4; ++c)
+		{
+			const double v = b[r][c] / det;
+			if (!(fabs(v) < INFINITY))
+				return NV_EINVAL;
+			out->inverseViewProjection[4 * c + r] = (float)v;
+		}
+	for (int k = 0; k < 3; ++k)
+	{
+		out->cameraPosition[k] = cameraPosition[k];
+		out->sunDirection[k] = sunDirection[k];
+	}
+	out->shadowsEnabled = shadowsEnabled;
+	out->imageSize[0] = (float)width;
+	out->imageSize[1] = (float)height;
+	return NV_OK;
+}
+
 // src/niagara.cpp:1002-1020
 int nv_assign_visibility_offsets(NvMeshDraw* draws, uint32_t drawCount, const NvMesh* meshes, uint32_t meshCount,
                                  uint32_t* out_slots, uint32_t* out_postPassMask)

@@ -43,6 +43,19 @@ def build_cull_data(cam_pos=(0, 0, 0), cam_quat=(0, 0, 0, 1), fovy=float(np.radi
     return cd
 
 
+def build_shade_data(globals_, camera_position=(0, 0, 0), sun_direction=(0, 1, 0), shadows_enabled=0, width=None, height=None):
+    """NvShadeData of nv_shade_final (src/niagara.cpp:1917-1922) from the frame's globals (synth.make_globals): inverseViewProjection =
+    inverse(projection * view) in fp64, rounded once; width / height default to the globals' screen size"""
+    sd = np.zeros(1, dtype=L.SHADEDATA)
+    g = np.ascontiguousarray(globals_)
+    w = int(g["screenWidth"][0]) if width is None else int(width)
+    h = int(g["screenHeight"][0]) if height is None else int(height)
+    pos = np.ascontiguousarray(camera_position, dtype=np.float32)
+    sun = np.ascontiguousarray(sun_direction, dtype=np.float32)
+    check(lib.nv_build_shade_data(_p(sd), _p(g), _p(pos), _p(sun), int(shadows_enabled), w, h), "nv_build_shade_data")
+    return sd
+
+
 def synth_draws(n, mesh_count, scene_radius=300.0):
     d = np.zeros(n, dtype=L.MESHDRAW)
     check(lib.nv_synth_draws(_p(d), n, mesh_count, scene_radius), "nv_synth_draws")

@@ -41,6 +41,10 @@ MATERIAL = np.dtype([("albedoTexture", "<u4"), ("normalTexture", "<u4"), ("specu
 PIXELATTR = np.dtype([("uv", "<f4", 2), ("bary", "<f4", 2), ("normal", "<f4", 3), ("drawId", "<u4"), ("tangent", "<f4", 4), ("wpos", "<f4", 3),
                       ("materialIndex", "<u4")])
 assert (MATERIAL.itemsize, PIXELATTR.itemsize) == (64, 64)
+# NvShadeData (src/niagara.cpp:280-290), the push constants of final.comp.glsl: 104 bytes used, alignas(16) pads to 112
+SHADEDATA = np.dtype([("cameraPosition", "<f4", 3), ("pad0", "<f4"), ("sunDirection", "<f4", 3), ("shadowsEnabled", "<i4"),
+                      ("inverseViewProjection", "<f4", 16), ("imageSize", "<f4", 2), ("_pad", "<f4", 2)])
+assert SHADEDATA.itemsize == 112
 VIS_ID_BITS = 34  # the stable form of the visibility word: bits(z) << 34 | ((mvi << 7 | triangle) + 1)
 
 TASK_WGSIZE = 64

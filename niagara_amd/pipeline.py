@@ -219,6 +219,23 @@ class Context:
                                            int(vertex_count), _ptr(materials), int(material_count), _ptr(attributes), _ptr(gbuffer0), _ptr(gbuffer1),
                                            _ptr(totals4)), "nv_visibility_attributes")
 
+    def shadow_fill(self, shadow, depth, width, height, checkerboard):
+        """shadowfill.comp.glsl in place (nv_shadow_fill): the texels of one checkerboard parity of the u8 shadow image become the
+        depth-weighted mean of their four neighbours; the other parity keeps its bytes"""
+        check(lib.nv_shadow_fill(self.h, _stream(), _ptr(shadow), _ptr(depth), int(width), int(height), int(checkerboard)), "nv_shadow_fill")
+
+    def shadow_blur(self, out, shadow, depth, width, height, direction, znear):
+        """shadowblur.comp.glsl (nv_shadow_blur): the 21-tap depth-aware filter of the u8 shadow image along one axis into `out` (another
+        image); direction 1 = horizontal, 0 = vertical"""
+        check(lib.nv_shadow_blur(self.h, _stream(), _ptr(out), _ptr(shadow), _ptr(depth), int(width), int(height), int(direction), float(znear)),
+              "nv_shadow_blur")
+
+    def shade_final(self, shade_data, gbuffer0, gbuffer1, depth, shadow, color, width, height):
+        """final.comp.glsl without the bloom term (nv_shade_final): the R8G8B8A8 colour (R in the low byte) of every pixel from the two
+        G-buffer words, the depth target and, with shade_data["shadowsEnabled"] == 1, the u8 shadow image (None otherwise)"""
+        check(lib.nv_shade_final(self.h, _stream(), C.c_void_p(shade_data.ctypes.data), _ptr(gbuffer0), _ptr(gbuffer1), _ptr(depth), _ptr(shadow),
+                                 _ptr(color), int(width), int(height)), "nv_shade_final")
+
     def depthreduce(self, depth, width, height, pyramid):
         check(lib.nv_depthreduce(self.h, _stream(), _ptr(depth), width, height, C.byref(pyramid)), "nv_depthreduce")
 
@@ -436,6 +453,33 @@ class VisibilityPipeline:
                                        self.mdb, self.mdb.numel() * self.mdb.element_size() // 4, self.vb, self.vertex_count, mat, n_mat,
                                        out["attributes"], out["gbuffer0"], out["gbuffer1"], out["totals"])
         return out
+
+    def shade(self, cull_data, gbuffer0, gbuffer1, camera_position, sun_direction, shadow=None, blur=True, checkerboard=False):
+        """the shading end of the frame over attributes()'s G-buffer words and the pipeline's own depth target (src/niagara.cpp:1822-1850,
+        1906-1925): returns the colour tensor (int32, height x width, R8G8B8A8 with R in the low byte).  shadow: a caller-supplied mask (uint8
+        tensor, height x width; the library traces no rays) — it is filled in place when `checkerboard`, blurred horizontally into an image
+        the pipeline owns and vertically back into the mask when `blur`, and final shades with shadows on; without a mask final runs
+        with shadows off"""
+        if self.depth is None:
+            raise NvError("shade reads the pipeline's depth target: VisibilityPipeline(..., meshlet_data=, vertices=)")
+        w, h = self.depth_w, self.depth_h
+        dev = self.ctx.device
+        if shadow is not None:
+            if shadow.dtype != torch.uint8 or shadow.numel() != w * h or not shadow.is_contiguous():
+                raise NvError("shade: the shadow mask is a contiguous uint8 tensor of the depth target's size")
+            if checkerboard:
+                self.ctx.shadow_fill(shadow, self.depth, w, h, 1)
+            if blur:
+                if getattr(self, "shadow_blur_image", None) is None:
+                    self.shadow_blur_image = torch.zeros((h, w), dtype=torch.uint8, device=dev)
+                znear = float(cull_data["znear"][0])
+                self.ctx.shadow_blur(self.shadow_blur_image, shadow, self.depth, w, h, 1, znear)  # src/niagara.cpp:1836-1850
+                self.ctx.shadow_blur(shadow, self.shadow_blur_image, self.depth, w, h, 0, znear)
+        g = synth.make_globals(cull_data, (w, h))
+        sd = host.build_shade_data(g, camera_position, sun_direction, 1 if shadow is not None else 0, w, h)
+        color = torch.zeros((h, w), dtype=torch.int32, device=dev)
+        self.ctx.shade_final(sd, gbuffer0, gbuffer1, self.depth, shadow, color, w, h)
+        return color
 
     def frame(self, cull_data, post_pass=False, on_phase=None, task=True, visibility=None):
         """one frame of src/niagara.cpp:1765-1788 with the raster in place of the graphics passes: early cull -> clusters -> raster ->

@@ -1,0 +1,154 @@
+#!/usr/bin/env python3
+"""A displayable image out of a scene on one GPU: synth.occluder_scene through frame(visibility=) -> resolve -> attributes -> shade
+(DESIGN.md §4.12-4.14).  A demonstration, not a test.
+
+    python3 tools/render_frame.py --out frame.ppm                       # the scene at its own viewport, a synthetic shadow mask
+    python3 tools/render_frame.py --no-shadow --viewport 1920x1080
+
+Writes a binary PPM (P6, R G B from the R8G8B8A8 colour words) and prints one JSON line with the passes' times by HIP events (one run
+each after a warm-up frame: launch gaps included, an upper bound of the kernel time; profiles/r13_shade.md has the kernel trace).
+--passes WxH[,WxH...] instead times the three shade passes alone on synthetic images of those sizes, cache-cold (a 512 MiB buffer is
+rewritten between the passes): the run to put under a kernel trace."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def _timed(events, name, fn):
+    import torch
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    events.append((name, a, b))
+    return out
+
+
+def passes(sizes, repeats):
+    """the three shade passes on synthetic images, each launch behind a flush of the caches"""
+    import numpy as np
+    import torch
+
+    from niagara_amd import host, synth
+    from niagara_amd import pipeline as P
+    ctx = P.Context()
+    dev = ctx.device
+    flush = torch.zeros(512 << 20, dtype=torch.uint8, device=dev)
+    for w, h in sizes:
+        rng = np.random.default_rng(w + h)
+        x, y = np.meshgrid(np.arange(w, dtype=np.float32), np.arange(h, dtype=np.float32))
+        depth = torch.from_numpy((0.1 / (4.0 + x / w + y / h)).astype(np.float32)).to(dev)
+        g0 = torch.from_numpy(rng.integers(0, 1 << 31, (h, w), dtype=np.int64).astype(np.int32)).to(dev)
+        g1 = torch.from_numpy(rng.integers(0, 1 << 31, (h, w), dtype=np.int64).astype(np.int32)).to(dev)
+        shadow = torch.from_numpy(rng.integers(0, 256, (h, w)).astype(np.uint8)).to(dev)
+        tmp, color = torch.zeros_like(shadow), torch.zeros((h, w), dtype=torch.int32, device=dev)
+        cd = host.build_cull_data(viewport=(w, h), pyramid=(host.previous_pow2(w), host.previous_pow2(h)))
+        sd = {k: host.build_shade_data(synth.make_globals(cd, (w, h)), (0, 0, 0), (0.35, 0.6, 0.72), k, w, h) for k in (0, 1)}
+        runs = dict(shadow_fill=lambda: ctx.shadow_fill(shadow, depth, w, h, 1), shadow_blur_h=lambda: ctx.shadow_blur(tmp, shadow, depth, w, h, 1, 0.1),
+                    shadow_blur_v=lambda: ctx.shadow_blur(shadow, tmp, depth, w, h, 0, 0.1),
+                    shade_final_shadow=lambda: ctx.shade_final(sd[1], g0, g1, depth, shadow, color, w, h),
+                    shade_final=lambda: ctx.shade_final(sd[0], g0, g1, depth, None, color, w, h))
+        n = w * h
+        algorithmic = dict(shadow_fill=(n // 2) * (5 * 4 + 4 + 1), shadow_blur_h=n * (4 + 1 + 1), shadow_blur_v=n * (4 + 1 + 1), shade_final_shadow=n * 17,
+                           shade_final=n * 16)
+        line = dict(size="%dx%d" % (w, h))
+        for name, fn in runs.items():
+            fn()
+            times = []
+            for _ in range(repeats):
+                flush.add_(1)
+                ev = []
+                _timed(ev, name, fn)
+                torch.cuda.synchronize()
+                times.append(ev[0][1].elapsed_time(ev[0][2]) * 1e3)
+            times.sort()
+            line[name] = dict(us_median=round(times[len(times) // 2], 2), us_min=round(times[0], 2), bytes=algorithmic[name],
+                              us_at_8TBs=round(algorithmic[name] / 8e12 * 1e6, 2))
+        print(json.dumps(line), flush=True)
+    ctx.status()
+    ctx.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="frame.ppm")
+    ap.add_argument("--viewport", default=None, help="WxH (default: the scene's own, 320x192)")
+    ap.add_argument("--no-shadow", action="store_true")
+    ap.add_argument("--checkerboard", action="store_true")
+    ap.add_argument("--passes", default=None)
+    ap.add_argument("--repeats", type=int, default=9)
+    args = ap.parse_args()
+    if args.passes:
+        passes([tuple(int(v) for v in s.split("x")) for s in args.passes.split(",")], args.repeats)
+        return
+    import numpy as np
+    import torch
+
+    from niagara_amd import layouts as L
+    from niagara_amd import pipeline as P
+    from niagara_amd import synth
+
+    def bounds(vertices, data, meshlets):
+        ctx = P.Context()
+        mlb = P.to_device(meshlets, ctx.device)
+        ctx.meshlet_bounds(P.to_device(vertices, ctx.device), P.to_device(data, ctx.device), mlb, len(meshlets))
+        ctx.status()
+        meshlets[:] = P.from_device(mlb, L.MESHLET)
+        ctx.close()
+    kw = dict(meshlet_bounds=bounds)
+    if args.viewport:
+        kw["viewport"] = tuple(int(v) for v in args.viewport.split("x"))
+    s = synth.occluder_scene(**kw)
+    w, h = s["viewport"]
+    # attributes for the vertices and a material per draw: unit normals from the positions, colours by draw
+    rng = np.random.default_rng(7)
+    v = s["vertices"].copy()
+    pos = np.stack([v["vx"], v["vy"], v["vz"]], -1).view(np.float16).astype(np.float64)
+    nrm = pos / np.maximum(np.linalg.norm(pos, axis=1, keepdims=True), 1e-6)
+    nrm[np.abs(pos[:, 2]) < 1e-3] = (0.0, 0.0, 1.0)  # the wall (a grid in z = 0) faces the camera
+    q = np.clip(np.rint((nrm + 1.0) * 511.0), 0, 1022).astype(np.uint32)
+    v["np"] = q[:, 0] | q[:, 1] << 10 | q[:, 2] << 20
+    v["tp"] = 127 | 127 << 8
+    draws = s["draws"].copy()
+    materials = np.zeros(6, L.MATERIAL)
+    materials["diffuseFactor"] = np.concatenate([rng.uniform(0.2, 0.95, (6, 3)), np.ones((6, 1))], 1).astype(np.float32)
+    materials["specularFactor"][:, 3] = rng.uniform(0.1, 0.9, 6).astype(np.float32)
+    draws["materialIndex"] = np.arange(len(draws)) % len(materials)
+    pipe = P.VisibilityPipeline(s["meshes"], s["meshlets"], draws, (w, h), fused=True, vertices=v, meshlet_data=s["data"], stable_ids=True)
+    x, y = np.meshgrid(np.arange(w), np.arange(h))
+    r = np.hypot(x - 0.45 * w, y - 0.5 * h) / (0.3 * h)
+    mask = np.clip(np.rint(255.0 * np.clip((r - 0.8) / 0.4, 0.0, 1.0)), 0, 255).astype(np.uint8)
+    sun = np.array([0.35, 0.6, 0.72]) / np.linalg.norm([0.35, 0.6, 0.72])
+    mat = P.to_device(materials, pipe.ctx.device)
+
+    def frame(events):
+        vis = pipe.new_visibility()
+        _timed(events, "frame", lambda: pipe.frame(s["cull"], post_pass=True, visibility=vis))
+        res = _timed(events, "resolve", lambda: pipe.resolve(s["cull"], vis))
+        att = _timed(events, "attributes", lambda: pipe.attributes(s["cull"], res["records"], mat, attributes=False))
+        shadow = None if args.no_shadow else torch.from_numpy(mask.copy()).to(pipe.ctx.device)
+        return _timed(events, "shade", lambda: pipe.shade(s["cull"], att["gbuffer0"], att["gbuffer1"], (0.0, 0.0, 0.0), sun, shadow=shadow,
+                                                          checkerboard=args.checkerboard))
+    frame([])  # warm-up (and the visibility bits of the closed loop)
+    events = []
+    color = frame(events)
+    torch.cuda.synchronize()
+    pipe.ctx.status()
+    words = color.cpu().numpy().view(np.uint32)
+    rgb = np.stack([(words >> np.uint32(8 * k)) & np.uint32(255) for k in range(3)], -1).astype(np.uint8)
+    with open(args.out, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (w, h))
+        f.write(rgb.tobytes())
+    print(json.dumps(dict(out=args.out, viewport=[w, h], shadow=not args.no_shadow, covered=int((pipe.depth > 0).sum().item()),
+                          mean_rgb=[round(float(c), 2) for c in rgb.reshape(-1, 3).mean(0)],
+                          us={name: round(a.elapsed_time(b) * 1e3, 1) for name, a, b in events})))
+    pipe.ctx.close()
+
+
+if __name__ == "__main__":
+    main()
