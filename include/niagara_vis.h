@@ -286,6 +286,11 @@ int nv_profile_variants(nv_context* ctx, uint32_t out_count[NV_VARIANT_SLOTS]);
  *       pieces of a triangle carry its id, as with 0.
  * The depth target, the totals and a launch without d_visibility do not depend on the option. */
 #define NV_OPT_RASTER_VISIBILITY_ID 11
+/* NV_OPT_BLOOM_FUSED_TAIL (default 0; 0 / 1, anything else NV_EINVAL): 1 = nv_bloom runs the small end of its chain — every level from the
+ * first one behind which the rest holds at most 5376 texels — as ONE launch of one workgroup out of LDS instead of one launch per pass
+ * (DESIGN.md §4.15).  The words written are the same at every level; the option changes launches only.  Off until an A/B on the device
+ * (tools/ab.sh -b) shows it faster than the per-level chain. */
+#define NV_OPT_BLOOM_FUSED_TAIL 12
 int nv_set_option(nv_context* ctx, int option, int value);
 
 /* ---- capacities ----
@@ -660,11 +665,52 @@ int nv_shadow_blur(nv_context* ctx, void* stream, uint8_t* d_out, const uint8_t*
 int nv_shade_final(nv_context* ctx, void* stream, const NvShadeData* shade, const uint32_t* d_gbuffer0, const uint32_t* d_gbuffer1,
                    const float* d_depth, const uint8_t* d_shadow /* optional */, uint32_t* d_color, uint32_t width, uint32_t height);
 
+/* ---- bloom (replaces bloom.comp.glsl and the bloom term of final.comp.glsl) ----
+ * The bloom target is ONE linear buffer of u32 holding VK_FORMAT_B10G11R11_UFLOAT_PACK32 texels (R in bits 0-10, G in bits 11-21, B in bits
+ * 22-31), the levels concatenated, row 0 at the top, row pitch = the level's width; level i is max(1, width >> i) x max(1, height >> i) texels
+ * at d_bloom + levelOffset[i] (src/niagara.cpp:1331-1333: width = (image width + 1) / 2, height likewise, levels = min(8, mip levels)).
+ * Rule set: the UFLOAT decode is exact; the store rounds toward zero, clamps a finite value to the largest finite code,
+ * keeps +inf, stores NaN as exponent 31 with the top mantissa bit and anything else with the sign bit as 0; texture() with filterSampler is
+ * bilinear with fp32 weights and clamp to edge, (t00 (1 - a) + t10 a) (1 - b) + (t01 (1 - a) + t11 a) b; everything else is §4.14's.
+ * Each single-pass entry point enqueues one launch, nv_bloom 2 * levels - 1 of them (no allocation, no synchronisation: capturable).
+ * NV_EINVAL: a NULL ctx, pointer or desc, an image width or height 0 or above 16384, a pointer that is not 4-byte aligned, a desc that is not
+ * what nv_bloom_desc_init gives for the image size (for the per-level passes: for its own width and height), a level out of range, a
+ * radius that is not finite or is negative.  A refused call launches nothing. */
+#define NV_BLOOM_MAX_LEVELS 8
+typedef struct NvBloomDesc
+{
+	uint32_t width;  /* level 0: (image width + 1) / 2 */
+	uint32_t height; /* level 0: (image height + 1) / 2 */
+	uint32_t levels; /* min(8, nv_image_mip_levels(width, height)) */
+	uint32_t levelOffset[NV_BLOOM_MAX_LEVELS]; /* in texels; entries from `levels` on hold totalTexels */
+	uint32_t totalTexels;
+} NvBloomDesc;
+
+/* bloom.comp.glsl:29-46, pass 0: the emissive term of the full-resolution gbuffer0 (width x height, as nv_visibility_attributes packs it),
+ * four bilinear samples a quarter texel around each half-resolution texel, into level 0 */
+int nv_bloom_extract(nv_context* ctx, void* stream, const uint32_t* d_gbuffer0, uint32_t width, uint32_t height, uint32_t* d_bloom,
+                     const NvBloomDesc* desc);
+/* bloom.comp.glsl:47-77, pass 1 (QUALITY 1): the 13-tap downsample of level - 1 into level, 1 <= level < desc->levels */
+int nv_bloom_downsample(nv_context* ctx, void* stream, uint32_t* d_bloom, const NvBloomDesc* desc, uint32_t level);
+/* bloom.comp.glsl:78-107, pass 2 (QUALITY 1): the 9-tap tent of level + 1, `radius` texels of `level` wide, added to level IN PLACE (an
+ * invocation reads and writes its own texel of `level` only), level <= desc->levels - 2 */
+int nv_bloom_upsample(nv_context* ctx, void* stream, uint32_t* d_bloom, const NvBloomDesc* desc, uint32_t level, float radius);
+/* src/niagara.cpp:1873-1901: extract, downsample 1 .. levels - 1, upsample levels - 2 .. 0 with radius 2.0 — by definition the result of
+ * the single-pass entry points called in that order (NV_OPT_BLOOM_FUSED_TAIL fuses launches, not results) */
+int nv_bloom(nv_context* ctx, void* stream, const uint32_t* d_gbuffer0, uint32_t width, uint32_t height, uint32_t* d_bloom, const NvBloomDesc* desc);
+/* final.comp.glsl:37-80 complete: nv_shade_final plus texture(bloomImage, uv).rgb * 0.1 from level 0 of d_bloom (read only),
+ * outputColor = ((albedo * lit + spec) + emissive) + bloom * 0.1 per channel.  NV_EINVAL as nv_shade_final, and for d_bloom / desc as above */
+int nv_shade_final_bloom(nv_context* ctx, void* stream, const NvShadeData* shade, const uint32_t* d_gbuffer0, const uint32_t* d_gbuffer1,
+                         const float* d_depth, const uint8_t* d_shadow /* optional */, uint32_t* d_color, uint32_t width, uint32_t height,
+                         const uint32_t* d_bloom, const NvBloomDesc* desc);
+
 /* ---- host helpers mirroring src/niagara.cpp / src/resources.cpp (no device work) ---- */
 uint32_t nv_previous_pow2(uint32_t v);                        /* src/niagara.cpp:439-447 */
 uint32_t nv_image_mip_levels(uint32_t width, uint32_t height); /* src/resources.cpp:280-292 */
 /* fills width/height/levels/mipOffset/totalTexels from the depth target size; d_base untouched */
 int nv_pyramid_desc_init(NvPyramidDesc* desc, uint32_t depthWidth, uint32_t depthHeight);
+/* src/niagara.cpp:1331-1333: the bloom target of a width x height image (every field; NV_EINVAL: NULL, a size 0 or above 16384) */
+int nv_bloom_desc_init(NvBloomDesc* desc, uint32_t width, uint32_t height);
 /* the multiplier with which the kernels divide by a launch constant d (grid sizes): mulhi(n, m) >> 7 == n / d for every
  * n < 2^39 / d; 0 (the kernels then divide) for d outside 256 .. 8192.  Exported so that the bound can be tested. */
 uint32_t nv_division_magic(uint32_t d);
@@ -760,6 +806,8 @@ static_assert(sizeof(NvMaterial) == 64 && offsetof(NvMaterial, diffuseFactor) ==
 static_assert(sizeof(NvPixelAttributes) == 64 && offsetof(NvPixelAttributes, drawId) == 28 && offsetof(NvPixelAttributes, materialIndex) == 60, "four 16-byte stores per pixel");
 static_assert(sizeof(NvShadeData) == 112 && offsetof(NvShadeData, sunDirection) == 16 && offsetof(NvShadeData, shadowsEnabled) == 28 &&
               offsetof(NvShadeData, inverseViewProjection) == 32 && offsetof(NvShadeData, imageSize) == 96, "ShadeData layout (src/niagara.cpp:280-290)");
+static_assert(sizeof(NvBloomDesc) == 48 && offsetof(NvBloomDesc, levels) == 8 && offsetof(NvBloomDesc, levelOffset) == 12 &&
+              offsetof(NvBloomDesc, totalTexels) == 44, "NvBloomDesc is mirrored by niagara_amd/_lib.py and niagara_amd/layouts.py");
 static_assert(sizeof(NvSceneCacheInfo) == 208, "NvSceneCacheInfo is mirrored by niagara_amd/_lib.py");
 #endif
 

@@ -27,6 +27,11 @@ class PyramidDesc(C.Structure):
                 ("mipOffset", C.c_uint32 * 16), ("totalTexels", C.c_uint32)]
 
 
+class BloomDesc(C.Structure):
+    """NvBloomDesc (include/niagara_vis.h): the bloom target's levels in one linear buffer of B10G11R11 words"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("levels", C.c_uint32), ("levelOffset", C.c_uint32 * 8), ("totalTexels", C.c_uint32)]
+
+
 class SceneCacheInfo(C.Structure):
     """NvSceneCacheInfo (include/niagara_vis.h)"""
     _fields_ = ([(n, C.c_uint32) for n in ("version", "compressed", "clrtMode", "ommStates")] + [("hashMeta", C.c_uint64)] +
@@ -85,6 +90,12 @@ _SIGS = {
     "nv_shadow_blur": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _i, _f]),
     "nv_shade_final": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32]),
     "nv_build_shade_data": (_i, [_vp, _vp, _vp, _vp, _i, _u32, _u32]),
+    "nv_bloom_desc_init": (_i, [C.POINTER(BloomDesc), _u32, _u32]),
+    "nv_bloom_extract": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, C.POINTER(BloomDesc)]),
+    "nv_bloom_downsample": (_i, [_vp, _vp, _vp, C.POINTER(BloomDesc), _u32]),
+    "nv_bloom_upsample": (_i, [_vp, _vp, _vp, C.POINTER(BloomDesc), _u32, _f]),
+    "nv_bloom": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, C.POINTER(BloomDesc)]),
+    "nv_shade_final_bloom": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, C.POINTER(BloomDesc)]),
     "nv_previous_pow2": (_u32, [_u32]),
     "nv_division_magic": (_u32, [_u32]),
     "nv_image_mip_levels": (_u32, [_u32, _u32]),

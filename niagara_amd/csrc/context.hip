@@ -54,7 +54,12 @@ int launch_visibility_attributes(hipStream_t, const NvGlobals& globals, const vo
 int launch_shadow_fill(hipStream_t, uint8_t* shadow, const float* depth, uint32_t width, uint32_t height, int checkerboard, uint32_t maxBlocks);
 int launch_shadow_blur(hipStream_t, uint8_t* out, const uint8_t* shadow, const float* depth, uint32_t width, uint32_t height, bool horizontal, float znear);
 int launch_shade_final(hipStream_t, const NvShadeData& sd, const uint32_t* gbuffer0, const uint32_t* gbuffer1, const float* depth, const uint8_t* shadow,
-                       uint32_t* color, uint32_t width, uint32_t height, uint32_t maxBlocks);
+                       uint32_t* color, uint32_t width, uint32_t height, uint32_t maxBlocks, const uint32_t* bloom, uint32_t bloomWidth, uint32_t bloomHeight);
+int launch_bloom_extract(hipStream_t, const uint32_t* gbuffer0, uint32_t width, uint32_t height, uint32_t* bloom, const NvBloomDesc& desc, uint32_t maxBlocks);
+int launch_bloom_downsample(hipStream_t, uint32_t* bloom, const NvBloomDesc& desc, uint32_t level);
+int launch_bloom_upsample(hipStream_t, uint32_t* bloom, const NvBloomDesc& desc, uint32_t level, float radius);
+uint32_t bloom_tail_first(const NvBloomDesc& desc);
+int launch_bloom_tail(hipStream_t, uint32_t* bloom, const NvBloomDesc& desc, uint32_t first, float radius);
 int launch_visibility_merge(hipStream_t, unsigned long long* dst, const unsigned long long* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks);
 int launch_rasterindexed(hipStream_t, RasterIndexedArgs a, void* scratch, uint32_t gridBlocks, bool nearClip);
 size_t rasterindexed_scratch_bytes(uint32_t drawCount);
@@ -148,6 +153,7 @@ struct nv_context
 	uint32_t rasterSmallLimit; // NV_OPT_RASTER_SMALL_LIMIT
 	uint32_t rasterNearClip;   // NV_OPT_RASTER_NEAR_CLIP: 1 = the clipping instantiations of both depth rasterisers
 	uint32_t rasterStableIds;  // NV_OPT_RASTER_VISIBILITY_ID: 1 = nv_rasterdepth writes the stable form of the visibility word
+	uint32_t bloomFusedTail;   // NV_OPT_BLOOM_FUSED_TAIL: 1 = nv_bloom runs the levels that fit one workgroup's LDS as one launch
 	uint32_t resolvePerPixel;  // experiments: nv_visibility_resolve without the per-run de-duplication
 	uint32_t attributesPerPixel; // experiments: nv_visibility_attributes without the per-run set-up
 };
@@ -453,6 +459,7 @@ int nv_create(nv_context** out_ctx, int device)
 	ctx->rasterSmallLimit = 16;
 	ctx->rasterNearClip = 0;
 	ctx->rasterStableIds = 0;
+	ctx->bloomFusedTail = 0;
 	ctx->directPercent = 35; // measured crossover (config 3A geometry at several densities): ~36 % of the commands passing the filter
 	ctx->forceDirect = -1;
 	ctx->bitsBlocksPerCU = 4;
@@ -617,6 +624,11 @@ int nv_set_option(nv_context* ctx, int option, int value)
 		if (value != 0 && value != 1)
 			return NV_EINVAL;
 		ctx->rasterStableIds = (uint32_t)value;
+		return NV_OK;
+	case NV_OPT_BLOOM_FUSED_TAIL:
+		if (value != 0 && value != 1)
+			return NV_EINVAL;
+		ctx->bloomFusedTail = (uint32_t)value;
 		return NV_OK;
 	case NV_OPT_CULL_WORKGROUPS_PER_CU:
 		if (value < 1 || value > 8)
@@ -1262,7 +1274,86 @@ int nv_shade_final(nv_context* ctx, void* stream, const NvShadeData* shade, cons
 	    misaligned(d_depth) || misaligned(d_color))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
-	return nv::launch_shade_final((hipStream_t)stream, *shade, d_gbuffer0, d_gbuffer1, d_depth, d_shadow, d_color, width, height, persistent_grid(ctx, 8));
+	return nv::launch_shade_final((hipStream_t)stream, *shade, d_gbuffer0, d_gbuffer1, d_depth, d_shadow, d_color, width, height, persistent_grid(ctx, 8), nullptr, 0, 0);
+}
+
+// ---- bloom (bloom.hip)
+static bool misaligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
+
+// desc is what nv_bloom_desc_init gives for a width x height image
+static bool bloom_desc_ok(const NvBloomDesc* desc, uint32_t width, uint32_t height)
+{
+	NvBloomDesc want;
+	return desc && nv_bloom_desc_init(&want, width, height) == NV_OK && memcmp(&want, desc, sizeof(want)) == 0;
+}
+
+// the per-level passes take no image size: desc is what nv_bloom_desc_init gives for its own level 0 (an image of twice that size)
+static bool bloom_desc_ok(const NvBloomDesc* desc)
+{
+	return desc && desc->width != 0 && desc->height != 0 && desc->width <= 8192 && desc->height <= 8192 && bloom_desc_ok(desc, desc->width * 2u, desc->height * 2u);
+}
+
+int nv_bloom_extract(nv_context* ctx, void* stream, const uint32_t* d_gbuffer0, uint32_t width, uint32_t height, uint32_t* d_bloom, const NvBloomDesc* desc)
+{
+	if (!ctx || !d_gbuffer0 || !d_bloom || !shade_size_ok(width, height) || !bloom_desc_ok(desc, width, height) || misaligned4(d_gbuffer0) || misaligned4(d_bloom))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_bloom_extract((hipStream_t)stream, d_gbuffer0, width, height, d_bloom, *desc, persistent_grid(ctx, 8));
+}
+
+int nv_bloom_downsample(nv_context* ctx, void* stream, uint32_t* d_bloom, const NvBloomDesc* desc, uint32_t level)
+{
+	if (!ctx || !d_bloom || !bloom_desc_ok(desc) || level < 1u || level >= desc->levels || misaligned4(d_bloom))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_bloom_downsample((hipStream_t)stream, d_bloom, *desc, level);
+}
+
+int nv_bloom_upsample(nv_context* ctx, void* stream, uint32_t* d_bloom, const NvBloomDesc* desc, uint32_t level, float radius)
+{
+	// (level + 2 > levels would wrap for a level near 2^32 and let it through)
+	if (!ctx || !d_bloom || !bloom_desc_ok(desc) || desc->levels < 2u || level > desc->levels - 2u || !(radius >= 0.0f) || !(radius <= 3.402823466e38f) || misaligned4(d_bloom))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_bloom_upsample((hipStream_t)stream, d_bloom, *desc, level, radius);
+}
+
+int nv_bloom(nv_context* ctx, void* stream, const uint32_t* d_gbuffer0, uint32_t width, uint32_t height, uint32_t* d_bloom, const NvBloomDesc* desc)
+{
+	if (!ctx || !d_gbuffer0 || !d_bloom || !shade_size_ok(width, height) || !bloom_desc_ok(desc, width, height) || misaligned4(d_gbuffer0) || misaligned4(d_bloom))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	// src/niagara.cpp:1873-1901
+	int rc = nv::launch_bloom_extract((hipStream_t)stream, d_gbuffer0, width, height, d_bloom, *desc, persistent_grid(ctx, 8));
+	// the fused tail takes the levels from `tail` on (pass 1 into tail + 1 .. levels - 1, pass 2 into levels - 2 .. tail) when that saves a launch
+	uint32_t tail = desc->levels;
+	if (ctx->bloomFusedTail)
+	{
+		tail = nv::bloom_tail_first(*desc);
+		if (tail + 2u > desc->levels)
+			tail = desc->levels;
+	}
+	const uint32_t lastDown = tail < desc->levels ? tail : desc->levels - 1u; // the per-level downsamples end here
+	for (uint32_t i = 1; rc == 0 && i <= lastDown; ++i)
+		rc = nv::launch_bloom_downsample((hipStream_t)stream, d_bloom, *desc, i);
+	if (rc == 0 && tail < desc->levels)
+		rc = nv::launch_bloom_tail((hipStream_t)stream, d_bloom, *desc, tail, 2.0f);
+	for (int i = (tail < desc->levels ? (int)tail - 1 : (int)desc->levels - 2); rc == 0 && i >= 0; --i)
+		rc = nv::launch_bloom_upsample((hipStream_t)stream, d_bloom, *desc, (uint32_t)i, 2.0f);
+	return rc;
+}
+
+int nv_shade_final_bloom(nv_context* ctx, void* stream, const NvShadeData* shade, const uint32_t* d_gbuffer0, const uint32_t* d_gbuffer1, const float* d_depth,
+                         const uint8_t* d_shadow, uint32_t* d_color, uint32_t width, uint32_t height, const uint32_t* d_bloom, const NvBloomDesc* desc)
+{
+	if (!ctx || !shade || !d_gbuffer0 || !d_gbuffer1 || !d_depth || !d_color || !d_bloom || !shade_size_ok(width, height) ||
+	    shade->imageSize[0] != (float)width || shade->imageSize[1] != (float)height || (shade->shadowsEnabled == 1 && !d_shadow) ||
+	    !bloom_desc_ok(desc, width, height) || misaligned4(d_gbuffer0) || misaligned4(d_gbuffer1) || misaligned4(d_depth) || misaligned4(d_color) ||
+	    misaligned4(d_bloom))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_shade_final((hipStream_t)stream, *shade, d_gbuffer0, d_gbuffer1, d_depth, d_shadow, d_color, width, height, persistent_grid(ctx, 8),
+	                              d_bloom + desc->levelOffset[0], desc->width, desc->height);
 }
 
 int nv_visibility_merge(nv_context* ctx, void* stream, uint64_t* d_dst, const uint64_t* const* d_srcs, uint32_t sources, uint32_t width, uint32_t height)

@@ -62,6 +62,29 @@ int nv_pyramid_desc_init(NvPyramidDesc* desc, uint32_t depthWidth, uint32_t dept
 	return NV_OK;
 }
 
+// src/niagara.cpp:1331-1333 (+ linear level offsets replacing the per-mip image views)
+int nv_bloom_desc_init(NvBloomDesc* desc, uint32_t width, uint32_t height)
+{
+	if (!desc || !width || !height || width > 16384 || height > 16384)
+		return NV_EINVAL;
+	desc->width = (width + 1) / 2;
+	desc->height = (height + 1) / 2;
+	const uint32_t levels = nv_image_mip_levels(desc->width, desc->height);
+	desc->levels = levels < NV_BLOOM_MAX_LEVELS ? levels : NV_BLOOM_MAX_LEVELS;
+	uint32_t offset = 0;
+	for (uint32_t i = 0; i < NV_BLOOM_MAX_LEVELS; ++i)
+	{
+		desc->levelOffset[i] = offset;
+		if (i < desc->levels)
+		{
+			uint32_t w = desc->width >> i, h = desc->height >> i;
+			offset += (w ? w : 1) * (h ? h : 1);
+		}
+	}
+	desc->totalTexels = offset;
+	return NV_OK;
+}
+
 // src/niagara.cpp:424-437 (perspectiveProjection, normalizePlane) and :1487-1516 (CullData).
 // view = scale(1,1,-1) * inverse(translate(pos) * mat4_cast(q)); the inverse of a rigid transform is taken in
 // closed form, [R^T | -(R^T t)] (glm is not vendored in the reference snapshot, so its cofactor inverse cannot be

@@ -1,5 +1,6 @@
 // shade.hip — the shading end of the frame for gfx950: nv_shadow_fill (shadowfill.comp.glsl), nv_shadow_blur
-// (shadowblur.comp.glsl, BLUR 1) and nv_shade_final (final.comp.glsl, the bloom term left out).
+// (shadowblur.comp.glsl, BLUR 1), nv_shade_final (final.comp.glsl, the bloom term left out) and nv_shade_final_bloom (final.comp.glsl complete:
+// the bloom term is §4.15's texture() of level 0 of the bloom target).
 //
 // Images are linear buffers, row 0 at the top: depth fp32 (reverse-Z, 0 = no sample), gbuffer0 R8G8B8A8 / gbuffer1 A2B10G10R10 as
 // nv_visibility_attributes packs them, shadow images u8 (R8_UNORM, row pitch = width), the colour R8G8B8A8 with R in the low byte.
@@ -12,6 +13,7 @@
 //
 // None of the kernels waits on another workgroup, nothing is allocated: the entry points only enqueue and can be captured.
 #include "cullmath.h"
+#include "bloommath.h"
 
 namespace nv
 {
@@ -147,6 +149,24 @@ struct ShadeFinalArgs
 	uint32_t width, n;
 };
 
+// the kernel argument of the BLOOM = true instantiations; the others keep ShadeFinalArgs, and with it their code
+struct ShadeFinalBloomArgs : ShadeFinalArgs
+{
+	const uint32_t* __restrict__ bloom; // level 0 of the bloom target
+	uint32_t bloomWidth, bloomHeight;
+};
+
+template <bool BLOOM>
+struct ShadeFinalArgsOf
+{
+	typedef ShadeFinalArgs type;
+};
+template <>
+struct ShadeFinalArgsOf<true>
+{
+	typedef ShadeFinalBloomArgs type;
+};
+
 NV_DEV f3 sh_normalize(f3 v)
 {
 	const float l = __builtin_sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z);
@@ -161,9 +181,10 @@ NV_DEV float sh_tonemap(float c)
 }
 
 // final.comp.glsl:37-80.  One lane per pixel of a persistent grid, straight-line: the loads of a pixel are issued together, the shadow load
-// exists only in the SHADOW instantiation (shadeData.shadowsEnabled == 1 is uniform per launch), one 4-byte store per pixel.
-template <bool SHADOW>
-__global__ __launch_bounds__(SH_THREADS) void shade_final_kernel(ShadeFinalArgs a)
+// exists only in the SHADOW instantiation (shadeData.shadowsEnabled == 1 is uniform per launch), one 4-byte store per pixel.  BLOOM adds
+// :76's texture(bloomImage, uv): four packed texels of the half-resolution level 0 (cached: neighbouring pixels share them), blended by §4.15.
+template <bool SHADOW, bool BLOOM>
+__global__ __launch_bounds__(SH_THREADS) void shade_final_kernel(typename ShadeFinalArgsOf<BLOOM>::type a)
 {
 	const uint32_t stride = gridDim.x * SH_THREADS;
 	const float* m = a.sd.inverseViewProjection;
@@ -209,13 +230,26 @@ __global__ __launch_bounds__(SH_THREADS) void shade_final_kernel(ShadeFinalArgs 
 		const float specular = __builtin_powf(ndoth, 1.0f * (1.0f - gloss) + 64.0f * gloss) * gloss;
 		// :64-66
 		const float shadow = SHADOW ? (float)sc / 255.0f : 1.0f;
-		// :73-76 (bloom: an all-zero image)
+		// :73-76 (without BLOOM: an all-zero image)
 		const float lit = (ndotl * gl_min(shadow + 0.05f, 1.0f)) * 2.5f + 0.07f;
 		const float spec = (specular * shadow) * 2.5f;
-		const float bloom = 0.0f * 0.1f;
-		const float ox = ((albedo.x * lit + spec) + emissive.x) + bloom;
-		const float oy = ((albedo.y * lit + spec) + emissive.y) + bloom;
-		const float oz = ((albedo.z * lit + spec) + emissive.z) + bloom;
+		float bloomx, bloomy, bloomz;
+		if constexpr (BLOOM)
+		{
+			const BlAxis ax = bl_axis(uvx, (float)a.bloomWidth), ay = bl_axis(uvy, (float)a.bloomHeight);
+			const uint32_t row0 = (uint32_t)ay.i0 * a.bloomWidth, row1 = (uint32_t)ay.i1 * a.bloomWidth;
+			const uint32_t b00 = a.bloom[row0 + (uint32_t)ax.i0], b10 = a.bloom[row0 + (uint32_t)ax.i1];
+			const uint32_t b01 = a.bloom[row1 + (uint32_t)ax.i0], b11 = a.bloom[row1 + (uint32_t)ax.i1];
+			bloomx = bl_lerp2(bl_decode<6>(b00 & 2047u), bl_decode<6>(b10 & 2047u), bl_decode<6>(b01 & 2047u), bl_decode<6>(b11 & 2047u), ax.alpha, ay.alpha) * 0.1f;
+			bloomy = bl_lerp2(bl_decode<6>(b00 >> 11 & 2047u), bl_decode<6>(b10 >> 11 & 2047u), bl_decode<6>(b01 >> 11 & 2047u), bl_decode<6>(b11 >> 11 & 2047u),
+			                  ax.alpha, ay.alpha) * 0.1f;
+			bloomz = bl_lerp2(bl_decode<5>(b00 >> 22), bl_decode<5>(b10 >> 22), bl_decode<5>(b01 >> 22), bl_decode<5>(b11 >> 22), ax.alpha, ay.alpha) * 0.1f;
+		}
+		else
+			bloomx = bloomy = bloomz = 0.0f * 0.1f;
+		const float ox = ((albedo.x * lit + spec) + emissive.x) + bloomx;
+		const float oy = ((albedo.y * lit + spec) + emissive.y) + bloomy;
+		const float oz = ((albedo.z * lit + spec) + emissive.z) + bloomz;
 		// :78 gradientNoise(vec2(pos)): no half-pixel offset (math.h:99-102)
 		const float inner = (float)px * 0.06711056f + (float)py * 0.00583715f;
 		const float f0 = inner - __builtin_floorf(inner);
@@ -253,9 +287,10 @@ int launch_shadow_blur(hipStream_t stream, uint8_t* out, const uint8_t* shadow, 
 }
 
 int launch_shade_final(hipStream_t stream, const NvShadeData& sd, const uint32_t* gbuffer0, const uint32_t* gbuffer1, const float* depth,
-                       const uint8_t* shadow, uint32_t* color, uint32_t width, uint32_t height, uint32_t maxBlocks)
+                       const uint8_t* shadow, uint32_t* color, uint32_t width, uint32_t height, uint32_t maxBlocks, const uint32_t* bloom, uint32_t bloomWidth,
+                       uint32_t bloomHeight)
 {
-	ShadeFinalArgs a;
+	ShadeFinalBloomArgs a;
 	a.sd = sd;
 	a.gbuffer0 = gbuffer0;
 	a.gbuffer1 = gbuffer1;
@@ -264,12 +299,22 @@ int launch_shade_final(hipStream_t stream, const NvShadeData& sd, const uint32_t
 	a.color = color;
 	a.width = width;
 	a.n = width * height;
+	a.bloom = bloom;
+	a.bloomWidth = bloomWidth;
+	a.bloomHeight = bloomHeight;
 	uint32_t grid = (a.n + SH_THREADS - 1u) / SH_THREADS;
 	grid = grid < maxBlocks ? grid : maxBlocks;
-	if (sd.shadowsEnabled == 1)
-		hipLaunchKernelGGL(shade_final_kernel<true>, dim3(grid), dim3(SH_THREADS), 0, stream, a);
+	if (bloom)
+	{
+		if (sd.shadowsEnabled == 1)
+			hipLaunchKernelGGL((shade_final_kernel<true, true>), dim3(grid), dim3(SH_THREADS), 0, stream, a);
+		else
+			hipLaunchKernelGGL((shade_final_kernel<false, true>), dim3(grid), dim3(SH_THREADS), 0, stream, a);
+	}
+	else if (sd.shadowsEnabled == 1)
+		hipLaunchKernelGGL((shade_final_kernel<true, false>), dim3(grid), dim3(SH_THREADS), 0, stream, static_cast<const ShadeFinalArgs&>(a));
 	else
-		hipLaunchKernelGGL(shade_final_kernel<false>, dim3(grid), dim3(SH_THREADS), 0, stream, a);
+		hipLaunchKernelGGL((shade_final_kernel<false, false>), dim3(grid), dim3(SH_THREADS), 0, stream, static_cast<const ShadeFinalArgs&>(a));
 	return (int)hipGetLastError();
 }
 

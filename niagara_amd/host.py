@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from . import layouts as L
-from ._lib import PyramidDesc, check, lib
+from ._lib import BloomDesc, PyramidDesc, check, lib
 
 
 def _p(a):
@@ -27,6 +27,13 @@ def image_mip_levels(w, h):
 def pyramid_desc(depth_w, depth_h):
     d = PyramidDesc()
     check(lib.nv_pyramid_desc_init(C.byref(d), depth_w, depth_h), "nv_pyramid_desc_init")
+    return d
+
+
+def bloom_desc(width, height):
+    """NvBloomDesc of a width x height image (src/niagara.cpp:1331-1333): half-resolution level 0, at most 8 levels, one linear buffer"""
+    d = BloomDesc()
+    check(lib.nv_bloom_desc_init(C.byref(d), int(width), int(height)), "nv_bloom_desc_init")
     return d
 
 

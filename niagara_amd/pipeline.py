@@ -47,6 +47,7 @@ NV_OPT_DRAW_RECORDS = 8
 NV_OPT_RASTER_SMALL_LIMIT = 9
 NV_OPT_RASTER_NEAR_CLIP = 10
 NV_OPT_RASTER_VISIBILITY_ID = 11
+NV_OPT_BLOOM_FUSED_TAIL = 12
 
 
 class Context:
@@ -236,6 +237,30 @@ class Context:
         check(lib.nv_shade_final(self.h, _stream(), C.c_void_p(shade_data.ctypes.data), _ptr(gbuffer0), _ptr(gbuffer1), _ptr(depth), _ptr(shadow),
                                  _ptr(color), int(width), int(height)), "nv_shade_final")
 
+    def bloom_extract(self, gbuffer0, width, height, bloom, desc):
+        """bloom.comp.glsl pass 0 (nv_bloom_extract): the emissive term of the full-resolution gbuffer0 into level 0 of the bloom target
+        (desc.totalTexels B10G11R11 words; desc = host.bloom_desc(width, height))"""
+        check(lib.nv_bloom_extract(self.h, _stream(), _ptr(gbuffer0), int(width), int(height), _ptr(bloom), None if desc is None else C.byref(desc)),
+              "nv_bloom_extract")
+
+    def bloom_downsample(self, bloom, desc, level):
+        """bloom.comp.glsl pass 1 (nv_bloom_downsample): the 13-tap downsample of level - 1 into level"""
+        check(lib.nv_bloom_downsample(self.h, _stream(), _ptr(bloom), None if desc is None else C.byref(desc), int(level)), "nv_bloom_downsample")
+
+    def bloom_upsample(self, bloom, desc, level, radius=2.0):
+        """bloom.comp.glsl pass 2 (nv_bloom_upsample): the 9-tap tent of level + 1 added to level in place"""
+        check(lib.nv_bloom_upsample(self.h, _stream(), _ptr(bloom), None if desc is None else C.byref(desc), int(level), float(radius)),
+              "nv_bloom_upsample")
+
+    def bloom(self, gbuffer0, width, height, bloom, desc):
+        """the whole chain of src/niagara.cpp:1873-1901 (nv_bloom): extract, downsample 1 .. levels - 1, upsample levels - 2 .. 0 with radius 2"""
+        check(lib.nv_bloom(self.h, _stream(), _ptr(gbuffer0), int(width), int(height), _ptr(bloom), None if desc is None else C.byref(desc)), "nv_bloom")
+
+    def shade_final_bloom(self, shade_data, gbuffer0, gbuffer1, depth, shadow, color, width, height, bloom, desc):
+        """final.comp.glsl complete (nv_shade_final_bloom): shade_final plus texture(bloomImage, uv) * 0.1 from level 0 of the bloom target"""
+        check(lib.nv_shade_final_bloom(self.h, _stream(), C.c_void_p(shade_data.ctypes.data), _ptr(gbuffer0), _ptr(gbuffer1), _ptr(depth), _ptr(shadow),
+                                       _ptr(color), int(width), int(height), _ptr(bloom), None if desc is None else C.byref(desc)), "nv_shade_final_bloom")
+
     def depthreduce(self, depth, width, height, pyramid):
         check(lib.nv_depthreduce(self.h, _stream(), _ptr(depth), width, height, C.byref(pyramid)), "nv_depthreduce")
 
@@ -338,6 +363,7 @@ class VisibilityPipeline:
         # geometry (meshlet payloads and / or the index buffer ib, + vertices, src/scene.cpp:24-47): with it the pipeline rasterises its own
         # depth target, through the clusters (meshlet_data) or through the indexed draws of the classic path (indices)
         self.mdb = self.vb = self.ib = self.depth = None
+        self.bloom_image = self.bloom_desc = None  # shade(bloom=True)'s target, allocated on first use
         self.index_count = self.vertex_count = 0
         if vertices is not None and (meshlet_data is not None or indices is not None):
             self.vertex_count = len(vertices)
@@ -454,12 +480,13 @@ class VisibilityPipeline:
                                        out["attributes"], out["gbuffer0"], out["gbuffer1"], out["totals"])
         return out
 
-    def shade(self, cull_data, gbuffer0, gbuffer1, camera_position, sun_direction, shadow=None, blur=True, checkerboard=False):
+    def shade(self, cull_data, gbuffer0, gbuffer1, camera_position, sun_direction, shadow=None, blur=True, checkerboard=False, bloom=False):
         """the shading end of the frame over attributes()'s G-buffer words and the pipeline's own depth target (src/niagara.cpp:1822-1850,
         1906-1925): returns the colour tensor (int32, height x width, R8G8B8A8 with R in the low byte).  shadow: a caller-supplied mask (uint8
         tensor, height x width; the library traces no rays) — it is filled in place when `checkerboard`, blurred horizontally into an image
         the pipeline owns and vertically back into the mask when `blur`, and final shades with shadows on; without a mask final runs
-        with shadows off"""
+        with shadows off.  bloom: run the bloom chain over gbuffer0 into a target the pipeline owns (self.bloom_image, self.bloom_desc) and
+        add its term in final (src/niagara.cpp:1866-1904); the default leaves it out, as before"""
         if self.depth is None:
             raise NvError("shade reads the pipeline's depth target: VisibilityPipeline(..., meshlet_data=, vertices=)")
         w, h = self.depth_w, self.depth_h
@@ -478,7 +505,14 @@ class VisibilityPipeline:
         g = synth.make_globals(cull_data, (w, h))
         sd = host.build_shade_data(g, camera_position, sun_direction, 1 if shadow is not None else 0, w, h)
         color = torch.zeros((h, w), dtype=torch.int32, device=dev)
-        self.ctx.shade_final(sd, gbuffer0, gbuffer1, self.depth, shadow, color, w, h)
+        if bloom:
+            if self.bloom_image is None:
+                self.bloom_desc = host.bloom_desc(w, h)
+                self.bloom_image = torch.zeros(self.bloom_desc.totalTexels, dtype=torch.int32, device=dev)
+            self.ctx.bloom(gbuffer0, w, h, self.bloom_image, self.bloom_desc)
+            self.ctx.shade_final_bloom(sd, gbuffer0, gbuffer1, self.depth, shadow, color, w, h, self.bloom_image, self.bloom_desc)
+        else:
+            self.ctx.shade_final(sd, gbuffer0, gbuffer1, self.depth, shadow, color, w, h)
         return color
 
     def frame(self, cull_data, post_pass=False, on_phase=None, task=True, visibility=None):

@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """A displayable image out of a scene on one GPU: synth.occluder_scene through frame(visibility=) -> resolve -> attributes -> shade
-(DESIGN.md §4.12-4.14).  A demonstration, not a test.
+(DESIGN.md §4.12-4.15).  A demonstration, not a test.
 
     python3 tools/render_frame.py --out frame.ppm                       # the scene at its own viewport, a synthetic shadow mask
     python3 tools/render_frame.py --no-shadow --viewport 1920x1080
+    python3 tools/render_frame.py --bloom                               # two materials emit; the bloom chain and final's bloom term
 
 Writes a binary PPM (P6, R G B from the R8G8B8A8 colour words) and prints one JSON line with the passes' times by HIP events (one run
 each after a warm-up frame: launch gaps included, an upper bound of the kernel time; profiles/r13_shade.md has the kernel trace).
 --passes WxH[,WxH...] instead times the three shade passes alone on synthetic images of those sizes, cache-cold (a 512 MiB buffer is
-rewritten between the passes): the run to put under a kernel trace."""
+rewritten between the passes): the run to put under a kernel trace.  With --bloom it times the bloom passes instead: pass 0, every level
+of passes 1 and 2, the whole chain per level and with the fused tail (NV_OPT_BLOOM_FUSED_TAIL) alternately — the A/B — and final with the
+bloom term (profiles/r14_bloom.md)."""
 import argparse
 import json
 import os
@@ -29,8 +32,8 @@ def _timed(events, name, fn):
     return out
 
 
-def passes(sizes, repeats):
-    """the three shade passes on synthetic images, each launch behind a flush of the caches"""
+def passes(sizes, repeats, bloom=False):
+    """the three shade passes (or, with `bloom`, the bloom passes) on synthetic images, each launch behind a flush of the caches"""
     import numpy as np
     import torch
 
@@ -49,25 +52,63 @@ def passes(sizes, repeats):
         tmp, color = torch.zeros_like(shadow), torch.zeros((h, w), dtype=torch.int32, device=dev)
         cd = host.build_cull_data(viewport=(w, h), pyramid=(host.previous_pow2(w), host.previous_pow2(h)))
         sd = {k: host.build_shade_data(synth.make_globals(cd, (w, h)), (0, 0, 0), (0.35, 0.6, 0.72), k, w, h) for k in (0, 1)}
-        runs = dict(shadow_fill=lambda: ctx.shadow_fill(shadow, depth, w, h, 1), shadow_blur_h=lambda: ctx.shadow_blur(tmp, shadow, depth, w, h, 1, 0.1),
-                    shadow_blur_v=lambda: ctx.shadow_blur(shadow, tmp, depth, w, h, 0, 0.1),
-                    shade_final_shadow=lambda: ctx.shade_final(sd[1], g0, g1, depth, shadow, color, w, h),
-                    shade_final=lambda: ctx.shade_final(sd[0], g0, g1, depth, None, color, w, h))
         n = w * h
-        algorithmic = dict(shadow_fill=(n // 2) * (5 * 4 + 4 + 1), shadow_blur_h=n * (4 + 1 + 1), shadow_blur_v=n * (4 + 1 + 1), shade_final_shadow=n * 17,
-                           shade_final=n * 16)
+        if bloom:
+            # an emissive block in a G-buffer without emission; the passes' cost does not depend on the values
+            g0 &= 0x00FFFFFF
+            g0[h // 4:h // 2, w // 4:w // 2] |= 0x60000000
+            d = host.bloom_desc(w, h)
+            target = torch.zeros(d.totalTexels, dtype=torch.int32, device=dev)
+            size = lambda i: max(1, d.width >> i) * max(1, d.height >> i)
+            runs = dict(bloom_extract=lambda: ctx.bloom_extract(g0, w, h, target, d))
+            algorithmic = dict(bloom_extract=n * 4 + size(0) * 4)
+            for i in range(1, d.levels):
+                runs["bloom_downsample_%d" % i] = lambda i=i: ctx.bloom_downsample(target, d, i)
+                algorithmic["bloom_downsample_%d" % i] = (size(i - 1) + size(i)) * 4
+            for i in range(d.levels - 2, -1, -1):
+                runs["bloom_upsample_%d" % i] = lambda i=i: ctx.bloom_upsample(target, d, i, 2.0)
+                algorithmic["bloom_upsample_%d" % i] = (size(i + 1) + 2 * size(i)) * 4
+            chain_bytes = sum(algorithmic.values())
+
+            def fused_chain():
+                ctx.set_option(P.NV_OPT_BLOOM_FUSED_TAIL, 1)
+                try:
+                    ctx.bloom(g0, w, h, target, d)
+                finally:
+                    ctx.set_option(P.NV_OPT_BLOOM_FUSED_TAIL, 0)
+            # the A/B of the fused tail: the two forms of the whole chain, measured alternately (ab below)
+            runs["bloom_chain"] = lambda: ctx.bloom(g0, w, h, target, d)
+            runs["bloom_chain_fused_tail"] = fused_chain
+            algorithmic["bloom_chain"] = algorithmic["bloom_chain_fused_tail"] = chain_bytes
+            runs["shade_final_bloom"] = lambda: ctx.shade_final_bloom(sd[1], g0, g1, depth, shadow, color, w, h, target, d)
+            algorithmic["shade_final_bloom"] = n * 17 + size(0) * 4
+            ab = ("bloom_chain", "bloom_chain_fused_tail")
+        else:
+            runs = dict(shadow_fill=lambda: ctx.shadow_fill(shadow, depth, w, h, 1), shadow_blur_h=lambda: ctx.shadow_blur(tmp, shadow, depth, w, h, 1, 0.1),
+                        shadow_blur_v=lambda: ctx.shadow_blur(shadow, tmp, depth, w, h, 0, 0.1),
+                        shade_final_shadow=lambda: ctx.shade_final(sd[1], g0, g1, depth, shadow, color, w, h),
+                        shade_final=lambda: ctx.shade_final(sd[0], g0, g1, depth, None, color, w, h))
+            algorithmic = dict(shadow_fill=(n // 2) * (5 * 4 + 4 + 1), shadow_blur_h=n * (4 + 1 + 1), shadow_blur_v=n * (4 + 1 + 1), shade_final_shadow=n * 17,
+                               shade_final=n * 16)
+            ab = ()
         line = dict(size="%dx%d" % (w, h))
+        def measure(name):
+            flush.add_(1)
+            ev = []
+            _timed(ev, name, runs[name])
+            torch.cuda.synchronize()
+            return ev[0][1].elapsed_time(ev[0][2]) * 1e3
+        times = {name: [] for name in runs}
         for name, fn in runs.items():
-            fn()
-            times = []
-            for _ in range(repeats):
-                flush.add_(1)
-                ev = []
-                _timed(ev, name, fn)
-                torch.cuda.synchronize()
-                times.append(ev[0][1].elapsed_time(ev[0][2]) * 1e3)
-            times.sort()
-            line[name] = dict(us_median=round(times[len(times) // 2], 2), us_min=round(times[0], 2), bytes=algorithmic[name],
+            fn()  # warm-up
+            if name not in ab:
+                times[name] = [measure(name) for _ in range(repeats)]
+        for _ in range(repeats):  # the A/B pair: alternating, so that a drift of the box hits both alike
+            for name in ab:
+                times[name].append(measure(name))
+        for name in runs:
+            t = sorted(times[name])
+            line[name] = dict(us_median=round(t[len(t) // 2], 2), us_min=round(t[0], 2), us_max=round(t[-1], 2), bytes=algorithmic[name],
                               us_at_8TBs=round(algorithmic[name] / 8e12 * 1e6, 2))
         print(json.dumps(line), flush=True)
     ctx.status()
@@ -80,11 +121,12 @@ def main():
     ap.add_argument("--viewport", default=None, help="WxH (default: the scene's own, 320x192)")
     ap.add_argument("--no-shadow", action="store_true")
     ap.add_argument("--checkerboard", action="store_true")
+    ap.add_argument("--bloom", action="store_true", help="two materials emit; run the bloom chain and final's bloom term")
     ap.add_argument("--passes", default=None)
     ap.add_argument("--repeats", type=int, default=9)
     args = ap.parse_args()
     if args.passes:
-        passes([tuple(int(v) for v in s.split("x")) for s in args.passes.split(",")], args.repeats)
+        passes([tuple(int(v) for v in s.split("x")) for s in args.passes.split(",")], args.repeats, args.bloom)
         return
     import numpy as np
     import torch
@@ -118,6 +160,8 @@ def main():
     materials = np.zeros(6, L.MATERIAL)
     materials["diffuseFactor"] = np.concatenate([rng.uniform(0.2, 0.95, (6, 3)), np.ones((6, 1))], 1).astype(np.float32)
     materials["specularFactor"][:, 3] = rng.uniform(0.1, 0.9, 6).astype(np.float32)
+    if args.bloom:
+        materials["emissiveFactor"][[1, 4]] = ((6.0, 2.5, 0.5), (0.5, 3.0, 8.0))
     draws["materialIndex"] = np.arange(len(draws)) % len(materials)
     pipe = P.VisibilityPipeline(s["meshes"], s["meshlets"], draws, (w, h), fused=True, vertices=v, meshlet_data=s["data"], stable_ids=True)
     x, y = np.meshgrid(np.arange(w), np.arange(h))
@@ -133,7 +177,7 @@ def main():
         att = _timed(events, "attributes", lambda: pipe.attributes(s["cull"], res["records"], mat, attributes=False))
         shadow = None if args.no_shadow else torch.from_numpy(mask.copy()).to(pipe.ctx.device)
         return _timed(events, "shade", lambda: pipe.shade(s["cull"], att["gbuffer0"], att["gbuffer1"], (0.0, 0.0, 0.0), sun, shadow=shadow,
-                                                          checkerboard=args.checkerboard))
+                                                          checkerboard=args.checkerboard, bloom=args.bloom))
     frame([])  # warm-up (and the visibility bits of the closed loop)
     events = []
     color = frame(events)
@@ -144,7 +188,7 @@ def main():
     with open(args.out, "wb") as f:
         f.write(b"P6\n%d %d\n255\n" % (w, h))
         f.write(rgb.tobytes())
-    print(json.dumps(dict(out=args.out, viewport=[w, h], shadow=not args.no_shadow, covered=int((pipe.depth > 0).sum().item()),
+    print(json.dumps(dict(out=args.out, viewport=[w, h], shadow=not args.no_shadow, bloom=args.bloom, covered=int((pipe.depth > 0).sum().item()),
                           mean_rgb=[round(float(c), 2) for c in rgb.reshape(-1, 3).mean(0)],
                           us={name: round(a.elapsed_time(b) * 1e3, 1) for name, a, b in events})))
     pipe.ctx.close()
