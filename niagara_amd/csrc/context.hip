@@ -373,7 +373,7 @@ uint32_t scatter_grid(const nv_context* ctx)
 	return g > nv::CC_MAX_SCATTER_TILES ? nv::CC_MAX_SCATTER_TILES : g;
 }
 
-// grid of the streaming kernels: blocksPerCU workgroups of 256 threads per CU
+// grid of the streaming kernels: blocksPerCU workgroups of 256 threads per CU (tests/pixel_cases.py trip_items restates it to size the second-trip tests)
 uint32_t persistent_grid(const nv_context* ctx, uint32_t blocksPerCU)
 {
 	return (uint32_t)ctx->numCUs * blocksPerCU;
