@@ -704,6 +704,75 @@ int nv_shade_final_bloom(nv_context* ctx, void* stream, const NvShadeData* shade
                          const float* d_depth, const uint8_t* d_shadow /* optional */, uint32_t* d_color, uint32_t width, uint32_t height,
                          const uint32_t* d_bloom, const NvBloomDesc* desc);
 
+/* ---- ray-traced sun shadows (replaces shadow.comp.glsl and the BLAS / TLAS of src/scenert.cpp) ----
+ * gfx950 has no ray accelerator and HIP no acceleration-structure API: the scene is a software BVH built on the host at load time
+ * (nv_rt_scene_build), kept on the device by the context (nv_rt_scene_upload) and walked by one kernel (nv_shadow_trace).
+ *
+ * The RESULT is defined without a BVH (tests/shadow_ref.c is the brute-force restatement): per invocation of shadow.comp.glsl:125-161 the ray
+ * origin = wpos (final.comp.glsl's arithmetic), direction = normalize(sunDirection + jitter), tmin = 1e-2, tmax = 1e3, and the byte is 0 when
+ * ANY casting triangle passes the triangle test T for it, 255 otherwise.  T is the watertight test of Woop, Benthin and Wald (JCGT 2013) with
+ * its fp64 fallback, every fp32 operation one IEEE operation in a fixed order (niagara_amd/csrc/rtmath.h); two triangles
+ * that share an edge cannot both miss a ray that crosses it.  No face culling.  A ray with a non-finite origin or direction component (a sky
+ * pixel: depth 0 gives wposh.w == 0; a zero sun vector) hits nothing and stores 255: Vulkan leaves it undefined, this is the defined semantic.
+ * Casting instances (src/scenert.cpp:504-518, src/niagara.cpp:1803): draw i casts iff meshIndex < meshCount, position, orientation and scale
+ * are finite, scale > 0, and postPass == 0 (quality 0) or postPass <= 1 (quality 1).  Its triangles are those of meshes[meshIndex].lods[lodRT]
+ * (none when lodRT >= 8 or >= lodCount): corner k of triangle t < indexCount / 3 is vertices[vertexOffset + indices[indexOffset + 3 t + k]],
+ * the fp16 position converted to fp32; a triangle with an index position >= indexCapacity or a corner >= vertexCapacity is left out
+ * (nv_rasterdepth_indexed's rule).  The ray is taken into object space with t preserved: o' = rotateQuat(o - position, conj(q)) / scale,
+ * d' = rotateQuat(d, conj(q)) / scale.
+ * NOT MODELLED: the library samples no textures, so the alpha test of shadow.comp.glsl:115-120 (quality 1) sees alpha = 1 and a post-pass
+ * material with an albedo texture casts a full shadow.  For quality 0 the reference's outcome for non-opaque instances depends on its driver's
+ * traversal order (one rayQueryProceedEXT, nothing confirmed): post-pass draws are defined as non-casters there.  Animation (a TLAS refit per
+ * frame, src/niagara.cpp:1396) is not modelled: rebuild and upload the scene when draws move. */
+
+/* shadow.comp.glsl:26-35, src/niagara.cpp:269-278; 96 B (92 used), align 16.  inverseViewProjection is column-major */
+typedef struct NvShadowData
+{
+	float sunDirection[3];
+	float sunJitter;
+	float inverseViewProjection[16];
+	float imageSize[2];
+	int32_t checkerboard;
+	uint32_t _pad;
+} NvShadowData;
+
+typedef struct NvRtSceneStats
+{
+	uint32_t bytes;
+	uint32_t instances;    /* casting draws (postPass <= 1) whose mesh has triangles */
+	uint32_t tlasNodes, tlasLeaves, tlasMaxLeaf;
+	uint32_t blasCount;    /* meshes with triangles */
+	uint32_t blasNodes, blasLeaves, blasMaxLeaf;
+	uint32_t triangles;    /* kept triangles of all BLAS */
+} NvRtSceneStats;
+
+/* Host only, no context.  Builds the scene blob: one BLAS per mesh that has triangles and one TLAS over the casting draws, both binary BVHs
+ * in depth-first preorder with skip links (a box hit goes to i + 1, a miss or a leaf to skip[i] > i), median split, leaves of at most 4
+ * triangles / 1 instance.  The blob is relocatable (offsets only, 16-byte aligned sections) and deterministic.  out == NULL: *bytes = the size
+ * needed.  Otherwise *bytes is the room at `out` (16-byte aligned) on entry and the bytes written on return.  NV_EINVAL: a NULL bytes, a NULL
+ * array with a non-zero count, too little room, a misaligned out, counts that do not fit the blob's 32-bit fields. */
+int nv_rt_scene_build(const NvMesh* meshes, uint32_t meshCount, const uint32_t* indices, uint32_t indexCapacity, const NvVertex* vertices,
+                      uint32_t vertexCapacity, const NvMeshDraw* draws, uint32_t drawCount, void* out, uint64_t* bytes);
+/* NV_OK, or NV_EINVAL when the blob is not one nv_rt_scene_trace_host / nv_shadow_trace can walk safely: header and section bounds, every skip
+ * > its index and <= the count, leaf ranges inside their arrays, BLAS references valid */
+int nv_rt_scene_validate(const void* blob, uint64_t bytes);
+int nv_rt_scene_stats(const void* blob, uint64_t bytes, NvRtSceneStats* out);
+/* the traversal nv_shadow_trace runs, on the CPU (the same text, rtmath.h): 1 = occluded, 0 = not; NV_EINVAL for a NULL pointer or quality
+ * outside 0..1.  The blob must have passed nv_rt_scene_validate. */
+int nv_rt_scene_trace_host(const void* blob, const float origin[3], const float dir[3], float tmin, float tmax, int quality);
+/* the same for `count` rays (origins, dirs: count x 3 floats): out[i] = 0 (occluded) or 255, the mask's bytes */
+int nv_rt_scene_trace_host_rays(const void* blob, const float* origins, const float* dirs, uint64_t count, float tmin, float tmax, int quality,
+                                uint8_t* out);
+/* Validates the blob and keeps a context-owned device copy (allocates and synchronises, like nv_reserve: load time); (NULL, 0) drops it */
+int nv_rt_scene_upload(nv_context* ctx, void* stream, const void* blob, uint64_t bytes);
+/* shadow.comp.glsl over W' x height invocations, W' = checkerboard > 0 ? (width + 1) / 2 : width: with checkerboard the invocation (x, y) owns
+ * the texel (2 x + ((y ^ checkerboard) & 1), y) and the texels of the other parity keep their bytes (nv_shadow_fill fills them); a store at
+ * x >= width is dropped.  d_depth: width * height fp32, d_shadow: width * height u8.  Enqueues one launch (no allocation, no synchronisation:
+ * it can be captured).  NV_EINVAL: no uploaded scene, a NULL pointer, width or height 0 or above 16384, shadow->imageSize not (width, height),
+ * quality outside 0..1, a depth pointer that is not 4-byte aligned. */
+int nv_shadow_trace(nv_context* ctx, void* stream, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width,
+                    uint32_t height, int quality);
+
 /* ---- host helpers mirroring src/niagara.cpp / src/resources.cpp (no device work) ---- */
 uint32_t nv_previous_pow2(uint32_t v);                        /* src/niagara.cpp:439-447 */
 uint32_t nv_image_mip_levels(uint32_t width, uint32_t height); /* src/resources.cpp:280-292 */
@@ -727,6 +796,10 @@ int nv_build_cull_data(NvCullData* out, const float cameraPosition[3], const flo
  * height 0, a singular or non-finite product. */
 int nv_build_shade_data(NvShadeData* out, const NvGlobals* globals, const float cameraPosition[3], const float sunDirection[3],
                         int shadowsEnabled, uint32_t width, uint32_t height);
+/* src/niagara.cpp:1806-1812: the ShadowData of nv_shadow_trace; inverseViewProjection exactly as nv_build_shade_data computes it (the same
+ * code), imageSize = (width, height).  niagara passes sunJitter = 1e-2 when the shadow blur is on, else 0.  NV_EINVAL as nv_build_shade_data */
+int nv_build_shadow_data(NvShadowData* out, const NvGlobals* globals, const float sunDirection[3], float sunJitter, int checkerboard,
+                         uint32_t width, uint32_t height);
 /* src/niagara.cpp:1002-1020: per-draw meshletVisibilityOffset prefix; returns the slot count
  * through out_slots (meshletVisibility bytes = (slots+31)/32*4) and the postPass mask. */
 int nv_assign_visibility_offsets(NvMeshDraw* draws, uint32_t drawCount, const NvMesh* meshes,
@@ -806,6 +879,9 @@ static_assert(sizeof(NvMaterial) == 64 && offsetof(NvMaterial, diffuseFactor) ==
 static_assert(sizeof(NvPixelAttributes) == 64 && offsetof(NvPixelAttributes, drawId) == 28 && offsetof(NvPixelAttributes, materialIndex) == 60, "four 16-byte stores per pixel");
 static_assert(sizeof(NvShadeData) == 112 && offsetof(NvShadeData, sunDirection) == 16 && offsetof(NvShadeData, shadowsEnabled) == 28 &&
               offsetof(NvShadeData, inverseViewProjection) == 32 && offsetof(NvShadeData, imageSize) == 96, "ShadeData layout (src/niagara.cpp:280-290)");
+static_assert(sizeof(NvShadowData) == 96 && offsetof(NvShadowData, sunJitter) == 12 && offsetof(NvShadowData, inverseViewProjection) == 16 &&
+              offsetof(NvShadowData, imageSize) == 80 && offsetof(NvShadowData, checkerboard) == 88, "ShadowData layout (src/niagara.cpp:269-278)");
+static_assert(sizeof(NvRtSceneStats) == 40, "NvRtSceneStats is mirrored by niagara_amd/_lib.py");
 static_assert(sizeof(NvBloomDesc) == 48 && offsetof(NvBloomDesc, levels) == 8 && offsetof(NvBloomDesc, levelOffset) == 12 &&
               offsetof(NvBloomDesc, totalTexels) == 44, "NvBloomDesc is mirrored by niagara_amd/_lib.py and niagara_amd/layouts.py");
 static_assert(sizeof(NvSceneCacheInfo) == 208, "NvSceneCacheInfo is mirrored by niagara_amd/_lib.py");

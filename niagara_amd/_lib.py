@@ -32,6 +32,12 @@ class BloomDesc(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("levels", C.c_uint32), ("levelOffset", C.c_uint32 * 8), ("totalTexels", C.c_uint32)]
 
 
+class RtSceneStats(C.Structure):
+    """NvRtSceneStats (include/niagara_vis.h): what nv_rt_scene_stats reports of a scene blob"""
+    _fields_ = [(n, C.c_uint32) for n in ("bytes", "instances", "tlasNodes", "tlasLeaves", "tlasMaxLeaf", "blasCount", "blasNodes", "blasLeaves",
+                                          "blasMaxLeaf", "triangles")]
+
+
 class SceneCacheInfo(C.Structure):
     """NvSceneCacheInfo (include/niagara_vis.h)"""
     _fields_ = ([(n, C.c_uint32) for n in ("version", "compressed", "clrtMode", "ommStates")] + [("hashMeta", C.c_uint64)] +
@@ -90,6 +96,14 @@ _SIGS = {
     "nv_shadow_blur": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _i, _f]),
     "nv_shade_final": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32]),
     "nv_build_shade_data": (_i, [_vp, _vp, _vp, _vp, _i, _u32, _u32]),
+    "nv_build_shadow_data": (_i, [_vp, _vp, _vp, _f, _i, _u32, _u32]),
+    "nv_rt_scene_build": (_i, [_vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, C.POINTER(C.c_uint64)]),
+    "nv_rt_scene_validate": (_i, [_vp, C.c_uint64]),
+    "nv_rt_scene_stats": (_i, [_vp, C.c_uint64, C.POINTER(RtSceneStats)]),
+    "nv_rt_scene_trace_host": (_i, [_vp, _vp, _vp, _f, _f, _i]),
+    "nv_rt_scene_trace_host_rays": (_i, [_vp, _vp, _vp, C.c_uint64, _f, _f, _i, _vp]),
+    "nv_rt_scene_upload": (_i, [_vp, _vp, _vp, C.c_uint64]),
+    "nv_shadow_trace": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _i]),
     "nv_bloom_desc_init": (_i, [C.POINTER(BloomDesc), _u32, _u32]),
     "nv_bloom_extract": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, C.POINTER(BloomDesc)]),
     "nv_bloom_downsample": (_i, [_vp, _vp, _vp, C.POINTER(BloomDesc), _u32]),

@@ -55,6 +55,8 @@ int launch_shadow_fill(hipStream_t, uint8_t* shadow, const float* depth, uint32_
 int launch_shadow_blur(hipStream_t, uint8_t* out, const uint8_t* shadow, const float* depth, uint32_t width, uint32_t height, bool horizontal, float znear);
 int launch_shade_final(hipStream_t, const NvShadeData& sd, const uint32_t* gbuffer0, const uint32_t* gbuffer1, const float* depth, const uint8_t* shadow,
                        uint32_t* color, uint32_t width, uint32_t height, uint32_t maxBlocks, const uint32_t* bloom, uint32_t bloomWidth, uint32_t bloomHeight);
+int launch_shadow_trace(hipStream_t, const NvShadowData& sd, const void* scene, const float* depth, uint8_t* shadow, uint32_t width, uint32_t height, int quality,
+                        uint32_t maxBlocks);
 int launch_bloom_extract(hipStream_t, const uint32_t* gbuffer0, uint32_t width, uint32_t height, uint32_t* bloom, const NvBloomDesc& desc, uint32_t maxBlocks);
 int launch_bloom_downsample(hipStream_t, uint32_t* bloom, const NvBloomDesc& desc, uint32_t level);
 int launch_bloom_upsample(hipStream_t, uint32_t* bloom, const NvBloomDesc& desc, uint32_t level, float radius);
@@ -156,6 +158,8 @@ struct nv_context
 	uint32_t bloomFusedTail;   // NV_OPT_BLOOM_FUSED_TAIL: 1 = nv_bloom runs the levels that fit one workgroup's LDS as one launch
 	uint32_t resolvePerPixel;  // experiments: nv_visibility_resolve without the per-run de-duplication
 	uint32_t attributesPerPixel; // experiments: nv_visibility_attributes without the per-run set-up
+	void* rtScene;               // nv_rt_scene_upload: the device copy of the validated scene blob nv_shadow_trace walks
+	uint64_t rtSceneBytes;
 };
 
 namespace
@@ -558,6 +562,8 @@ void nv_destroy(nv_context* ctx)
 	scene_release(ctx->scene);
 	if (ctx->timing)
 		scratch_free(ctx->timing);
+	if (ctx->rtScene)
+		scratch_free(ctx->rtScene);
 	delete ctx->prof;
 	delete ctx;
 }
@@ -1275,6 +1281,48 @@ int nv_shade_final(nv_context* ctx, void* stream, const NvShadeData* shade, cons
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	return nv::launch_shade_final((hipStream_t)stream, *shade, d_gbuffer0, d_gbuffer1, d_depth, d_shadow, d_color, width, height, persistent_grid(ctx, 8), nullptr, 0, 0);
+}
+
+// ---- ray-traced sun shadows (shadowtrace.hip, rtbuild.cpp)
+// Load time, like nv_reserve: allocates, copies and synchronises.  Only a blob nv_rt_scene_validate accepts reaches the device: every index the
+// kernel follows stays inside the copy and every loop it runs ends.
+int nv_rt_scene_upload(nv_context* ctx, void* stream, const void* blob, uint64_t bytes)
+{
+	if (!ctx || (blob == nullptr) != (bytes == 0))
+		return NV_EINVAL;
+	if (blob && nv_rt_scene_validate(blob, bytes) != NV_OK)
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	hipError_t e = hipStreamSynchronize((hipStream_t)stream); // a launch that still reads the old copy
+	if (e != hipSuccess)
+		return (int)e;
+	void* fresh = nullptr;
+	if (blob)
+	{
+		if (scratch_alloc(&fresh, (size_t)bytes) != hipSuccess)
+			return NV_ENOMEM;
+		e = hipMemcpy(fresh, blob, (size_t)bytes, hipMemcpyHostToDevice);
+		if (e != hipSuccess)
+		{
+			scratch_free(fresh);
+			return (int)e;
+		}
+	}
+	if (ctx->rtScene)
+		scratch_free(ctx->rtScene);
+	ctx->rtScene = fresh;
+	ctx->rtSceneBytes = bytes;
+	return NV_OK;
+}
+
+int nv_shadow_trace(nv_context* ctx, void* stream, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width, uint32_t height,
+                    int quality)
+{
+	if (!ctx || !ctx->rtScene || !shadow || !d_depth || !d_shadow || !shade_size_ok(width, height) || shadow->imageSize[0] != (float)width ||
+	    shadow->imageSize[1] != (float)height || quality < 0 || quality > 1 || (reinterpret_cast<uintptr_t>(d_depth) & 3u))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_shadow_trace((hipStream_t)stream, *shadow, ctx->rtScene, d_depth, d_shadow, width, height, quality, persistent_grid(ctx, 8));
 }
 
 // ---- bloom (bloom.hip)

@@ -152,11 +152,8 @@ int nv_build_cull_data(NvCullData* out, const float cameraPosition[3], const flo
 // src/niagara.cpp:1917-1922.  inverse(projection * view) in fp64 from the fp32 entries (the product's sums left to right, the inverse as adjugate /
 // determinant from the 2 x 2 minors of the row pairs), rounded once to fp32.  A structural zero of the product stays an exact zero: with niagara's
 // projection the w row of the result is (0, 0, 1 / znear, 0), so a sky pixel (depth 0) has wposh.w == 0 exactly, as in the shader.
-int nv_build_shade_data(NvShadeData* out, const NvGlobals* globals, const float cameraPosition[3], const float sunDirection[3], int shadowsEnabled,
-                        uint32_t width, uint32_t height)
+static int inverse_view_projection(const NvGlobals* globals, float inverse[16])
 {
-	if (!out || !globals || !cameraPosition || !sunDirection || !width || !height)
-		return NV_EINVAL;
 	const float* P = globals->projection;
 	const float* V = globals->cullData.view;
 	double a[4][4]; // a[row][col] of projection * view (both column-major)
@@ -187,15 +184,27 @@ int nv_build_shade_data(NvShadeData* out, const NvGlobals* globals, const float 
 	b[3][1] = (a[0][0] * c3 - a[0][1] * c1) + a[0][2] * c0;
 	b[3][2] = (-a[3][0] * s3 + a[3][1] * s1) - a[3][2] * s0;
 	b[3][3] = (a[2][0] * s3 - a[2][1] * s1) + a[2][2] * s0;
-	memset(out, 0, sizeof(*out));
 	for (int r = 0; r < 4; ++r)
 		for (int c = 0; c < 4; ++c)
 		{
 			const double v = b[r][c] / det;
 			if (!(fabs(v) < INFINITY))
 				return NV_EINVAL;
-			out->inverseViewProjection[4 * c + r] = (float)v;
+			inverse[4 * c + r] = (float)v;
 		}
+	return NV_OK;
+}
+
+int nv_build_shade_data(NvShadeData* out, const NvGlobals* globals, const float cameraPosition[3], const float sunDirection[3], int shadowsEnabled,
+                        uint32_t width, uint32_t height)
+{
+	if (!out || !globals || !cameraPosition || !sunDirection || !width || !height)
+		return NV_EINVAL;
+	float inverse[16];
+	if (inverse_view_projection(globals, inverse) != NV_OK)
+		return NV_EINVAL;
+	memset(out, 0, sizeof(*out));
+	memcpy(out->inverseViewProjection, inverse, sizeof(inverse));
 	for (int k = 0; k < 3; ++k)
 	{
 		out->cameraPosition[k] = cameraPosition[k];
@@ -204,6 +213,26 @@ int nv_build_shade_data(NvShadeData* out, const NvGlobals* globals, const float 
 	out->shadowsEnabled = shadowsEnabled;
 	out->imageSize[0] = (float)width;
 	out->imageSize[1] = (float)height;
+	return NV_OK;
+}
+
+// src/niagara.cpp:1810-1815: the same inverse as nv_build_shade_data's
+int nv_build_shadow_data(NvShadowData* out, const NvGlobals* globals, const float sunDirection[3], float sunJitter, int checkerboard, uint32_t width,
+                         uint32_t height)
+{
+	if (!out || !globals || !sunDirection || !width || !height)
+		return NV_EINVAL;
+	float inverse[16];
+	if (inverse_view_projection(globals, inverse) != NV_OK)
+		return NV_EINVAL;
+	memset(out, 0, sizeof(*out));
+	memcpy(out->inverseViewProjection, inverse, sizeof(inverse));
+	for (int k = 0; k < 3; ++k)
+		out->sunDirection[k] = sunDirection[k];
+	out->sunJitter = sunJitter;
+	out->imageSize[0] = (float)width;
+	out->imageSize[1] = (float)height;
+	out->checkerboard = checkerboard;
 	return NV_OK;
 }
 

@@ -14,6 +14,7 @@
 // None of the kernels waits on another workgroup, nothing is allocated: the entry points only enqueue and can be captured.
 #include "cullmath.h"
 #include "bloommath.h"
+#include "rtmath.h"
 
 namespace nv
 {
@@ -216,11 +217,7 @@ __global__ __launch_bounds__(SH_THREADS) void shade_final_kernel(typename ShadeF
 		const float ndotl = gl_max(dot3(normal, sun), 0.0f);
 		// :52-54
 		const float cx = uvx * 2.0f - 1.0f, cy = 1.0f - uvy * 2.0f;
-		const float hx = ((m[0] * cx + m[4] * cy) + m[8] * depth) + m[12] * 1.0f;
-		const float hy = ((m[1] * cx + m[5] * cy) + m[9] * depth) + m[13] * 1.0f;
-		const float hz = ((m[2] * cx + m[6] * cy) + m[10] * depth) + m[14] * 1.0f;
-		const float hw = ((m[3] * cx + m[7] * cy) + m[11] * depth) + m[15] * 1.0f;
-		const f3 wpos = { hx / hw, hy / hw, hz / hw };
+		const rt3 wpos = rt_unproject(m, cx, cy, depth); // (rtmath.h: the shadow trace's ray origin is the same arithmetic)
 		// :56-59
 		const f3 view = sh_normalize(f3{ a.sd.cameraPosition[0] - wpos.x, a.sd.cameraPosition[1] - wpos.y, a.sd.cameraPosition[2] - wpos.z });
 		const f3 halfv = sh_normalize(f3{ view.x + sun.x, view.y + sun.y, view.z + sun.z });

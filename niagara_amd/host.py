@@ -63,6 +63,62 @@ def build_shade_data(globals_, camera_position=(0, 0, 0), sun_direction=(0, 1, 0
     return sd
 
 
+def build_shadow_data(globals_, sun_direction=(0, 1, 0), sun_jitter=0.0, checkerboard=0, width=None, height=None):
+    """NvShadowData of nv_shadow_trace (src/niagara.cpp:1810-1815) from the frame's globals: inverseViewProjection as build_shade_data
+    computes it; niagara's sun_jitter is 1e-2 when the shadow blur is on, else 0; width / height default to the globals' screen size"""
+    sd = np.zeros(1, dtype=L.SHADOWDATA)
+    g = np.ascontiguousarray(globals_)
+    w = int(g["screenWidth"][0]) if width is None else int(width)
+    h = int(g["screenHeight"][0]) if height is None else int(height)
+    sun = np.ascontiguousarray(sun_direction, dtype=np.float32)
+    check(lib.nv_build_shadow_data(_p(sd), _p(g), _p(sun), float(sun_jitter), int(checkerboard), w, h), "nv_build_shadow_data")
+    return sd
+
+
+RT_TMIN, RT_TMAX = 1e-2, 1e3  # shadow.comp.glsl:81
+
+
+def rt_scene_build(meshes, indices, vertices, draws):
+    """The scene blob of the ray-traced shadow pass (nv_rt_scene_build; host only): one BLAS per mesh with triangles (lods[lodRT], through the
+    index buffer of the classic path) and one TLAS over the casting draws.  Returns a 16-byte aligned uint8 array"""
+    m = np.ascontiguousarray(meshes, L.MESH)
+    i = np.ascontiguousarray(indices, np.uint32)
+    v = np.ascontiguousarray(vertices, L.VERTEX)
+    d = np.ascontiguousarray(draws, L.MESHDRAW)
+    args = (_p(m) if len(m) else None, len(m), _p(i) if len(i) else None, len(i), _p(v) if len(v) else None, len(v), _p(d) if len(d) else None, len(d))
+    n = C.c_uint64(0)
+    check(lib.nv_rt_scene_build(*args, None, C.byref(n)), "nv_rt_scene_build")
+    raw = np.zeros(n.value + 16, np.uint8)
+    off = (-raw.ctypes.data) % 16
+    blob = raw[off:off + n.value]
+    room = C.c_uint64(n.value)
+    check(lib.nv_rt_scene_build(*args, _p(blob), C.byref(room)), "nv_rt_scene_build")
+    assert room.value == n.value
+    return blob
+
+
+def rt_scene_validate(blob):
+    """True when nv_rt_scene_validate accepts the blob (a uint8 array whose data is 16-byte aligned)"""
+    return lib.nv_rt_scene_validate(_p(blob), blob.nbytes) == 0
+
+
+def rt_scene_stats(blob):
+    from ._lib import RtSceneStats
+    st = RtSceneStats()
+    check(lib.nv_rt_scene_stats(_p(blob), blob.nbytes, C.byref(st)), "nv_rt_scene_stats")
+    return {n: int(getattr(st, n)) for n, _ in RtSceneStats._fields_}
+
+
+def rt_scene_trace_host(blob, origins, dirs, quality=1, tmin=RT_TMIN, tmax=RT_TMAX):
+    """nv_shadow_trace's traversal on the CPU for (n, 3) float32 rays: the mask's bytes, 0 = occluded, 255 = not"""
+    o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    assert o.shape == d.shape
+    out = np.zeros(len(o), np.uint8)
+    check(lib.nv_rt_scene_trace_host_rays(_p(blob), _p(o), _p(d), len(o), float(tmin), float(tmax), int(quality), _p(out)), "nv_rt_scene_trace_host_rays")
+    return out
+
+
 def synth_draws(n, mesh_count, scene_radius=300.0):
     d = np.zeros(n, dtype=L.MESHDRAW)
     check(lib.nv_synth_draws(_p(d), n, mesh_count, scene_radius), "nv_synth_draws")

@@ -45,6 +45,10 @@ assert (MATERIAL.itemsize, PIXELATTR.itemsize) == (64, 64)
 SHADEDATA = np.dtype([("cameraPosition", "<f4", 3), ("pad0", "<f4"), ("sunDirection", "<f4", 3), ("shadowsEnabled", "<i4"),
                       ("inverseViewProjection", "<f4", 16), ("imageSize", "<f4", 2), ("_pad", "<f4", 2)])
 assert SHADEDATA.itemsize == 112
+# NvShadowData (src/niagara.cpp:269-278), the push constants of shadow.comp.glsl: 92 bytes used, alignas(16) pads to 96
+SHADOWDATA = np.dtype([("sunDirection", "<f4", 3), ("sunJitter", "<f4"), ("inverseViewProjection", "<f4", 16), ("imageSize", "<f4", 2),
+                       ("checkerboard", "<i4"), ("_pad", "<u4")])
+assert SHADOWDATA.itemsize == 96
 # NvBloomDesc (src/niagara.cpp:1331-1333): level 0 size, level count and the levels' offsets (texels) in the one B10G11R11 buffer
 BLOOMDESC = np.dtype([("width", "<u4"), ("height", "<u4"), ("levels", "<u4"), ("levelOffset", "<u4", 8), ("totalTexels", "<u4")])
 assert BLOOMDESC.itemsize == 48

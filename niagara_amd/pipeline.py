@@ -231,6 +231,23 @@ class Context:
         check(lib.nv_shadow_blur(self.h, _stream(), _ptr(out), _ptr(shadow), _ptr(depth), int(width), int(height), int(direction), float(znear)),
               "nv_shadow_blur")
 
+    def rt_scene_build(self, meshes, indices, vertices, draws):
+        """the scene blob of the shadow trace (host.rt_scene_build; host only)"""
+        return host.rt_scene_build(meshes, indices, vertices, draws)
+
+    def rt_scene_upload(self, blob):
+        """validate the blob and keep a context-owned device copy (nv_rt_scene_upload: load time, synchronises); None drops it"""
+        if blob is None:
+            check(lib.nv_rt_scene_upload(self.h, _stream(), None, 0), "nv_rt_scene_upload")
+        else:
+            check(lib.nv_rt_scene_upload(self.h, _stream(), C.c_void_p(blob.ctypes.data), blob.nbytes), "nv_rt_scene_upload")
+
+    def shadow_trace(self, shadow_data, depth, shadow, width, height, quality=1):
+        """shadow.comp.glsl (nv_shadow_trace): the u8 sun shadow mask (0 = in shadow, 255 = lit) of the depth target from the uploaded scene;
+        with shadow_data["checkerboard"] > 0 only one parity of the texels is written (shadow_fill fills the other)"""
+        check(lib.nv_shadow_trace(self.h, _stream(), C.c_void_p(shadow_data.ctypes.data), _ptr(depth), _ptr(shadow), int(width), int(height), int(quality)),
+              "nv_shadow_trace")
+
     def shade_final(self, shade_data, gbuffer0, gbuffer1, depth, shadow, color, width, height):
         """final.comp.glsl without the bloom term (nv_shade_final): the R8G8B8A8 colour (R in the low byte) of every pixel from the two
         G-buffer words, the depth target and, with shade_data["shadowsEnabled"] == 1, the u8 shadow image (None otherwise)"""
@@ -364,6 +381,7 @@ class VisibilityPipeline:
         # depth target, through the clusters (meshlet_data) or through the indexed draws of the classic path (indices)
         self.mdb = self.vb = self.ib = self.depth = None
         self.bloom_image = self.bloom_desc = None  # shade(bloom=True)'s target, allocated on first use
+        self.rt_scene = self.shadow_image = None   # build_rt_scene's blob; shade(shadow="trace")'s mask, allocated on first use
         self.index_count = self.vertex_count = 0
         if vertices is not None and (meshlet_data is not None or indices is not None):
             self.vertex_count = len(vertices)
@@ -480,17 +498,38 @@ class VisibilityPipeline:
                                        out["attributes"], out["gbuffer0"], out["gbuffer1"], out["totals"])
         return out
 
-    def shade(self, cull_data, gbuffer0, gbuffer1, camera_position, sun_direction, shadow=None, blur=True, checkerboard=False, bloom=False):
-        """the shading end of the frame over attributes()'s G-buffer words and the pipeline's own depth target (src/niagara.cpp:1822-1850,
+    def build_rt_scene(self, meshes, indices, vertices, draws):
+        """build the ray-tracing scene of shade(shadow="trace") on the host and upload it, once per scene (niagara builds its BLAS / TLAS at
+        load time, src/scenert.cpp): `meshes` with their LODs' index ranges set (synth.indexed_geometry) and the index buffer of the classic
+        path.  The scene is static: call again when draws move.  Returns the blob"""
+        self.rt_scene = self.ctx.rt_scene_build(meshes, indices, vertices, draws)
+        self.ctx.rt_scene_upload(self.rt_scene)
+        return self.rt_scene
+
+    def shade(self, cull_data, gbuffer0, gbuffer1, camera_position, sun_direction, shadow=None, blur=True, checkerboard=False, bloom=False, quality=1):
+        """the shading end of the frame over attributes()'s G-buffer words and the pipeline's own depth target (src/niagara.cpp:1792-1850,
         1906-1925): returns the colour tensor (int32, height x width, R8G8B8A8 with R in the low byte).  shadow: a caller-supplied mask (uint8
-        tensor, height x width; the library traces no rays) — it is filled in place when `checkerboard`, blurred horizontally into an image
+        tensor, height x width) — it is filled in place when `checkerboard`, blurred horizontally into an image
         the pipeline owns and vertically back into the mask when `blur`, and final shades with shadows on; without a mask final runs
-        with shadows off.  bloom: run the bloom chain over gbuffer0 into a target the pipeline owns (self.bloom_image, self.bloom_desc) and
+        with shadows off.  shadow="trace" (after build_rt_scene): the mask is ray traced first (nv_shadow_trace with `quality`, sunJitter 1e-2
+        when `blur`, else 0, one checkerboard parity when `checkerboard`) into a mask the pipeline owns (self.shadow_image), then treated the
+        same way.  bloom: run the bloom chain over gbuffer0 into a target the pipeline owns (self.bloom_image, self.bloom_desc) and
         add its term in final (src/niagara.cpp:1866-1904); the default leaves it out, as before"""
         if self.depth is None:
             raise NvError("shade reads the pipeline's depth target: VisibilityPipeline(..., meshlet_data=, vertices=)")
         w, h = self.depth_w, self.depth_h
         dev = self.ctx.device
+        g = synth.make_globals(cull_data, (w, h))
+        if isinstance(shadow, str):
+            if shadow != "trace":
+                raise NvError("shade: shadow is None, a mask or \"trace\"")
+            if self.rt_scene is None:
+                raise NvError("shade(shadow=\"trace\") walks the ray-tracing scene: build_rt_scene(meshes, indices, vertices, draws) first")
+            if self.shadow_image is None:
+                self.shadow_image = torch.zeros((h, w), dtype=torch.uint8, device=dev)
+            shadow = self.shadow_image
+            sh = host.build_shadow_data(g, sun_direction, 1e-2 if blur else 0.0, 1 if checkerboard else 0, w, h)  # src/niagara.cpp:1810-1815
+            self.ctx.shadow_trace(sh, self.depth, shadow, w, h, quality)
         if shadow is not None:
             if shadow.dtype != torch.uint8 or shadow.numel() != w * h or not shadow.is_contiguous():
                 raise NvError("shade: the shadow mask is a contiguous uint8 tensor of the depth target's size")
@@ -502,7 +541,6 @@ class VisibilityPipeline:
                 znear = float(cull_data["znear"][0])
                 self.ctx.shadow_blur(self.shadow_blur_image, shadow, self.depth, w, h, 1, znear)  # src/niagara.cpp:1836-1850
                 self.ctx.shadow_blur(shadow, self.shadow_blur_image, self.depth, w, h, 0, znear)
-        g = synth.make_globals(cull_data, (w, h))
         sd = host.build_shade_data(g, camera_position, sun_direction, 1 if shadow is not None else 0, w, h)
         color = torch.zeros((h, w), dtype=torch.int32, device=dev)
         if bloom:

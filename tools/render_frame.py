@@ -5,13 +5,15 @@
     python3 tools/render_frame.py --out frame.ppm                       # the scene at its own viewport, a synthetic shadow mask
     python3 tools/render_frame.py --no-shadow --viewport 1920x1080
     python3 tools/render_frame.py --bloom                               # two materials emit; the bloom chain and final's bloom term
+    python3 tools/render_frame.py --traced-shadows                      # the mask is ray traced (nv_shadow_trace)
 
 Writes a binary PPM (P6, R G B from the R8G8B8A8 colour words) and prints one JSON line with the passes' times by HIP events (one run
 each after a warm-up frame: launch gaps included, an upper bound of the kernel time; profiles/r13_shade.md has the kernel trace).
 --passes WxH[,WxH...] instead times the three shade passes alone on synthetic images of those sizes, cache-cold (a 512 MiB buffer is
 rewritten between the passes): the run to put under a kernel trace.  With --bloom it times the bloom passes instead: pass 0, every level
 of passes 1 and 2, the whole chain per level and with the fused tail (NV_OPT_BLOOM_FUSED_TAIL) alternately — the A/B — and final with the
-bloom term (profiles/r14_bloom.md)."""
+bloom term (profiles/r14_bloom.md).  --traced-shadows --passes shadow_trace times nv_shadow_trace alone on the scene at --viewport over the
+depth target its own frames leave, both qualities, with and without checkerboard, cache-cold (profiles/r15_shadowtrace.md)."""
 import argparse
 import json
 import os
@@ -115,22 +117,8 @@ def passes(sizes, repeats, bloom=False):
     ctx.close()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="frame.ppm")
-    ap.add_argument("--viewport", default=None, help="WxH (default: the scene's own, 320x192)")
-    ap.add_argument("--no-shadow", action="store_true")
-    ap.add_argument("--checkerboard", action="store_true")
-    ap.add_argument("--bloom", action="store_true", help="two materials emit; run the bloom chain and final's bloom term")
-    ap.add_argument("--passes", default=None)
-    ap.add_argument("--repeats", type=int, default=9)
-    args = ap.parse_args()
-    if args.passes:
-        passes([tuple(int(v) for v in s.split("x")) for s in args.passes.split(",")], args.repeats, args.bloom)
-        return
-    import numpy as np
-    import torch
-
+def _scene(args, indexed):
+    """the occluder scene at the asked viewport with its meshlet bounds computed on the device"""
     from niagara_amd import layouts as L
     from niagara_amd import pipeline as P
     from niagara_amd import synth
@@ -145,7 +133,85 @@ def main():
     kw = dict(meshlet_bounds=bounds)
     if args.viewport:
         kw["viewport"] = tuple(int(v) for v in args.viewport.split("x"))
-    s = synth.occluder_scene(**kw)
+    return synth.occluder_scene_indexed(**kw) if indexed else synth.occluder_scene(**kw)
+
+
+def trace_passes(args):
+    """nv_shadow_trace alone: the scene's own depth target (two closed-loop frames), every launch behind a flush of the caches"""
+    import numpy as np
+    import torch
+
+    from niagara_amd import host, synth
+    from niagara_amd import pipeline as P
+    s = _scene(args, True)
+    w, h = s["viewport"]
+    pipe = P.VisibilityPipeline(s["meshes"], s["meshlets"], s["draws"], (w, h), fused=True, vertices=s["vertices"], meshlet_data=s["data"], stable_ids=True)
+    vis = pipe.new_visibility()
+    for _ in range(2):
+        pipe.frame(s["cull"], post_pass=True, visibility=vis)
+    blob = pipe.build_rt_scene(s["meshes"], s["indices"], s["vertices"], s["draws"])
+    ctx, dev = pipe.ctx, pipe.ctx.device
+    flush = torch.zeros(512 << 20, dtype=torch.uint8, device=dev)
+    mask = torch.zeros((h, w), dtype=torch.uint8, device=dev)
+    sun = np.array([2.0, 0.3, 1.0]) / np.linalg.norm([2.0, 0.3, 1.0])
+    g = synth.make_globals(s["cull"], (w, h))
+    line = dict(size="%dx%d" % (w, h), covered=int((pipe.depth > 0).sum().item()), scene=host.rt_scene_stats(blob))
+    for quality in (0, 1):
+        for checkerboard in (0, 1):
+            for jitter in (0.0, 1e-2):
+                sd = host.build_shadow_data(g, sun, jitter, checkerboard, w, h)
+                run = lambda: ctx.shadow_trace(sd, pipe.depth, mask, w, h, quality)
+                run()  # warm-up
+                times = []
+                for _ in range(args.repeats):
+                    flush.add_(1)
+                    ev = []
+                    _timed(ev, "shadow_trace", run)
+                    torch.cuda.synchronize()
+                    times.append(ev[0][1].elapsed_time(ev[0][2]) * 1e3)
+                warm = []  # back to back: the scene and the depth target stay in the caches
+                for _ in range(args.repeats):
+                    ev = []
+                    _timed(ev, "shadow_trace", run)
+                    torch.cuda.synchronize()
+                    warm.append(ev[0][1].elapsed_time(ev[0][2]) * 1e3)
+                t, tw = sorted(times), sorted(warm)
+                rays = ((w + 1) // 2 if checkerboard else w) * h
+                line["shadow_trace_q%d_cb%d_jitter%g" % (quality, checkerboard, jitter)] = dict(
+                    us_median=round(t[len(t) // 2], 2), us_min=round(t[0], 2), us_max=round(t[-1], 2), us_warm_median=round(tw[len(tw) // 2], 2),
+                    us_warm_min=round(tw[0], 2), us_warm_max=round(tw[-1], 2), rays=rays, occluded=int((mask == 0).sum().item()))
+    print(json.dumps(line), flush=True)
+    ctx.status()
+    ctx.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="frame.ppm")
+    ap.add_argument("--viewport", default=None, help="WxH (default: the scene's own, 320x192)")
+    ap.add_argument("--no-shadow", action="store_true")
+    ap.add_argument("--checkerboard", action="store_true")
+    ap.add_argument("--bloom", action="store_true", help="two materials emit; run the bloom chain and final's bloom term")
+    ap.add_argument("--traced-shadows", action="store_true", help="ray trace the shadow mask (the default stays the synthetic mask)")
+    ap.add_argument("--quality", type=int, default=1, help="--traced-shadows: 0 = opaque draws cast, 1 = post-pass draws too")
+    ap.add_argument("--passes", default=None, help="WxH[,WxH...], or shadow_trace (with --traced-shadows)")
+    ap.add_argument("--repeats", type=int, default=9)
+    args = ap.parse_args()
+    if args.passes == "shadow_trace":
+        if not args.traced_shadows:
+            ap.error("--passes shadow_trace times the ray-traced pass: give --traced-shadows")
+        trace_passes(args)
+        return
+    if args.passes:
+        passes([tuple(int(v) for v in s.split("x")) for s in args.passes.split(",")], args.repeats, args.bloom)
+        return
+    import numpy as np
+    import torch
+
+    from niagara_amd import layouts as L
+    from niagara_amd import pipeline as P
+
+    s = _scene(args, args.traced_shadows)  # the traced mask needs the index buffer of the classic path
     w, h = s["viewport"]
     # attributes for the vertices and a material per draw: unit normals from the positions, colours by draw
     rng = np.random.default_rng(7)
@@ -169,15 +235,17 @@ def main():
     mask = np.clip(np.rint(255.0 * np.clip((r - 0.8) / 0.4, 0.0, 1.0)), 0, 255).astype(np.uint8)
     sun = np.array([0.35, 0.6, 0.72]) / np.linalg.norm([0.35, 0.6, 0.72])
     mat = P.to_device(materials, pipe.ctx.device)
+    if args.traced_shadows and not args.no_shadow:
+        pipe.build_rt_scene(s["meshes"], s["indices"], v, draws)
 
     def frame(events):
         vis = pipe.new_visibility()
         _timed(events, "frame", lambda: pipe.frame(s["cull"], post_pass=True, visibility=vis))
         res = _timed(events, "resolve", lambda: pipe.resolve(s["cull"], vis))
         att = _timed(events, "attributes", lambda: pipe.attributes(s["cull"], res["records"], mat, attributes=False))
-        shadow = None if args.no_shadow else torch.from_numpy(mask.copy()).to(pipe.ctx.device)
+        shadow = None if args.no_shadow else "trace" if args.traced_shadows else torch.from_numpy(mask.copy()).to(pipe.ctx.device)
         return _timed(events, "shade", lambda: pipe.shade(s["cull"], att["gbuffer0"], att["gbuffer1"], (0.0, 0.0, 0.0), sun, shadow=shadow,
-                                                          checkerboard=args.checkerboard, bloom=args.bloom))
+                                                          checkerboard=args.checkerboard, bloom=args.bloom, quality=args.quality))
     frame([])  # warm-up (and the visibility bits of the closed loop)
     events = []
     color = frame(events)
@@ -188,7 +256,7 @@ def main():
     with open(args.out, "wb") as f:
         f.write(b"P6\n%d %d\n255\n" % (w, h))
         f.write(rgb.tobytes())
-    print(json.dumps(dict(out=args.out, viewport=[w, h], shadow=not args.no_shadow, bloom=args.bloom, covered=int((pipe.depth > 0).sum().item()),
+    print(json.dumps(dict(out=args.out, viewport=[w, h], shadow=not args.no_shadow, traced=bool(args.traced_shadows and not args.no_shadow), bloom=args.bloom, covered=int((pipe.depth > 0).sum().item()),
                           mean_rgb=[round(float(c), 2) for c in rgb.reshape(-1, 3).mean(0)],
                           us={name: round(a.elapsed_time(b) * 1e3, 1) for name, a, b in events})))
     pipe.ctx.close()
