@@ -722,8 +722,10 @@ int nv_shade_final_bloom(nv_context* ctx, void* stream, const NvShadeData* shade
  * d' = rotateQuat(d, conj(q)) / scale.
  * NOT MODELLED: the library samples no textures, so the alpha test of shadow.comp.glsl:115-120 (quality 1) sees alpha = 1 and a post-pass
  * material with an albedo texture casts a full shadow.  For quality 0 the reference's outcome for non-opaque instances depends on its driver's
- * traversal order (one rayQueryProceedEXT, nothing confirmed): post-pass draws are defined as non-casters there.  Animation (a TLAS refit per
- * frame, src/niagara.cpp:1396) is not modelled: rebuild and upload the scene when draws move. */
+ * traversal order (one rayQueryProceedEXT, nothing confirmed): post-pass draws are defined as non-casters there.  Animation: when draws move,
+ * nv_rt_tlas_build (below) rebuilds the TLAS on the device from the rewritten draw records, in place of the reference's
+ * buildTLAS(MODE_UPDATE) (src/niagara.cpp:1396, :1482).  The mask does not depend on which TLAS is walked.  Not modelled: keyframe evaluation
+ * (src/niagara.cpp:1386-1388: the caller writes the draws), a BLAS rebuild (geometry is static), lights. */
 
 /* shadow.comp.glsl:26-35, src/niagara.cpp:269-278; 96 B (92 used), align 16.  inverseViewProjection is column-major */
 typedef struct NvShadowData
@@ -772,6 +774,32 @@ int nv_rt_scene_upload(nv_context* ctx, void* stream, const void* blob, uint64_t
  * quality outside 0..1, a depth pointer that is not 4-byte aligned. */
 int nv_shadow_trace(nv_context* ctx, void* stream, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width,
                     uint32_t height, int quality);
+
+/* ---- the TLAS rebuilt for moving draws (niagara_amd/csrc/rttlas.h is the definition) ----
+ * The rebuilt TLAS is a function of the blob's BLAS side and the current draw array alone: the instances are the draws that cast by the rule
+ * above (re-derived at every rebuild), each with nv_rt_scene_build's fp64 box; they are ordered by (key, drawId), key the 30-bit Morton code of
+ * the box middles quantised to 1024 cells per axis of the middles' own range; the tree is the binary radix tree of the strings key << 32 | k
+ * over the sorted instances k, laid out in preorder with skip links: 2 n - 1 nodes for n instances, leaf k holds instance k.
+ *
+ * Host twin, no context: a canonical blob (nv_rt_scene_build's section order and packing) whose BLAS table, BLAS nodes and triangles are copied
+ * from `blob` and whose TLAS, instances, padOrigin and drawCount are rebuilt from `draws`.  The size protocol of nv_rt_scene_build.  NV_EINVAL:
+ * a blob nv_rt_scene_validate refuses, a NULL bytes, a NULL array with a non-zero count, too little room, a misaligned out, drawCount above
+ * 2^29 - 1. */
+int nv_rt_tlas_build_host(const void* blob, uint64_t blobBytes, const NvMeshDraw* draws, uint32_t drawCount, void* out, uint64_t* bytes);
+/* Load time, like nv_reserve (allocates and synchronises): re-houses the uploaded scene in one allocation that holds the static blob, room for
+ * 2 maxDraws TLAS nodes and maxDraws instances, and the rebuild's scratch.  The device header keeps pointing at the static TLAS until the first
+ * nv_rt_tlas_build.  NV_EINVAL: no uploaded scene, maxDraws 0 or above 2^29 - 1, an allocation that does not fit the blob's 32-bit offsets
+ * (4 GiB).  A later nv_rt_scene_upload drops the reservation: the scene is static again and nv_rt_tlas_build refuses. */
+int nv_rt_scene_reserve_dynamic(nv_context* ctx, void* stream, uint32_t maxDraws);
+/* Rebuilds the TLAS from d_draws[0, drawCount), read ON THE DEVICE when the launches run.  Only enqueues on `stream` (two memset nodes and
+ * kernel launches; no allocation, no synchronisation, no read-back: it can be captured); the last launch rewrites tlasNodes, instances, tlasOff,
+ * instOff, padOrigin and drawCount of the device header, and nv_shadow_trace calls behind it in stream order walk the new TLAS.  drawCount 0 or
+ * no casting draw: tlasNodes = 0, every ray is lit.  NV_EINVAL with nothing launched: no reservation, drawCount above the reserved maxDraws, a
+ * NULL d_draws with a non-zero count, a d_draws that is not 4-byte aligned. */
+int nv_rt_tlas_build(nv_context* ctx, void* stream, const NvMeshDraw* d_draws, uint32_t drawCount);
+/* Test and tooling accessor (synchronises): the context's current scene as a canonical blob in nv_rt_tlas_build_host's packing, with the size
+ * protocol of nv_rt_scene_build.  NV_EINVAL: no scene, a NULL bytes, a misaligned out, too little room. */
+int nv_rt_scene_download(nv_context* ctx, void* stream, void* out, uint64_t* bytes);
 
 /* ---- host helpers mirroring src/niagara.cpp / src/resources.cpp (no device work) ---- */
 uint32_t nv_previous_pow2(uint32_t v);                        /* src/niagara.cpp:439-447 */

@@ -104,6 +104,10 @@ _SIGS = {
     "nv_rt_scene_trace_host_rays": (_i, [_vp, _vp, _vp, C.c_uint64, _f, _f, _i, _vp]),
     "nv_rt_scene_upload": (_i, [_vp, _vp, _vp, C.c_uint64]),
     "nv_shadow_trace": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _i]),
+    "nv_rt_tlas_build_host": (_i, [_vp, C.c_uint64, _vp, _u32, _vp, C.POINTER(C.c_uint64)]),
+    "nv_rt_scene_reserve_dynamic": (_i, [_vp, _vp, _u32]),
+    "nv_rt_tlas_build": (_i, [_vp, _vp, _vp, _u32]),
+    "nv_rt_scene_download": (_i, [_vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "nv_bloom_desc_init": (_i, [C.POINTER(BloomDesc), _u32, _u32]),
     "nv_bloom_extract": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, C.POINTER(BloomDesc)]),
     "nv_bloom_downsample": (_i, [_vp, _vp, _vp, C.POINTER(BloomDesc), _u32]),

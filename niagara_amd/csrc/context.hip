@@ -17,6 +17,7 @@
 #include "args.h"
 #include "filtermath.h"
 #include "cullform.h"
+#include "rttlas.h"
 
 namespace nv
 {
@@ -66,6 +67,10 @@ int launch_visibility_merge(hipStream_t, unsigned long long* dst, const unsigned
 int launch_rasterindexed(hipStream_t, RasterIndexedArgs a, void* scratch, uint32_t gridBlocks, bool nearClip);
 size_t rasterindexed_scratch_bytes(uint32_t drawCount);
 int launch_meshlet_bounds(hipStream_t, const NvVertex* vertices, const uint32_t* data, NvMeshlet* meshlets, uint32_t count, float* out8, uint32_t gridBlocks);
+uint64_t tlas_plan(uint64_t staticBytes, uint32_t maxDraws, TlasPlan* plan);
+int launch_tlas_build(hipStream_t, void* scene, const TlasPlan& plan, const NvMeshDraw* draws, uint32_t drawCount);
+int rt_pack_blob(const RtHeader& src, const RtBlas* table, const RtNode* tlas, uint32_t tlasNodes, const RtInstance* inst, uint32_t instances,
+                 const RtNode* blas, const RtF4* tris, float padOrigin, uint32_t drawCount, void* out, uint64_t* bytes);
 
 } // namespace nv
 
@@ -159,7 +164,8 @@ struct nv_context
 	uint32_t resolvePerPixel;  // experiments: nv_visibility_resolve without the per-run de-duplication
 	uint32_t attributesPerPixel; // experiments: nv_visibility_attributes without the per-run set-up
 	void* rtScene;               // nv_rt_scene_upload: the device copy of the validated scene blob nv_shadow_trace walks
-	uint64_t rtSceneBytes;
+	uint64_t rtSceneBytes;       // of the static blob (a dynamic reservation's allocation is rtPlan.bytes)
+	nv::TlasPlan rtPlan;         // nv_rt_scene_reserve_dynamic: where the dynamic sections and the rebuild's scratch lie; maxDraws == 0 = static
 };
 
 namespace
@@ -1312,7 +1318,116 @@ int nv_rt_scene_upload(nv_context* ctx, void* stream, const void* blob, uint64_t
 		scratch_free(ctx->rtScene);
 	ctx->rtScene = fresh;
 	ctx->rtSceneBytes = bytes;
+	memset(&ctx->rtPlan, 0, sizeof(ctx->rtPlan)); // static again
 	return NV_OK;
+}
+
+// ---- the TLAS rebuilt on the device (rttlas.hip)
+// Load time: re-houses the device scene in one allocation [static blob][2 maxDraws TLAS nodes][maxDraws instances][scratch].  The header is
+// copied with the blob: it keeps pointing at the static TLAS until the first nv_rt_tlas_build.
+int nv_rt_scene_reserve_dynamic(nv_context* ctx, void* stream, uint32_t maxDraws)
+{
+	if (!ctx || !ctx->rtScene || maxDraws == 0 || maxDraws > nv::RT_LEAF_FIRST)
+		return NV_EINVAL;
+	nv::TlasPlan plan;
+	if (nv::tlas_plan(ctx->rtSceneBytes, maxDraws, &plan) == 0)
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	hipError_t e = hipStreamSynchronize((hipStream_t)stream); // a launch that still reads the old copy
+	if (e != hipSuccess)
+		return (int)e;
+	void* fresh = nullptr;
+	if (scratch_alloc(&fresh, (size_t)plan.bytes) != hipSuccess)
+		return NV_ENOMEM;
+	nv::RtHeader h;
+	e = hipMemcpy(&h, ctx->rtScene, sizeof(h), hipMemcpyDeviceToHost);
+	if (e == hipSuccess && ctx->rtPlan.maxDraws) // reserved before: back to the canonical sections, the current TLAS included
+	{
+		std::vector<unsigned char> blob;
+		uint64_t bytes = 0;
+		int rc = nv_rt_scene_download(ctx, stream, nullptr, &bytes);
+		if (rc == NV_OK)
+		{
+			blob.resize((size_t)bytes + 16u);
+			unsigned char* at = blob.data() + ((16u - (reinterpret_cast<uintptr_t>(blob.data()) & 15u)) & 15u);
+			rc = nv_rt_scene_download(ctx, stream, at, &bytes);
+			if (rc == NV_OK && nv::tlas_plan(bytes, maxDraws, &plan) != 0)
+			{
+				scratch_free(fresh);
+				fresh = nullptr;
+				if (scratch_alloc(&fresh, (size_t)plan.bytes) != hipSuccess)
+					return NV_ENOMEM;
+				e = hipMemcpy(fresh, at, (size_t)bytes, hipMemcpyHostToDevice);
+				ctx->rtSceneBytes = e == hipSuccess ? bytes : ctx->rtSceneBytes;
+			}
+			else
+				rc = rc == NV_OK ? NV_EINVAL : rc;
+		}
+		if (rc != NV_OK)
+		{
+			scratch_free(fresh);
+			return rc;
+		}
+	}
+	else if (e == hipSuccess)
+		e = hipMemcpy(fresh, ctx->rtScene, (size_t)ctx->rtSceneBytes, hipMemcpyDeviceToDevice);
+	if (e != hipSuccess)
+	{
+		scratch_free(fresh);
+		return (int)e;
+	}
+	scratch_free(ctx->rtScene);
+	ctx->rtScene = fresh;
+	ctx->rtPlan = plan;
+	return NV_OK;
+}
+
+// Only enqueues: two memset nodes and the launches of rttlas.hip; the draws are read on the device when the launches run
+int nv_rt_tlas_build(nv_context* ctx, void* stream, const NvMeshDraw* d_draws, uint32_t drawCount)
+{
+	if (!ctx || !ctx->rtScene || ctx->rtPlan.maxDraws == 0 || drawCount > ctx->rtPlan.maxDraws || (drawCount && !d_draws) ||
+	    (reinterpret_cast<uintptr_t>(d_draws) & 3u))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_tlas_build((hipStream_t)stream, ctx->rtScene, ctx->rtPlan, d_draws, drawCount);
+}
+
+// Test and tooling accessor (synchronises): the context's current scene as a canonical blob
+int nv_rt_scene_download(nv_context* ctx, void* stream, void* out, uint64_t* bytes)
+{
+	if (!ctx || !ctx->rtScene || !bytes || (reinterpret_cast<uintptr_t>(out) & 15u))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+	if (e != hipSuccess)
+		return (int)e;
+	const unsigned char* base = static_cast<const unsigned char*>(ctx->rtScene);
+	nv::RtHeader h;
+	if ((e = hipMemcpy(&h, base, sizeof(h), hipMemcpyDeviceToHost)) != hipSuccess)
+		return (int)e;
+	const uint64_t room = ctx->rtPlan.maxDraws ? ctx->rtPlan.bytes : ctx->rtSceneBytes;
+	const uint64_t sizes[5] = { (uint64_t)h.meshCount * sizeof(nv::RtBlas), (uint64_t)h.tlasNodes * sizeof(nv::RtNode), (uint64_t)h.instances * sizeof(nv::RtInstance),
+		                        (uint64_t)h.blasNodes * sizeof(nv::RtNode), (uint64_t)h.triangles * 48u };
+	const uint32_t offs[5] = { h.tableOff, h.tlasOff, h.instOff, h.blasOff, h.triOff };
+	try
+	{
+		std::vector<unsigned char> parts[5];
+		for (int i = 0; i < 5; ++i)
+		{
+			if ((uint64_t)offs[i] + sizes[i] > room)
+				return NV_EINVAL;
+			parts[i].resize((size_t)sizes[i] + 1u);
+			if (sizes[i] && (e = hipMemcpy(parts[i].data(), base + offs[i], (size_t)sizes[i], hipMemcpyDeviceToHost)) != hipSuccess)
+				return (int)e;
+		}
+		return nv::rt_pack_blob(h, reinterpret_cast<const nv::RtBlas*>(parts[0].data()), reinterpret_cast<const nv::RtNode*>(parts[1].data()), h.tlasNodes,
+		                        reinterpret_cast<const nv::RtInstance*>(parts[2].data()), h.instances, reinterpret_cast<const nv::RtNode*>(parts[3].data()),
+		                        reinterpret_cast<const nv::RtF4*>(parts[4].data()), h.padOrigin, h.drawCount, out, bytes);
+	}
+	catch (const std::bad_alloc&)
+	{
+		return NV_ENOMEM;
+	}
 }
 
 int nv_shadow_trace(nv_context* ctx, void* stream, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width, uint32_t height,

@@ -12,6 +12,7 @@
 
 #include "../../include/niagara_vis.h"
 #include "rtmath.h"
+#include "rttlas.h"
 
 namespace
 {
@@ -34,10 +35,7 @@ float half_to_float(uint32_t h) // exact
 	return v;
 }
 
-struct Box
-{
-	float lo[3], hi[3];
-};
+using Box = TlBox; // rttlas.h
 
 Box box_empty()
 {
@@ -142,94 +140,6 @@ void mesh_triangles(const NvMesh& mesh, const uint32_t* indices, uint32_t indexC
 	}
 }
 
-bool draw_casts(const NvMeshDraw& d, uint32_t meshCount)
-{
-	bool finite = rt_finite(d.scale);
-	for (int k = 0; k < 3; ++k)
-		finite = finite && rt_finite(d.position[k]);
-	for (int k = 0; k < 4; ++k)
-		finite = finite && rt_finite(d.orientation[k]);
-	return d.meshIndex < meshCount && finite && d.scale > 0.0f && d.postPass <= 1u;
-}
-
-float round_down(double v)
-{
-	float f = (float)v;
-	return (double)f > v ? nextafterf(f, -INFINITY) : f;
-}
-float round_up(double v)
-{
-	float f = (float)v;
-	return (double)f < v ? nextafterf(f, INFINITY) : f;
-}
-
-// The padded world box of an instance whose BLAS root box is `root` (DESIGN.md §4.16 "the TLAS box").  The object-space ray is
-// L (x - p), L = M / s with M the matrix of rotateQuat(., conj(q)) (any finite q, unit or not), so the instance occupies p + s M^-1 (box).
-// Static padding cB + cO max|p| is added here, the traversal adds padOrigin max|o| with padOrigin >= cO.  An instance whose map is singular
-// or so ill-conditioned that cO would exceed 2^-10 gets the infinite box: it is never rejected.  All of it in fp64, rounded outward.
-Box instance_box(const NvMeshDraw& d, const Box& root, float maxAbs, double* cO_)
-{
-	const Box everything = { { -INFINITY, -INFINITY, -INFINITY }, { INFINITY, INFINITY, INFINITY } };
-	*cO_ = 0.0;
-	const double x = -(double)d.orientation[0], y = -(double)d.orientation[1], z = -(double)d.orientation[2], w = d.orientation[3], s = d.scale;
-	// v + 2 c x (c x v + w v) = (I + 2 (C C + w C)) v, C = [c]x
-	const double C[3][3] = { { 0, -z, y }, { z, 0, -x }, { -y, x, 0 } };
-	double M[3][3];
-	for (int r = 0; r < 3; ++r)
-		for (int c = 0; c < 3; ++c)
-		{
-			double cc = 0;
-			for (int k = 0; k < 3; ++k)
-				cc += C[r][k] * C[k][c];
-			M[r][c] = (r == c ? 1.0 : 0.0) + 2.0 * (cc + w * C[r][c]);
-		}
-	const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
-	                   M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-	if (!(fabs(det) > 0.0) || !(fabs(det) < INFINITY))
-		return everything;
-	double I[3][3];
-	for (int r = 0; r < 3; ++r)
-		for (int c = 0; c < 3; ++c)
-		{
-			const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3; // cofactor of (c, r)
-			I[r][c] = (M[r1][c1] * M[r2][c2] - M[r1][c2] * M[r2][c1]) / det;
-		}
-	double nM = 0, nI = 0; // infinity norms
-	for (int r = 0; r < 3; ++r)
-	{
-		nM = std::max(nM, fabs(M[r][0]) + fabs(M[r][1]) + fabs(M[r][2]));
-		nI = std::max(nI, fabs(I[r][0]) + fabs(I[r][1]) + fabs(I[r][2]));
-	}
-	const double Qa = fabs(x) + fabs(y) + fabs(z), rotAbs = 1.0 + 2.0 * Qa * (Qa + fabs(w)), kappa = nM * nI, u = (double)RT_U, K = (double)RT_PAD_K;
-	const double cO = u * (K * kappa + 16.0 * rotAbs * nI * (1.0 + kappa));
-	const double cB = u * s * (double)maxAbs * nI * (K + 16.0 * rotAbs * nI);
-	if (!(cO <= 0.0009765625) || !(cB < INFINITY))
-		return everything;
-	const double pmax = std::max(std::max(fabs((double)d.position[0]), fabs((double)d.position[1])), fabs((double)d.position[2]));
-	const double pad = (cB + cO * pmax) * 1.0000001;
-	double lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-	for (int corner = 0; corner < 8; ++corner)
-	{
-		const double c[3] = { corner & 1 ? root.hi[0] : root.lo[0], corner & 2 ? root.hi[1] : root.lo[1], corner & 4 ? root.hi[2] : root.lo[2] };
-		for (int r = 0; r < 3; ++r)
-		{
-			const double v = (double)d.position[r] + s * ((I[r][0] * c[0] + I[r][1] * c[1]) + I[r][2] * c[2]);
-			lo[r] = std::min(lo[r], v);
-			hi[r] = std::max(hi[r], v);
-		}
-	}
-	Box b;
-	for (int r = 0; r < 3; ++r)
-	{
-		// the fp64 evaluation above errs by a few 2^-53 of its terms: far inside the padding's slack (RT_PAD_K is > 2 x what the analysis needs)
-		b.lo[r] = round_down(lo[r] - pad), b.hi[r] = round_up(hi[r] + pad);
-		if (!(b.lo[r] <= b.hi[r])) // NaN
-			return everything;
-	}
-	*cO_ = cO;
-	return b;
-}
-
 uint64_t align16(uint64_t v) { return (v + 15u) & ~(uint64_t)15u; }
 
 const RtHeader* checked_header(const void* blob, uint64_t bytes)
@@ -251,6 +161,90 @@ const RtHeader* checked_header(const void* blob, uint64_t bytes)
 		at = (uint64_t)offs[i] + sizes[i];
 	}
 	return h;
+}
+
+} // namespace
+
+namespace nv
+{
+
+// The canonical blob — nv_rt_scene_build's section order and packing — from its parts: the BLAS side as `src` describes it, a TLAS and its
+// instances.  The size protocol of nv_rt_scene_build.  nv_rt_tlas_build_host and nv_rt_scene_download (context.hip) end here, so that a host
+// and a device rebuild compare with == on bytes.
+int rt_pack_blob(const RtHeader& src, const RtBlas* table, const RtNode* tlas, uint32_t tlasNodes, const RtInstance* inst, uint32_t instances,
+                 const RtNode* blas, const RtF4* tris, float padOrigin, uint32_t drawCount, void* out, uint64_t* bytes)
+{
+	RtHeader h;
+	memset(&h, 0, sizeof(h));
+	h.magic = RT_MAGIC, h.version = RT_VERSION;
+	h.meshCount = src.meshCount, h.tlasNodes = tlasNodes, h.instances = instances;
+	h.blasNodes = src.blasNodes, h.triangles = src.triangles, h.drawCount = drawCount;
+	h.padOrigin = padOrigin;
+	const uint64_t sizes[5] = { (uint64_t)h.meshCount * sizeof(RtBlas), (uint64_t)tlasNodes * sizeof(RtNode), (uint64_t)instances * sizeof(RtInstance),
+		                        (uint64_t)h.blasNodes * sizeof(RtNode), (uint64_t)h.triangles * 48u };
+	const void* parts[5] = { table, tlas, inst, blas, tris };
+	uint64_t offs[5], at = sizeof(RtHeader);
+	for (int i = 0; i < 5; ++i)
+	{
+		offs[i] = at;
+		at = align16(at + sizes[i]);
+	}
+	if (at > 0xffffffffull)
+		return NV_EINVAL;
+	h.tableOff = (uint32_t)offs[0], h.tlasOff = (uint32_t)offs[1], h.instOff = (uint32_t)offs[2], h.blasOff = (uint32_t)offs[3], h.triOff = (uint32_t)offs[4];
+	h.bytes = (uint32_t)at;
+	if (!out)
+	{
+		*bytes = at;
+		return NV_OK;
+	}
+	if (*bytes < at)
+		return NV_EINVAL;
+	unsigned char* p = static_cast<unsigned char*>(out);
+	memset(p, 0, (size_t)at);
+	memcpy(p, &h, sizeof(h));
+	for (int i = 0; i < 5; ++i)
+		if (sizes[i])
+			memcpy(p + offs[i], parts[i], (size_t)sizes[i]);
+	*bytes = at;
+	return NV_OK;
+}
+
+} // namespace nv
+
+namespace
+{
+
+// The tree of rttlas.h by plain recursion: the sorted range [l, r] splits in front of the first string whose highest differing bit is set.
+// (The device finds every inner node's range on its own from the neighbouring strings: a different algorithm for the same, unique tree.)
+void tlas_emit(std::vector<RtNode>& nodes, const std::vector<uint64_t>& strings, const std::vector<Box>& leaves, uint32_t l, uint32_t r, uint32_t lefts)
+{
+	const uint32_t pos = tl_pos(l, lefts);
+	RtNode& n = nodes[pos];
+	n.skip = tl_skip(pos, l, r);
+	if (l == r)
+	{
+		for (int k = 0; k < 3; ++k)
+			n.lo[k] = leaves[l].lo[k], n.hi[k] = leaves[l].hi[k];
+		n.leaf = 1u << RT_LEAF_SHIFT | l;
+		return;
+	}
+	const uint64_t bit = 1ull << (63 - __builtin_clzll(strings[l] ^ strings[r]));
+	uint32_t a = l, b = r; // strings[a] has the bit clear, strings[b] has it set
+	while (b - a > 1u)
+	{
+		const uint32_t m = a + (b - a) / 2u;
+		if (strings[m] & bit)
+			b = m;
+		else
+			a = m;
+	}
+	tlas_emit(nodes, strings, leaves, l, b - 1u, lefts + 1u);
+	tlas_emit(nodes, strings, leaves, b, r, lefts);
+	const RtNode &cl = nodes[pos + 1u], &cr = nodes[tl_pos(b, lefts)];
+	for (int k = 0; k < 3; ++k)
+		n.lo[k] = tl_fmin(cl.lo[k], cr.lo[k]), n.hi[k] = tl_fmax(cl.hi[k], cr.hi[k]);
+	n.leaf = 0u;
 }
 
 } // namespace
@@ -319,16 +313,11 @@ int nv_rt_scene_build(const NvMesh* meshes, uint32_t meshCount, const uint32_t* 
 		for (uint32_t i = 0; i < drawCount; ++i)
 		{
 			const NvMeshDraw& d = draws[i];
-			if (!draw_casts(d, meshCount) || table[d.meshIndex].nodeCount == 0)
+			if (!tl_draw_casts(d, meshCount) || table[d.meshIndex].nodeCount == 0)
 				continue;
-			RtInstance in;
-			memset(&in, 0, sizeof(in));
-			memcpy(in.position, d.position, 12);
-			in.scale = d.scale;
-			memcpy(in.orientation, d.orientation, 16);
-			in.drawId = i, in.postPass = d.postPass, in.blas = d.meshIndex;
+			const RtInstance in = tl_instance(d, i);
 			double cO;
-			boxes.push_back(instance_box(d, roots[d.meshIndex], table[d.meshIndex].maxAbs, &cO));
+			boxes.push_back(tl_instance_box(d, roots[d.meshIndex], table[d.meshIndex].maxAbs, &cO));
 			cOmax = cO > cOmax ? cO : cOmax;
 			instances.push_back(in);
 		}
@@ -345,7 +334,7 @@ int nv_rt_scene_build(const NvMesh* meshes, uint32_t meshCount, const uint32_t* 
 		h.magic = RT_MAGIC, h.version = RT_VERSION;
 		h.meshCount = meshCount, h.tlasNodes = (uint32_t)tlasNodes.size(), h.instances = (uint32_t)instances.size();
 		h.blasNodes = (uint32_t)blasNodes.size(), h.triangles = (uint32_t)(tris.size() / 3u), h.drawCount = drawCount;
-		h.padOrigin = round_up(cOmax * 1.0000001);
+		h.padOrigin = tl_pad_origin(cOmax);
 		uint64_t at = sizeof(RtHeader);
 		const uint64_t tableOff = at;
 		at = align16(at + table.size() * sizeof(RtBlas));
@@ -423,6 +412,69 @@ int nv_rt_scene_validate(const void* blob, uint64_t bytes)
 		}
 	}
 	return NV_OK;
+}
+
+int nv_rt_tlas_build_host(const void* blob, uint64_t blobBytes, const NvMeshDraw* draws, uint32_t drawCount, void* out, uint64_t* bytes)
+{
+	if (!bytes || (drawCount && !draws) || (reinterpret_cast<uintptr_t>(out) & 15u) || drawCount > RT_LEAF_FIRST ||
+	    nv_rt_scene_validate(blob, blobBytes) != NV_OK)
+		return NV_EINVAL;
+	try
+	{
+		const RtHeader* h = static_cast<const RtHeader*>(blob);
+		const unsigned char* p = static_cast<const unsigned char*>(blob);
+		const RtBlas* table = reinterpret_cast<const RtBlas*>(p + h->tableOff);
+		const RtNode* blas = reinterpret_cast<const RtNode*>(p + h->blasOff);
+		struct Caster
+		{
+			uint32_t key, draw;
+			Box box;
+		};
+		std::vector<Caster> casters;
+		double cOmax = 0.0;
+		float midLo[3] = { INFINITY, INFINITY, INFINITY }, midHi[3] = { -INFINITY, -INFINITY, -INFINITY };
+		for (uint32_t i = 0; i < drawCount; ++i)
+		{
+			const NvMeshDraw& d = draws[i];
+			if (!tl_draw_casts(d, h->meshCount) || table[d.meshIndex].nodeCount == 0)
+				continue;
+			const RtNode& rn = blas[table[d.meshIndex].nodeFirst];
+			const Box root = { { rn.lo[0], rn.lo[1], rn.lo[2] }, { rn.hi[0], rn.hi[1], rn.hi[2] } };
+			double cO;
+			Caster c;
+			c.key = 0u, c.draw = i;
+			c.box = tl_instance_box(d, root, table[d.meshIndex].maxAbs, &cO);
+			cOmax = cO > cOmax ? cO : cOmax;
+			for (int k = 0; k < 3; ++k)
+			{
+				const float m = tl_mid(c.box.lo[k], c.box.hi[k]);
+				midLo[k] = tl_fmin(midLo[k], m), midHi[k] = tl_fmax(midHi[k], m);
+			}
+			casters.push_back(c);
+		}
+		for (Caster& c : casters)
+			c.key = tl_key(c.box, midLo, midHi);
+		std::stable_sort(casters.begin(), casters.end(), [](const Caster& a, const Caster& b) { return a.key < b.key; }); // (key, drawId)
+		const uint32_t n = (uint32_t)casters.size();
+		std::vector<RtNode> nodes(n ? 2u * (size_t)n - 1u : 0u);
+		std::vector<RtInstance> instances(n);
+		std::vector<uint64_t> strings(n);
+		std::vector<Box> leaves(n);
+		for (uint32_t k = 0; k < n; ++k)
+		{
+			strings[k] = tl_string(casters[k].key, k);
+			leaves[k] = casters[k].box;
+			instances[k] = tl_instance(draws[casters[k].draw], casters[k].draw);
+		}
+		if (n)
+			tlas_emit(nodes, strings, leaves, 0u, n - 1u, 0u);
+		return rt_pack_blob(*h, table, nodes.data(), (uint32_t)nodes.size(), instances.data(), n, blas, reinterpret_cast<const RtF4*>(p + h->triOff),
+		                    tl_pad_origin(cOmax), drawCount, out, bytes);
+	}
+	catch (const std::bad_alloc&)
+	{
+		return NV_ENOMEM;
+	}
 }
 
 int nv_rt_scene_stats(const void* blob, uint64_t bytes, NvRtSceneStats* out)

@@ -97,6 +97,27 @@ def rt_scene_build(meshes, indices, vertices, draws):
     return blob
 
 
+def _aligned_bytes(n):
+    """a zeroed uint8 array of n bytes whose data is 16-byte aligned"""
+    raw = np.zeros(n + 16, np.uint8)
+    off = (-raw.ctypes.data) % 16
+    return raw[off:off + n]
+
+
+def rt_tlas_build_host(blob, draws):
+    """The host twin of nv_rt_tlas_build (nv_rt_tlas_build_host; no device work): a canonical blob with `blob`'s BLAS side and the TLAS of
+    DESIGN.md §4.17 over the casting draws of `draws`.  Returns a 16-byte aligned uint8 array"""
+    d = np.ascontiguousarray(draws, L.MESHDRAW)
+    args = (_p(blob), blob.nbytes, _p(d) if len(d) else None, len(d))
+    n = C.c_uint64(0)
+    check(lib.nv_rt_tlas_build_host(*args, None, C.byref(n)), "nv_rt_tlas_build_host")
+    out = _aligned_bytes(n.value)
+    room = C.c_uint64(n.value)
+    check(lib.nv_rt_tlas_build_host(*args, _p(out), C.byref(room)), "nv_rt_tlas_build_host")
+    assert room.value == n.value
+    return out
+
+
 def rt_scene_validate(blob):
     """True when nv_rt_scene_validate accepts the blob (a uint8 array whose data is 16-byte aligned)"""
     return lib.nv_rt_scene_validate(_p(blob), blob.nbytes) == 0

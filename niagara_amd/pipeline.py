@@ -242,6 +242,26 @@ class Context:
         else:
             check(lib.nv_rt_scene_upload(self.h, _stream(), C.c_void_p(blob.ctypes.data), blob.nbytes), "nv_rt_scene_upload")
 
+    def rt_scene_reserve_dynamic(self, max_draws):
+        """room for a TLAS over up to max_draws draws and the rebuild's scratch behind the uploaded scene (nv_rt_scene_reserve_dynamic: load
+        time, allocates and synchronises); a later rt_scene_upload drops it"""
+        check(lib.nv_rt_scene_reserve_dynamic(self.h, _stream(), int(max_draws)), "nv_rt_scene_reserve_dynamic")
+
+    def rt_tlas_build(self, draws_device, count):
+        """rebuild the TLAS of the reserved scene from the first `count` MeshDraw records of the device buffer, read when the launches run
+        (nv_rt_tlas_build: only enqueues, can be captured); shadow_trace calls behind it walk the new TLAS"""
+        check(lib.nv_rt_tlas_build(self.h, _stream(), _ptr(draws_device), int(count)), "nv_rt_tlas_build")
+
+    def rt_scene_download(self):
+        """the context's current scene as a canonical blob, a 16-byte aligned uint8 array (nv_rt_scene_download: synchronises; tests, tools)"""
+        n = C.c_uint64(0)
+        check(lib.nv_rt_scene_download(self.h, _stream(), None, C.byref(n)), "nv_rt_scene_download")
+        out = host._aligned_bytes(n.value)
+        room = C.c_uint64(n.value)
+        check(lib.nv_rt_scene_download(self.h, _stream(), C.c_void_p(out.ctypes.data), C.byref(room)), "nv_rt_scene_download")
+        assert room.value == n.value
+        return out
+
     def shadow_trace(self, shadow_data, depth, shadow, width, height, quality=1):
         """shadow.comp.glsl (nv_shadow_trace): the u8 sun shadow mask (0 = in shadow, 255 = lit) of the depth target from the uploaded scene;
         with shadow_data["checkerboard"] > 0 only one parity of the texels is written (shadow_fill fills the other)"""
@@ -377,10 +397,12 @@ class VisibilityPipeline:
                 self.ctx.upload_meshlets(self.mlb, self.meshlet_count)
             if use_soa and self.draw_count:
                 self.ctx.upload_draws(self.db, self.draw_count, self.mb)
+        self.draws_mirrored = share is None and bool(use_soa) and self.draw_count > 0  # move_draws keeps the mirror in step
         # geometry (meshlet payloads and / or the index buffer ib, + vertices, src/scene.cpp:24-47): with it the pipeline rasterises its own
         # depth target, through the clusters (meshlet_data) or through the indexed draws of the classic path (indices)
         self.mdb = self.vb = self.ib = self.depth = None
         self.bloom_image = self.bloom_desc = None  # shade(bloom=True)'s target, allocated on first use
+        self.rt_dynamic = False                    # build_rt_scene(dynamic=True): move_draws rebuilds the TLAS
         self.rt_scene = self.shadow_image = None   # build_rt_scene's blob; shade(shadow="trace")'s mask, allocated on first use
         self.index_count = self.vertex_count = 0
         if vertices is not None and (meshlet_data is not None or indices is not None):
@@ -498,13 +520,42 @@ class VisibilityPipeline:
                                        out["attributes"], out["gbuffer0"], out["gbuffer1"], out["totals"])
         return out
 
-    def build_rt_scene(self, meshes, indices, vertices, draws):
+    def build_rt_scene(self, meshes, indices, vertices, draws, dynamic=False):
         """build the ray-tracing scene of shade(shadow="trace") on the host and upload it, once per scene (niagara builds its BLAS / TLAS at
         load time, src/scenert.cpp): `meshes` with their LODs' index ranges set (synth.indexed_geometry) and the index buffer of the classic
-        path.  The scene is static: call again when draws move.  Returns the blob"""
+        path.  The scene is static: call again when draws move — or pass dynamic=True, which reserves room for a TLAS over the pipeline's
+        draw count (nv_rt_scene_reserve_dynamic), and move the draws through move_draws, which rebuilds the TLAS on the device.  Returns the
+        blob"""
         self.rt_scene = self.ctx.rt_scene_build(meshes, indices, vertices, draws)
         self.ctx.rt_scene_upload(self.rt_scene)
+        if dynamic and isinstance(self, ShardedVisibilityPipeline):
+            raise NvError("build_rt_scene(dynamic=True) is not available on a sharded pipeline")
+        self.rt_dynamic = bool(dynamic) and self.draw_count > 0
+        if self.rt_dynamic:
+            self.ctx.rt_scene_reserve_dynamic(self.draw_count)
         return self.rt_scene
+
+    def move_draws(self, first, records):
+        """the animation path (src/niagara.cpp:1385-1400, :1482): copies `records` (layouts.MESHDRAW; the caller evaluates its keyframes) over
+        the draws [first, first + len(records)) of the device draw buffer, keeping the pipeline's own visibility slots, re-evaluates the cull
+        mirror (nv_update_draws) and, with a dynamic ray-tracing scene, rebuilds its TLAS from the whole draw buffer (nv_rt_tlas_build).  All
+        in stream order: the next frame() and shade(shadow="trace") see the moved draws"""
+        rec = np.ascontiguousarray(records, L.MESHDRAW).copy()
+        first = int(first)
+        if first < 0 or first + len(rec) > self.draw_count:
+            raise NvError("move_draws: [%d, %d) is outside the pipeline's %d draws" % (first, first + len(rec), self.draw_count))
+        if isinstance(self, ShardedVisibilityPipeline):
+            raise NvError("move_draws is not available on a sharded pipeline")
+        if len(rec) == 0:
+            return
+        rec["meshletVisibilityOffset"] = self.draws_host["meshletVisibilityOffset"][first:first + len(rec)]
+        self.draws_host[first:first + len(rec)] = rec
+        size = L.MESHDRAW.itemsize
+        self.db.view(torch.uint8).reshape(-1)[first * size:(first + len(rec)) * size].copy_(to_device(rec, self.ctx.device).view(torch.uint8).reshape(-1))
+        if self.draws_mirrored:
+            self.ctx.update_draws(self.db, first, len(rec))
+        if getattr(self, "rt_dynamic", False):
+            self.ctx.rt_tlas_build(self.db, self.draw_count)
 
     def shade(self, cull_data, gbuffer0, gbuffer1, camera_position, sun_direction, shadow=None, blur=True, checkerboard=False, bloom=False, quality=1):
         """the shading end of the frame over attributes()'s G-buffer words and the pipeline's own depth target (src/niagara.cpp:1792-1850,
@@ -602,7 +653,10 @@ class ShardedVisibilityPipeline(VisibilityPipeline):
     them each rank drops its own tail).  With stable_ids=True frame(visibility=) also composites the visibility target (unsigned 64-bit
     maximum: every rank writes the same word for the same sample, so the composite is the unsharded buffer) and resolve() on any rank
     returns the unsharded frame's records with the scene's draw ids; without it the slot index of the word is rank-local and a
-    visibility target is refused."""
+    visibility target is refused.
+
+    Out of scope here: moving draws.  move_draws and build_rt_scene(dynamic=True) (the TLAS rebuilt on the device) are
+    refused on a sharded pipeline: the ranks' draw buffers and mirrors would have to move together."""
 
     def __init__(self, meshes, meshlets, draws, depth_size, rank=0, world=1, draw_range=None, weight="draws", group=None, **kw):
         from . import shard

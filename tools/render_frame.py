@@ -6,6 +6,7 @@
     python3 tools/render_frame.py --no-shadow --viewport 1920x1080
     python3 tools/render_frame.py --bloom                               # two materials emit; the bloom chain and final's bloom term
     python3 tools/render_frame.py --traced-shadows                      # the mask is ray traced (nv_shadow_trace)
+    python3 tools/render_frame.py --traced-shadows --animate 8          # 8 images, one box on a circle: its shadow follows (§4.17)
 
 Writes a binary PPM (P6, R G B from the R8G8B8A8 colour words) and prints one JSON line with the passes' times by HIP events (one run
 each after a warm-up frame: launch gaps included, an upper bound of the kernel time; profiles/r13_shade.md has the kernel trace).
@@ -194,6 +195,8 @@ def main():
     ap.add_argument("--bloom", action="store_true", help="two materials emit; run the bloom chain and final's bloom term")
     ap.add_argument("--traced-shadows", action="store_true", help="ray trace the shadow mask (the default stays the synthetic mask)")
     ap.add_argument("--quality", type=int, default=1, help="--traced-shadows: 0 = opaque draws cast, 1 = post-pass draws too")
+    ap.add_argument("--animate", type=int, default=0, help="--traced-shadows: write N images (out_000.ppm ...) with one draw displaced along a circle "
+                    "per frame through move_draws, which rebuilds the TLAS on the device")
     ap.add_argument("--passes", default=None, help="WxH[,WxH...], or shadow_trace (with --traced-shadows)")
     ap.add_argument("--repeats", type=int, default=9)
     args = ap.parse_args()
@@ -236,7 +239,7 @@ def main():
     sun = np.array([0.35, 0.6, 0.72]) / np.linalg.norm([0.35, 0.6, 0.72])
     mat = P.to_device(materials, pipe.ctx.device)
     if args.traced_shadows and not args.no_shadow:
-        pipe.build_rt_scene(s["meshes"], s["indices"], v, draws)
+        pipe.build_rt_scene(s["meshes"], s["indices"], v, draws, dynamic=args.animate > 0)
 
     def frame(events):
         vis = pipe.new_visibility()
@@ -246,19 +249,41 @@ def main():
         shadow = None if args.no_shadow else "trace" if args.traced_shadows else torch.from_numpy(mask.copy()).to(pipe.ctx.device)
         return _timed(events, "shade", lambda: pipe.shade(s["cull"], att["gbuffer0"], att["gbuffer1"], (0.0, 0.0, 0.0), sun, shadow=shadow,
                                                           checkerboard=args.checkerboard, bloom=args.bloom, quality=args.quality))
+    def write(path, color, events, extra):
+        words = color.cpu().numpy().view(np.uint32)
+        rgb = np.stack([(words >> np.uint32(8 * k)) & np.uint32(255) for k in range(3)], -1).astype(np.uint8)
+        with open(path, "wb") as f:
+            f.write(b"P6\n%d %d\n255\n" % (w, h))
+            f.write(rgb.tobytes())
+        print(json.dumps(dict(out=path, viewport=[w, h], shadow=not args.no_shadow, traced=bool(args.traced_shadows and not args.no_shadow), bloom=args.bloom,
+                              covered=int((pipe.depth > 0).sum().item()), mean_rgb=[round(float(c), 2) for c in rgb.reshape(-1, 3).mean(0)],
+                              us={name: round(a.elapsed_time(b) * 1e3, 1) for name, a, b in events}, **extra)))
     frame([])  # warm-up (and the visibility bits of the closed loop)
+    if args.animate > 0:
+        if not (args.traced_shadows and not args.no_shadow):
+            ap.error("--animate moves a draw under the traced shadows: give --traced-shadows")
+        which = s["beside"][0]  # a box next to the wall, carried around the wall's edge: its shadow crosses the boxes behind
+        home = draws[which:which + 1].copy()
+        stem, ext = os.path.splitext(args.out)
+        for k in range(args.animate):
+            a = 2.0 * np.pi * k / args.animate
+            rec = home.copy()
+            rec["position"][0] = home["position"][0] + np.array([6.0 * np.cos(a) - 6.0, 6.0 * np.sin(a), 0.0], np.float32)
+            events = []
+            _timed(events, "move_draws", lambda: pipe.move_draws(which, rec))
+            frame(events)  # the closed loop's visibility bits follow the move one frame late, as niagara's do
+            color = frame(events)
+            torch.cuda.synchronize()
+            pipe.ctx.status()
+            write("%s_%03d%s" % (stem, k, ext), color, events, dict(moved_draw=int(which), position=[round(float(c), 3) for c in rec["position"][0]],
+                                                                     shadowed=int((pipe.shadow_image == 0).sum().item())))
+        pipe.ctx.close()
+        return
     events = []
     color = frame(events)
     torch.cuda.synchronize()
     pipe.ctx.status()
-    words = color.cpu().numpy().view(np.uint32)
-    rgb = np.stack([(words >> np.uint32(8 * k)) & np.uint32(255) for k in range(3)], -1).astype(np.uint8)
-    with open(args.out, "wb") as f:
-        f.write(b"P6\n%d %d\n255\n" % (w, h))
-        f.write(rgb.tobytes())
-    print(json.dumps(dict(out=args.out, viewport=[w, h], shadow=not args.no_shadow, traced=bool(args.traced_shadows and not args.no_shadow), bloom=args.bloom, covered=int((pipe.depth > 0).sum().item()),
-                          mean_rgb=[round(float(c), 2) for c in rgb.reshape(-1, 3).mean(0)],
-                          us={name: round(a.elapsed_time(b) * 1e3, 1) for name, a, b in events})))
+    write(args.out, color, events, {})
     pipe.ctx.close()
 
 
