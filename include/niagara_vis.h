@@ -595,8 +595,8 @@ typedef struct NvPixelAttributes
  * (vertices with w <= 0 of a near-clipped triangle need no special case), and every varying is (l0 a0 + l1 a1) + l2 a2.  A pixel whose s is 0
  * or whose lambdas are not all finite is DEGENERATE: lambda = (1, 0, 0), counted.  The lambdas are not clamped: the rasteriser covers by
  * positions snapped to 1/256 pixel, so a lambda of a covered pixel can be slightly negative.  With d_materials the fragment stage
- * (mesh.frag.glsl:57-89) is evaluated from the material's factors — the library samples no textures; a material with a texture index > 0 is
- * shaded from its factors and its pixels are counted — and packed: d_gbuffer0 R8G8B8A8_UNORM {tosrgb(albedo).rgb, log2(1 + emissivef) / 5},
+ * (mesh.frag.glsl:57-89) is evaluated from the material's factors — this entry point samples no textures (nv_visibility_attributes_textured
+ * does); a material with a texture index > 0 is shaded from its factors and its pixels are counted — and packed: d_gbuffer0 R8G8B8A8_UNORM {tosrgb(albedo).rgb, log2(1 + emissivef) / 5},
  * d_gbuffer1 A2B10G10R10_UNORM_PACK32 {encodeOct(nrm) * 0.5 + 0.5 + deband * (0.5 / 1023), specgloss.a, 0} (src/niagara.cpp:634-637), UNORM =
  * clamp to [0, 1] with NaN -> 0, times 2^bits - 1, rounded half to even.  The POST alpha discard (:88) is coverage and is not modelled.
  * Every fp32 operation is one IEEE operation in a fixed order; pow and log2 (gbuffer0 only) are the device's.
@@ -615,6 +615,90 @@ int nv_visibility_attributes(nv_context* ctx, void* stream, const NvGlobals* glo
                              const uint32_t* d_meshletData, uint32_t meshletDataWords, const NvVertex* d_vertices, uint32_t vertexCount,
                              const NvMaterial* d_materials /* optional */, uint32_t materialCount, NvPixelAttributes* d_attributes /* optional */,
                              uint32_t* d_gbuffer0 /* optional */, uint32_t* d_gbuffer1 /* optional */, uint64_t* d_totals4 /* optional */);
+
+/* ---- material textures (replaces binding 8 `textureSampler` and set 1 `textures[]` of mesh.frag.glsl) ----
+ * CDNA has no texture unit a HIP kernel can use: the library reads niagara's DDS files, decodes their BC blocks to RGBA8 once at load time
+ * and samples the decoded mip chains in software.  The caller owns every buffer.
+ *
+ * nv_dds_parse restates loadImage's accept / reject rules (src/textures.cpp:159-210) on a file image in memory: the magic "DDS ", a 124-byte
+ * header with a 32-byte pixel format, the DX10 header when the FourCC says so, no cube map and no volume, a DX10 resourceDimension of
+ * TEXTURE2D, the FourCC / DXGI table of getFormat (:82-127), and a payload of EXACTLY getImageSizeBC(width, height, mipCount, blockSize) bytes
+ * with nothing behind it (level l is max(1, w >> l) x max(1, h >> l), partial blocks round up).  NV_EFORMAT otherwise (also: width, height or
+ * the mip count 0, a side above 16384, more than NV_TEXTURE_MAX_LEVELS levels — shapes the library's own arithmetic excludes).  Host only. */
+#define NV_TEXTURE_MAX_LEVELS 15
+#define NV_ETEXFORMAT (-7) /* a well-formed texture in a format the library does not decode (BC4, BC5, BC6H) */
+enum
+{
+	NV_FORMAT_BC1 = 1,
+	NV_FORMAT_BC2 = 2,
+	NV_FORMAT_BC3 = 3,
+	NV_FORMAT_BC4 = 4, /* parses; refused by nv_texture_set_layout and the decoders with NV_ETEXFORMAT */
+	NV_FORMAT_BC5 = 5, /* as BC4 */
+	NV_FORMAT_BC6H = 6, /* as BC4 */
+	NV_FORMAT_BC7 = 7
+};
+typedef struct NvDdsInfo
+{
+	uint32_t format;    /* NV_FORMAT_* */
+	uint32_t width, height, levels;
+	uint32_t blockBytes; /* 8: BC1, BC4; 16: the rest */
+	uint32_t payloadOffset; /* of level 0's first block in the file: 128, or 148 with a DX10 header */
+	uint64_t payloadBytes;
+	uint64_t levelOffset[NV_TEXTURE_MAX_LEVELS]; /* byte offset of each level's blocks FROM payloadOffset; entries past `levels` are 0 */
+} NvDdsInfo;
+int nv_dds_parse(const void* bytes, uint64_t size, NvDdsInfo* out);
+
+/* One decoded texture: its RGBA8 levels (R in the low byte; UNORM, never SRGB — getFormat, textures.cpp:82-127) lie one after the other, each
+ * row-major without padding, from word `offset` of the set's texel buffer.  16 bytes, fixed (niagara_amd/layouts.py TEXTUREDESC). */
+typedef struct NvTextureDesc
+{
+	uint32_t offset; /* in 32-bit words */
+	uint32_t width, height, levels;
+} NvTextureDesc;
+
+/* nv_texture_set_layout: a pure function that places `count` textures in one linear buffer.  descs has count + 1 entries: entry 0 is the
+ * reserved "no texture" entry (all zero; textures[id] binds texturePaths[id - 1], src/niagara.cpp:934), entry i + 1 belongs to infos[i].
+ * *texelWords = the words the caller allocates.  NV_ETEXFORMAT: a BC4 / BC5 / BC6H texture; NV_EINVAL: a NULL pointer, a shape nv_dds_parse
+ * would not report, or a total of 2^32 words or more. */
+int nv_texture_set_layout(const NvDdsInfo* infos, uint32_t count, NvTextureDesc* descs, uint64_t* texelWords);
+
+/* the decode of one texture's levels on the CPU (csrc/texmath.h, the text the kernel runs): blocks = the file's payload (info->payloadBytes
+ * bytes), texels = the set's buffer (texelWords words), written at desc->offset.  NV_EINVAL when desc and info disagree or the chain does not
+ * fit texelWords; NV_ETEXFORMAT as above. */
+int nv_texture_decode_host(const NvDdsInfo* info, const void* blocks, const NvTextureDesc* desc, uint32_t* texels, uint64_t texelWords);
+
+/* nv_texture_decode: the same on the device, every level in one launch (d_blocks: the payload, 8-byte aligned; d_texels + desc->offset .. :
+ * width x height x levels chain).  A work item decodes one row of a block and stores it cropped at the level's right and bottom edges, so
+ * nothing past a level's last texel is written; the caller's buffer holds desc->offset + the chain's words (nv_texture_set_layout).  desc is
+ * read on the host.  Only enqueued work: capturable.  NV_EINVAL: a NULL or misaligned pointer, a shape nv_dds_parse would not report, desc
+ * not of this shape; NV_ETEXFORMAT as the host function. */
+int nv_texture_decode(nv_context* ctx, void* stream, const void* d_blocks, uint32_t format, uint32_t width, uint32_t height, uint32_t levels,
+                      uint32_t* d_texels, const NvTextureDesc* desc);
+
+/* one sample of textures[id] on the CPU, the sampler of §4.18 (`textureSampler`: LINEAR / LINEAR / mipmap LINEAR, REPEAT, lod 0..16, no
+ * anisotropy): uv, and its derivatives per pixel step in x and y (the level of detail is the Vulkan isotropic rule).  out_rgba: four floats.
+ * NV_EINVAL: id == 0 or >= textureCount (descs has textureCount entries, entry 0 reserved), or a descriptor whose chain does not lie inside
+ * texelWords.  No index reaches a load out of range for ANY bit pattern of uv and the derivatives. */
+int nv_texture_sample_host(const NvTextureDesc* descs, uint32_t textureCount, const uint32_t* texels, uint64_t texelWords, uint32_t id,
+                           const float uv[2], const float duvdx[2], const float duvdy[2], float out_rgba[4]);
+
+/* nv_visibility_attributes_textured: nv_visibility_attributes with the COMPLETE fragment stage (mesh.frag.glsl:57-89): albedo, specgloss
+ * and emissive times fromsrgb(texture(...)), nmap = texture(...).rgb * 2 - 1 through tangent, bitangent and normal.  All arguments, outputs,
+ * rules and errors of nv_visibility_attributes hold; d_materials is required.  d_textures: textureCount descriptors (entry 0 reserved),
+ * d_texels: the decoded set, texelWords words.  The derivatives are analytic: the triangle's barycentrics are evaluated again at the
+ * centres of (px + 1, py) and (px, py + 1) (nothing is loaded there; a degenerate neighbour contributes a zero difference).  Before any
+ * texel load the index is checked against textureCount and the descriptor's whole chain against texelWords; a texture that fails is treated
+ * as absent and the pixel is counted in d_totals4[3], which keeps its meaning — pixels whose material names a texture the pass did not
+ * sample — and is 0 on a complete set.  With d_textures NULL (textureCount 0) the outputs equal nv_visibility_attributes' bit for bit.
+ * One launch, capturable.  NV_EINVAL also: d_materials NULL, textureCount > 0 with d_textures or d_texels NULL, a misaligned d_textures
+ * (16) or d_texels (4). */
+int nv_visibility_attributes_textured(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisRecord* d_records, uint32_t width,
+                                      uint32_t height, const NvMeshDraw* d_draws, uint32_t drawCount, const NvMeshlet* d_meshlets,
+                                      uint32_t meshletCount, const uint32_t* d_meshletData, uint32_t meshletDataWords, const NvVertex* d_vertices,
+                                      uint32_t vertexCount, const NvMaterial* d_materials, uint32_t materialCount,
+                                      NvPixelAttributes* d_attributes /* optional */, uint32_t* d_gbuffer0 /* optional */,
+                                      uint32_t* d_gbuffer1 /* optional */, uint64_t* d_totals4 /* optional */, const NvTextureDesc* d_textures,
+                                      uint32_t textureCount, const uint32_t* d_texels, uint64_t texelWords);
 
 /* ---- the shading end of the frame (replaces shadowfill.comp.glsl, shadowblur.comp.glsl and final.comp.glsl) ----
  * Three of niagara's compute passes behind the G-buffer.  All images are linear buffers with row 0 at the top, as the raster target is:
@@ -720,7 +804,7 @@ int nv_shade_final_bloom(nv_context* ctx, void* stream, const NvShadeData* shade
  * the fp16 position converted to fp32; a triangle with an index position >= indexCapacity or a corner >= vertexCapacity is left out
  * (nv_rasterdepth_indexed's rule).  The ray is taken into object space with t preserved: o' = rotateQuat(o - position, conj(q)) / scale,
  * d' = rotateQuat(d, conj(q)) / scale.
- * NOT MODELLED: the library samples no textures, so the alpha test of shadow.comp.glsl:115-120 (quality 1) sees alpha = 1 and a post-pass
+ * NOT MODELLED: the trace samples no textures yet (tx_sample_lod0 of csrc/texmath.h, DESIGN.md §4.18, is its sampler), so the alpha test of shadow.comp.glsl:115-120 (quality 1) sees alpha = 1 and a post-pass
  * material with an albedo texture casts a full shadow.  For quality 0 the reference's outcome for non-opaque instances depends on its driver's
  * traversal order (one rayQueryProceedEXT, nothing confirmed): post-pass draws are defined as non-casters there.  Animation: when draws move,
  * nv_rt_tlas_build (below) rebuilds the TLAS on the device from the rewritten draw records, in place of the reference's
@@ -876,6 +960,10 @@ typedef struct NvSceneCacheInfo
 } NvSceneCacheInfo;
 int nv_scenecache_info(const char* path, NvSceneCacheInfo* out);
 int nv_scenecache_read(const char* path, const NvSceneCacheInfo* info, NvMesh* meshes, NvMeshlet* meshlets, NvMeshDraw* draws);
+/* the info->texturePathCount fixed 256-byte, NUL-padded records the file ends with (src/scenecache.cpp:192-197,355): textures[i + 1] is the
+ * DDS file paths[i] names.  The records sit behind sections this reader does not size (lights, animations, opacity micromaps), so they are
+ * taken from the END of the file; every record is NUL-terminated on return.  NV_EFORMAT: the file is too short to hold them. */
+int nv_scenecache_texture_paths(const char* path, const NvSceneCacheInfo* info, char (*paths)[256]);
 
 /* ---- verification probe (tests only): per-meshlet scalar intermediates of the cluster cull
  * (view-space centre xyz, radius, cone lhs, cone rhs, aabb[4], mip level, sampled depth,
@@ -912,6 +1000,8 @@ static_assert(sizeof(NvShadowData) == 96 && offsetof(NvShadowData, sunJitter) ==
 static_assert(sizeof(NvRtSceneStats) == 40, "NvRtSceneStats is mirrored by niagara_amd/_lib.py");
 static_assert(sizeof(NvBloomDesc) == 48 && offsetof(NvBloomDesc, levels) == 8 && offsetof(NvBloomDesc, levelOffset) == 12 &&
               offsetof(NvBloomDesc, totalTexels) == 44, "NvBloomDesc is mirrored by niagara_amd/_lib.py and niagara_amd/layouts.py");
+static_assert(sizeof(NvTextureDesc) == 16 && offsetof(NvTextureDesc, width) == 4 && offsetof(NvTextureDesc, levels) == 12, "NvTextureDesc is mirrored by niagara_amd/layouts.py");
+static_assert(sizeof(NvDdsInfo) == 152 && offsetof(NvDdsInfo, payloadBytes) == 24 && offsetof(NvDdsInfo, levelOffset) == 32, "NvDdsInfo is mirrored by niagara_amd/_lib.py");
 static_assert(sizeof(NvSceneCacheInfo) == 208, "NvSceneCacheInfo is mirrored by niagara_amd/_lib.py");
 #endif
 

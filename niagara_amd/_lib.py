@@ -50,6 +50,17 @@ class SceneCacheInfo(C.Structure):
                                            "drawOffset", "vertexBytes", "indexBytes", "meshletdataBytes")])
 
 
+class DdsInfo(C.Structure):
+    """NvDdsInfo (include/niagara_vis.h): what nv_dds_parse reports of a DDS file image"""
+    _fields_ = [(n, C.c_uint32) for n in ("format", "width", "height", "levels", "blockBytes", "payloadOffset")] + [
+        ("payloadBytes", C.c_uint64), ("levelOffset", C.c_uint64 * 15)]
+
+
+class TextureDesc(C.Structure):
+    """NvTextureDesc (include/niagara_vis.h, layouts.TEXTUREDESC): one decoded texture of a set"""
+    _fields_ = [(n, C.c_uint32) for n in ("offset", "width", "height", "levels")]
+
+
 if not os.path.exists(SO_PATH):
     raise ImportError("niagara_amd: %s is missing — build it with `make -C niagara_amd/csrc` (or __graft_entry__.build()); "
                       "there is no fallback path" % SO_PATH)
@@ -92,6 +103,14 @@ _SIGS = {
     "nv_visibility_merge": (_i, [_vp, _vp, _vp, C.POINTER(_vp), _u32, _u32, _u32]),
     "nv_visibility_resolve": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
     "nv_visibility_attributes": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "nv_visibility_attributes_textured": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp,
+                                               _vp, _u32, _vp, C.c_uint64]),
+    "nv_dds_parse": (_i, [_vp, C.c_uint64, C.POINTER(DdsInfo)]),
+    "nv_texture_set_layout": (_i, [C.POINTER(DdsInfo), _u32, _vp, C.POINTER(C.c_uint64)]),
+    "nv_texture_decode_host": (_i, [C.POINTER(DdsInfo), _vp, _vp, _vp, C.c_uint64]),
+    "nv_texture_decode": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, C.POINTER(TextureDesc)]),
+    "nv_texture_sample_host": (_i, [_vp, _u32, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp]),
+    "nv_scenecache_texture_paths": (_i, [C.c_char_p, C.POINTER(SceneCacheInfo), _vp]),
     "nv_shadow_fill": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _i]),
     "nv_shadow_blur": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _i, _f]),
     "nv_shade_final": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32]),
@@ -138,5 +157,5 @@ for _name, (_res, _args) in _SIGS.items():
 
 def check(rc, what):
     if rc != 0:
-        names = {-1: "NV_EINVAL", -2: "NV_ENOMEM", -3: "NV_ESTATE", -4: "NV_ENODEV", -5: "NV_EIO", -6: "NV_EFORMAT"}
+        names = {-1: "NV_EINVAL", -2: "NV_ENOMEM", -3: "NV_ESTATE", -4: "NV_ENODEV", -5: "NV_EIO", -6: "NV_EFORMAT", -7: "NV_ETEXFORMAT"}
         raise NvError("%s failed: %s" % (what, names.get(rc, "hipError %d" % rc)))

@@ -48,6 +48,12 @@ int launch_rasterdepth(hipStream_t, const RasterArgs& a, uint32_t gridBlocks, bo
 int launch_visibility_resolve(hipStream_t, const NvCullData& cd, const unsigned long long* visibility, uint32_t n, const NvMeshDraw* draws, uint32_t drawCount,
                               const NvMesh* meshes, uint32_t meshCount, void* records, uint32_t* meshletSeen, uint32_t* drawPixels, unsigned long long* totals,
                               uint32_t maxBlocks, bool perPixel);
+int launch_visibility_attributes_textured(hipStream_t, const NvGlobals& globals, const void* records, uint32_t width, uint32_t height, const NvMeshDraw* draws,
+                                          uint32_t drawCount, const NvMeshlet* meshlets, uint32_t meshletCount, const uint32_t* meshletData, uint32_t dataWords,
+                                          const NvVertex* vertices, uint32_t vertexCount, const NvMaterial* materials, uint32_t materialCount, void* attributes,
+                                          uint32_t* gbuffer0, uint32_t* gbuffer1, unsigned long long* totals, const void* textures, uint32_t textureCount,
+                                          const uint32_t* texels, unsigned long long texelWords, uint32_t maxBlocks);
+int launch_texture_decode(hipStream_t, const void* blocks, uint32_t format, uint32_t width, uint32_t height, uint32_t levels, uint32_t* texels);
 int launch_visibility_attributes(hipStream_t, const NvGlobals& globals, const void* records, uint32_t width, uint32_t height, const NvMeshDraw* draws,
                                  uint32_t drawCount, const NvMeshlet* meshlets, uint32_t meshletCount, const uint32_t* meshletData, uint32_t dataWords,
                                  const NvVertex* vertices, uint32_t vertexCount, const NvMaterial* materials, uint32_t materialCount, void* attributes,
@@ -1254,6 +1260,44 @@ int nv_visibility_attributes(nv_context* ctx, void* stream, const NvGlobals* glo
 	return nv::launch_visibility_attributes((hipStream_t)stream, *globals, d_records, width, height, d_draws, drawCount, d_meshlets, meshletCount, d_meshletData,
 	                                        meshletDataWords, d_vertices, vertexCount, d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1,
 	                                        reinterpret_cast<unsigned long long*>(d_totals4), persistent_grid(ctx, 8), ctx->attributesPerPixel != 0);
+}
+
+// ---- material textures (texdecode.hip, visattr_tex.hip)
+int nv_visibility_attributes_textured(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisRecord* d_records, uint32_t width,
+                                      uint32_t height, const NvMeshDraw* d_draws, uint32_t drawCount, const NvMeshlet* d_meshlets,
+                                      uint32_t meshletCount, const uint32_t* d_meshletData, uint32_t meshletDataWords, const NvVertex* d_vertices,
+                                      uint32_t vertexCount, const NvMaterial* d_materials, uint32_t materialCount, NvPixelAttributes* d_attributes,
+                                      uint32_t* d_gbuffer0, uint32_t* d_gbuffer1, uint64_t* d_totals4, const NvTextureDesc* d_textures,
+                                      uint32_t textureCount, const uint32_t* d_texels, uint64_t texelWords)
+{
+	const auto misaligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+	if (!ctx || !globals || !d_records || width == 0 || height == 0 || width > 16384 || height > 16384 || globals->screenWidth != (float)width ||
+	    globals->screenHeight != (float)height || (drawCount && !d_draws) || (meshletCount && !d_meshlets) || (meshletDataWords && !d_meshletData) ||
+	    (vertexCount && !d_vertices) || !d_materials || (textureCount && (!d_textures || !d_texels)) || misaligned(d_records, 15u) ||
+	    misaligned(d_attributes, 15u) || misaligned(d_draws, 15u) || misaligned(d_vertices, 15u) || misaligned(d_materials, 15u) ||
+	    misaligned(d_totals4, 7u) || misaligned(d_meshlets, 3u) || misaligned(d_meshletData, 3u) || misaligned(d_gbuffer0, 3u) || misaligned(d_gbuffer1, 3u) ||
+	    misaligned(d_textures, 15u) || misaligned(d_texels, 3u))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_visibility_attributes_textured((hipStream_t)stream, *globals, d_records, width, height, d_draws, drawCount, d_meshlets, meshletCount,
+	                                                 d_meshletData, meshletDataWords, d_vertices, vertexCount, d_materials, materialCount, d_attributes,
+	                                                 d_gbuffer0, d_gbuffer1, reinterpret_cast<unsigned long long*>(d_totals4), d_textures,
+	                                                 d_textures ? textureCount : 0u, d_texels, texelWords, persistent_grid(ctx, 8));
+}
+
+int nv_texture_decode(nv_context* ctx, void* stream, const void* d_blocks, uint32_t format, uint32_t width, uint32_t height, uint32_t levels,
+                      uint32_t* d_texels, const NvTextureDesc* desc)
+{
+	if (!ctx || !d_blocks || !d_texels || !desc || width == 0 || height == 0 || levels == 0 || width > 16384 || height > 16384 ||
+	    levels > NV_TEXTURE_MAX_LEVELS || desc->width != width || desc->height != height || desc->levels != levels ||
+	    (reinterpret_cast<uintptr_t>(d_blocks) & 7u) || (reinterpret_cast<uintptr_t>(d_texels) & 3u))
+		return NV_EINVAL;
+	if (format == NV_FORMAT_BC4 || format == NV_FORMAT_BC5 || format == NV_FORMAT_BC6H)
+		return NV_ETEXFORMAT;
+	if (format != NV_FORMAT_BC1 && format != NV_FORMAT_BC2 && format != NV_FORMAT_BC3 && format != NV_FORMAT_BC7)
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_texture_decode((hipStream_t)stream, d_blocks, format, width, height, levels, d_texels + desc->offset);
 }
 
 // ---- the shading end of the frame (shade.hip)

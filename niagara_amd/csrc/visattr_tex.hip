@@ -1,0 +1,35 @@
+// visattr_tex.hip — nv_visibility_attributes_textured: the attribute pass with the complete fragment stage.
+//
+// The pass is visattr.h's kernel — run detection, set-up, barycentrics and varyings of §4.13, shared with nv_visibility_attributes, not
+// copied — instantiated with TEX: per pixel the triangle's barycentrics are taken twice more, at the centres of (px + 1, py) and (px, py + 1),
+// from the run's set-up that is already in registers; uv there minus the pixel's own uv are the derivatives the level of detail needs (a
+// visibility buffer has no quads).  Then up to four textures are sampled through texmath.h's software `textureSampler` (REPEAT, trilinear:
+// 8 taps each), one texture after the other so that only one texture's taps are live at a time, and enter mesh.frag.glsl:62-80.  Before any
+// texel load the index is checked against the table and the descriptor's whole chain against the texel buffer.  One launch, no scratch
+// memory, only enqueued work.
+#include "visattr.h"
+
+namespace nv
+{
+
+int launch_visibility_attributes_textured(hipStream_t stream, const NvGlobals& globals, const void* records, uint32_t width, uint32_t height,
+                                          const NvMeshDraw* draws, uint32_t drawCount, const NvMeshlet* meshlets, uint32_t meshletCount,
+                                          const uint32_t* meshletData, uint32_t dataWords, const NvVertex* vertices, uint32_t vertexCount,
+                                          const NvMaterial* materials, uint32_t materialCount, void* attributes, uint32_t* gbuffer0, uint32_t* gbuffer1,
+                                          unsigned long long* totals, const void* textures, uint32_t textureCount, const uint32_t* texels,
+                                          unsigned long long texelWords, uint32_t maxBlocks)
+{
+	VisAttrTexArgs a;
+	static_cast<VisAttrArgs&>(a) = va_make_args(globals, records, width, height, draws, drawCount, meshlets, meshletCount, meshletData, dataWords, vertices, vertexCount,
+	                                   materials, materialCount, attributes, gbuffer0, gbuffer1, totals);
+	a.tx.descs = static_cast<const uint4*>(textures);
+	a.tx.count = textureCount;
+	a.tx.texels = texels;
+	a.tx.texelWords = texelWords;
+	uint32_t grid = (a.n + VA_THREADS - 1u) / VA_THREADS;
+	grid = grid < maxBlocks ? grid : maxBlocks;
+	hipLaunchKernelGGL((visibility_attributes_kernel<true, true, VisAttrTexArgs>), dim3(grid), dim3(VA_THREADS), 0, stream, a);
+	return (int)hipGetLastError();
+}
+
+} // namespace nv

@@ -167,6 +167,64 @@ def scenecache_info(path):
     return info
 
 
+def scenecache_texture_paths(path):
+    """the texture paths a niagara .cache file ends with (src/scenecache.cpp:192-197): textures[i + 1] is the DDS file paths[i] names"""
+    info = scenecache_info(path)
+    buf = (C.c_char * 256 * max(1, info.texturePathCount))()
+    check(lib.nv_scenecache_texture_paths(os.fsencode(path), C.byref(info), C.cast(buf, C.c_void_p)), "nv_scenecache_texture_paths")
+    return [os.fsdecode(bytes(buf[i]).split(b"\0", 1)[0]) for i in range(info.texturePathCount)]
+
+
+def dds_parse(data):
+    """nv_dds_parse of a DDS file image (bytes): a dict of format (layouts.FORMAT_*), width, height, levels, blockBytes, payloadOffset,
+    payloadBytes and levelOffset (one byte offset per level, from payloadOffset).  Raises NvError(NV_EFORMAT) where niagara's loadImage refuses"""
+    info = _dds_info(data)
+    d = {n: int(getattr(info, n)) for n in ("format", "width", "height", "levels", "blockBytes", "payloadOffset", "payloadBytes")}
+    d["levelOffset"] = [int(info.levelOffset[i]) for i in range(info.levels)]
+    return d
+
+
+def _dds_info(data):
+    from ._lib import DdsInfo
+    info = DdsInfo()
+    data = bytes(data)
+    check(lib.nv_dds_parse(data, len(data), C.byref(info)), "nv_dds_parse")
+    return info
+
+
+def texture_set_layout(files):
+    """nv_texture_set_layout over DDS file images: (descs, texel_words, infos) — descs a layouts.TEXTUREDESC array of len(files) + 1 entries
+    (entry 0 reserved), texel_words the size of the set's RGBA8 buffer in 32-bit words"""
+    from ._lib import DdsInfo
+    infos = (DdsInfo * max(1, len(files)))()
+    for i, data in enumerate(files):
+        infos[i] = _dds_info(data)
+    descs = np.zeros(len(files) + 1, L.TEXTUREDESC)
+    words = C.c_uint64(0)
+    check(lib.nv_texture_set_layout(infos, len(files), _p(descs), C.byref(words)), "nv_texture_set_layout")
+    return descs, int(words.value), infos
+
+
+def texture_decode_host(files):
+    """the whole set decoded on the CPU (nv_texture_decode_host, the text the kernel runs): (descs, texels uint32 array)"""
+    descs, words, infos = texture_set_layout(files)
+    texels = np.zeros(max(1, words), np.uint32)
+    for i, data in enumerate(files):
+        payload = np.frombuffer(bytes(data), np.uint8)[infos[i].payloadOffset:].copy()
+        check(lib.nv_texture_decode_host(C.byref(infos[i]), _p(payload), _p(descs[i + 1:i + 2]), _p(texels), words), "nv_texture_decode_host")
+    return descs, texels[:words]
+
+
+def texture_sample_host(descs, texels, tex_id, uv, duvdx=(0.0, 0.0), duvdy=(0.0, 0.0)):
+    """one sample of textures[tex_id] on the CPU (nv_texture_sample_host): four float32"""
+    descs = np.ascontiguousarray(descs, L.TEXTUREDESC)
+    texels = np.ascontiguousarray(texels, np.uint32)
+    a, b, c = (np.asarray(v, np.float32).copy() for v in (uv, duvdx, duvdy))
+    out = np.zeros(4, np.float32)
+    check(lib.nv_texture_sample_host(_p(descs), len(descs), _p(texels), len(texels), int(tex_id), _p(a), _p(b), _p(c), _p(out)), "nv_texture_sample_host")
+    return out
+
+
 def scenecache_read(path):
     """(info, meshes, meshlets, draws) of a niagara .cache file; the arrays are the raw struct arrays of the file"""
     info = scenecache_info(path)

@@ -53,6 +53,12 @@ assert SHADOWDATA.itemsize == 96
 BLOOMDESC = np.dtype([("width", "<u4"), ("height", "<u4"), ("levels", "<u4"), ("levelOffset", "<u4", 8), ("totalTexels", "<u4")])
 assert BLOOMDESC.itemsize == 48
 BLOOM_MAX_LEVELS = 8
+# NvTextureDesc: one decoded texture of a set — the word offset of level 0 in the set's RGBA8 texel buffer, level 0's size, the level count
+# (the levels follow one another, each row-major without padding).  Entry 0 of a table is the reserved "no texture" entry
+TEXTUREDESC = np.dtype([("offset", "<u4"), ("width", "<u4"), ("height", "<u4"), ("levels", "<u4")])
+assert TEXTUREDESC.itemsize == 16
+TEXTURE_MAX_LEVELS = 15
+FORMAT_BC1, FORMAT_BC2, FORMAT_BC3, FORMAT_BC4, FORMAT_BC5, FORMAT_BC6H, FORMAT_BC7 = 1, 2, 3, 4, 5, 6, 7
 VIS_ID_BITS = 34  # the stable form of the visibility word: bits(z) << 34 | ((mvi << 7 | triangle) + 1)
 
 TASK_WGSIZE = 64

@@ -220,6 +220,38 @@ class Context:
                                            int(vertex_count), _ptr(materials), int(material_count), _ptr(attributes), _ptr(gbuffer0), _ptr(gbuffer1),
                                            _ptr(totals4)), "nv_visibility_attributes")
 
+    def visibility_attributes_textured(self, globals_, records, width, height, db, draw_count, mlb, meshlet_count, meshlet_data, data_words, vertices,
+                                       vertex_count, materials, material_count, attributes=None, gbuffer0=None, gbuffer1=None, totals4=None,
+                                       textures=None, texture_count=0, texels=None, texel_words=0):
+        """visibility_attributes with the complete fragment stage (nv_visibility_attributes_textured): textures = a device table of
+        layouts.TEXTUREDESC (entry 0 reserved), texels = the decoded set (texture_decode).  totals4[3] counts the pixels whose material names a
+        texture the pass could not sample: 0 on a complete set"""
+        check(lib.nv_visibility_attributes_textured(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(records), int(width), int(height), _ptr(db),
+                                                    int(draw_count), _ptr(mlb), int(meshlet_count), _ptr(meshlet_data), int(data_words), _ptr(vertices),
+                                                    int(vertex_count), _ptr(materials), int(material_count), _ptr(attributes), _ptr(gbuffer0),
+                                                    _ptr(gbuffer1), _ptr(totals4), _ptr(textures), int(texture_count), _ptr(texels), int(texel_words)),
+              "nv_visibility_attributes_textured")
+
+    # ---- material textures (DESIGN.md §4.18); the three host functions need no device and are host.py's
+    dds_parse = staticmethod(host.dds_parse)
+    texture_set_layout = staticmethod(host.texture_set_layout)
+    scenecache_texture_paths = staticmethod(host.scenecache_texture_paths)
+
+    def texture_decode(self, files):
+        """decode a texture set on the device (nv_texture_decode, one launch per texture): files = DDS file images (bytes).  Returns (descs:
+        host layouts.TEXTUREDESC array with the reserved entry 0, texels: int32 device tensor of the set's RGBA8 words)"""
+        from ._lib import TextureDesc
+        descs, words, infos = host.texture_set_layout(files)
+        texels = torch.zeros(max(1, words), dtype=torch.int32, device=self.device)
+        for i, data in enumerate(files):
+            info = infos[i]
+            payload = np.frombuffer(bytes(data), np.uint8)[info.payloadOffset:]
+            blocks = to_device(np.ascontiguousarray(payload), self.device)
+            d = TextureDesc(*[int(descs[i + 1][k]) for k in ("offset", "width", "height", "levels")])
+            check(lib.nv_texture_decode(self.h, _stream(), _ptr(blocks), info.format, info.width, info.height, info.levels, _ptr(texels), C.byref(d)),
+                  "nv_texture_decode")
+        return descs, texels
+
     def shadow_fill(self, shadow, depth, width, height, checkerboard):
         """shadowfill.comp.glsl in place (nv_shadow_fill): the texels of one checkerboard parity of the u8 shadow image become the
         depth-weighted mean of their four neighbours; the other parity keeps its bytes"""
@@ -493,11 +525,28 @@ class VisibilityPipeline:
                                     out["records"], out["meshlet_seen"], out["draw_pixels"], out["totals"])
         return out
 
-    def attributes(self, cull_data, records, materials=None, attributes=True, gbuffers=True):
+    def set_textures(self, files):
+        """the scene's material textures, once per scene: a list of DDS file images (bytes) or paths, in texturePaths order — textures[i + 1]
+        is files[i], as niagara binds them (src/niagara.cpp:934).  Decoded on the device to RGBA8 mip chains; attributes(textures=True) samples
+        them"""
+        data = []
+        for f in files:
+            if isinstance(f, (bytes, bytearray, memoryview)):
+                data.append(bytes(f))
+            else:
+                with open(f, "rb") as fh:
+                    data.append(fh.read())
+        descs, self.texels = self.ctx.texture_decode(data)
+        self.texture_descs = descs
+        self.texture_table = to_device(descs, self.ctx.device)
+
+    def attributes(self, cull_data, records, materials=None, attributes=True, gbuffers=True, textures=False):
         """nv_visibility_attributes over resolve()'s "records" under the frame's CullData: a dict with "attributes" (uint8 tensor, height *
         width NvPixelAttributes), "gbuffer0" / "gbuffer1" (int32, height x width; only with `materials`, a host array of layouts.MATERIAL or a
         device tensor of them) and "totals" (int64: shaded, invalid, degenerate, textured); an output switched off is None.  The records are
-        global (the scene's draw ids), so this works unchanged on any rank of a sharded frame after the composite"""
+        global (the scene's draw ids), so this works unchanged on any rank of a sharded frame after the composite.  textures=True runs
+        nv_visibility_attributes_textured over set_textures()'s set: the complete fragment stage; totals[3] then counts only the pixels whose
+        material names a texture the set does not hold"""
         if not self.stable_ids:
             raise NvError("attributes reads resolve()'s records: VisibilityPipeline(..., stable_ids=True)")
         if self.mdb is None:
@@ -515,6 +564,16 @@ class VisibilityPipeline:
                    totals=torch.zeros(4, dtype=torch.int64, device=dev))
         g = synth.make_globals(cull_data, (self.depth_w, self.depth_h))
         n_draws = getattr(self, "total_draws", self.draw_count)
+        if textures:
+            if getattr(self, "texture_table", None) is None:
+                raise NvError("attributes(textures=True) samples set_textures()'s set: call set_textures first")
+            if mat is None:
+                raise NvError("attributes(textures=True) needs the material table")
+            self.ctx.visibility_attributes_textured(g, records, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws, self.mlb,
+                                                    self.meshlet_count, self.mdb, self.mdb.numel() * self.mdb.element_size() // 4, self.vb,
+                                                    self.vertex_count, mat, n_mat, out["attributes"], out["gbuffer0"], out["gbuffer1"], out["totals"],
+                                                    self.texture_table, len(self.texture_descs), self.texels, self.texels.numel())
+            return out
         self.ctx.visibility_attributes(g, records, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws, self.mlb, self.meshlet_count,
                                        self.mdb, self.mdb.numel() * self.mdb.element_size() // 4, self.vb, self.vertex_count, mat, n_mat,
                                        out["attributes"], out["gbuffer0"], out["gbuffer1"], out["totals"])
@@ -655,8 +714,13 @@ class ShardedVisibilityPipeline(VisibilityPipeline):
     returns the unsharded frame's records with the scene's draw ids; without it the slot index of the word is rank-local and a
     visibility target is refused.
 
-    Out of scope here: moving draws.  move_draws and build_rt_scene(dynamic=True) (the TLAS rebuilt on the device) are
+    Out of scope here: material textures (set_textures is refused; the textured pass is per pixel and works on any rank through the
+    Context) and moving draws.  move_draws and build_rt_scene(dynamic=True) (the TLAS rebuilt on the device) are
     refused on a sharded pipeline: the ranks' draw buffers and mirrors would have to move together."""
+
+    def set_textures(self, files):
+        raise NvError("set_textures is not available on a sharded pipeline: decode the set with Context.texture_decode and run the textured "
+                      "attribute pass (per pixel, on any rank) through Context.visibility_attributes_textured")
 
     def __init__(self, meshes, meshlets, draws, depth_size, rank=0, world=1, draw_range=None, weight="draws", group=None, **kw):
         from . import shard

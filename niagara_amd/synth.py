@@ -396,3 +396,115 @@ def interior_scene_indexed(**kw):
     s = interior_scene(**kw)
     indices, meshes = indexed_geometry(s["meshes"], s["meshlets"], s["data"])
     return dict(s, meshes=meshes, indices=indices)
+
+
+# ---- material textures: content for tools and tests
+
+def _rgb565(c):
+    """(..., 3) uint8 -> the 565 code (truncating: the encoder's endpoints need not be the nearest codes)"""
+    c = c.astype(np.uint32)
+    return (c[..., 0] >> 3) << 11 | (c[..., 1] >> 2) << 5 | c[..., 2] >> 3
+
+
+def _expand565(code):
+    r, g, b = code >> 11 & 31, code >> 5 & 63, code & 31
+    return np.stack([(r * 255 + 15) // 31, (g * 255 + 31) // 63, (b * 255 + 15) // 31], -1).astype(np.int64)
+
+
+def bc1_encode(image):
+    """a minimal BC1 encoder: image (h, w, 3 or 4) uint8 -> the blocks' bytes, row-major.  Per block the endpoints are the per-channel maximum
+    and minimum (c0 > c1: the four-colour mode; a flat block stores c0 = c1 and index 0), every texel takes the nearest of the four colours.
+    Partial blocks repeat the edge texels.  Alpha is ignored (BC1 here is opaque)"""
+    img = np.asarray(image, np.uint8)[..., :3]
+    h, w = img.shape[:2]
+    img = np.pad(img, ((0, -h % 4), (0, -w % 4), (0, 0)), mode="edge")
+    bh, bw = img.shape[0] // 4, img.shape[1] // 4
+    blocks = img.reshape(bh, 4, bw, 4, 3).transpose(0, 2, 1, 3, 4).reshape(bh * bw, 16, 3)
+    c0, c1 = _rgb565(blocks.max(axis=1)), _rgb565(blocks.min(axis=1))
+    swap = c0 < c1  # per-channel extremes are ordered channel by channel; the packed codes almost always are too
+    c0, c1 = np.where(swap, c1, c0), np.where(swap, c0, c1)
+    e0, e1 = _expand565(c0), _expand565(c1)
+    palette = np.stack([e0, e1, (2 * e0 + e1) // 3, (e0 + 2 * e1) // 3], axis=1)  # (n, 4, 3)
+    dist = ((blocks[:, :, None, :].astype(np.int64) - palette[:, None, :, :]) ** 2).sum(-1)  # (n, 16, 4)
+    idx = np.where((c0 == c1)[:, None], 0, dist.argmin(-1)).astype(np.uint32)
+    bits = (idx << (2 * np.arange(16, dtype=np.uint32))[None, :]).sum(axis=1).astype(np.uint32)
+    out = np.zeros((bh * bw, 2), np.uint32)
+    out[:, 0] = c0.astype(np.uint32) | c1.astype(np.uint32) << 16
+    out[:, 1] = bits
+    return out.tobytes()
+
+
+def _half_image(img):
+    """the next mip level: max(1, side // 2) per axis, the mean of the 2 x 2 (or 2 x 1, 1 x 2) source texels"""
+    h, w = img.shape[:2]
+    nh, nw = max(1, h // 2), max(1, w // 2)
+    ys, xs = np.minimum(np.arange(nh) * 2, h - 1), np.minimum(np.arange(nw) * 2, w - 1)
+    ys1, xs1 = np.minimum(ys + 1, h - 1), np.minimum(xs + 1, w - 1)
+    s = img.astype(np.uint32)
+    return ((s[ys][:, xs] + s[ys][:, xs1] + s[ys1][:, xs] + s[ys1][:, xs1] + 2) // 4).astype(np.uint8)
+
+
+def dds_bytes(image, mips=True):
+    """a DDS file image as niagara's loadImage accepts it (src/textures.cpp:159-210): FourCC DXT1, the BC1 blocks of `image` and, with mips,
+    of its whole chain down to 1 x 1"""
+    img = np.asarray(image, np.uint8)
+    h, w = img.shape[:2]
+    levels, payload = 0, b""
+    while True:
+        payload += bc1_encode(img)
+        levels += 1
+        if not mips or (img.shape[0] == 1 and img.shape[1] == 1):
+            break
+        img = _half_image(img)
+    head = np.zeros(32, np.uint32)
+    head[0] = 0x20534444                      # "DDS "
+    head[1], head[2] = 124, 0x1 | 0x2 | 0x4 | 0x1000 | 0x20000 | 0x80000  # dwSize; CAPS | HEIGHT | WIDTH | PIXELFORMAT | MIPMAPCOUNT | LINEARSIZE
+    head[3], head[4] = h, w
+    head[5] = ((w + 3) // 4) * ((h + 3) // 4) * 8
+    head[7] = levels
+    head[19], head[20], head[21] = 32, 0x4, 0x31545844  # ddspf: dwSize, DDPF_FOURCC, "DXT1"
+    head[27] = 0x1000 | (0x400008 if levels > 1 else 0)  # DDSCAPS_TEXTURE (| COMPLEX | MIPMAP)
+    return head.tobytes() + payload
+
+
+def texture_images(size=64):
+    """the four images of with_textures: a checker albedo, a bump normal map, a specular map, an emissive map; (size, size, 4) uint8 each"""
+    y, x = np.mgrid[0:size, 0:size]
+    cell = size // 8 or 1
+    check = ((x // cell + y // cell) % 2).astype(np.float64)
+    albedo = np.stack([0.9 - 0.6 * check, 0.35 + 0.5 * check, 0.25 + 0.1 * check, np.ones_like(check)], -1)
+    fx, fy = 2 * np.pi * x / size, 2 * np.pi * y / size
+    nx, ny = 0.45 * np.cos(2 * fx), 0.45 * np.cos(2 * fy)
+    nz = np.sqrt(np.maximum(0.0, 1 - nx * nx - ny * ny))
+    normal = np.stack([nx * 0.5 + 0.5, ny * 0.5 + 0.5, nz * 0.5 + 0.5, np.ones_like(nx)], -1)
+    spec = np.stack([0.5 + 0.5 * np.sin(fx), 0.5 + 0.5 * np.sin(fy), check, np.ones_like(check)], -1)
+    glow = np.exp(-(((x - size / 2) ** 2 + (y - size / 2) ** 2) / (size / 4) ** 2))
+    emissive = np.stack([glow, 0.6 * glow, 0.2 * glow, np.ones_like(glow)], -1)
+    return [np.rint(np.clip(i, 0, 1) * 255).astype(np.uint8) for i in (albedo, normal, spec, emissive)]
+
+
+def with_textures(scene, size=64, mips=True):
+    """a copy of a scene dict with "textures" — four DDS file images (BC1): a checker albedo, a bump normal map, a specular map and an emissive
+    map, textures[1..4] of the set — and a material table ("materials"; created with five entries spread over the draws when the scene has
+    none) whose every entry names all four.  Vertices without texcoords (all zero, as make_geometry leaves them) get a planar map of their
+    positions"""
+    s = dict(scene)
+    s["textures"] = [dds_bytes(i, mips) for i in texture_images(size)]
+    if "materials" in s:
+        m = s["materials"].copy()
+    else:
+        m = np.zeros(5, L.MATERIAL)
+        m["diffuseFactor"], m["specularFactor"] = (0.9, 0.9, 0.9, 1.0), (0.5, 0.5, 0.5, 0.6)
+        m["emissiveFactor"] = (1.0, 1.0, 1.0)
+        s["draws"] = s["draws"].copy()
+        s["draws"]["materialIndex"] = np.arange(len(s["draws"])) % len(m)
+    m["albedoTexture"], m["normalTexture"], m["specularTexture"], m["emissiveTexture"] = 1, 2, 3, 4
+    s["materials"] = m
+    v = s["vertices"]
+    if not (v["tu"].any() or v["tv"].any()):
+        v = v.copy()
+        pos = np.stack([v["vx"], v["vy"], v["vz"]], -1).view(np.float16).astype(np.float32)
+        uv = (np.stack([pos[:, 0] + 0.25 * pos[:, 2], pos[:, 1] - 0.25 * pos[:, 2]], -1) * 0.5 + 0.5).astype(np.float16)
+        v["tu"], v["tv"] = uv[:, 0].view(np.uint16), uv[:, 1].view(np.uint16)
+        s["vertices"] = v
+    return s

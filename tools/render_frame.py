@@ -193,6 +193,8 @@ def main():
     ap.add_argument("--no-shadow", action="store_true")
     ap.add_argument("--checkerboard", action="store_true")
     ap.add_argument("--bloom", action="store_true", help="two materials emit; run the bloom chain and final's bloom term")
+    ap.add_argument("--textures", action="store_true", help="synth.with_textures' checker albedo, bump normal map, specular and emissive maps through "
+                    "nv_visibility_attributes_textured (DESIGN.md §4.18)")
     ap.add_argument("--traced-shadows", action="store_true", help="ray trace the shadow mask (the default stays the synthetic mask)")
     ap.add_argument("--quality", type=int, default=1, help="--traced-shadows: 0 = opaque draws cast, 1 = post-pass draws too")
     ap.add_argument("--animate", type=int, default=0, help="--traced-shadows: write N images (out_000.ppm ...) with one draw displaced along a circle "
@@ -232,7 +234,14 @@ def main():
     if args.bloom:
         materials["emissiveFactor"][[1, 4]] = ((6.0, 2.5, 0.5), (0.5, 3.0, 8.0))
     draws["materialIndex"] = np.arange(len(draws)) % len(materials)
+    textures = None
+    if args.textures:
+        from niagara_amd import synth
+        t = synth.with_textures(dict(vertices=v, draws=draws, materials=materials))  # planar texcoords, the four maps, materials that name them
+        v, materials, textures = t["vertices"], t["materials"], t["textures"]
     pipe = P.VisibilityPipeline(s["meshes"], s["meshlets"], draws, (w, h), fused=True, vertices=v, meshlet_data=s["data"], stable_ids=True)
+    if textures:
+        pipe.set_textures(textures)
     x, y = np.meshgrid(np.arange(w), np.arange(h))
     r = np.hypot(x - 0.45 * w, y - 0.5 * h) / (0.3 * h)
     mask = np.clip(np.rint(255.0 * np.clip((r - 0.8) / 0.4, 0.0, 1.0)), 0, 255).astype(np.uint8)
@@ -245,7 +254,7 @@ def main():
         vis = pipe.new_visibility()
         _timed(events, "frame", lambda: pipe.frame(s["cull"], post_pass=True, visibility=vis))
         res = _timed(events, "resolve", lambda: pipe.resolve(s["cull"], vis))
-        att = _timed(events, "attributes", lambda: pipe.attributes(s["cull"], res["records"], mat, attributes=False))
+        att = _timed(events, "attributes", lambda: pipe.attributes(s["cull"], res["records"], mat, attributes=False, textures=args.textures))
         shadow = None if args.no_shadow else "trace" if args.traced_shadows else torch.from_numpy(mask.copy()).to(pipe.ctx.device)
         return _timed(events, "shade", lambda: pipe.shade(s["cull"], att["gbuffer0"], att["gbuffer1"], (0.0, 0.0, 0.0), sun, shadow=shadow,
                                                           checkerboard=args.checkerboard, bloom=args.bloom, quality=args.quality))
