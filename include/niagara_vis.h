@@ -804,8 +804,9 @@ int nv_shade_final_bloom(nv_context* ctx, void* stream, const NvShadeData* shade
  * the fp16 position converted to fp32; a triangle with an index position >= indexCapacity or a corner >= vertexCapacity is left out
  * (nv_rasterdepth_indexed's rule).  The ray is taken into object space with t preserved: o' = rotateQuat(o - position, conj(q)) / scale,
  * d' = rotateQuat(d, conj(q)) / scale.
- * NOT MODELLED: the trace samples no textures yet (tx_sample_lod0 of csrc/texmath.h, DESIGN.md §4.18, is its sampler), so the alpha test of shadow.comp.glsl:115-120 (quality 1) sees alpha = 1 and a post-pass
- * material with an albedo texture casts a full shadow.  For quality 0 the reference's outcome for non-opaque instances depends on its driver's
+ * nv_shadow_trace samples no textures: its quality 1 sees alpha = 1, and a post-pass material with a cut-out albedo texture casts the shadow of its
+ * whole triangles.  nv_shadow_trace_textured (below) runs the alpha test of shadow.comp.glsl:86-123.  NOT MODELLED by either:
+ * opacity micromaps.  For quality 0 the reference's outcome for non-opaque instances depends on its driver's
  * traversal order (one rayQueryProceedEXT, nothing confirmed): post-pass draws are defined as non-casters there.  Animation: when draws move,
  * nv_rt_tlas_build (below) rebuilds the TLAS on the device from the rewritten draw records, in place of the reference's
  * buildTLAS(MODE_UPDATE) (src/niagara.cpp:1396, :1482).  The mask does not depend on which TLAS is walked.  Not modelled: keyframe evaluation
@@ -858,6 +859,49 @@ int nv_rt_scene_upload(nv_context* ctx, void* stream, const void* blob, uint64_t
  * quality outside 0..1, a depth pointer that is not 4-byte aligned. */
 int nv_shadow_trace(nv_context* ctx, void* stream, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width,
                     uint32_t height, int quality);
+
+/* ---- the alpha-tested trace (shadowTraceTransparent, shadow.comp.glsl:86-123; niagara_amd/csrc/rtalpha.h is the text) ----
+ * Every rule of nv_shadow_trace holds: ray set-up, casting rule, object-space ray, T with its fp64 fallback, tmin / tmax, checkerboard ownership,
+ * non-finite rays lit; one IEEE fp32 operation per source operation, no contraction, sums left to right.  tests/shadow_alpha_ref.c is the
+ * brute-force restatement.
+ * Quality 0: nv_shadow_trace's bytes.  Quality 1: the byte is 0 iff some casting instance (postPass <= 1) has a triangle that T accepts for the
+ * ray and that is CONFIRMED.  A triangle of a postPass == 0 instance is always confirmed (fillInstanceRT sets FORCE_OPAQUE there,
+ * src/scenert.cpp:516: the loop never sees it, whatever its material).  A triangle of a postPass == 1 instance is confirmed iff alpha >= 0.5f (a
+ * NaN alpha does not confirm), where, with draw = d_draws[instance.drawId], material = d_materials[draw.materialIndex] and tex =
+ * material.albedoTexture: alpha = 1 when drawId >= drawCount, materialIndex >= materialCount, tex == 0 (:116), tex >= textureCount, or the
+ * descriptor's chain does not lie inside texelWords (a texture the pass cannot sample is absent, as in nv_visibility_attributes_textured; no
+ * load leaves the caller's buffers for any input bits).  Otherwise, with T's U, V, W and det (after the fp64 fallback where T took it):
+ * b1 = V / det, b2 = W / det, w0 = (1 - b1) - b2, per component uv = (uv0 w0 + uv1 b1) + uv2 b2 (:113) with uvk the fp16 tu, tv of the
+ * triangle's corner k converted exactly, and alpha = textureLod(textures[tex], uv, 0).w by the sampler of §4.18: REPEAT, bilinear, level 0 only.
+ * The result is an OR over the accepted triangles: it does not depend on the order of the walk (what TerminateOnFirstHit with a confirming loop
+ * computes).  Vulkan leaves the bits of the barycentrics to the implementation: the formula above is this library's definition.
+ *
+ * The scene must carry the texcoords: nv_rt_scene_build_textured is nv_rt_scene_build (arguments, size protocol, errors) whose triangles hold
+ * in corner k's w word the BITS tu | tv << 16 of that corner's vertex, and whose header's flags word (the reserved word of nv_rt_scene_build's
+ * blob, 0 there) has bit 0 set.  Everything else is byte for byte nv_rt_scene_build's blob.  nv_rt_scene_validate accepts flags 0 or 1 and
+ * refuses any other bit; any bit pattern in a w word is safe.  nv_rt_tlas_build_host, nv_rt_scene_reserve_dynamic, nv_rt_tlas_build and
+ * nv_rt_scene_download keep the flag and the w words. */
+int nv_rt_scene_build_textured(const NvMesh* meshes, uint32_t meshCount, const uint32_t* indices, uint32_t indexCapacity, const NvVertex* vertices,
+                               uint32_t vertexCapacity, const NvMeshDraw* draws, uint32_t drawCount, void* out, uint64_t* bytes);
+/* the traversal nv_shadow_trace_textured runs, on the CPU (the same text), for `count` rays: out[i] = 0 (occluded) or 255.  draws, materials,
+ * textures (entry 0 reserved) and texels are host arrays.  The blob must have passed nv_rt_scene_validate.  NV_EINVAL: a NULL blob, a NULL
+ * array with a non-zero count, quality outside 0..1, a blob without the texcoord flag. */
+int nv_rt_scene_trace_host_textured_rays(const void* blob, const float* origins, const float* dirs, uint64_t count, float tmin, float tmax, int quality,
+                                         const NvMeshDraw* draws, uint32_t drawCount, const NvMaterial* materials, uint32_t materialCount,
+                                         const NvTextureDesc* textures, uint32_t textureCount, const uint32_t* texels, uint64_t texelWords, uint8_t* out);
+/* Test accessor: the pass's four-tap alpha (fourTap) and textureLod(..., 0).w of the full sampler (sampler) of one texture at `count` uv pairs;
+ * the two must agree bit for bit.  NV_EINVAL: a NULL pointer, a descriptor whose chain does not lie inside texelWords. */
+int nv_rt_alpha_sample_host(const NvTextureDesc* desc, const uint32_t* texels, uint64_t texelWords, const float* uv, uint64_t count, float* fourTap,
+                            float* sampler);
+/* nv_shadow_trace with the alpha test.  d_draws: the draw array the scene's instances index (the one nv_rt_scene_build_textured or the last
+ * nv_rt_tlas_build read); d_materials, d_textures (entry 0 reserved), d_texels: as nv_visibility_attributes_textured takes them.  Quality 0
+ * dispatches nv_shadow_trace's kernel; quality 1 enqueues one launch of its own (no allocation, no synchronisation: it can be captured).
+ * NV_EINVAL, with nothing launched: everything nv_shadow_trace refuses, an uploaded scene without the texcoord flag, a NULL array with a
+ * non-zero count, a misaligned pointer (16 bytes: draws, materials, descriptors; 4: texels). */
+int nv_shadow_trace_textured(nv_context* ctx, void* stream, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width,
+                             uint32_t height, int quality, const NvMeshDraw* d_draws, uint32_t drawCount, const NvMaterial* d_materials,
+                             uint32_t materialCount, const NvTextureDesc* d_textures, uint32_t textureCount, const uint32_t* d_texels,
+                             uint64_t texelWords);
 
 /* ---- the TLAS rebuilt for moving draws (niagara_amd/csrc/rttlas.h is the definition) ----
  * The rebuilt TLAS is a function of the blob's BLAS side and the current draw array alone: the instances are the draws that cast by the rule

@@ -117,6 +117,10 @@ _SIGS = {
     "nv_build_shade_data": (_i, [_vp, _vp, _vp, _vp, _i, _u32, _u32]),
     "nv_build_shadow_data": (_i, [_vp, _vp, _vp, _f, _i, _u32, _u32]),
     "nv_rt_scene_build": (_i, [_vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, C.POINTER(C.c_uint64)]),
+    "nv_rt_scene_build_textured": (_i, [_vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, C.POINTER(C.c_uint64)]),
+    "nv_rt_scene_trace_host_textured_rays": (_i, [_vp, _vp, _vp, C.c_uint64, _f, _f, _i, _vp, _u32, _vp, _u32, _vp, _u32, _vp, C.c_uint64, _vp]),
+    "nv_rt_alpha_sample_host": (_i, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
+    "nv_shadow_trace_textured": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _i, _vp, _u32, _vp, _u32, _vp, _u32, _vp, C.c_uint64]),
     "nv_rt_scene_validate": (_i, [_vp, C.c_uint64]),
     "nv_rt_scene_stats": (_i, [_vp, C.c_uint64, C.POINTER(RtSceneStats)]),
     "nv_rt_scene_trace_host": (_i, [_vp, _vp, _vp, _f, _f, _i]),

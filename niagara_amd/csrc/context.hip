@@ -64,6 +64,9 @@ int launch_shade_final(hipStream_t, const NvShadeData& sd, const uint32_t* gbuff
                        uint32_t* color, uint32_t width, uint32_t height, uint32_t maxBlocks, const uint32_t* bloom, uint32_t bloomWidth, uint32_t bloomHeight);
 int launch_shadow_trace(hipStream_t, const NvShadowData& sd, const void* scene, const float* depth, uint8_t* shadow, uint32_t width, uint32_t height, int quality,
                         uint32_t maxBlocks);
+int launch_shadow_trace_alpha(hipStream_t, const NvShadowData& sd, const void* scene, const float* depth, uint8_t* shadow, uint32_t width, uint32_t height,
+                              const NvMeshDraw* draws, uint32_t drawCount, const NvMaterial* materials, uint32_t materialCount, const NvTextureDesc* textures,
+                              uint32_t textureCount, const uint32_t* texels, unsigned long long texelWords, uint32_t maxBlocks);
 int launch_bloom_extract(hipStream_t, const uint32_t* gbuffer0, uint32_t width, uint32_t height, uint32_t* bloom, const NvBloomDesc& desc, uint32_t maxBlocks);
 int launch_bloom_downsample(hipStream_t, uint32_t* bloom, const NvBloomDesc& desc, uint32_t level);
 int launch_bloom_upsample(hipStream_t, uint32_t* bloom, const NvBloomDesc& desc, uint32_t level, float radius);
@@ -171,6 +174,7 @@ struct nv_context
 	uint32_t attributesPerPixel; // experiments: nv_visibility_attributes without the per-run set-up
 	void* rtScene;               // nv_rt_scene_upload: the device copy of the validated scene blob nv_shadow_trace walks
 	uint64_t rtSceneBytes;       // of the static blob (a dynamic reservation's allocation is rtPlan.bytes)
+	uint32_t rtSceneFlags;       // the uploaded blob's header flags (RT_FLAG_*): a rebuild and a re-housing keep them
 	nv::TlasPlan rtPlan;         // nv_rt_scene_reserve_dynamic: where the dynamic sections and the rebuild's scratch lie; maxDraws == 0 = static
 };
 
@@ -1362,6 +1366,7 @@ int nv_rt_scene_upload(nv_context* ctx, void* stream, const void* blob, uint64_t
 		scratch_free(ctx->rtScene);
 	ctx->rtScene = fresh;
 	ctx->rtSceneBytes = bytes;
+	ctx->rtSceneFlags = blob ? static_cast<const nv::RtHeader*>(blob)->flags : 0u;
 	memset(&ctx->rtPlan, 0, sizeof(ctx->rtPlan)); // static again
 	return NV_OK;
 }
@@ -1482,6 +1487,24 @@ int nv_shadow_trace(nv_context* ctx, void* stream, const NvShadowData* shadow, c
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	return nv::launch_shadow_trace((hipStream_t)stream, *shadow, ctx->rtScene, d_depth, d_shadow, width, height, quality, persistent_grid(ctx, 8));
+}
+
+// the alpha-tested trace (shadowtrace_alpha.hip); quality 0 has no alpha test and is nv_shadow_trace's launch
+int nv_shadow_trace_textured(nv_context* ctx, void* stream, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width, uint32_t height,
+                             int quality, const NvMeshDraw* d_draws, uint32_t drawCount, const NvMaterial* d_materials, uint32_t materialCount,
+                             const NvTextureDesc* d_textures, uint32_t textureCount, const uint32_t* d_texels, uint64_t texelWords)
+{
+	const auto misaligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+	if (!ctx || !ctx->rtScene || !shadow || !d_depth || !d_shadow || !shade_size_ok(width, height) || shadow->imageSize[0] != (float)width ||
+	    shadow->imageSize[1] != (float)height || quality < 0 || quality > 1 || misaligned(d_depth, 3u) || !(ctx->rtSceneFlags & nv::RT_FLAG_TEXCOORDS) ||
+	    (drawCount && !d_draws) || (materialCount && !d_materials) || (textureCount && !d_textures) || (texelWords && !d_texels) || misaligned(d_draws, 15u) ||
+	    misaligned(d_materials, 15u) || misaligned(d_textures, 15u) || misaligned(d_texels, 3u))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	if (quality == 0)
+		return nv::launch_shadow_trace((hipStream_t)stream, *shadow, ctx->rtScene, d_depth, d_shadow, width, height, 0, persistent_grid(ctx, 8));
+	return nv::launch_shadow_trace_alpha((hipStream_t)stream, *shadow, ctx->rtScene, d_depth, d_shadow, width, height, d_draws, drawCount, d_materials,
+	                                     materialCount, d_textures, textureCount, d_texels, texelWords, persistent_grid(ctx, 8));
 }
 
 // ---- bloom (bloom.hip)

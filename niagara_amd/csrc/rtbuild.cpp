@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/niagara_vis.h"
+#include "rtalpha.h"
 #include "rtmath.h"
 #include "rttlas.h"
 
@@ -19,6 +20,7 @@ namespace
 
 using namespace nv;
 
+static_assert(sizeof(TxDesc) == sizeof(NvTextureDesc) && sizeof(NvMeshDraw) == 48 && sizeof(NvMaterial) == 64, "the alpha test's records");
 static_assert(sizeof(RtHeader) == 64 && sizeof(RtBlas) == 32 && sizeof(RtNode) == 32 && sizeof(RtInstance) == 64 && sizeof(RtF4) == 16, "blob records");
 
 float half_to_float(uint32_t h) // exact
@@ -105,6 +107,7 @@ void build_nodes(std::vector<RtNode>& nodes, std::vector<uint32_t>& order, const
 struct Tri
 {
 	float v[3][3];
+	uint32_t tc[3]; // tu | tv << 16 of each corner
 };
 
 // the kept triangles of meshes[mi].lods[lodRT] (the rule of include/niagara_vis.h)
@@ -134,6 +137,7 @@ void mesh_triangles(const NvMesh& mesh, const uint32_t* indices, uint32_t indexC
 			}
 			const NvVertex& v = vertices[corner];
 			tri.v[k][0] = half_to_float(v.vx), tri.v[k][1] = half_to_float(v.vy), tri.v[k][2] = half_to_float(v.vz);
+			tri.tc[k] = (uint32_t)v.tu | (uint32_t)v.tv << 16;
 		}
 		if (keep)
 			out.push_back(tri);
@@ -180,6 +184,7 @@ int rt_pack_blob(const RtHeader& src, const RtBlas* table, const RtNode* tlas, u
 	h.meshCount = src.meshCount, h.tlasNodes = tlasNodes, h.instances = instances;
 	h.blasNodes = src.blasNodes, h.triangles = src.triangles, h.drawCount = drawCount;
 	h.padOrigin = padOrigin;
+	h.flags = src.flags; // the triangles are src's: what their w words mean goes with them
 	const uint64_t sizes[5] = { (uint64_t)h.meshCount * sizeof(RtBlas), (uint64_t)tlasNodes * sizeof(RtNode), (uint64_t)instances * sizeof(RtInstance),
 		                        (uint64_t)h.blasNodes * sizeof(RtNode), (uint64_t)h.triangles * 48u };
 	const void* parts[5] = { table, tlas, inst, blas, tris };
@@ -249,10 +254,20 @@ void tlas_emit(std::vector<RtNode>& nodes, const std::vector<uint64_t>& strings,
 
 } // namespace
 
-extern "C" {
+namespace
+{
 
-int nv_rt_scene_build(const NvMesh* meshes, uint32_t meshCount, const uint32_t* indices, uint32_t indexCapacity, const NvVertex* vertices,
-                      uint32_t vertexCapacity, const NvMeshDraw* draws, uint32_t drawCount, void* out, uint64_t* bytes)
+// a float with the bits `u`: a triangle's w word is carried, never computed with
+float bits_as_float(uint32_t u)
+{
+	float f;
+	memcpy(&f, &u, 4);
+	return f;
+}
+
+// nv_rt_scene_build (texcoords false: w = 0, flags = 0) and nv_rt_scene_build_textured (the corners' packed texcoords in w, RT_FLAG_TEXCOORDS)
+int scene_build(const NvMesh* meshes, uint32_t meshCount, const uint32_t* indices, uint32_t indexCapacity, const NvVertex* vertices, uint32_t vertexCapacity,
+                const NvMeshDraw* draws, uint32_t drawCount, void* out, uint64_t* bytes, bool texcoords)
 {
 	if (!bytes || (meshCount && !meshes) || (indexCapacity && !indices) || (vertexCapacity && !vertices) || (drawCount && !draws) ||
 	    (reinterpret_cast<uintptr_t>(out) & 15u))
@@ -305,7 +320,8 @@ int nv_rt_scene_build(const NvMesh* meshes, uint32_t meshCount, const uint32_t* 
 				             { blasNodes[e.nodeFirst].hi[0], blasNodes[e.nodeFirst].hi[1], blasNodes[e.nodeFirst].hi[2] } };
 			for (uint32_t t = 0; t < e.triCount; ++t) // leaf order
 				for (int c = 0; c < 3; ++c)
-					tris.push_back(RtF4{ meshTris[order[t]].v[c][0], meshTris[order[t]].v[c][1], meshTris[order[t]].v[c][2], 0.0f });
+					tris.push_back(RtF4{ meshTris[order[t]].v[c][0], meshTris[order[t]].v[c][1], meshTris[order[t]].v[c][2],
+						                 texcoords ? bits_as_float(meshTris[order[t]].tc[c]) : 0.0f });
 		}
 		std::vector<RtInstance> instances;
 		boxes.clear();
@@ -335,6 +351,7 @@ int nv_rt_scene_build(const NvMesh* meshes, uint32_t meshCount, const uint32_t* 
 		h.meshCount = meshCount, h.tlasNodes = (uint32_t)tlasNodes.size(), h.instances = (uint32_t)instances.size();
 		h.blasNodes = (uint32_t)blasNodes.size(), h.triangles = (uint32_t)(tris.size() / 3u), h.drawCount = drawCount;
 		h.padOrigin = tl_pad_origin(cOmax);
+		h.flags = texcoords ? RT_FLAG_TEXCOORDS : 0u;
 		uint64_t at = sizeof(RtHeader);
 		const uint64_t tableOff = at;
 		at = align16(at + table.size() * sizeof(RtBlas));
@@ -379,10 +396,26 @@ int nv_rt_scene_build(const NvMesh* meshes, uint32_t meshCount, const uint32_t* 
 	}
 }
 
+} // namespace
+
+extern "C" {
+
+int nv_rt_scene_build(const NvMesh* meshes, uint32_t meshCount, const uint32_t* indices, uint32_t indexCapacity, const NvVertex* vertices,
+                      uint32_t vertexCapacity, const NvMeshDraw* draws, uint32_t drawCount, void* out, uint64_t* bytes)
+{
+	return scene_build(meshes, meshCount, indices, indexCapacity, vertices, vertexCapacity, draws, drawCount, out, bytes, false);
+}
+
+int nv_rt_scene_build_textured(const NvMesh* meshes, uint32_t meshCount, const uint32_t* indices, uint32_t indexCapacity, const NvVertex* vertices,
+                               uint32_t vertexCapacity, const NvMeshDraw* draws, uint32_t drawCount, void* out, uint64_t* bytes)
+{
+	return scene_build(meshes, meshCount, indices, indexCapacity, vertices, vertexCapacity, draws, drawCount, out, bytes, true);
+}
+
 int nv_rt_scene_validate(const void* blob, uint64_t bytes)
 {
 	const RtHeader* h = checked_header(blob, bytes);
-	if (!h)
+	if (!h || (h->flags & ~RT_FLAGS_KNOWN)) // a flag this library does not know changes what the bytes mean: refused
 		return NV_EINVAL;
 	const unsigned char* p = static_cast<const unsigned char*>(blob);
 	const RtBlas* table = reinterpret_cast<const RtBlas*>(p + h->tableOff);
@@ -523,6 +556,43 @@ int nv_rt_scene_trace_host_rays(const void* blob, const float* origins, const fl
 		                     rt3{ dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2] }, tmin, tmax, (uint32_t)quality)
 		             ? 0
 		             : 255;
+	return NV_OK;
+}
+
+int nv_rt_scene_trace_host_textured_rays(const void* blob, const float* origins, const float* dirs, uint64_t count, float tmin, float tmax, int quality,
+                                         const NvMeshDraw* draws, uint32_t drawCount, const NvMaterial* materials, uint32_t materialCount,
+                                         const NvTextureDesc* textures, uint32_t textureCount, const uint32_t* texels, uint64_t texelWords, uint8_t* out)
+{
+	if (!blob || (count && (!origins || !dirs || !out)) || quality < 0 || quality > 1 || (drawCount && !draws) || (materialCount && !materials) ||
+	    (textureCount && !textures) || (texelWords && !texels) || !(static_cast<const RtHeader*>(blob)->flags & RT_FLAG_TEXCOORDS))
+		return NV_EINVAL;
+	if (quality == 0)
+		return nv_rt_scene_trace_host_rays(blob, origins, dirs, count, tmin, tmax, 0, out);
+	RtAlphaInputs in;
+	in.draws = draws, in.materials = materials, in.textures = reinterpret_cast<const TxDesc*>(textures), in.texels = texels;
+	in.texelWords = texelWords, in.drawCount = drawCount, in.materialCount = materialCount, in.textureCount = textureCount;
+	for (uint64_t i = 0; i < count; ++i)
+		out[i] = rt_occluded_alpha(static_cast<const unsigned char*>(blob), in, rt3{ origins[3 * i], origins[3 * i + 1], origins[3 * i + 2] },
+		                           rt3{ dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2] }, tmin, tmax)
+		             ? 0
+		             : 255;
+	return NV_OK;
+}
+
+int nv_rt_alpha_sample_host(const NvTextureDesc* desc, const uint32_t* texels, uint64_t texelWords, const float* uv, uint64_t count, float* fourTap,
+                            float* sampler)
+{
+	if (!desc || !texels || (count && (!uv || !fourTap || !sampler)))
+		return NV_EINVAL;
+	TxDesc t;
+	memcpy(&t, desc, sizeof(t));
+	if (!tx_desc_ok(t, texelWords))
+		return NV_EINVAL;
+	for (uint64_t i = 0; i < count; ++i)
+	{
+		fourTap[i] = rt_alpha_lod0(texels, t, uv[2 * i], uv[2 * i + 1]);
+		sampler[i] = tx_sample_lod0(texels, t, uv[2 * i], uv[2 * i + 1]).w;
+	}
 	return NV_OK;
 }
 

@@ -42,7 +42,7 @@ struct RtHeader // 64 bytes
 	uint32_t tableOff, tlasOff, instOff, blasOff;
 	uint32_t triOff;
 	float padOrigin; // the TLAS boxes' ray-dependent padding per unit of max |origin component| (RT_PAD_K u times the worst instance's factor)
-	uint32_t drawCount, reserved;
+	uint32_t drawCount, flags; // flags: RT_FLAG_* (0 in nv_rt_scene_build's blob)
 };
 struct RtBlas // 32 bytes = two RtF4
 {
@@ -63,7 +63,10 @@ struct RtInstance // 64 bytes: {position, scale} {orientation} {drawId, postPass
 	float position[3], scale, orientation[4];
 	uint32_t drawId, postPass, blas, reserved[5];
 };
-// a triangle is three RtF4 {v.x, v.y, v.z, 0}, in leaf order
+// a triangle is three RtF4 {v.x, v.y, v.z, w}, in leaf order; w is 0, or with RT_FLAG_TEXCOORDS the BITS tu | tv << 16 of the corner's fp16 texcoord
+// (never a number: rtalpha.h reads them with rt_bits)
+constexpr uint32_t RT_FLAG_TEXCOORDS = 1u; // nv_rt_scene_build_textured wrote the blob
+constexpr uint32_t RT_FLAGS_KNOWN = RT_FLAG_TEXCOORDS;
 
 // ---- margins of the box test
 constexpr float RT_U = 5.9604644775390625e-8f; // 2^-24

@@ -78,21 +78,24 @@ def build_shadow_data(globals_, sun_direction=(0, 1, 0), sun_jitter=0.0, checker
 RT_TMIN, RT_TMAX = 1e-2, 1e3  # shadow.comp.glsl:81
 
 
-def rt_scene_build(meshes, indices, vertices, draws):
+def rt_scene_build(meshes, indices, vertices, draws, texcoords=False):
     """The scene blob of the ray-traced shadow pass (nv_rt_scene_build; host only): one BLAS per mesh with triangles (lods[lodRT], through the
-    index buffer of the classic path) and one TLAS over the casting draws.  Returns a 16-byte aligned uint8 array"""
+    index buffer of the classic path) and one TLAS over the casting draws.  texcoords: nv_rt_scene_build_textured, the blob the alpha-tested
+    trace walks (the corners' fp16 texcoords in the triangles' w words, header flag bit 0).  Returns a 16-byte aligned uint8 array"""
+    build = lib.nv_rt_scene_build_textured if texcoords else lib.nv_rt_scene_build
+    name = "nv_rt_scene_build_textured" if texcoords else "nv_rt_scene_build"
     m = np.ascontiguousarray(meshes, L.MESH)
     i = np.ascontiguousarray(indices, np.uint32)
     v = np.ascontiguousarray(vertices, L.VERTEX)
     d = np.ascontiguousarray(draws, L.MESHDRAW)
     args = (_p(m) if len(m) else None, len(m), _p(i) if len(i) else None, len(i), _p(v) if len(v) else None, len(v), _p(d) if len(d) else None, len(d))
     n = C.c_uint64(0)
-    check(lib.nv_rt_scene_build(*args, None, C.byref(n)), "nv_rt_scene_build")
+    check(build(*args, None, C.byref(n)), name)
     raw = np.zeros(n.value + 16, np.uint8)
     off = (-raw.ctypes.data) % 16
     blob = raw[off:off + n.value]
     room = C.c_uint64(n.value)
-    check(lib.nv_rt_scene_build(*args, _p(blob), C.byref(room)), "nv_rt_scene_build")
+    check(build(*args, _p(blob), C.byref(room)), name)
     assert room.value == n.value
     return blob
 
@@ -138,6 +141,33 @@ def rt_scene_trace_host(blob, origins, dirs, quality=1, tmin=RT_TMIN, tmax=RT_TM
     out = np.zeros(len(o), np.uint8)
     check(lib.nv_rt_scene_trace_host_rays(_p(blob), _p(o), _p(d), len(o), float(tmin), float(tmax), int(quality), _p(out)), "nv_rt_scene_trace_host_rays")
     return out
+
+
+def rt_scene_trace_host_textured(blob, origins, dirs, draws, materials, textures, texels, quality=1, tmin=RT_TMIN, tmax=RT_TMAX, texel_words=None):
+    """nv_shadow_trace_textured's traversal on the CPU (nv_rt_scene_trace_host_textured_rays) for (n, 3) float32 rays over a blob built with
+    texcoords=True: draws (layouts.MESHDRAW), materials (layouts.MATERIAL), textures (layouts.TEXTUREDESC, entry 0 reserved) and texels
+    (uint32, the decoded RGBA8 set) are host arrays; texel_words defaults to len(texels).  The mask's bytes, 0 = occluded, 255 = not"""
+    o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    assert o.shape == d.shape
+    dr, m = np.ascontiguousarray(draws, L.MESHDRAW), np.ascontiguousarray(materials, L.MATERIAL)
+    t, x = np.ascontiguousarray(textures, L.TEXTUREDESC), np.ascontiguousarray(texels, np.uint32)
+    out = np.zeros(len(o), np.uint8)
+    opt = lambda a: _p(a) if len(a) else None
+    check(lib.nv_rt_scene_trace_host_textured_rays(_p(blob), _p(o), _p(d), len(o), float(tmin), float(tmax), int(quality), opt(dr), len(dr), opt(m), len(m),
+                                                   opt(t), len(t), opt(x), len(x) if texel_words is None else int(texel_words), _p(out)),
+          "nv_rt_scene_trace_host_textured_rays")
+    return out
+
+
+def rt_alpha_sample_host(desc, texels, uv):
+    """(four_tap, sampler): the alpha-tested trace's four-tap alpha and textureLod(..., 0).w of the full sampler at (n, 2) float32 uv
+    (nv_rt_alpha_sample_host; a test accessor: the two agree bit for bit)"""
+    d, x = np.ascontiguousarray(desc, L.TEXTUREDESC).reshape(1), np.ascontiguousarray(texels, np.uint32)
+    u = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    a, b = np.zeros(len(u), np.float32), np.zeros(len(u), np.float32)
+    check(lib.nv_rt_alpha_sample_host(_p(d), _p(x), len(x), _p(u), len(u), _p(a), _p(b)), "nv_rt_alpha_sample_host")
+    return a, b
 
 
 def synth_draws(n, mesh_count, scene_radius=300.0):

@@ -263,9 +263,9 @@ class Context:
         check(lib.nv_shadow_blur(self.h, _stream(), _ptr(out), _ptr(shadow), _ptr(depth), int(width), int(height), int(direction), float(znear)),
               "nv_shadow_blur")
 
-    def rt_scene_build(self, meshes, indices, vertices, draws):
-        """the scene blob of the shadow trace (host.rt_scene_build; host only)"""
-        return host.rt_scene_build(meshes, indices, vertices, draws)
+    def rt_scene_build(self, meshes, indices, vertices, draws, texcoords=False):
+        """the scene blob of the shadow trace (host.rt_scene_build; host only); texcoords: the blob shadow_trace_textured walks"""
+        return host.rt_scene_build(meshes, indices, vertices, draws, texcoords=texcoords)
 
     def rt_scene_upload(self, blob):
         """validate the blob and keep a context-owned device copy (nv_rt_scene_upload: load time, synchronises); None drops it"""
@@ -293,6 +293,17 @@ class Context:
         check(lib.nv_rt_scene_download(self.h, _stream(), C.c_void_p(out.ctypes.data), C.byref(room)), "nv_rt_scene_download")
         assert room.value == n.value
         return out
+
+    def shadow_trace_textured(self, shadow_data, depth, shadow, width, height, quality, draws, draw_count, materials, material_count, textures,
+                              texture_count, texels, texel_words):
+        """shadow_trace with the alpha test of shadow.comp.glsl:86-123 (nv_shadow_trace_textured): at quality 1 a hit on a post-pass instance
+        counts only where its material's albedo texture has alpha >= 0.5.  The uploaded scene was built with texcoords=True; draws = the device
+        draw array its instances index, materials = a device table of layouts.MATERIAL, textures / texels = texture_decode's set.  One launch,
+        can be captured"""
+        check(lib.nv_shadow_trace_textured(self.h, _stream(), C.c_void_p(shadow_data.ctypes.data) if shadow_data is not None else None, _ptr(depth),
+                                           _ptr(shadow), int(width), int(height), int(quality), _ptr(draws), int(draw_count), _ptr(materials),
+                                           int(material_count), _ptr(textures), int(texture_count), _ptr(texels), int(texel_words)),
+              "nv_shadow_trace_textured")
 
     def shadow_trace(self, shadow_data, depth, shadow, width, height, quality=1):
         """shadow.comp.glsl (nv_shadow_trace): the u8 sun shadow mask (0 = in shadow, 255 = lit) of the depth target from the uploaded scene;
@@ -435,6 +446,7 @@ class VisibilityPipeline:
         self.mdb = self.vb = self.ib = self.depth = None
         self.bloom_image = self.bloom_desc = None  # shade(bloom=True)'s target, allocated on first use
         self.rt_dynamic = False                    # build_rt_scene(dynamic=True): move_draws rebuilds the TLAS
+        self.rt_texcoords = False                  # build_rt_scene(texcoords=True): shade(shadow="trace", textures=True) can run its alpha test
         self.rt_scene = self.shadow_image = None   # build_rt_scene's blob; shade(shadow="trace")'s mask, allocated on first use
         self.index_count = self.vertex_count = 0
         if vertices is not None and (meshlet_data is not None or indices is not None):
@@ -579,13 +591,16 @@ class VisibilityPipeline:
                                        out["attributes"], out["gbuffer0"], out["gbuffer1"], out["totals"])
         return out
 
-    def build_rt_scene(self, meshes, indices, vertices, draws, dynamic=False):
+    def build_rt_scene(self, meshes, indices, vertices, draws, dynamic=False, texcoords=False):
         """build the ray-tracing scene of shade(shadow="trace") on the host and upload it, once per scene (niagara builds its BLAS / TLAS at
         load time, src/scenert.cpp): `meshes` with their LODs' index ranges set (synth.indexed_geometry) and the index buffer of the classic
         path.  The scene is static: call again when draws move — or pass dynamic=True, which reserves room for a TLAS over the pipeline's
-        draw count (nv_rt_scene_reserve_dynamic), and move the draws through move_draws, which rebuilds the TLAS on the device.  Returns the
-        blob"""
-        self.rt_scene = self.ctx.rt_scene_build(meshes, indices, vertices, draws)
+        draw count (nv_rt_scene_reserve_dynamic), and move the draws through move_draws, which rebuilds the TLAS on the device.
+        texcoords=True builds the scene shade(shadow="trace", textures=True) needs (nv_rt_scene_build_textured).  Returns the blob"""
+        if texcoords and isinstance(self, ShardedVisibilityPipeline):
+            raise NvError("build_rt_scene(texcoords=True) is not available on a sharded pipeline")
+        self.rt_scene = self.ctx.rt_scene_build(meshes, indices, vertices, draws, texcoords=texcoords)
+        self.rt_texcoords = bool(texcoords)
         self.ctx.rt_scene_upload(self.rt_scene)
         if dynamic and isinstance(self, ShardedVisibilityPipeline):
             raise NvError("build_rt_scene(dynamic=True) is not available on a sharded pipeline")
@@ -616,14 +631,17 @@ class VisibilityPipeline:
         if getattr(self, "rt_dynamic", False):
             self.ctx.rt_tlas_build(self.db, self.draw_count)
 
-    def shade(self, cull_data, gbuffer0, gbuffer1, camera_position, sun_direction, shadow=None, blur=True, checkerboard=False, bloom=False, quality=1):
+    def shade(self, cull_data, gbuffer0, gbuffer1, camera_position, sun_direction, shadow=None, blur=True, checkerboard=False, bloom=False, quality=1,
+              textures=False, materials=None):
         """the shading end of the frame over attributes()'s G-buffer words and the pipeline's own depth target (src/niagara.cpp:1792-1850,
         1906-1925): returns the colour tensor (int32, height x width, R8G8B8A8 with R in the low byte).  shadow: a caller-supplied mask (uint8
         tensor, height x width) — it is filled in place when `checkerboard`, blurred horizontally into an image
         the pipeline owns and vertically back into the mask when `blur`, and final shades with shadows on; without a mask final runs
         with shadows off.  shadow="trace" (after build_rt_scene): the mask is ray traced first (nv_shadow_trace with `quality`, sunJitter 1e-2
         when `blur`, else 0, one checkerboard parity when `checkerboard`) into a mask the pipeline owns (self.shadow_image), then treated the
-        same way.  bloom: run the bloom chain over gbuffer0 into a target the pipeline owns (self.bloom_image, self.bloom_desc) and
+        same way.  textures=True (with shadow="trace"): the trace runs the alpha test of shadow.comp.glsl:86-123 (nv_shadow_trace_textured) over
+        set_textures()'s set, `materials` (a host array of layouts.MATERIAL or a device tensor of them) and a scene built with
+        build_rt_scene(..., texcoords=True); NvError names whichever of the three is missing.  bloom: run the bloom chain over gbuffer0 into a target the pipeline owns (self.bloom_image, self.bloom_desc) and
         add its term in final (src/niagara.cpp:1866-1904); the default leaves it out, as before"""
         if self.depth is None:
             raise NvError("shade reads the pipeline's depth target: VisibilityPipeline(..., meshlet_data=, vertices=)")
@@ -639,7 +657,21 @@ class VisibilityPipeline:
                 self.shadow_image = torch.zeros((h, w), dtype=torch.uint8, device=dev)
             shadow = self.shadow_image
             sh = host.build_shadow_data(g, sun_direction, 1e-2 if blur else 0.0, 1 if checkerboard else 0, w, h)  # src/niagara.cpp:1810-1815
-            self.ctx.shadow_trace(sh, self.depth, shadow, w, h, quality)
+            if textures:
+                if isinstance(self, ShardedVisibilityPipeline):
+                    raise NvError("shade(shadow=\"trace\", textures=True) is not available on a sharded pipeline")
+                missing = [what for what, absent in (("set_textures()", getattr(self, "texture_table", None) is None),
+                                                     ("a material table (materials=)", materials is None),
+                                                     ("a scene with texcoords (build_rt_scene(..., texcoords=True))", not getattr(self, "rt_texcoords", False)))
+                           if absent]
+                if missing:
+                    raise NvError("shade(shadow=\"trace\", textures=True) needs " + ", ".join(missing))
+                mat = to_device(np.ascontiguousarray(materials, L.MATERIAL), dev) if isinstance(materials, np.ndarray) else materials
+                self.ctx.shadow_trace_textured(sh, self.depth, shadow, w, h, quality, self.db, self.draw_count, mat,
+                                               mat.numel() * mat.element_size() // L.MATERIAL.itemsize, self.texture_table, len(self.texture_descs),
+                                               self.texels, self.texels.numel())
+            else:
+                self.ctx.shadow_trace(sh, self.depth, shadow, w, h, quality)
         if shadow is not None:
             if shadow.dtype != torch.uint8 or shadow.numel() != w * h or not shadow.is_contiguous():
                 raise NvError("shade: the shadow mask is a contiguous uint8 tensor of the depth target's size")

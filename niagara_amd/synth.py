@@ -411,11 +411,16 @@ def _expand565(code):
     return np.stack([(r * 255 + 15) // 31, (g * 255 + 31) // 63, (b * 255 + 15) // 31], -1).astype(np.int64)
 
 
-def bc1_encode(image):
+def bc1_encode(image, cutout=False):
     """a minimal BC1 encoder: image (h, w, 3 or 4) uint8 -> the blocks' bytes, row-major.  Per block the endpoints are the per-channel maximum
     and minimum (c0 > c1: the four-colour mode; a flat block stores c0 = c1 and index 0), every texel takes the nearest of the four colours.
-    Partial blocks repeat the edge texels.  Alpha is ignored (BC1 here is opaque)"""
-    img = np.asarray(image, np.uint8)[..., :3]
+    Partial blocks repeat the edge texels.  Alpha is ignored (BC1 here is opaque) unless `cutout`: then a block with a texel of alpha < 128
+    is stored in the punch-through mode (c0 <= c1: two endpoints and their half, index 3 = transparent black), its transparent texels take
+    index 3 and the others the nearest of the three colours; blocks without such a texel are encoded as before"""
+    full = np.asarray(image, np.uint8)
+    if cutout and full.shape[-1] == 4:
+        return _bc1_encode_cutout(full)
+    img = full[..., :3]
     h, w = img.shape[:2]
     img = np.pad(img, ((0, -h % 4), (0, -w % 4), (0, 0)), mode="edge")
     bh, bw = img.shape[0] // 4, img.shape[1] // 4
@@ -434,6 +439,31 @@ def bc1_encode(image):
     return out.tobytes()
 
 
+def _bc1_encode_cutout(image):
+    """bc1_encode(image, cutout=True): the opaque encoding with the blocks that hold a transparent texel replaced by punch-through blocks"""
+    h, w = image.shape[:2]
+    out = np.frombuffer(bc1_encode(image[..., :3]), np.uint32).reshape(-1, 2).copy()
+    img = np.pad(image, ((0, -h % 4), (0, -w % 4), (0, 0)), mode="edge")
+    bh, bw = img.shape[0] // 4, img.shape[1] // 4
+    blocks = img.reshape(bh, 4, bw, 4, 4).transpose(0, 2, 1, 3, 4).reshape(bh * bw, 16, 4)
+    clear = blocks[:, :, 3] < 128
+    punch = clear.any(axis=1)
+    if not punch.any():
+        return out.tobytes()
+    b, t = blocks[punch][:, :, :3], clear[punch]
+    solid = np.where(t[:, :, None], 0, b)  # the endpoints come from the opaque texels alone (a block without one stores black)
+    low = np.where(t[:, :, None], 255, b)
+    hi, lo = _rgb565(solid.max(axis=1)), _rgb565(np.where(t.all(axis=1)[:, None], 0, low.min(axis=1)))
+    c0, c1 = np.minimum(hi, lo), np.maximum(hi, lo)  # c0 <= c1: the three-colour mode
+    e0, e1 = _expand565(c0), _expand565(c1)
+    palette = np.stack([e0, e1, (e0 + e1) // 2], axis=1)
+    dist = ((b[:, :, None, :].astype(np.int64) - palette[:, None, :, :]) ** 2).sum(-1)
+    idx = np.where(t, 3, dist.argmin(-1)).astype(np.uint32)
+    out[punch, 0] = c0.astype(np.uint32) | c1.astype(np.uint32) << 16
+    out[punch, 1] = (idx << (2 * np.arange(16, dtype=np.uint32))[None, :]).sum(axis=1).astype(np.uint32)
+    return out.tobytes()
+
+
 def _half_image(img):
     """the next mip level: max(1, side // 2) per axis, the mean of the 2 x 2 (or 2 x 1, 1 x 2) source texels"""
     h, w = img.shape[:2]
@@ -444,14 +474,14 @@ def _half_image(img):
     return ((s[ys][:, xs] + s[ys][:, xs1] + s[ys1][:, xs] + s[ys1][:, xs1] + 2) // 4).astype(np.uint8)
 
 
-def dds_bytes(image, mips=True):
+def dds_bytes(image, mips=True, cutout=False):
     """a DDS file image as niagara's loadImage accepts it (src/textures.cpp:159-210): FourCC DXT1, the BC1 blocks of `image` and, with mips,
-    of its whole chain down to 1 x 1"""
+    of its whole chain down to 1 x 1; cutout: bc1_encode's punch-through alpha"""
     img = np.asarray(image, np.uint8)
     h, w = img.shape[:2]
     levels, payload = 0, b""
     while True:
-        payload += bc1_encode(img)
+        payload += bc1_encode(img, cutout)
         levels += 1
         if not mips or (img.shape[0] == 1 and img.shape[1] == 1):
             break
@@ -483,13 +513,20 @@ def texture_images(size=64):
     return [np.rint(np.clip(i, 0, 1) * 255).astype(np.uint8) for i in (albedo, normal, spec, emissive)]
 
 
-def with_textures(scene, size=64, mips=True):
-    """a copy of a scene dict with "textures" — four DDS file images (BC1): a checker albedo, a bump normal map, a specular map and an emissive
+def with_textures(scene, size=64, mips=True, cutout=False):
+    """cutout: the albedo's darker checker cells are transparent (alpha 0, BC1 punch-through): a cut-out caster for the alpha-tested shadow
+    trace.  A copy of a scene dict with "textures" — four DDS file images (BC1): a checker albedo, a bump normal map, a specular map and an emissive
     map, textures[1..4] of the set — and a material table ("materials"; created with five entries spread over the draws when the scene has
     none) whose every entry names all four.  Vertices without texcoords (all zero, as make_geometry leaves them) get a planar map of their
     positions"""
     s = dict(scene)
-    s["textures"] = [dds_bytes(i, mips) for i in texture_images(size)]
+    images = texture_images(size)
+    if cutout:
+        cell = size // 8 or 1
+        y, x = np.mgrid[0:size, 0:size]
+        images[0] = images[0].copy()
+        images[0][..., 3] = np.where((x // cell + y // cell) % 2 == 1, 0, 255)
+    s["textures"] = [dds_bytes(img, mips, cutout and k == 0) for k, img in enumerate(images)]
     if "materials" in s:
         m = s["materials"].copy()
     else:

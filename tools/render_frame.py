@@ -7,6 +7,7 @@
     python3 tools/render_frame.py --bloom                               # two materials emit; the bloom chain and final's bloom term
     python3 tools/render_frame.py --traced-shadows                      # the mask is ray traced (nv_shadow_trace)
     python3 tools/render_frame.py --traced-shadows --animate 8          # 8 images, one box on a circle: its shadow follows (§4.17)
+    python3 tools/render_frame.py --alpha-shadows                       # the wall is a cut-out in the post pass: its shadow has holes (§4.19)
 
 Writes a binary PPM (P6, R G B from the R8G8B8A8 colour words) and prints one JSON line with the passes' times by HIP events (one run
 each after a warm-up frame: launch gaps included, an upper bound of the kernel time; profiles/r13_shade.md has the kernel trace).
@@ -150,6 +151,9 @@ def trace_passes(args):
     vis = pipe.new_visibility()
     for _ in range(2):
         pipe.frame(s["cull"], post_pass=True, visibility=vis)
+    if args.alpha_shadows:
+        alpha_passes(args, s, pipe)
+        return
     blob = pipe.build_rt_scene(s["meshes"], s["indices"], s["vertices"], s["draws"])
     ctx, dev = pipe.ctx, pipe.ctx.device
     flush = torch.zeros(512 << 20, dtype=torch.uint8, device=dev)
@@ -186,6 +190,50 @@ def trace_passes(args):
     ctx.close()
 
 
+def alpha_passes(args, s, pipe):
+    """--alpha-shadows --passes shadow_trace: nv_shadow_trace_textured against nv_shadow_trace at quality 1 on the same scene blob and depth target,
+    the wall a cut-out in the post pass; alternating, every launch behind a flush of the caches"""
+    import numpy as np
+    import torch
+
+    from niagara_amd import host, synth
+    from niagara_amd import pipeline as P
+    w, h = s["viewport"]
+    t = synth.with_textures(dict(vertices=s["vertices"], draws=s["draws"]), cutout=True)
+    draws = t["draws"].copy()
+    draws["postPass"][s["wall"]] = 1
+    ctx, dev = pipe.ctx, pipe.ctx.device
+    pipe.set_textures(t["textures"])
+    blob = ctx.rt_scene_build(s["meshes"], s["indices"], t["vertices"], draws, texcoords=True)
+    ctx.rt_scene_upload(blob)
+    db, mat = P.to_device(draws, dev), P.to_device(t["materials"], dev)
+    flush = torch.zeros(512 << 20, dtype=torch.uint8, device=dev)
+    mask = torch.zeros((h, w), dtype=torch.uint8, device=dev)
+    sun = np.array([2.0, 0.3, 1.0]) / np.linalg.norm([2.0, 0.3, 1.0])
+    sd = host.build_shadow_data(synth.make_globals(s["cull"], (w, h)), sun, 0.0, 0, w, h)
+    runs = dict(opaque=lambda: ctx.shadow_trace(sd, pipe.depth, mask, w, h, 1),
+                alpha=lambda: ctx.shadow_trace_textured(sd, pipe.depth, mask, w, h, 1, db, len(draws), mat, len(t["materials"]), pipe.texture_table,
+                                                        len(pipe.texture_descs), pipe.texels, pipe.texels.numel()))
+    line = dict(size="%dx%d" % (w, h), covered=int((pipe.depth > 0).sum().item()), scene=host.rt_scene_stats(blob))
+    times = {name: [] for name in runs}
+    for name, run in runs.items():
+        run()  # warm-up
+        line["occluded_" + name] = int((mask == 0).sum().item())
+    for _ in range(args.repeats):
+        for name, run in runs.items():
+            flush.add_(1)
+            ev = []
+            _timed(ev, name, run)
+            torch.cuda.synchronize()
+            times[name].append(ev[0][1].elapsed_time(ev[0][2]) * 1e3)
+    for name, v in times.items():
+        v = sorted(v)
+        line["shadow_trace_" + name] = dict(us_median=round(v[len(v) // 2], 2), us_min=round(v[0], 2), us_max=round(v[-1], 2))
+    print(json.dumps(line), flush=True)
+    ctx.status()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="frame.ppm")
@@ -196,12 +244,16 @@ def main():
     ap.add_argument("--textures", action="store_true", help="synth.with_textures' checker albedo, bump normal map, specular and emissive maps through "
                     "nv_visibility_attributes_textured (DESIGN.md §4.18)")
     ap.add_argument("--traced-shadows", action="store_true", help="ray trace the shadow mask (the default stays the synthetic mask)")
+    ap.add_argument("--alpha-shadows", action="store_true", help="--traced-shadows --textures with the wall in the post pass and a cut-out albedo: the trace "
+                    "runs the alpha test (nv_shadow_trace_textured, DESIGN.md §4.19) and the wall's shadow has the checker's holes")
     ap.add_argument("--quality", type=int, default=1, help="--traced-shadows: 0 = opaque draws cast, 1 = post-pass draws too")
     ap.add_argument("--animate", type=int, default=0, help="--traced-shadows: write N images (out_000.ppm ...) with one draw displaced along a circle "
                     "per frame through move_draws, which rebuilds the TLAS on the device")
     ap.add_argument("--passes", default=None, help="WxH[,WxH...], or shadow_trace (with --traced-shadows)")
     ap.add_argument("--repeats", type=int, default=9)
     args = ap.parse_args()
+    if args.alpha_shadows:
+        args.traced_shadows = args.textures = True
     if args.passes == "shadow_trace":
         if not args.traced_shadows:
             ap.error("--passes shadow_trace times the ray-traced pass: give --traced-shadows")
@@ -237,8 +289,10 @@ def main():
     textures = None
     if args.textures:
         from niagara_amd import synth
-        t = synth.with_textures(dict(vertices=v, draws=draws, materials=materials))  # planar texcoords, the four maps, materials that name them
+        t = synth.with_textures(dict(vertices=v, draws=draws, materials=materials), cutout=args.alpha_shadows)  # planar texcoords, the four maps, materials that name them
         v, materials, textures = t["vertices"], t["materials"], t["textures"]
+    if args.alpha_shadows:
+        draws["postPass"][s["wall"]] = 1  # the alpha test sees post-pass instances only (src/scenert.cpp:516)
     pipe = P.VisibilityPipeline(s["meshes"], s["meshlets"], draws, (w, h), fused=True, vertices=v, meshlet_data=s["data"], stable_ids=True)
     if textures:
         pipe.set_textures(textures)
@@ -248,7 +302,7 @@ def main():
     sun = np.array([0.35, 0.6, 0.72]) / np.linalg.norm([0.35, 0.6, 0.72])
     mat = P.to_device(materials, pipe.ctx.device)
     if args.traced_shadows and not args.no_shadow:
-        pipe.build_rt_scene(s["meshes"], s["indices"], v, draws, dynamic=args.animate > 0)
+        pipe.build_rt_scene(s["meshes"], s["indices"], v, draws, dynamic=args.animate > 0, texcoords=args.alpha_shadows)
 
     def frame(events):
         vis = pipe.new_visibility()
@@ -257,7 +311,8 @@ def main():
         att = _timed(events, "attributes", lambda: pipe.attributes(s["cull"], res["records"], mat, attributes=False, textures=args.textures))
         shadow = None if args.no_shadow else "trace" if args.traced_shadows else torch.from_numpy(mask.copy()).to(pipe.ctx.device)
         return _timed(events, "shade", lambda: pipe.shade(s["cull"], att["gbuffer0"], att["gbuffer1"], (0.0, 0.0, 0.0), sun, shadow=shadow,
-                                                          checkerboard=args.checkerboard, bloom=args.bloom, quality=args.quality))
+                                                          checkerboard=args.checkerboard, bloom=args.bloom, quality=args.quality,
+                                                          textures=args.alpha_shadows and isinstance(shadow, str), materials=mat))
     def write(path, color, events, extra):
         words = color.cpu().numpy().view(np.uint32)
         rgb = np.stack([(words >> np.uint32(8 * k)) & np.uint32(255) for k in range(3)], -1).astype(np.uint8)
