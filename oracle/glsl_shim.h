@@ -57,12 +57,16 @@ struct vec2
 	explicit vec2(float s) : x(s), y(s) {}
 	vec2(float x_, float y_) : x(x_), y(y_) {}
 	explicit vec2(uvec2 v) : x((float)v.x), y((float)v.y) {}
+	vec2 xy() const { return *this; }
+	vec2 yx() const { return vec2(y, x); }
 };
 struct ivec2
 {
 	int x, y;
 	ivec2() : x(0), y(0) {}
 	ivec2(int x_, int y_) : x(x_), y(y_) {}
+	explicit ivec2(int s) : x(s), y(s) {}
+	explicit ivec2(uint s) : x((int)s), y((int)s) {}
 	explicit ivec2(uvec2 v) : x((int)v.x), y((int)v.y) {}
 };
 struct uvec3
@@ -85,6 +89,7 @@ struct vec3
 	vec3(float x_, float y_, float z_) : x(x_), y(y_), z(z_) {}
 	vec3(vec2 v, float z_) : x(v.x), y(v.y), z(z_) {}
 	vec2 xy() const { return vec2(x, y); }
+	vec3 xyz() const { return *this; }
 };
 struct vec4
 {
@@ -93,6 +98,7 @@ struct vec4
 	explicit vec4(float s) : x(s), y(s), z(s), w(s) {}
 	vec4(float x_, float y_, float z_, float w_) : x(x_), y(y_), z(z_), w(w_) {}
 	vec4(vec3 v, float w_) : x(v.x), y(v.y), z(v.z), w(w_) {}
+	vec4(vec2 v, float z_, float w_) : x(v.x), y(v.y), z(z_), w(w_) {}
 	vec2 xy() const { return vec2(x, y); }
 	vec2 zw() const { return vec2(z, w); }
 	vec3 xyz() const { return vec3(x, y, z); }
@@ -190,11 +196,13 @@ inline vec2 max(vec2 a, vec2 b) { return vec2(max(a.x, b.x), max(a.y, b.y)); }
 inline float round(float x) { return rintf(x); }
 /* shading attributes (normal / tangent unpacking, src/shaders/math.h:131-136) are outside the visibility path: the
  * translation keeps only math.h:2-49, and the mesh shader's call resolves to this stub */
+#ifndef REF_SHADING /* the shading translation units carry math.h whole, unpackTBN included (glsl_shade_shim.h) */
 inline void unpackTBN(uint, uint, vec3& normal, vec4& tangent)
 {
 	normal = vec3(0, 0, 1);
 	tangent = vec4(1, 0, 0, 1);
 }
+#endif
 inline bvec2 lessThanEqual(vec2 a, vec2 b)
 {
 	bvec2 r = { a.x <= b.x, a.y <= b.y };
@@ -228,6 +236,12 @@ inline uint atomicAnd(uint& mem, uint v)
 	return old;
 }
 
+#ifdef REF_SHADING
+} // namespace glsl
+#include "glsl_shade_shim.h"
+namespace glsl
+{
+#else
 /* ---- images and the MIN-reduction sampler ---- */
 struct texture2D
 {
@@ -290,6 +304,8 @@ inline vec4 textureLod(sampler2D s, vec2 uv, float lod)
 }
 inline vec4 texture(sampler2D s, vec2 uv) { return textureLod(s, uv, 0.0f); }
 inline void imageStore(image2D img, ivec2 p, vec4 v) { img.data[(size_t)p.y * img.width + p.x] = v.x; }
+
+#endif /* REF_SHADING */
 
 /* invocation ids (gl_GlobalInvocationID etc.) are per-TU statics defined by oracle/ref_runner.cpp */
 

@@ -132,3 +132,140 @@ def load_scene_cache(path, mesh_dtype, meshlet_dtype, draw_dtype, hash_meta=0x11
     meshes, meshlets, draws = np.zeros(counts[0], mesh_dtype), np.zeros(counts[1], meshlet_dtype), np.zeros(counts[2], draw_dtype)
     lib().ref_loaded_arrays(_p(meshes), _p(meshlets), _p(draws))
     return meshes, meshlets, draws, cam, sun
+
+
+# ---- the shading end of the frame (shadowfill, shadowblur, final, bloom, mesh.frag and the helpers of src/shaders/math.h:51-109) ----
+def _f32(a):
+    return np.ascontiguousarray(a, np.float32)
+
+
+def stats(shader):
+    """the shim's counters of `shader` ("shadowfill", "shadowblur", "final", "bloom") since the last call: dict(outside: fetches outside the
+    image, dropped: stores outside it, dropped_at_width: those with x == width, edges: texture() taps clamped left / right / top / bottom)"""
+    out = np.zeros(7, np.uint32)
+    getattr(lib(), "ref_stats_" + shader)(_p(out))
+    return dict(outside=int(out[0]), dropped=int(out[1]), dropped_at_width=int(out[2]), edges=out[3:].astype(np.int64))
+
+
+def shadow_fill(shadow, depth, checkerboard):
+    """shadowfill.comp.glsl over its dispatch, in place on a copy -> (filled (h, w) u8, handed (h, w, 4) f32: the vec4 each store was given,
+    zeros where nothing was stored)"""
+    h, w = shadow.shape
+    s, d = np.ascontiguousarray(shadow, np.uint8).copy(), _f32(depth).reshape(h, w)
+    handed = np.zeros((h, w, 4), np.float32)
+    lib().ref_shadowfill(_p(s), _p(d), C.c_uint32(w), C.c_uint32(h), C.c_int(checkerboard), _p(handed))
+    return s, handed
+
+
+def shadow_blur(shadow, depth, direction, znear):
+    """shadowblur.comp.glsl (BLUR 1) -> (out (h, w) u8, handed (h, w, 4) f32)"""
+    h, w = shadow.shape
+    s, d = np.ascontiguousarray(shadow, np.uint8), _f32(depth).reshape(h, w)
+    out, handed = np.zeros((h, w), np.uint8), np.zeros((h, w, 4), np.float32)
+    lib().ref_shadowblur(_p(out), _p(s), _p(d), C.c_uint32(w), C.c_uint32(h), C.c_float(direction), C.c_float(znear), _p(handed))
+    return out, handed
+
+
+def final(sd, gbuffer0, gbuffer1, depth, shadow=None, bloom0=None):
+    """final.comp.glsl -> (colour (h, w) u32, handed (h, w, 4) f32).  sd: the 112-byte ShadeData record; bloom0: level 0 of the bloom target
+    ((h + 1) // 2, (w + 1) // 2) u32, all zero when None"""
+    h, w = depth.shape
+    sdw = np.frombuffer(np.ascontiguousarray(sd).tobytes(), np.float32).copy()
+    g0 = np.ascontiguousarray(gbuffer0).view(np.uint32).reshape(h, w)
+    g1 = np.ascontiguousarray(gbuffer1).view(np.uint32).reshape(h, w)
+    b = np.zeros(((h + 1) // 2, (w + 1) // 2), np.uint32) if bloom0 is None else np.ascontiguousarray(bloom0, np.uint32)
+    s = None if shadow is None else np.ascontiguousarray(shadow, np.uint8).reshape(h, w)
+    out, handed = np.zeros((h, w), np.uint32), np.zeros((h, w, 4), np.float32)
+    lib().ref_final(_p(sdw), _p(g0), _p(g1), _p(_f32(depth)), _p(s), _p(b), C.c_uint32(b.shape[1]), C.c_uint32(b.shape[0]), _p(out), C.c_uint32(w),
+                    C.c_uint32(h), _p(handed))
+    return out, handed
+
+
+def bloom_pass(which, src, dst_shape, radius=0.0, dst=None):
+    """one dispatch of bloom.comp.glsl: which 0 (src = gbuffer0 words), 1, 2 (src = a bloom level; dst = the level accumulated into)
+    -> (level (h, w) u32, handed (h, w, 4) f32)"""
+    s = np.ascontiguousarray(src).view(np.uint32)
+    h, w = dst_shape
+    d = np.zeros((h, w), np.uint32) if dst is None else np.ascontiguousarray(dst, np.uint32).copy()
+    handed = np.zeros((h, w, 4), np.float32)
+    lib().ref_bloom_pass(C.c_int(which), _p(s), C.c_uint32(s.shape[1]), C.c_uint32(s.shape[0]), C.c_int(1 if which == 0 else 0), _p(d), C.c_uint32(w),
+                         C.c_uint32(h), C.c_float(radius), _p(handed))
+    return d, handed
+
+
+def bloom(gbuffer0, width, height, levels, offsets, total):
+    """the loop of src/niagara.cpp:1873-1901 over one linear bloom target -> (total,) u32"""
+    g0 = np.ascontiguousarray(gbuffer0).view(np.uint32)
+    target, off = np.zeros(total, np.uint32), np.ascontiguousarray(offsets, np.uint32)
+    lib().ref_bloom(_p(g0), C.c_uint32(g0.shape[1]), C.c_uint32(g0.shape[0]), _p(target), C.c_uint32(width), C.c_uint32(height), C.c_uint32(levels), _p(off))
+    return target
+
+
+def mesh_frag(records, width, draws, materials, taps=None, post=0):
+    """mesh.frag.glsl per fragment of `records` (64-byte NvPixelAttributes) -> dict(gbuffer0, gbuffer1 (n) u32, discard (n) bool,
+    written (n, 8) f32).  taps: (n, 4, 4) f32, the texel of the albedo / normal / specular / emissive slot per fragment"""
+    rec = np.ascontiguousarray(records).reshape(-1)
+    n = len(rec)
+    assert rec.dtype.itemsize == 64 and draws.dtype.itemsize == 48 and materials.dtype.itemsize == 64
+    dr, mt = np.ascontiguousarray(draws), np.ascontiguousarray(materials)
+    t = None if taps is None else _f32(taps).reshape(n, 4, 4)
+    g0, g1, disc, written = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint8), np.zeros((n, 8), np.float32)
+    lib().ref_mesh_frag(_p(rec), C.c_uint32(n), C.c_uint32(width), _p(dr), _p(mt), C.c_uint32(len(mt)), _p(t), C.c_int(post), _p(g0), _p(g1), _p(disc),
+                        _p(written))
+    return dict(gbuffer0=g0, gbuffer1=g1, discard=disc.astype(bool), written=written)
+
+
+def encode_oct(v):
+    v = _f32(v).reshape(-1, 3)
+    out = np.zeros((len(v), 2), np.float32)
+    lib().ref_encode_oct(_p(v), C.c_uint32(len(v)), _p(out))
+    return out
+
+
+def decode_oct(e):
+    e = _f32(e).reshape(-1, 2)
+    out = np.zeros((len(e), 3), np.float32)
+    lib().ref_decode_oct(_p(e), C.c_uint32(len(e)), _p(out))
+    return out
+
+
+def _colour(which, c, width):
+    c = _f32(c).reshape(-1, width)
+    out = np.zeros_like(c)
+    lib().ref_colour(C.c_int(which), _p(c), C.c_uint32(len(c)), _p(out))
+    return out
+
+
+def tosrgb(c):
+    return _colour(0, c, 3)
+
+
+def fromsrgb(c):
+    return _colour(1, c, 3)
+
+
+def tonemap(c):
+    return _colour(2, c, 3)
+
+
+def tosrgb4(c):
+    return _colour(3, c, 4)
+
+
+def fromsrgb4(c):
+    return _colour(4, c, 4)
+
+
+def gradient_noise(uv):
+    uv = _f32(uv).reshape(-1, 2)
+    out = np.zeros(len(uv), np.float32)
+    lib().ref_gradient_noise(_p(uv), C.c_uint32(len(uv)), _p(out))
+    return out
+
+
+def unpack_tbn(np_codes, tp_codes):
+    a, b = np.ascontiguousarray(np_codes, np.uint32).reshape(-1), np.ascontiguousarray(tp_codes, np.uint32).reshape(-1)
+    assert len(a) == len(b)
+    normal, tangent = np.zeros((len(a), 3), np.float32), np.zeros((len(a), 4), np.float32)
+    lib().ref_unpack_tbn(_p(a), _p(b), C.c_uint32(len(a)), _p(normal), _p(tangent))
+    return normal, tangent

@@ -45,6 +45,12 @@ static void EmitMeshTasksEXT(uint x, uint, uint) { ref_emitCount = x; }
 static void barrier() {}
 #endif
 
+#ifdef REF_MESH_FRAG
+/* fragment-stage built-ins: gl_FragCoord, and `discard` (rewritten by the translator to set this flag and return) */
+static vec4 gl_FragCoord;
+static bool ref_discard;
+#endif
+
 namespace REF_NS
 {
 #include REF_GEN
@@ -388,5 +394,273 @@ extern "C" void ref_meshlet_task(const void* cull, int late, void* commands, con
 				payloads[(size_t)commandId * 64 + i] = payload.clusterIndices[i];
 			payloadCounts[commandId] = ref_emitCount;
 		}
+}
+#endif
+
+/* ================= the shading end of the frame (built with -DREF_SHADING: typed images, oracle/glsl_shade_shim.h) =================
+ *
+ * Every binding's format is the reference host code's:
+ *   depthTarget       VK_FORMAT_D32_SFLOAT                 src/niagara.cpp:631, :1326
+ *   gbufferTargets[0] VK_FORMAT_R8G8B8A8_UNORM             src/niagara.cpp:634-637, :1325
+ *   gbufferTargets[1] VK_FORMAT_A2B10G10R10_UNORM_PACK32   src/niagara.cpp:634-637, :1325
+ *   shadowTarget, shadowblurTarget  VK_FORMAT_R8_UNORM     src/niagara.cpp:1328-1329
+ *   bloomTarget and its mip views   VK_FORMAT_B10G11R11_UFLOAT_PACK32   src/niagara.cpp:1335-1337
+ *   the output of final.comp.glsl   the swapchain's format (src/niagara.cpp:1197, :1864), VK_FORMAT_R8G8B8A8_UNORM where the surface leaves
+ *                                   the choice (src/swapchain.cpp:54-55); a BGRA surface stores the same codes in another byte order
+ * dispatch() rounds the grid up to whole 8x8 workgroups (src/niagara.cpp:213-225, src/shaders.h:71-74); every invocation of that grid runs. */
+#ifdef REF_SHADING
+template <typename F>
+static void run_grid(uint32_t threadsX, uint32_t threadsY, F&& body)
+{
+	uint32_t gx = (threadsX + 7) / 8, gy = (threadsY + 7) / 8;
+	for (uint32_t y = 0; y < gy * 8; ++y)
+		for (uint32_t x = 0; x < gx * 8; ++x)
+		{
+			gl_GlobalInvocationID.x = x;
+			gl_GlobalInvocationID.y = y;
+			gl_LocalInvocationID.x = x & 7, gl_LocalInvocationID.y = y & 7;
+			gl_WorkGroupID.x = x >> 3, gl_WorkGroupID.y = y >> 3;
+			body();
+		}
+}
+static texture2D bind_texture(const void* data, uint32_t w, uint32_t h, ImageFormat f)
+{
+	texture2D t = { data, w, h, f, 0 };
+	return t;
+}
+static image2D bind_image(void* data, uint32_t w, uint32_t h, ImageFormat f, float* handed)
+{
+	image2D t = { data, w, h, f, (vec4*)handed };
+	return t;
+}
+/* the shim's counters since the last call (glsl_shade_shim.h, shim_stats): the tests' input conditions */
+extern "C" void REF_STATS(uint32_t out[7])
+{
+	memcpy(out, shim_stats, sizeof(shim_stats));
+	memset(shim_stats, 0, sizeof(shim_stats));
+}
+#endif
+
+#ifdef REF_SHADOWFILL
+/* src/niagara.cpp:1822-1834: dispatch((width + 1) / 2, height) of shadowfill.comp.glsl, in place on shadowTarget */
+extern "C" void ref_shadowfill(uint8_t* shadow, const float* depth, uint32_t w, uint32_t h, int checker, float* handed)
+{
+	imageSize = vec2((float)w, (float)h);
+	checkerboard = checker;
+	shadowImage = bind_image(shadow, w, h, FORMAT_R8_UNORM, handed);
+	depthImage = bind_texture(depth, w, h, FORMAT_R32_SFLOAT);
+	run_grid((w + 1) / 2, h, [] { shader_main(); });
+}
+#endif
+
+#ifdef REF_SHADOWBLUR
+/* src/niagara.cpp:1836-1850: dispatch(width, height) of shadowblur.comp.glsl; direction 1 in the first pass, 0 in the second */
+extern "C" void ref_shadowblur(uint8_t* out, const uint8_t* shadow, const float* depth, uint32_t w, uint32_t h, float dir, float zn, float* handed)
+{
+	imageSize = vec2((float)w, (float)h);
+	direction = dir;
+	znear = zn;
+	outImage = bind_image(out, w, h, FORMAT_R8_UNORM, handed);
+	shadowImage = bind_texture(shadow, w, h, FORMAT_R8_UNORM);
+	depthImage = bind_texture(depth, w, h, FORMAT_R32_SFLOAT);
+	run_grid(w, h, [] { shader_main(); });
+}
+#endif
+
+#ifdef REF_FINAL
+/* src/niagara.cpp:1911-1925: dispatch(width, height) of final.comp.glsl.  sd: ShadeData as the host lays it out (src/niagara.cpp:280-290:
+ * vec3, pad, vec3, int, mat4, vec2).  bloom: level 0 of the bloom target (the view bloomTarget.imageView starts there). */
+extern "C" void ref_final(const float* sd, const uint32_t* g0, const uint32_t* g1, const float* depth, const uint8_t* shadow, const uint32_t* bloom,
+                          uint32_t bw, uint32_t bh, uint32_t* color, uint32_t w, uint32_t h, float* handed)
+{
+	shadeData.cameraPosition = vec3(sd[0], sd[1], sd[2]);
+	shadeData.sunDirection = vec3(sd[4], sd[5], sd[6]);
+	memcpy(&shadeData.shadowsEnabled, sd + 7, 4);
+	for (int c = 0; c < 4; ++c)
+		shadeData.inverseViewProjection[c] = vec4(sd[8 + 4 * c], sd[9 + 4 * c], sd[10 + 4 * c], sd[11 + 4 * c]);
+	shadeData.imageSize = vec2(sd[24], sd[25]);
+	outImage = bind_image(color, w, h, FORMAT_R8G8B8A8_UNORM, handed);
+	gbufferImage0 = bind_texture(g0, w, h, FORMAT_R8G8B8A8_UNORM);
+	gbufferImage1 = bind_texture(g1, w, h, FORMAT_A2B10G10R10_UNORM_PACK32);
+	depthImage = bind_texture(depth, w, h, FORMAT_R32_SFLOAT);
+	shadowImage = shadow ? bind_texture(shadow, w, h, FORMAT_R8_UNORM) : bind_texture(0, 0, 0, FORMAT_R8_UNORM);
+	bloomImage = bind_texture(bloom, bw, bh, FORMAT_B10G11R11_UFLOAT_PACK32);
+	run_grid(w, h, [] { shader_main(); });
+}
+
+/* the helpers of src/shaders/math.h:51-109, one by one over arrays of n arguments */
+extern "C" void ref_encode_oct(const float* v, uint32_t n, float* out)
+{
+	for (uint32_t i = 0; i < n; ++i)
+	{
+		vec2 r = encodeOct(vec3(v[3 * i], v[3 * i + 1], v[3 * i + 2]));
+		out[2 * i] = r.x, out[2 * i + 1] = r.y;
+	}
+}
+extern "C" void ref_decode_oct(const float* e, uint32_t n, float* out)
+{
+	for (uint32_t i = 0; i < n; ++i)
+	{
+		vec3 r = decodeOct(vec2(e[2 * i], e[2 * i + 1]));
+		out[3 * i] = r.x, out[3 * i + 1] = r.y, out[3 * i + 2] = r.z;
+	}
+}
+/* which: 0 tosrgb(vec3), 1 fromsrgb(vec3), 2 tonemap, 3 tosrgb(vec4), 4 fromsrgb(vec4) (the vec4 forms pass .w through); c, out: 3 or 4 floats each */
+extern "C" void ref_colour(int which, const float* c, uint32_t n, float* out)
+{
+	for (uint32_t i = 0; i < n; ++i)
+		if (which < 3)
+		{
+			vec3 a(c[3 * i], c[3 * i + 1], c[3 * i + 2]);
+			vec3 r = which == 0 ? tosrgb(a) : which == 1 ? fromsrgb(a) : tonemap(a);
+			out[3 * i] = r.x, out[3 * i + 1] = r.y, out[3 * i + 2] = r.z;
+		}
+		else
+		{
+			vec4 a(c[4 * i], c[4 * i + 1], c[4 * i + 2], c[4 * i + 3]);
+			vec4 r = which == 3 ? tosrgb(a) : fromsrgb(a);
+			out[4 * i] = r.x, out[4 * i + 1] = r.y, out[4 * i + 2] = r.z, out[4 * i + 3] = r.w;
+		}
+}
+extern "C" void ref_gradient_noise(const float* uv, uint32_t n, float* out)
+{
+	for (uint32_t i = 0; i < n; ++i)
+		out[i] = gradientNoise(vec2(uv[2 * i], uv[2 * i + 1]));
+}
+extern "C" void ref_unpack_tbn(const uint32_t* np, const uint32_t* tp, uint32_t n, float* normal3, float* tangent4)
+{
+	for (uint32_t i = 0; i < n; ++i)
+	{
+		vec3 nrm;
+		vec4 tan;
+		REF_NS::unpackTBN(np[i], tp[i], nrm, tan);
+		normal3[3 * i] = nrm.x, normal3[3 * i + 1] = nrm.y, normal3[3 * i + 2] = nrm.z;
+		tangent4[4 * i] = tan.x, tangent4[4 * i + 1] = tan.y, tangent4[4 * i + 2] = tan.z, tangent4[4 * i + 3] = tan.w;
+	}
+}
+#endif
+
+#ifdef REF_BLOOM
+/* one dispatch of bloom.comp.glsl (QUALITY 1) as src/niagara.cpp:1882-1885 / :1897-1898 issue it: dispatch(levelWidth, levelHeight) with
+ * imageSize = the target level's size.  srcIsGbuffer: the source is gbufferTargets[0] (pass 0), else a level of the bloom target.
+ */
+static void bloom_dispatch(int pass_, const uint32_t* src, uint32_t W, uint32_t H, int srcIsGbuffer, uint32_t* dst, uint32_t w, uint32_t h, float radius_,
+                           float* handed)
+{
+	imageSize = vec2((float)w, (float)h);
+	pass = pass_;
+	radius = radius_;
+	outImage = bind_image(dst, w, h, FORMAT_B10G11R11_UFLOAT_PACK32, handed);
+	sourceImage = bind_texture(src, W, H, srcIsGbuffer ? FORMAT_R8G8B8A8_UNORM : FORMAT_B10G11R11_UFLOAT_PACK32);
+	run_grid(w, h, [] { shader_main(); });
+}
+extern "C" void ref_bloom_pass(int pass_, const uint32_t* src, uint32_t W, uint32_t H, int srcIsGbuffer, uint32_t* dst, uint32_t w, uint32_t h,
+                               float radius_, float* handed)
+{
+	bloom_dispatch(pass_, src, W, H, srcIsGbuffer, dst, w, h, radius_, handed);
+}
+/* the loop of src/niagara.cpp:1873-1901: pass 0 into level 0, pass 1 into levels 1 .. levels - 1, pass 2 into levels - 2 .. 0 with radius 2;
+ * bloomWidth / bloomHeight / levels as src/niagara.cpp:1331-1333 computes them (handed in), levelOffset in texels of the one buffer */
+extern "C" void ref_bloom(const uint32_t* g0, uint32_t W, uint32_t H, uint32_t* target, uint32_t bloomWidth, uint32_t bloomHeight, uint32_t bloomLevels,
+                          const uint32_t* levelOffset)
+{
+	for (uint32_t i = 0; i < bloomLevels; ++i)
+	{
+		uint32_t levelWidth = bloomWidth >> i ? bloomWidth >> i : 1u, levelHeight = bloomHeight >> i ? bloomHeight >> i : 1u;
+		uint32_t srcWidth = bloomWidth >> (i - 1) ? bloomWidth >> (i - 1) : 1u, srcHeight = bloomHeight >> (i - 1) ? bloomHeight >> (i - 1) : 1u;
+		if (i == 0)
+			bloom_dispatch(0, g0, W, H, 1, target + levelOffset[0], levelWidth, levelHeight, 0.f, 0);
+		else
+			bloom_dispatch(1, target + levelOffset[i - 1], srcWidth, srcHeight, 0, target + levelOffset[i], levelWidth, levelHeight, 0.f, 0);
+	}
+	for (int i = (int)bloomLevels - 2; i >= 0; --i)
+	{
+		uint32_t levelWidth = bloomWidth >> i ? bloomWidth >> i : 1u, levelHeight = bloomHeight >> i ? bloomHeight >> i : 1u;
+		uint32_t srcWidth = bloomWidth >> (i + 1) ? bloomWidth >> (i + 1) : 1u, srcHeight = bloomHeight >> (i + 1) ? bloomHeight >> (i + 1) : 1u;
+		bloom_dispatch(2, target + levelOffset[i + 1], srcWidth, srcHeight, 0, target + levelOffset[i], levelWidth, levelHeight, 2.0f, 0);
+	}
+}
+#endif
+
+#ifdef REF_MESH_FRAG
+/* mesh.frag.glsl:55-95 once per fragment.  The inputs of :27-31 are one 64-byte record {vec2 uv, vec2 bary, vec3 normal, uint drawId,
+ * vec4 tangent, vec3 wpos, uint materialIndex}; fragment i sits at pixel (i % width, i / width), gl_FragCoord.xy = pixel + 0.5.  A record with
+ * drawId == ~0 has no fragment (outputs stay 0).  draws: 48-byte MeshDraw, materials: 64-byte Material (src/shaders/mesh.h:80-102).
+ * texture(SAMP(id), uv) is the caller's: taps (optional, n x 4 x 4 floats) holds per fragment the texel of the albedo, normal, specular and
+ * emissive slot; a slot whose texture id is > 0 is renumbered to slot + 1 so the shim can tell the four apart.
+ * Outputs: the attachments packed by the shim's UNORM store in the formats of src/niagara.cpp:634-637, the discard flag, and (optional,
+ * n x 8 floats) gbuffer[0] and gbuffer[1] as written. */
+extern "C" void ref_mesh_frag(const void* records, uint32_t n, uint32_t width, const void* draws_, const void* materials_, uint32_t materialCount,
+                              const float* taps, int post, uint32_t* gb0, uint32_t* gb1, uint8_t* discarded, float* written)
+{
+	struct Record
+	{
+		float uv[2], bary[2], normal[3];
+		uint32_t drawId;
+		float tangent[4], wpos[3];
+		uint32_t materialIndex;
+	};
+	struct DrawIn
+	{
+		float position[3], scale, orientation[4];
+		uint32_t meshIndex, meshletVisibilityOffset, postPass, materialIndex;
+	};
+	struct MaterialIn
+	{
+		uint32_t tex[4];
+		float diffuse[4], specular[4], emissive[3];
+		uint32_t padding;
+	};
+	const Record* rec = (const Record*)records;
+	const DrawIn* din = (const DrawIn*)draws_;
+	const MaterialIn* min_ = (const MaterialIn*)materials_;
+	static MeshDraw oneDraw;
+	static Material* table = 0;
+	delete[] table;
+	table = new Material[materialCount ? materialCount : 1];
+	for (uint32_t m = 0; m < materialCount; ++m)
+	{
+		table[m].albedoTexture = min_[m].tex[0] > 0 ? 1u : 0u;
+		table[m].normalTexture = min_[m].tex[1] > 0 ? 2u : 0u;
+		table[m].specularTexture = min_[m].tex[2] > 0 ? 3u : 0u;
+		table[m].emissiveTexture = min_[m].tex[3] > 0 ? 4u : 0u;
+		table[m].diffuseFactor = vec4(min_[m].diffuse[0], min_[m].diffuse[1], min_[m].diffuse[2], min_[m].diffuse[3]);
+		table[m].specularFactor = vec4(min_[m].specular[0], min_[m].specular[1], min_[m].specular[2], min_[m].specular[3]);
+		table[m].emissiveFactor = vec3(min_[m].emissive[0], min_[m].emissive[1], min_[m].emissive[2]);
+	}
+	materials = table;
+	draws = &oneDraw;
+	POST = post;
+	for (uint32_t i = 0; i < n; ++i)
+	{
+		gb0[i] = gb1[i] = 0;
+		discarded[i] = 0;
+		if (rec[i].drawId == ~0u)
+			continue;
+		const DrawIn& d = din[rec[i].drawId];
+		oneDraw.materialIndex = d.materialIndex; /* :57-58 read nothing else of the draw */
+		drawId = 0;
+		uv = vec2(rec[i].uv[0], rec[i].uv[1]);
+		normal = vec3(rec[i].normal[0], rec[i].normal[1], rec[i].normal[2]);
+		tangent = vec4(rec[i].tangent[0], rec[i].tangent[1], rec[i].tangent[2], rec[i].tangent[3]);
+		wpos = vec3(rec[i].wpos[0], rec[i].wpos[1], rec[i].wpos[2]);
+		gl_FragCoord = vec4((float)(i % width) + 0.5f, (float)(i / width) + 0.5f, 0, 1);
+		for (int s = 0; s < 4; ++s)
+			shim_taps.texel[s + 1] = taps ? vec4(taps[(size_t)i * 16 + 4 * s], taps[(size_t)i * 16 + 4 * s + 1], taps[(size_t)i * 16 + 4 * s + 2],
+			                                     taps[(size_t)i * 16 + 4 * s + 3])
+			                              : vec4(0);
+		ref_discard = false;
+		gbuffer[0] = gbuffer[1] = vec4(0);
+		shader_main();
+		gb0[i] = shim_encode_word(gbuffer[0], FORMAT_R8G8B8A8_UNORM);
+		gb1[i] = shim_encode_word(gbuffer[1], FORMAT_A2B10G10R10_UNORM_PACK32);
+		discarded[i] = ref_discard;
+		if (written)
+		{
+			float* o = written + (size_t)i * 8;
+			o[0] = gbuffer[0].x, o[1] = gbuffer[0].y, o[2] = gbuffer[0].z, o[3] = gbuffer[0].w;
+			o[4] = gbuffer[1].x, o[5] = gbuffer[1].y, o[6] = gbuffer[1].z, o[7] = gbuffer[1].w;
+		}
+	}
 }
 #endif

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""ref_translate.py — rewrite one of the reference's GLSL compute shaders into compilable C++.
+"""ref_translate.py — rewrite one of the reference's GLSL shaders into compilable C++.
 
 TEST INFRASTRUCTURE.  Reads the shader where it lies under the reference tree (never copied into this
 repository), inlines its #includes, and applies purely syntactic rewrites so that the reference's own
@@ -21,6 +21,15 @@ Rewrites (nothing semantic):
   * `void main()` -> `void shader_main()`.
   * mesh-shader declarations (meshlet.mesh.glsl): `layout(triangles, ...) out;` dropped, `layout(location=N) out [flat] T
     name[];` -> `T name[256];`, `taskPayloadSharedEXT` / `shared` qualifiers dropped (the runner serialises a workgroup).
+`--shading` adds the rewrites the shading shaders need (shadowfill, shadowblur, final, bloom, mesh.frag), still purely syntactic; the cull
+shaders are translated without it, so their generated text does not depend on any of these:
+  * literals with an exponent and no point (`1e-2`) get the `f` suffix too;
+  * the colour swizzles: `.rgb` -> `.xyz()`, `.rg` -> `.xy()`, `.r .g .b .a` -> `.x .y .z .w`; `.yx` -> `.yx()`;
+  * the two lvalue swizzles (`v.xy += ...`, `tangent.xyz = ...`, math.h:65,107) -> `lv_xy(v) += ...`, `lv_xyz(tangent) = ...`;
+  * fragment-stage declarations: `layout(location=N) in [flat] T name;` -> `T name;`, `layout(location=N) out vec4 gbuffer[2];` ->
+    `vec4 gbuffer[2];`, `layout(constant_id=N) const int X = v;` -> `int X = v;`, `uniform texture2D textures[];` -> the shim's table
+    (`nonuniformEXT` is a function of the shim);
+  * `discard;` -> `{ ref_discard = true; return; }` (the runner reads the flag back).
 `--limit math.h:49` keeps only the first 49 lines of that include (the cull helpers; the rest is shading).
 `--define NAME=V` flips one of the reference's own `#define NAME ...` configuration switches (MESH_CULL, src/config.h:10-11).
 `--once "stmt;"` guards ONE statement with `if (gl_LocalInvocationID.x == 0u)`: a workgroup-shared variable that every
@@ -35,6 +44,7 @@ import sys
 
 LIMITS = {}  # basename -> number of leading lines to keep (e.g. math.h:49 = the cull helpers only)
 DEFINES = {}  # NAME -> value: rewrites the reference's own `#define NAME x` line
+SHADING = [False]  # --shading: the extra rewrites of the shading shaders
 ONCE = []  # statements executed by the first invocation of a workgroup only (barrier emulation)
 
 
@@ -61,6 +71,12 @@ def inline_includes(path, seen=None):
 def translate(src):
     src = re.sub(r"^\s*#(version|extension)[^\n]*\n", "", src, flags=re.M)
     src = re.sub(r"layout\s*\(\s*constant_id\s*=\s*\d+\s*\)\s*const\s+bool\s+(\w+)\s*=\s*(\w+)\s*;", r"bool \1 = \2;", src)
+    if SHADING[0]:
+        src = re.sub(r"layout\s*\(\s*constant_id\s*=\s*\d+\s*\)\s*const\s+int\s+(\w+)\s*=\s*(-?\w+)\s*;", r"int \1 = \2;", src)
+        src = re.sub(r"layout\s*\(\s*location\s*=\s*\d+\s*\)\s*out\s+(\w+)\s+(\w+)\s*\[\s*(\d+)\s*\]\s*;", r"\1 \2[\3];", src)
+        src = re.sub(r"layout\s*\(\s*location\s*=\s*\d+\s*\)\s*in\s+(?:flat\s+)?(\w+)\s+(\w+)\s*;", r"\1 \2;", src)
+        src = re.sub(r"layout\s*\([^)]*\)\s*uniform\s+texture2D\s+(\w+)\s*\[\s*\]\s*;", r"ShimTextureTable \1;", src)
+        src = re.sub(r"\bdiscard\s*;", "{ ref_discard = true; return; }", src)
     src = re.sub(r"layout\s*\(\s*local_size_x[^)]*\)\s*in\s*;", "", src)
     src = re.sub(r"layout\s*\(\s*triangles[^)]*\)\s*out\s*;", "", src)
     src = re.sub(r"layout\s*\(\s*location\s*=\s*\d+\s*\)\s*out\s+(?:flat\s+)?(\w+)\s+(\w+)\s*\[\s*\]\s*;", r"\1 \2[256];", src)
@@ -97,6 +113,14 @@ def translate(src):
     src = re.sub(r"layout\s*\([^)]*\)\s*uniform\s+(?:writeonly\s+|readonly\s+)?(texture2D|sampler|image2D)\s+(\w+)\s*;", r"\1 \2;", src)
     src = re.sub(r"\bout\s+(vec[234]|float|uint|int)\s+(\w+)", r"\1& \2", src)
     src = re.sub(r"(?<![\w.])(\d+\.\d*|\.\d+)(?![\w.])", r"\1f", src)
+    if SHADING[0]:
+        src = re.sub(r"(?<![\w.])(\d+[eE][-+]?\d+)(?![\w.])", r"\1f", src)
+        src = re.sub(r"\b(\w+)\.(xyz|xy)\s*(\+=|=(?!=))", r"lv_\2(\1) \3", src)
+        src = re.sub(r"\.rgb\b", ".xyz", src)
+        src = re.sub(r"\.rg\b", ".xy", src)
+        for colour, axis in zip("rgba", "xyzw"):
+            src = re.sub(r"\.%s\b(?!\s*\()" % colour, "." + axis, src)
+        src = re.sub(r"\.yx\b(?!\s*\()", ".yx()", src)
     src = re.sub(r"\.(xyz|xy|zw|xwzy)\b(?!\s*\()", r".\1()", src)
     src = re.sub(r"\bvoid\s+main\s*\(\s*\)", "void shader_main()", src)
     return src
@@ -114,7 +138,11 @@ def main():
             chunks.append("\n".join(lines[int(a) - 1:int(b)]))
         open(out, "w").write("\n\n".join(chunks) + "\n")
         return
-    while args[0] in ("--limit", "--define", "--once"):
+    while args[0] in ("--limit", "--define", "--once", "--shading"):
+        if args[0] == "--shading":
+            SHADING[0] = True
+            args = args[1:]
+            continue
         if args[0] == "--limit":
             name, n = args[1].split(":")
             LIMITS[name] = int(n)

@@ -111,8 +111,8 @@ static void br_texture_unorm8(const uint32_t* img, uint32_t w, uint32_t h, REAL 
 
 /* ---- bloom.comp.glsl */
 
-/* :29-46, pass 0: gbuffer0 (W x H) into level 0 (w x h) */
-void br_extract(const uint32_t* gbuffer0, uint32_t W, uint32_t H, uint32_t* out, uint32_t w, uint32_t h)
+/* :29-46, pass 0: gbuffer0 (W x H) into level 0 (w x h).  value (optional, w * h * 3, here and in passes 1 and 2): what is handed to the store */
+void br_extract(const uint32_t* gbuffer0, uint32_t W, uint32_t H, uint32_t* out, uint32_t w, uint32_t h, REAL* value)
 {
 	static const float off[4][2] = { { -0.25f, -0.25f }, { +0.25f, -0.25f }, { -0.25f, +0.25f }, { +0.25f, +0.25f } }; /* :33-36 */
 	REAL tx = K(1.0f) / (REAL)w, ty = K(1.0f) / (REAL)h;                                                               /* :27 */
@@ -133,11 +133,13 @@ void br_extract(const uint32_t* gbuffer0, uint32_t W, uint32_t H, uint32_t* out,
 			for (int k = 0; k < 3; ++k)
 				result[k] = (((e[0][k] + e[1][k]) + e[2][k]) + e[3][k]) * K(0.25f); /* :43 */
 			out[(size_t)y * w + x] = br_pack(result);
+			if (value)
+				memcpy(value + ((size_t)y * w + x) * 3, result, sizeof(result));
 		}
 }
 
 /* :47-77, pass 1 with QUALITY 1: src (W x H) into dst (w x h) */
-void br_downsample(const uint32_t* src, uint32_t W, uint32_t H, uint32_t* dst, uint32_t w, uint32_t h)
+void br_downsample(const uint32_t* src, uint32_t W, uint32_t H, uint32_t* dst, uint32_t w, uint32_t h, REAL* value)
 {
 	/* :54-66: the offsets in texels of dst and the weights as the shader writes them */
 	static const float tap[13][2] = { { 0, 0 }, { +0.5f, +0.5f }, { +0.5f, -0.5f }, { -0.5f, +0.5f }, { -0.5f, -0.5f }, { +1, +1 }, { +1, -1 },
@@ -160,11 +162,13 @@ void br_downsample(const uint32_t* src, uint32_t W, uint32_t H, uint32_t* dst, u
 					result[k] = result[k] + t[k] * weight[s];
 			}
 			dst[(size_t)y * w + x] = br_pack(result);
+			if (value)
+				memcpy(value + ((size_t)y * w + x) * 3, result, sizeof(result));
 		}
 }
 
 /* :78-107, pass 2 with QUALITY 1: src (W x H) added to dst (w x h) in place; an invocation touches its own texel of dst only */
-void br_upsample(const uint32_t* src, uint32_t W, uint32_t H, uint32_t* dst, uint32_t w, uint32_t h, float radiusf)
+void br_upsample(const uint32_t* src, uint32_t W, uint32_t H, uint32_t* dst, uint32_t w, uint32_t h, float radiusf, REAL* value)
 {
 	static const float tap[9][2] = { { 0, 0 }, { +1, 0 }, { -1, 0 }, { 0, +1 }, { 0, -1 }, { +1, +1 }, { +1, -1 }, { -1, +1 }, { -1, -1 } }; /* :85-93 */
 	const REAL weight[9] = { K(4.0f) / K(16.0f), K(2.0f) / K(16.0f), K(2.0f) / K(16.0f), K(2.0f) / K(16.0f), K(2.0f) / K(16.0f),
@@ -185,6 +189,8 @@ void br_upsample(const uint32_t* src, uint32_t W, uint32_t H, uint32_t* dst, uin
 					result[k] = result[k] + t[k] * weight[s];
 			}
 			dst[(size_t)y * w + x] = br_pack(result);
+			if (value)
+				memcpy(value + ((size_t)y * w + x) * 3, result, sizeof(result));
 		}
 }
 

@@ -86,30 +86,34 @@ class BloomRef:
         self.libs[real].br_encode_array(_p(v), C.c_uint32(v.size), C.c_int(mbits), _p(out))
         return out
 
-    def extract(self, gbuffer0, real="f32"):
-        """pass 0: gbuffer0 (H, W) u32 -> level 0 ((H + 1) // 2, (W + 1) // 2) u32"""
+    def extract(self, gbuffer0, real="f32", value=False):
+        """pass 0: gbuffer0 (H, W) u32 -> level 0 ((H + 1) // 2, (W + 1) // 2) u32 [, the values handed to the store (h, w, 3)], here and in
+        passes 1 and 2"""
         g0 = np.ascontiguousarray(gbuffer0).view(np.uint32)
         H, W = g0.shape
         w, h = (W + 1) // 2, (H + 1) // 2
         out = np.zeros((h, w), np.uint32)
-        self.libs[real].br_extract(_p(g0), C.c_uint32(W), C.c_uint32(H), _p(out), C.c_uint32(w), C.c_uint32(h))
-        return out
+        v = np.zeros((h, w, 3), self._rt(real)) if value else None
+        self.libs[real].br_extract(_p(g0), C.c_uint32(W), C.c_uint32(H), _p(out), C.c_uint32(w), C.c_uint32(h), _p(v))
+        return (out, v) if value else out
 
-    def downsample(self, src, real="f32"):
+    def downsample(self, src, real="f32", value=False):
         """pass 1: a level (H, W) -> the next one (max(1, H >> 1), max(1, W >> 1))"""
         s = np.ascontiguousarray(src, np.uint32)
         H, W = s.shape
         w, h = max(1, W >> 1), max(1, H >> 1)
         out = np.zeros((h, w), np.uint32)
-        self.libs[real].br_downsample(_p(s), C.c_uint32(W), C.c_uint32(H), _p(out), C.c_uint32(w), C.c_uint32(h))
-        return out
+        v = np.zeros((h, w, 3), self._rt(real)) if value else None
+        self.libs[real].br_downsample(_p(s), C.c_uint32(W), C.c_uint32(H), _p(out), C.c_uint32(w), C.c_uint32(h), _p(v))
+        return (out, v) if value else out
 
-    def upsample(self, src, dst, radius, real="f32"):
+    def upsample(self, src, dst, radius, real="f32", value=False):
         """pass 2: the accumulated copy of `dst` (h, w) from `src` (H, W)"""
         s, d = np.ascontiguousarray(src, np.uint32), np.ascontiguousarray(dst, np.uint32).copy()
+        v = np.zeros(d.shape + (3,), self._rt(real)) if value else None
         self.libs[real].br_upsample(_p(s), C.c_uint32(s.shape[1]), C.c_uint32(s.shape[0]), _p(d), C.c_uint32(d.shape[1]), C.c_uint32(d.shape[0]),
-                                    C.c_float(radius))
-        return d
+                                    C.c_float(radius), _p(v))
+        return (d, v) if value else d
 
     def chain_from(self, level0, levels, real="f32"):
         """src/niagara.cpp:1873-1901 behind pass 0: downsample 1 .. levels - 1, upsample levels - 2 .. 0 with radius 2"""

@@ -89,6 +89,68 @@ def task_fixture():
                                                                      int(out["late1_counts"].sum())))
 
 
+def shade_fixtures():
+    """tests/golden/shade/<w>x<h>.npz: the inputs of the shading passes at three image sizes (tests/shade_cases.py) and what the REFERENCE'S
+    shaders, translated and run on the CPU (oracle/_ref), make of them: the stored words and the values handed to the stores of shadowfill,
+    shadowblur, final (without and with a bloom image), the three bloom passes and the bloom loop, and the attachments and discard flags of
+    mesh.frag over the records of one scene, factor-only and textured.  Data only.  A directory of its own: tests/test_golden.py reads the
+    .npz files directly under tests/golden as cull scenes."""
+    import tempfile
+
+    import bloom_ref as BR
+    import shade_cases as SC
+    import texture_ref as TR
+    import visattr_ref as VA
+    os.makedirs(SC.GOLDEN, exist_ok=True)
+    tmp = tempfile.mkdtemp()
+    aref, tref = VA.load(tmp), TR.load(tmp)
+    files, descs, texels = SC.frag_textures()
+    total = 0
+    for group, (w, h) in enumerate(SC.FIXTURE_SIZES):
+        i = SC.pass_inputs(w, h)
+        d = i["desc"]
+        f = dict(depth=i["depth"], shadow=i["shadow"], gbuffer0=i["gbuffer0"], gbuffer1=i["gbuffer1"], znear=np.float32(i["znear"]),
+                 sd=np.stack([np.frombuffer(sd.tobytes(), np.uint8) for sd in i["sd"]]), bloom_g0=i["bloom_g0"], levels=BR.pack(i["levels"]),
+                 levels2=BR.pack(i["levels2"]), bloom0=SC.bloom_levels(w, h, seed=4)[0])
+        for cb in (0, 1):
+            words, handed = R.shadow_fill(i["shadow"], i["depth"], cb)
+            f["fill%d_words" % cb], f["fill%d_value" % cb] = words, handed[..., 0]
+        for direction in (0, 1):
+            words, handed = R.shadow_blur(i["shadow"], i["depth"], direction, i["znear"])
+            f["blur%d_words" % direction], f["blur%d_value" % direction] = words, handed[..., 0]
+        for shadows in (0, 1):
+            shadow = i["shadow"] if shadows else None
+            words, handed = R.final(i["sd"][shadows], i["gbuffer0"], i["gbuffer1"], i["depth"], shadow)
+            f["final%d_words" % shadows], f["final%d_value" % shadows] = words, handed[..., :3]
+            words, handed = R.final(i["sd"][shadows], i["gbuffer0"], i["gbuffer1"], i["depth"], shadow, f["bloom0"])
+            f["finalbloom%d_words" % shadows], f["finalbloom%d_value" % shadows] = words, handed[..., :3]
+        words, handed = R.bloom_pass(0, i["bloom_g0"], d["sizes"][0][::-1])
+        f["extract_words"], f["extract_value"] = words, handed[..., :3]
+        down = [R.bloom_pass(1, i["levels"][l - 1], i["levels"][l].shape) for l in range(1, d["levels"])]
+        f["down_words"] = BR.pack([i["levels"][0]] + [a for a, _ in down])  # (level 0 is not written by pass 1: the given words)
+        f["down_value"] = np.concatenate([b[..., :3].reshape(-1, 3) for _, b in down])
+        for k, radius in enumerate(SC.RADII):
+            up = [R.bloom_pass(2, i["levels2"][l + 1], i["levels2"][l].shape, radius, dst=i["levels2"][l]) for l in range(d["levels"] - 1)]
+            f["up%d_words" % k] = BR.pack([a for a, _ in up] + [i["levels2"][-1]])  # (the last level is not written by pass 2)
+            f["up%d_value" % k] = np.concatenate([b[..., :3].reshape(-1, 3) for _, b in up])
+        f["loop_words"] = R.bloom(i["bloom_g0"], d["width"], d["height"], d["levels"], d["offsets"], d["total"])
+        s, rec = SC.frag_scene(w, h, group)
+        f["records"], f["materials"], f["material_index"] = rec, s["materials"], s["draws"]["materialIndex"]
+        plain = SC.untextured(s["materials"])
+        want = aref.attributes(s["g"], rec, w, h, s["draws"], s["meshlets"], s["data"], s["vertices"], plain)
+        out = R.mesh_frag(want["attributes"], w, s["draws"], plain, None, 1)
+        f["frag_gbuffer0"], f["frag_gbuffer1"], f["frag_discard"] = out["gbuffer0"], out["gbuffer1"], out["discard"]
+        want = tref.attributes(s["g"], rec, w, h, s["draws"], s["meshlets"], s["data"], s["vertices"], s["materials"], descs, texels, taps=True)
+        out = R.mesh_frag(want["attributes"], w, s["draws"], s["materials"], want["taps"], 1)
+        f["fragtex_gbuffer0"], f["fragtex_gbuffer1"], f["fragtex_discard"] = out["gbuffer0"], out["gbuffer1"], out["discard"]
+        path = os.path.join(SC.GOLDEN, "%dx%d.npz" % (w, h))
+        np.savez_compressed(path, **f)
+        total += os.path.getsize(path)
+        print("%-28s %6d bytes, %d arrays" % ("shade/%dx%d.npz" % (w, h), os.path.getsize(path), len(f)))
+    kitten = os.path.getsize(os.path.join(HERE, "mesh", "kitten.npz"))
+    assert total <= kitten, "the shade fixtures (%d bytes) outgrow the largest committed fixture (%d)" % (total, kitten)
+
+
 def kitten_fixture(obj):
     """tests/golden/mesh/kitten.npz: the reference's data/kitten.obj as arrays (the text file is too large to commit): positions and normals as
     float32 exactly as float() + np.float32 parse them, and every face corner as 0-based (position, normal) indices, three corners per triangle
@@ -115,6 +177,10 @@ if __name__ == "__main__":
     if len(sys.argv) == 3 and sys.argv[1] == "--kitten":
         kitten_fixture(sys.argv[2])
         raise SystemExit(0)
+    if len(sys.argv) == 2 and sys.argv[1] == "--shade":
+        shade_fixtures()
+        raise SystemExit(0)
     main()
     mesh_fixture()
     task_fixture()
+    shade_fixtures()

@@ -183,6 +183,29 @@ static REAL sr_gradient_noise(REAL x, REAL y)
 	return n - floor(n);
 }
 
+/* thin exported wrappers over the static helpers above, for tests/test_shading_vs_ref.py (arrays of n arguments) */
+void sr_x_decode_oct(const REAL* e, uint32_t n, REAL* out3)
+{
+	for (uint32_t i = 0; i < n; ++i)
+		sr_decode_oct(e[2 * (size_t)i], e[2 * (size_t)i + 1], out3 + 3 * (size_t)i);
+}
+void sr_x_tonemap(const REAL* c, uint32_t n, REAL* out)
+{
+	for (uint32_t i = 0; i < n; ++i)
+		out[i] = sr_tonemap(c[i]);
+}
+void sr_x_gradient_noise(const REAL* xy, uint32_t n, REAL* out)
+{
+	for (uint32_t i = 0; i < n; ++i)
+		out[i] = sr_gradient_noise(xy[2 * (size_t)i], xy[2 * (size_t)i + 1]);
+}
+/* fromsrgb as :46 of final.comp.glsl is restated below (:210 here) */
+void sr_x_fromsrgb(const REAL* c, uint32_t n, REAL* out)
+{
+	for (uint32_t i = 0; i < n; ++i)
+		out[i] = sr_pow(c[i], K(2.2f));
+}
+
 /* final.comp.glsl:37-80 with an all-zero bloom image.  shadow may be NULL unless sd->shadowsEnabled == 1.  value (optional, w * h * 4):
  * tonemap(outputColor).rgb and the deband term deband * (0.5 / 255) per pixel, before they are added and stored. */
 void sr_shade_final(const ShadeData* sd, const uint32_t* gbuffer0, const uint32_t* gbuffer1, const float* depthImage, const uint8_t* shadowImage,

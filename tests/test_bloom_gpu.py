@@ -10,6 +10,7 @@ import pytest
 
 import bloom_ref as BR
 import oracle
+import shade_cases as SC
 import shade_ref as SR
 import visattr_ref as VA
 from niagara_amd import host, synth
@@ -288,6 +289,61 @@ def test_shade_final_bloom_equals_the_restatement(size, shadows, ctx, bref):
     ctx.shade_final_bloom(sd, g0, g1, depth, shadow, with_zero, w, h, zero, desc)
     ctx.status()
     assert _host(plain, w * h * 4).tobytes() == _host(with_zero, w * h * 4).tobytes()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", SC.FIXTURES, ids=SC.FIXTURE_IDS)
+def test_fixtures_of_the_reference_shader_replay(path, ctx, bref):
+    """tests/golden/shade: the inputs and what the reference's own bloom.comp.glsl and final.comp.glsl, run on the CPU, stored for them (DESIGN.md
+    §2; tests/test_shade_fixtures_cpu.py holds the restatement to these words bit for bit).  The rules are this file's, unchanged: pass 0
+    adjacent codes, passes 1 and 2 bit-identical, nv_bloom as pass 0 at level 0 and bit-identical from there, final as §4.14."""
+    f = np.load(path)
+    w, h = SC.fixture_size(f)
+    d, desc = BR.desc(w, h), host.bloom_desc(w, h)
+    name = "fixture %dx%d" % (w, h)
+    n0 = d["sizes"][0][0] * d["sizes"][0][1]
+    src, out = _dev(ctx, f["bloom_g0"]), _out(ctx, d["total"] * 4)
+    ctx.bloom_extract(src, w, h, out, desc)
+    ctx.status()
+    got = _host(out, d["total"] * 4)
+    assert (got[n0:] == POISON * 0x01010101).all()
+    level0 = got[:n0].reshape(f["extract_words"].shape).copy()
+    _adjacent(name + ", extract", level0, f["extract_words"])
+    for level in range(1, d["levels"]):  # pass 1, each level from the given words
+        buf = _dev(ctx, f["levels"], TAIL)
+        ctx.bloom_downsample(buf, desc, level)
+        ctx.status()
+        got, want = BR.unpack(_host(buf, d["total"] * 4), d), BR.unpack(f["down_words"], d)
+        assert got[level].tobytes() == want[level].tobytes(), (name, "downsample", level, int((got[level] != want[level]).sum()))
+    for k, radius in enumerate(SC.RADII):  # pass 2, the staged form and the direct one
+        for level in range(d["levels"] - 1):
+            buf = _dev(ctx, f["levels2"], TAIL)
+            ctx.bloom_upsample(buf, desc, level, radius)
+            ctx.status()
+            got, want = BR.unpack(_host(buf, d["total"] * 4), d), BR.unpack(f["up%d_words" % k], d)
+            assert got[level].tobytes() == want[level].tobytes(), (name, "upsample", radius, level, int((got[level] != want[level]).sum()))
+    # the loop: from the reference's level 0 the single passes give the reference's words; nv_bloom gives what they give from its own level 0
+    words = _poison_words(d)
+    words[:n0] = f["extract_words"].reshape(-1)
+    single, chain = _dev(ctx, words, TAIL), _out(ctx, d["total"] * 4)
+    for i in range(1, d["levels"]):
+        ctx.bloom_downsample(single, desc, i)
+    for i in range(d["levels"] - 2, -1, -1):
+        ctx.bloom_upsample(single, desc, i, 2.0)
+    ctx.bloom(src, w, h, chain, desc)
+    ctx.status()
+    assert _host(single, d["total"] * 4).tobytes() == f["loop_words"].tobytes()
+    assert _host(chain, d["total"] * 4).tobytes() == BR.pack(bref.chain_from(level0, d["levels"])).tobytes()
+    # final with the fixture's bloom image
+    g0, g1, depth = _dev(ctx, f["gbuffer0"]), _dev(ctx, f["gbuffer1"]), _dev(ctx, f["depth"])
+    words = _poison_words(d)
+    words[:n0] = f["bloom0"].reshape(-1)
+    bloom = _dev(ctx, words)
+    for shadows in (0, 1):
+        out, shadow = _out(ctx, w * h * 4), _dev(ctx, f["shadow"]) if shadows else None
+        ctx.shade_final_bloom(SC.fixture_shade_data(f, shadows), g0, g1, depth, shadow, out, w, h, bloom, desc)
+        ctx.status()
+        _close8("%s, final with bloom, shadows %d" % (name, shadows), _host(out, w * h * 4).reshape(h, w), f["finalbloom%d_words" % shadows])
 
 
 @pytest.mark.gpu

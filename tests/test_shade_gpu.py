@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import oracle
+import shade_cases as SC
 import shade_ref as SR
 import visattr_ref as VA
 from niagara_amd import layouts as L
@@ -107,6 +108,37 @@ def test_shade_final_equals_the_restatement(size, shadows, ctx, sref):
     ctx.shade_final(sd, g0, g1, depth, shadow, out, w, h)
     ctx.status()
     _close("final %dx%d shadows %d" % (w, h, shadows), SR.channels(_host(out, w * h * 4, np.uint32, (h, w))), SR.channels(want), alpha=True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", SC.FIXTURES, ids=SC.FIXTURE_IDS)
+def test_fixtures_of_the_reference_shaders_replay(path, ctx):
+    """tests/golden/shade: the inputs and what the reference's own shadowfill / shadowblur / final, run on the CPU, stored for them (DESIGN.md
+    §2).  tests/test_shade_fixtures_cpu.py holds the restatement to these words bit for bit, so the comparison and its bounds are the ones
+    above, unchanged."""
+    f = np.load(path)
+    w, h = SC.fixture_size(f)
+    name = "fixture %dx%d" % (w, h)
+    depth = _dev(ctx, f["depth"])
+    x, y = np.meshgrid(np.arange(w), np.arange(h))
+    for cb in (0, 1):
+        shadow = _dev(ctx, f["shadow"], TAIL)
+        ctx.shadow_fill(shadow, depth, w, h, cb)
+        ctx.status()
+        got, owned = _host(shadow, w * h, np.uint8, (h, w)), (~(y ^ cb) & 1) == (x & 1)
+        assert (got[~owned] == f["shadow"][~owned]).all()
+        _close("%s, fill cb %d" % (name, cb), got[owned], f["fill%d_words" % cb][owned])
+    for direction in (1, 0):
+        shadow, out = _dev(ctx, f["shadow"]), _out(ctx, w * h)
+        ctx.shadow_blur(out, shadow, depth, w, h, direction, float(f["znear"]))
+        ctx.status()
+        _close("%s, blur direction %d" % (name, direction), _host(out, w * h, np.uint8, (h, w)), f["blur%d_words" % direction])
+    g0, g1 = _dev(ctx, f["gbuffer0"]), _dev(ctx, f["gbuffer1"])
+    for shadows in (0, 1):
+        out, shadow = _out(ctx, w * h * 4), _dev(ctx, f["shadow"]) if shadows else None
+        ctx.shade_final(SC.fixture_shade_data(f, shadows), g0, g1, depth, shadow, out, w, h)
+        ctx.status()
+        _close("%s, final shadows %d" % (name, shadows), SR.channels(_host(out, w * h * 4, np.uint32, (h, w))), SR.channels(f["final%d_words" % shadows]), alpha=True)
 
 
 @pytest.mark.gpu

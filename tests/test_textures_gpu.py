@@ -11,6 +11,7 @@ import pytest
 import oracle
 import pixel_cases as PC
 import raster_ref as RR
+import shade_cases as SC
 import texture_ref as TR
 import visattr_ref as VA
 import visbuffer_ref as VB
@@ -306,6 +307,26 @@ def test_textured_occluder_scene_equals_the_restatement_and_untextured_without_a
     a, b = _host(bare), _host(plain)
     assert all(a[k].tobytes() == b[k].tobytes() for k in a) and a["totals"][3] > 0
     assert (a["gbuffer0"] != _host(out)["gbuffer0"]).any()  # and the textures do change the picture
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", SC.FIXTURES, ids=SC.FIXTURE_IDS)
+def test_fixture_of_the_reference_fragment_shader_replays_textured(path, ctx, tref):
+    """tests/golden/shade: records of one scene and the attachments the reference's own mesh.frag.glsl, run on the CPU, writes for them with
+    the restatement's taps (tests/test_shade_fixtures_cpu.py holds the restatement to them bit for bit).  _same's rule, unchanged."""
+    from niagara_amd import pipeline as P
+    f = np.load(path)
+    w, h = SC.fixture_size(f)
+    s, rec = SC.fixture_frag_scene(path, f)
+    files, hdescs, htexels = SC.frag_textures()
+    want = _reference(tref, s, rec, w, h, hdescs, htexels)
+    assert want["totals"][3] == 0 and tref.bad_indices() == 0
+    want["gbuffer0"], want["gbuffer1"] = f["fragtex_gbuffer0"], f["fragtex_gbuffer1"]  # the expectation is the reference's
+    descs, texels = ctx.texture_decode(files)
+    assert texels.cpu().numpy().view(np.uint32)[:len(htexels)].tobytes() == htexels.tobytes()
+    out, _ = _textured(ctx, s, rec, w, h, P.to_device(descs, ctx.device), len(descs), texels, len(htexels))
+    ctx.status()
+    _same("fixture %dx%d" % (w, h), _host(out), want, hdescs, s["materials"])
 
 
 # ---- edges

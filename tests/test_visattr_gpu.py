@@ -11,6 +11,7 @@ import pytest
 
 import oracle
 import raster_ref as RR
+import shade_cases as SC
 import visattr_ref as VA
 import visbuffer_ref as VB
 from niagara_amd import layouts as L
@@ -137,6 +138,37 @@ def test_attributes_after_frame_and_resolve_equal_the_restatement(name, vref, ar
     finally:
         pipe.ctx.close()
     assert want["totals"][0] > 0 and want["totals"][1] == 0 and want["totals"][2] == 0 and want["totals"][3] > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", SC.FIXTURES, ids=SC.FIXTURE_IDS)
+def test_fixture_of_the_reference_fragment_shader_replays(path, aref):
+    """tests/golden/shade: records of one scene and the attachments the reference's own mesh.frag.glsl, run on the CPU, writes for them with
+    factor-only materials (tests/test_shade_fixtures_cpu.py holds the restatement to them bit for bit).  This file's rule,
+    unchanged: records and gbuffer1 bit for bit, gbuffer0 within one code and 90 % of the channels equal."""
+    import torch
+    from niagara_amd import pipeline as P
+    f = np.load(path)
+    w, h = SC.fixture_size(f)
+    s, rec = SC.fixture_frag_scene(path, f)
+    s["materials"] = SC.untextured(s["materials"])
+    want = aref.attributes(s["g"], rec, w, h, s["draws"], s["meshlets"], s["data"], s["vertices"], s["materials"])
+    want["gbuffer0"], want["gbuffer1"] = f["frag_gbuffer0"], f["frag_gbuffer1"]  # the expectation is the reference's
+    ctx = P.Context()
+    try:
+        dev, n = ctx.device, w * h
+        t = [P.to_device(s[k], dev) for k in ("draws", "meshlets", "data", "vertices", "materials")] + [P.to_device(rec, dev)]
+        out = dict(attributes=torch.full((n * 64 + 64,), POISON, dtype=torch.uint8, device=dev), gbuffer0=torch.full((n + 16,), 0x5A5A5A5A, dtype=torch.int32, device=dev),
+                   gbuffer1=torch.full((n + 16,), 0x5A5A5A5A, dtype=torch.int32, device=dev), totals=torch.zeros(4, dtype=torch.int64, device=dev))
+        ctx.visibility_attributes(s["g"], t[5], w, h, t[0], len(s["draws"]), t[1], len(s["meshlets"]), t[2], len(s["data"]), t[3], len(s["vertices"]), t[4],
+                                  len(s["materials"]), out["attributes"], out["gbuffer0"], out["gbuffer1"], out["totals"])
+        ctx.status()
+        assert (out["attributes"][n * 64:].cpu().numpy() == POISON).all() and (out["gbuffer0"][n:].cpu().numpy() == 0x5A5A5A5A).all()
+        assert (out["gbuffer1"][n:].cpu().numpy() == 0x5A5A5A5A).all(), "words behind the images were written"
+        got = _host(dict(attributes=out["attributes"][:n * 64], gbuffer0=out["gbuffer0"][:n], gbuffer1=out["gbuffer1"][:n], totals=out["totals"]))
+        _same_attributes(got, want)
+    finally:
+        ctx.close()
 
 
 def _frame_records(pipe, s):

@@ -344,6 +344,14 @@ void tr_hits(uint64_t out[16], int reset)
 
 /* ---- nv_visibility_attributes_textured: visattr_ref.c's pass with the complete fragment stage.  Outputs as va_attributes; flag 16 = the
  * material names a texture that was NOT sampled; flag 32 = a normal map was sampled; lod: lambda of the last texture sampled (optional) */
+/* the texel a slot (0 albedo, 1 normal, 2 specular, 3 emissive) was given, recorded for tests/test_shading_vs_ref.py; always 1 */
+static int tr_tap(REAL* taps, uint32_t pixel, int slot, const REAL s[4])
+{
+	if (taps)
+		memcpy(taps + (size_t)pixel * 16 + 4 * slot, s, 4 * sizeof(REAL));
+	return 1;
+}
+
 static int tr_bary(const Corner c[3], REAL fx, REAL fy, uint32_t W, uint32_t H, REAL l[3])
 {
 	REAL nx = (fx / (REAL)W) * K(2.0f) - K(1.0f), ny = K(1.0f) - (fy / (REAL)H) * K(2.0f), dx[3], dy[3], b[3];
@@ -363,10 +371,11 @@ static int tr_bary(const Corner c[3], REAL fx, REAL fy, uint32_t W, uint32_t H, 
 	return 0;
 }
 
-void tr_attributes(const Globals* g, const VisRecord* records, uint32_t W, uint32_t H, const Draw* draws, uint32_t drawCount, const Meshlet* meshlets,
+static void tr_attributes_impl(const Globals* g, const VisRecord* records, uint32_t W, uint32_t H, const Draw* draws, uint32_t drawCount, const Meshlet* meshlets,
                    uint32_t meshletCount, const uint32_t* data, uint32_t dataWords, const Vertex* vertices, uint32_t vertexCount,
                    const Material* materials, uint32_t materialCount, const TexDesc* descs, uint32_t textureCount, const uint32_t* texels,
-                   uint64_t texelWords, REAL* vals, uint32_t* ids, uint32_t* gb0, uint32_t* gb1, uint64_t* totals4, uint8_t* flags, REAL* chan)
+                   uint64_t texelWords, REAL* vals, uint32_t* ids, uint32_t* gb0, uint32_t* gb1, uint64_t* totals4, uint8_t* flags, REAL* chan,
+                   REAL* taps)
 {
 	for (uint32_t i = 0; i < W * H; ++i)
 	{
@@ -420,7 +429,7 @@ void tr_attributes(const Globals* g, const VisRecord* records, uint32_t W, uint3
 				em[k] = (REAL)m->emissiveFactor[k];
 			if (m->albedoTexture > 0)
 			{
-				if (tr_sample(descs, textureCount, texels, texelWords, m->albedoTexture, uv, dx, dy, s))
+				if (tr_sample(descs, textureCount, texels, texelWords, m->albedoTexture, uv, dx, dy, s) && tr_tap(taps, i, 0, s))
 				{
 					for (int k = 0; k < 3; ++k)
 						albedo[k] = albedo[k] * pow(s[k], K(2.2f));
@@ -431,7 +440,7 @@ void tr_attributes(const Globals* g, const VisRecord* records, uint32_t W, uint3
 			}
 			if (m->normalTexture > 0)
 			{
-				if (tr_sample(descs, textureCount, texels, texelWords, m->normalTexture, uv, dx, dy, s))
+				if (tr_sample(descs, textureCount, texels, texelWords, m->normalTexture, uv, dx, dy, s) && tr_tap(taps, i, 1, s))
 				{
 					for (int k = 0; k < 3; ++k)
 						nmap[k] = s[k] * K(2.0f) - K(1.0f);
@@ -442,14 +451,14 @@ void tr_attributes(const Globals* g, const VisRecord* records, uint32_t W, uint3
 			}
 			if (m->specularTexture > 0)
 			{
-				if (tr_sample(descs, textureCount, texels, texelWords, m->specularTexture, uv, dx, dy, s))
+				if (tr_sample(descs, textureCount, texels, texelWords, m->specularTexture, uv, dx, dy, s) && tr_tap(taps, i, 2, s))
 					gloss = gloss * s[3];
 				else
 					fl |= 16;
 			}
 			if (m->emissiveTexture > 0)
 			{
-				if (tr_sample(descs, textureCount, texels, texelWords, m->emissiveTexture, uv, dx, dy, s))
+				if (tr_sample(descs, textureCount, texels, texelWords, m->emissiveTexture, uv, dx, dy, s) && tr_tap(taps, i, 3, s))
 					for (int k = 0; k < 3; ++k)
 						em[k] = em[k] * pow(s[k], K(2.2f));
 				else
@@ -465,16 +474,13 @@ void tr_attributes(const Globals* g, const VisRecord* records, uint32_t W, uint3
 			}
 			va_normalize(nrm);
 			REAL emissivef = ((em[0] * K(0.3f) + em[1] * K(0.6f)) + em[2] * K(0.1f)) / (((albedo[0] * K(0.3f) + albedo[1] * K(0.6f)) + albedo[2] * K(0.1f)) + K(1e-3f));
-			REAL gamma = K(1.0f) / K(2.2f);
 			for (int k = 0; k < 3; ++k)
-				ch[k] = pow(albedo[k], gamma);
+				ch[k] = va_tosrgb(albedo[k]);
 			ch[3] = log2(K(1.0f) + emissivef) / K(5.0f);
 			g0 = va_unorm(ch[0], K(255.0f)) | va_unorm(ch[1], K(255.0f)) << 8 | va_unorm(ch[2], K(255.0f)) << 16 | va_unorm(ch[3], K(255.0f)) << 24;
-			REAL inv = K(1.0f) / ((fabs(nrm[0]) + fabs(nrm[1])) + fabs(nrm[2]));
-			REAL ox = nrm[0] * inv, oy = nrm[1] * inv;
-			REAL sx = nrm[0] >= K(0.0f) ? K(1.0f) : K(-1.0f), sy = nrm[1] >= K(0.0f) ? K(1.0f) : K(-1.0f);
-			REAL ex = nrm[2] <= K(0.0f) ? (K(1.0f) - fabs(oy)) * sx : ox;
-			REAL ey = nrm[2] <= K(0.0f) ? (K(1.0f) - fabs(ox)) * sy : oy;
+			REAL oct[2];
+			va_encode_oct(nrm, oct);
+			REAL ex = oct[0], ey = oct[1];
 			REAL band = deband * (K(0.5f) / K(1023.0f));
 			ch[4] = (ex * K(0.5f) + K(0.5f)) + band;
 			ch[5] = (ey * K(0.5f) + K(0.5f)) + band;
@@ -502,4 +508,25 @@ void tr_attributes(const Globals* g, const VisRecord* records, uint32_t W, uint3
 		if (chan)
 			memcpy(chan + (size_t)i * 8, ch, sizeof(ch));
 	}
+}
+
+void tr_attributes(const Globals* g, const VisRecord* records, uint32_t W, uint32_t H, const Draw* draws, uint32_t drawCount, const Meshlet* meshlets,
+                   uint32_t meshletCount, const uint32_t* data, uint32_t dataWords, const Vertex* vertices, uint32_t vertexCount,
+                   const Material* materials, uint32_t materialCount, const TexDesc* descs, uint32_t textureCount, const uint32_t* texels,
+                   uint64_t texelWords, REAL* vals, uint32_t* ids, uint32_t* gb0, uint32_t* gb1, uint64_t* totals4, uint8_t* flags, REAL* chan)
+{
+	tr_attributes_impl(g, records, W, H, draws, drawCount, meshlets, meshletCount, data, dataWords, vertices, vertexCount, materials, materialCount, descs,
+	                   textureCount, texels, texelWords, vals, ids, gb0, gb1, totals4, flags, chan, 0);
+}
+
+/* tr_attributes, and per pixel the four texels tr_sample returned (taps: W * H * 16 REAL, slots albedo / normal / specular / emissive; a slot
+ * that was not sampled keeps what the caller put there): a thin wrapper for tests/test_shading_vs_ref.py */
+void tr_attributes_taps(const Globals* g, const VisRecord* records, uint32_t W, uint32_t H, const Draw* draws, uint32_t drawCount, const Meshlet* meshlets,
+                        uint32_t meshletCount, const uint32_t* data, uint32_t dataWords, const Vertex* vertices, uint32_t vertexCount,
+                        const Material* materials, uint32_t materialCount, const TexDesc* descs, uint32_t textureCount, const uint32_t* texels,
+                        uint64_t texelWords, REAL* vals, uint32_t* ids, uint32_t* gb0, uint32_t* gb1, uint64_t* totals4, uint8_t* flags, REAL* chan,
+                        REAL* taps)
+{
+	tr_attributes_impl(g, records, W, H, draws, drawCount, meshlets, meshletCount, data, dataWords, vertices, vertexCount, materials, materialCount, descs,
+	                   textureCount, texels, texelWords, vals, ids, gb0, gb1, totals4, flags, chan, taps);
 }

@@ -41,7 +41,7 @@ class TexRef:
         self.libs = {"f32": C.CDLL(so32), "f64": C.CDLL(so64)}
         for k, size in (("f32", 4), ("f64", 8)):
             assert self.libs[k].va_real_bytes() == size
-            for f in ("tr_decode_block", "tr_decode_chain", "tr_sample_many", "tr_attributes", "tr_hits"):
+            for f in ("tr_decode_block", "tr_decode_chain", "tr_sample_many", "tr_attributes", "tr_attributes_taps", "tr_hits"):
                 getattr(self.libs[k], f).restype = None
             self.libs[k].tr_bad_indices.restype = C.c_uint64
 
@@ -97,8 +97,9 @@ class TexRef:
         return out
 
     def attributes(self, g, records, width, height, draws, meshlets, data, vertices, materials, descs, texels, real="f32", texel_words=None,
-                   texture_count=None):
-        """visattr_ref.AttrRef.attributes with the complete fragment stage; flags: NOT_SAMPLED, NORMAL_MAPPED besides visattr_ref's"""
+                   texture_count=None, taps=False):
+        """visattr_ref.AttrRef.attributes with the complete fragment stage; flags: NOT_SAMPLED, NORMAL_MAPPED besides visattr_ref's.
+        taps=True adds "taps" (h * w, 4, 4): the texel the albedo / normal / specular / emissive slot was given (0 where it was not sampled)"""
         rt = np.float32 if real == "f32" else np.float64
         n = width * height
         records = np.ascontiguousarray(records, L.VISRECORD).reshape(-1)
@@ -112,10 +113,15 @@ class TexRef:
         count = len(descs) if texture_count is None else texture_count
         out = dict(vals=np.zeros((n, 14), rt), ids=np.zeros((n, 2), np.uint32), gbuffer0=np.zeros(n, np.uint32), gbuffer1=np.zeros(n, np.uint32),
                    totals=np.zeros(4, np.uint64), flags=np.zeros(n, np.uint8), chan=np.zeros((n, 8), rt))
-        self.libs[real].tr_attributes(_p(np.ascontiguousarray(g)), _p(records), C.c_uint32(width), C.c_uint32(height), _p(draws), C.c_uint32(len(draws)),
-                                      _p(meshlets), C.c_uint32(len(meshlets)), _p(data), C.c_uint32(len(data)), _p(vertices), C.c_uint32(len(vertices)),
-                                      _p(mats), C.c_uint32(len(mats)), _p(descs), C.c_uint32(count), _p(tex), C.c_uint64(words), _p(out["vals"]),
-                                      _p(out["ids"]), _p(out["gbuffer0"]), _p(out["gbuffer1"]), _p(out["totals"]), _p(out["flags"]), _p(out["chan"]))
+        args = [_p(np.ascontiguousarray(g)), _p(records), C.c_uint32(width), C.c_uint32(height), _p(draws), C.c_uint32(len(draws)),
+                _p(meshlets), C.c_uint32(len(meshlets)), _p(data), C.c_uint32(len(data)), _p(vertices), C.c_uint32(len(vertices)),
+                _p(mats), C.c_uint32(len(mats)), _p(descs), C.c_uint32(count), _p(tex), C.c_uint64(words), _p(out["vals"]),
+                _p(out["ids"]), _p(out["gbuffer0"]), _p(out["gbuffer1"]), _p(out["totals"]), _p(out["flags"]), _p(out["chan"])]
+        if taps:
+            out["taps"] = np.zeros((n, 4, 4), rt)
+            self.libs[real].tr_attributes_taps(*args, _p(out["taps"]))
+        else:
+            self.libs[real].tr_attributes(*args)
         if real == "f32":
             a = np.zeros(n, L.PIXELATTR)
             for name, sl in VA._SLICES.items():

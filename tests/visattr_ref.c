@@ -3,7 +3,8 @@
  * Test infrastructure: compiled by tests/visattr_ref.py with raster_ref.c's flags, twice: as it stands (REAL = float: every statement one
  * IEEE fp32 operation, the bits the HIP kernel must write) and with -DREAL=double (the same statements in fp64 from the same fp32 / fp16
  * inputs and the same fp32 constants: the yardstick of the accuracy checks).  raster_ref.c is included for the record layouts, f16 and fbits;
- * the arithmetic is restated here in REAL.  There is no oracle for this stage: oracle/_ref stubs unpackTBN, parity is to this file. */
+ * the arithmetic is restated here in REAL.  tests/test_shading_vs_ref.py holds this file's fp32 build bit for bit
+ * to the reference's unpackTBN and mesh.frag.glsl executed by oracle/_ref. */
 #include "raster_ref.c"
 #include <tgmath.h>
 
@@ -66,14 +67,56 @@ static void va_decode_oct(REAL ex, REAL ey, REAL v[3])
 	va_normalize(v);
 }
 
+/* src/shaders/math.h:104-109 unpackTBN */
+static void va_unpack_tbn(uint32_t np, uint32_t tp, REAL normal[3], REAL tangent[4])
+{
+	for (int k = 0; k < 3; ++k)
+		normal[k] = (REAL)(int32_t)(np >> (10 * k) & 1023u) / K(511.0f) - K(1.0f);
+	va_decode_oct((REAL)(int32_t)(tp & 255u) / K(127.0f) - K(1.0f), (REAL)(int32_t)(tp >> 8 & 255u) / K(127.0f) - K(1.0f), tangent);
+	tangent[3] = (np & (1u << 30)) != 0 ? K(-1.0f) : K(1.0f);
+}
+
+/* src/shaders/math.h:52-58 encodeOct */
+static void va_encode_oct(const REAL nrm[3], REAL e[2])
+{
+	REAL inv = K(1.0f) / ((fabs(nrm[0]) + fabs(nrm[1])) + fabs(nrm[2]));
+	REAL ox = nrm[0] * inv, oy = nrm[1] * inv;
+	REAL sx = nrm[0] >= K(0.0f) ? K(1.0f) : K(-1.0f), sy = nrm[1] >= K(0.0f) ? K(1.0f) : K(-1.0f);
+	e[0] = nrm[2] <= K(0.0f) ? (K(1.0f) - fabs(oy)) * sx : ox;
+	e[1] = nrm[2] <= K(0.0f) ? (K(1.0f) - fabs(ox)) * sy : oy;
+}
+
+/* src/shaders/math.h:74-77 tosrgb, one component */
+static REAL va_tosrgb(REAL c) { return pow(c, K(1.0f) / K(2.2f)); }
+
+/* thin exported wrappers over the helpers above, for tests/test_shading_vs_ref.py (arrays of n arguments) */
+void va_x_unpack_tbn(const uint32_t* np, const uint32_t* tp, uint32_t n, REAL* normal3, REAL* tangent4)
+{
+	for (uint32_t i = 0; i < n; ++i)
+		va_unpack_tbn(np[i], tp[i], normal3 + 3 * (size_t)i, tangent4 + 4 * (size_t)i);
+}
+void va_x_decode_oct(const REAL* e, uint32_t n, REAL* out3)
+{
+	for (uint32_t i = 0; i < n; ++i)
+		va_decode_oct(e[2 * (size_t)i], e[2 * (size_t)i + 1], out3 + 3 * (size_t)i);
+}
+void va_x_encode_oct(const REAL* v, uint32_t n, REAL* out2)
+{
+	for (uint32_t i = 0; i < n; ++i)
+		va_encode_oct(v + 3 * (size_t)i, out2 + 2 * (size_t)i);
+}
+void va_x_tosrgb(const REAL* c, uint32_t n, REAL* out)
+{
+	for (uint32_t i = 0; i < n; ++i)
+		out[i] = va_tosrgb(c[i]);
+}
+
 /* src/shaders/meshlet.mesh.glsl:129-140: one vertex (unpackTBN: src/shaders/math.h:104-109) */
 static void va_vertex(const Globals* g, const Draw* d, const Vertex* v, Corner* o)
 {
-	REAL normal[3], tangent[3], position[3] = { f16(v->vx), f16(v->vy), f16(v->vz) }, rot[3], v4[4];
-	for (int k = 0; k < 3; ++k)
-		normal[k] = (REAL)(int32_t)(v->np >> (10 * k) & 1023u) / K(511.0f) - K(1.0f);
-	va_decode_oct((REAL)(int32_t)(v->tp & 255u) / K(127.0f) - K(1.0f), (REAL)(int32_t)(v->tp >> 8 & 255u) / K(127.0f) - K(1.0f), tangent);
-	o->t[3] = (v->np & (1u << 30)) != 0 ? K(-1.0f) : K(1.0f);
+	REAL normal[3], tangent[4], position[3] = { f16(v->vx), f16(v->vy), f16(v->vz) }, rot[3], v4[4];
+	va_unpack_tbn(v->np, v->tp, normal, tangent);
+	o->t[3] = tangent[3];
 	va_rotate(normal, d->orientation, o->n);
 	va_rotate(tangent, d->orientation, o->t);
 	o->uv[0] = f16(v->tu), o->uv[1] = f16(v->tv);
@@ -233,17 +276,14 @@ void va_attributes(const Globals* g, const VisRecord* records, uint32_t W, uint3
 				REAL emissivef = (((REAL)m->emissiveFactor[0] * K(0.3f) + (REAL)m->emissiveFactor[1] * K(0.6f)) + (REAL)m->emissiveFactor[2] * K(0.1f)) /
 				                 ((((REAL)m->diffuseFactor[0] * K(0.3f) + (REAL)m->diffuseFactor[1] * K(0.6f)) + (REAL)m->diffuseFactor[2] * K(0.1f)) + K(1e-3f));
 				/* :85, src/shaders/math.h:74-77 tosrgb */
-				REAL gamma = K(1.0f) / K(2.2f);
 				for (int k = 0; k < 3; ++k)
-					ch[k] = pow((REAL)m->diffuseFactor[k], gamma);
+					ch[k] = va_tosrgb((REAL)m->diffuseFactor[k]);
 				ch[3] = log2(K(1.0f) + emissivef) / K(5.0f);
 				g0 = va_unorm(ch[0], K(255.0f)) | va_unorm(ch[1], K(255.0f)) << 8 | va_unorm(ch[2], K(255.0f)) << 16 | va_unorm(ch[3], K(255.0f)) << 24;
 				/* :86, src/shaders/math.h:52-58 encodeOct */
-				REAL inv = K(1.0f) / ((fabs(nrm[0]) + fabs(nrm[1])) + fabs(nrm[2]));
-				REAL ox = nrm[0] * inv, oy = nrm[1] * inv;
-				REAL sx = nrm[0] >= K(0.0f) ? K(1.0f) : K(-1.0f), sy = nrm[1] >= K(0.0f) ? K(1.0f) : K(-1.0f);
-				REAL ex = nrm[2] <= K(0.0f) ? (K(1.0f) - fabs(oy)) * sx : ox;
-				REAL ey = nrm[2] <= K(0.0f) ? (K(1.0f) - fabs(ox)) * sy : oy;
+				REAL oct[2];
+				va_encode_oct(nrm, oct);
+				REAL ex = oct[0], ey = oct[1];
 				REAL band = deband * (K(0.5f) / K(1023.0f));
 				ch[4] = (ex * K(0.5f) + K(0.5f)) + band;
 				ch[5] = (ey * K(0.5f) + K(0.5f)) + band;
