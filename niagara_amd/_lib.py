@@ -67,6 +67,8 @@ if not os.path.exists(SO_PATH):
 
 lib = C.CDLL(SO_PATH)
 
+# nv_profile_read: the NV_PROF_* slots of include/niagara_vis.h in their order (NV_PROF_SLOTS names); pipeline.Context.profile_read's keys
+PROF_NAMES = ("cluster_cull", "cluster_scatter", "drawcull", "depthreduce", "cluster_hiz")
 # nv_profile_variants: the NV_VARIANT_* slots of include/niagara_vis.h in their order (NV_VARIANT_SLOTS names); pipeline.Context.VARIANTS is this tuple
 VARIANT_NAMES = ("cull_filter_ring4", "cull_filter_ring8", "cull_direct", "cull_lanes_bits", "cull_lanes", "cull_aos", "hiz_stage", "task_list", "task_per_draw", "cull_direct_packed")
 
@@ -80,7 +82,7 @@ _SIGS = {
     "nv_reserve": (_i, [_vp, _u32, _u32]),
     "nv_share_scene": (_i, [_vp, _vp]),
     "nv_profile_enable": (_i, [_vp, _i]),
-    "nv_profile_read": (_i, [_vp, C.POINTER(C.c_float * 5), C.POINTER(C.c_uint32 * 5)]),
+    "nv_profile_read": (_i, [_vp, C.POINTER(C.c_float * len(PROF_NAMES)), C.POINTER(C.c_uint32 * len(PROF_NAMES))]),
     "nv_profile_variants": (_i, [_vp, C.POINTER(C.c_uint32 * len(VARIANT_NAMES))]),
     "nv_upload_meshlets": (_i, [_vp, _vp, _vp, _u32]),
     "nv_debug_block_table": (_i, [_vp, _vp, _u32, C.POINTER(_u32)]),

@@ -1,5 +1,6 @@
-// args.h — kernel argument blocks shared by the launchers (context.hip) and the kernels, and the ordered-append scheme
-// both cull passes use.
+// args.h — the kernel argument blocks, one struct per launch: the entry points (context.hip) fill the caller-facing fields, the launchers
+// (launch.h) take the struct by value and complete the fields derived from them, the kernels read it.  And the ordered-append scheme both
+// cull passes use.
 //
 // Ordered append — deterministic (invocation-ordered) append for gfx950: the scheme shared by clustercull.hip and drawcull.hip.
 //
@@ -29,6 +30,7 @@
 
 #include "../../include/niagara_vis.h"
 #include "dealing.h"
+#include "rtmath.h" // RtAlphaInputs (ShadowTraceAlphaArgs)
 
 // Tuning experiments (wave stamps, partial passes, alternative dealing ...) exist only in a separate build
 // (-DNV_EXPERIMENTS -> libniagara_vis_exp.so, tools/): the product library carries no switch that could change a result
@@ -150,7 +152,7 @@ struct ClusterArgs
 	uint32_t scatterTiles; // grid of the scatter kernel (<= CC_MAX_SCATTER_TILES)
 	uint32_t generations;  // workgroups of the cull kernel per CU (its grid = generations x CUs)
 	uint32_t dealScale;    // percent of the nominal start-delay compensation of the dealing (tuning; 100)
-	// Divisions by launch constants, prepared by the host (context.hip magic_for): q = mulhi(n, magic) >> 7, exact for n < 2^39 / d;
+	// Divisions by launch constants, prepared by the host (host.cpp nv_division_magic): q = mulhi(n, magic) >> 7, exact for n < 2^39 / d;
 	// 0 = not available (d < 256 or > 8192: the kernels divide).  The cull launch's prologue is on every wave's start-up path and
 	// an instruction there costs what one per command costs in the filter loop (filler_sensitivity.sh).
 	uint32_t cullWavesMagic;  // d = waves of the cull launch (grid x 4)
@@ -158,7 +160,7 @@ struct ClusterArgs
 	uint32_t tilesMagic;      // d = scatterTiles
 	DealPlan plan;            // the cull launch's dealing for the command count the host expects (dealing.h); used iff the count word agrees
 	float filterK;         // 4 K u S of the conservative filter / certified test (clustercull.hip make_filter); 0 = both off
-	// what make_filter derives from the view matrix alone, done once on the host in the same fp32 operations (context.hip view_norms):
+	// what make_filter derives from the view matrix alone, done once on the host in the same fp32 operations (filtermath.h filter_view_norms):
 	// every wave computed these ~40 instructions in its prologue, and an instruction there costs what 1 / 25 per command costs (§4.1)
 	float viewRowNorm;     // max over rows r of |V(r,0)| + |V(r,1)| + |V(r,2)|
 	float viewTransNorm;   // max over rows r of |V(r,3)|
@@ -271,6 +273,119 @@ struct RasterIndexedArgs
 	uint32_t scanBlocks, perBlock;      // workgroups of the count launch, commands per workgroup
 	unsigned long long* __restrict__ totals;   // optional
 	unsigned long long* __restrict__ partials; // library scratch: 4 counters per workgroup of the raster launch
+};
+
+// nv_cluster_expand (submit.hip): the launch's arguments on the host; the kernel takes them one by one
+struct ClusterExpandArgs
+{
+	const NvMeshTaskCommand* commands;
+	const NvMeshlet* meshlets;
+	const uint32_t* clusterIndices;
+	const uint32_t* cc4;
+	NvClusterRecord* records; // optional
+	uint32_t capacity;
+	unsigned long long* totals;
+	unsigned long long* partials; // library scratch: 3 counters per workgroup of the launch
+};
+
+// nv_visibility_resolve (visresolve.hip)
+struct VisResolveArgs
+{
+	NvCullData cd;
+	const unsigned long long* __restrict__ visibility;
+	uint32_t n; // pixels, <= 16384 * 16384
+	const NvMeshDraw* __restrict__ draws;
+	uint32_t drawCount;
+	const NvMesh* __restrict__ meshes;
+	uint32_t meshCount;
+	uint4* __restrict__ records;        // optional
+	uint32_t* meshletSeen;              // optional
+	uint32_t* drawPixels;               // optional
+	unsigned long long* totals;         // optional
+};
+
+// nv_visibility_attributes (visattr.h, visattr.hip)
+typedef uint32_t va_u4 __attribute__((ext_vector_type(4))); // (a native vector: what the non-temporal load builtin takes)
+
+struct VisAttrArgs
+{
+	NvGlobals globals;
+	const va_u4* __restrict__ records;
+	uint32_t width, n; // n = width * height <= 16384 * 16384 (the launcher's)
+	float fw, fh;      // (float)width, (float)height (the launcher's)
+	const NvMeshDraw* __restrict__ draws;
+	uint32_t drawCount;
+	const NvMeshlet* __restrict__ meshlets;
+	uint32_t meshletCount;
+	const uint32_t* __restrict__ meshletData;
+	uint32_t dataWords;
+	const NvVertex* __restrict__ vertices;
+	uint32_t vertexCount;
+	const NvMaterial* __restrict__ materials; // optional
+	uint32_t materialCount;
+	uint4* __restrict__ attributes;           // optional
+	uint32_t* __restrict__ gbuffer0;          // optional
+	uint32_t* __restrict__ gbuffer1;          // optional
+	unsigned long long* totals;               // optional
+};
+
+// the texture set of the textured pass
+struct VaTextures
+{
+	const uint4* __restrict__ descs; // NvTextureDesc, entry 0 reserved
+	uint32_t count;
+	const uint32_t* __restrict__ texels;
+	unsigned long long texelWords;
+};
+
+// nv_visibility_attributes_textured (visattr.h, visattr_tex.hip): VisAttrArgs plus the texture set
+struct VisAttrTexArgs : VisAttrArgs
+{
+	VaTextures tx;
+};
+
+// nv_shade_final (shade.hip)
+struct ShadeFinalArgs
+{
+	NvShadeData sd;
+	const uint32_t* __restrict__ gbuffer0;
+	const uint32_t* __restrict__ gbuffer1;
+	const float* __restrict__ depth;
+	const uint8_t* __restrict__ shadow; // read only by the SHADOW = true instantiation
+	uint32_t* __restrict__ color;
+	uint32_t width, n; // n = width * height (the launcher's)
+};
+
+// nv_shade_final_bloom: the kernel argument of the BLOOM = true instantiations; the others keep ShadeFinalArgs, and with it their code
+struct ShadeFinalBloomArgs : ShadeFinalArgs
+{
+	const uint32_t* __restrict__ bloom; // level 0 of the bloom target; nullptr: nv_shade_final
+	uint32_t bloomWidth, bloomHeight;
+};
+
+// nv_shadow_trace (shadowtrace.h, shadowtrace.hip)
+struct ShadowTraceArgs
+{
+	NvShadowData sd;
+	const unsigned char* __restrict__ scene;
+	const float* __restrict__ depth;
+	uint8_t* __restrict__ shadow;
+	uint32_t width, height;
+	uint32_t invocationsX; // checkerboard > 0 ? (width + 1) / 2 : width (the launcher's, like the next two)
+	uint32_t tilesX, tiles;
+};
+
+// nv_shadow_trace_textured at quality 1 (shadowtrace.h, shadowtrace_alpha.hip)
+struct ShadowTraceAlphaArgs
+{
+	NvShadowData sd;
+	RtAlphaInputs in;
+	const unsigned char* __restrict__ scene;
+	const float* __restrict__ depth;
+	uint8_t* __restrict__ shadow;
+	uint32_t width, height;
+	uint32_t invocationsX; // as ShadowTraceArgs
+	uint32_t tilesX, tiles;
 };
 
 } // namespace nv

@@ -10,6 +10,7 @@
 // None of the kernels waits on another workgroup, nothing is allocated: the entry points only enqueue and can be captured.
 #include "cullmath.h"
 #include "bloommath.h"
+#include "launch.h"
 
 namespace nv
 {
@@ -296,9 +297,7 @@ int launch_bloom_tail(hipStream_t stream, uint32_t* bloom, const NvBloomDesc& d,
 int launch_bloom_extract(hipStream_t stream, const uint32_t* gbuffer0, uint32_t width, uint32_t height, uint32_t* bloom, const NvBloomDesc& d, uint32_t maxBlocks)
 {
 	const uint32_t n = d.width * d.height;
-	uint32_t grid = (n + BL_THREADS - 1u) / BL_THREADS;
-	grid = grid < maxBlocks ? grid : maxBlocks;
-	hipLaunchKernelGGL(bloom_extract_kernel, dim3(grid), dim3(BL_THREADS), 0, stream, gbuffer0, bloom + d.levelOffset[0], width, height, d.width, d.height, n);
+	hipLaunchKernelGGL(bloom_extract_kernel, dim3(capped_grid(n, BL_THREADS, maxBlocks)), dim3(BL_THREADS), 0, stream, gbuffer0, bloom + d.levelOffset[0], width, height, d.width, d.height, n);
 	return (int)hipGetLastError();
 }
 

@@ -18,7 +18,7 @@
 //     sphere grows by exactly that point, and the search resumes behind it — the same sequence of updates as the loop,
 //     in a handful of rounds instead of up to 288 dependent steps.
 #include "cullmath.h"
-#include "args.h"
+#include "launch.h"
 
 namespace nv
 {

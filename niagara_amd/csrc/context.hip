@@ -1,6 +1,10 @@
-// context.hip — the extern "C" boundary declared in include/niagara_vis.h: context lifetime, argument packing and
-// kernel launches.  No torch types, no exceptions across the ABI; every entry point only enqueues on the caller's
-// stream (nv_status and scratch growth are the only synchronising calls).
+// context.hip — the extern "C" boundary declared in include/niagara_vis.h: context lifetime, argument checks and packing, kernel launches.
+// No torch types, no exceptions across the ABI; every entry point only enqueues on the caller's stream (nv_status and scratch growth are the
+// only synchronising calls).
+//
+// One convention for every pass: the entry point refuses what it can see is wrong BEFORE anything is enqueued, in the vocabulary defined once
+// below (misaligned, image_size_ok, ...), fills the caller-facing fields of the launch's args struct (args.h) by name and hands it to the
+// launcher declared in launch.h, which completes the derived fields.  Library-owned device memory goes through scratch_alloc / scratch_reset.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -14,74 +18,8 @@
 
 #include "../../include/niagara_vis.h"
 #include "cullmath.h"
-#include "args.h"
 #include "filtermath.h"
-#include "cullform.h"
-#include "rttlas.h"
-
-namespace nv
-{
-
-int launch_cluster_mask(hipStream_t, const ClusterArgs&, const CullForm&, uint32_t maskBlocks);
-int launch_cluster_scatter(hipStream_t, const ClusterArgs&, uint32_t scatterBlocks, uint32_t waves);
-int launch_cluster_hiz(hipStream_t, const ClusterArgs&, bool soa, uint32_t gridBlocks);
-int launch_cluster_bits(hipStream_t, const ClusterArgs&, bool soa, uint32_t gridBlocks);
-size_t clustercull_mask_bytes();
-size_t clustercull_list_bytes();
-uint32_t clustercull_list_stride();
-int launch_taskcull(hipStream_t, const ClusterArgs&, int late, bool soa, uint32_t gridBlocks);
-int launch_probe(hipStream_t, const ClusterArgs&, bool soa, uint32_t gridBlocks);
-int launch_soa_split(hipStream_t, const NvMeshlet*, uint32_t count, uint32_t padded, uint2* bounds, uint32_t* cones, uint32_t* poolWords, uint4* blocks);
-int launch_drawcull(hipStream_t, const DrawArgs&, int late, int task);
-int launch_draw_split(hipStream_t, const NvMeshDraw*, const NvMesh*, uint32_t meshCount, uint32_t first, uint32_t count, float4* world, uint2* scaleMesh, uint32_t* postPass);
-size_t drawcull_result_bytes(uint32_t drawCount);
-int launch_tasksubmit(hipStream_t, uint32_t* count4, NvMeshTaskCommand* commands);
-int launch_reset_count(hipStream_t, uint32_t* a, uint32_t* b);
-int launch_cluster_expand(hipStream_t, const NvMeshTaskCommand*, const NvMeshlet*, const uint32_t* clusterIndices, const uint32_t* cc4,
-                          NvClusterRecord* records, uint32_t capacity, uint64_t* totals, unsigned long long* partials, uint32_t gridBlocks);
-int launch_clustersubmit(hipStream_t, uint32_t* cc4, uint32_t* clusterIndices);
-int launch_pack_counts(hipStream_t, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*);
-int launch_depthreduce(hipStream_t, const float* depth, uint32_t w, uint32_t h, const NvPyramidDesc& pyr);
-int launch_depth_merge(hipStream_t, float* dst, const float* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks);
-int launch_trianglecull(hipStream_t, const TriangleArgs& a, uint32_t gridBlocks);
-int launch_rasterdepth(hipStream_t, const RasterArgs& a, uint32_t gridBlocks, bool nearClip, bool stableIds);
-int launch_visibility_resolve(hipStream_t, const NvCullData& cd, const unsigned long long* visibility, uint32_t n, const NvMeshDraw* draws, uint32_t drawCount,
-                              const NvMesh* meshes, uint32_t meshCount, void* records, uint32_t* meshletSeen, uint32_t* drawPixels, unsigned long long* totals,
-                              uint32_t maxBlocks, bool perPixel);
-int launch_visibility_attributes_textured(hipStream_t, const NvGlobals& globals, const void* records, uint32_t width, uint32_t height, const NvMeshDraw* draws,
-                                          uint32_t drawCount, const NvMeshlet* meshlets, uint32_t meshletCount, const uint32_t* meshletData, uint32_t dataWords,
-                                          const NvVertex* vertices, uint32_t vertexCount, const NvMaterial* materials, uint32_t materialCount, void* attributes,
-                                          uint32_t* gbuffer0, uint32_t* gbuffer1, unsigned long long* totals, const void* textures, uint32_t textureCount,
-                                          const uint32_t* texels, unsigned long long texelWords, uint32_t maxBlocks);
-int launch_texture_decode(hipStream_t, const void* blocks, uint32_t format, uint32_t width, uint32_t height, uint32_t levels, uint32_t* texels);
-int launch_visibility_attributes(hipStream_t, const NvGlobals& globals, const void* records, uint32_t width, uint32_t height, const NvMeshDraw* draws,
-                                 uint32_t drawCount, const NvMeshlet* meshlets, uint32_t meshletCount, const uint32_t* meshletData, uint32_t dataWords,
-                                 const NvVertex* vertices, uint32_t vertexCount, const NvMaterial* materials, uint32_t materialCount, void* attributes,
-                                 uint32_t* gbuffer0, uint32_t* gbuffer1, unsigned long long* totals, uint32_t maxBlocks, bool perPixel);
-int launch_shadow_fill(hipStream_t, uint8_t* shadow, const float* depth, uint32_t width, uint32_t height, int checkerboard, uint32_t maxBlocks);
-int launch_shadow_blur(hipStream_t, uint8_t* out, const uint8_t* shadow, const float* depth, uint32_t width, uint32_t height, bool horizontal, float znear);
-int launch_shade_final(hipStream_t, const NvShadeData& sd, const uint32_t* gbuffer0, const uint32_t* gbuffer1, const float* depth, const uint8_t* shadow,
-                       uint32_t* color, uint32_t width, uint32_t height, uint32_t maxBlocks, const uint32_t* bloom, uint32_t bloomWidth, uint32_t bloomHeight);
-int launch_shadow_trace(hipStream_t, const NvShadowData& sd, const void* scene, const float* depth, uint8_t* shadow, uint32_t width, uint32_t height, int quality,
-                        uint32_t maxBlocks);
-int launch_shadow_trace_alpha(hipStream_t, const NvShadowData& sd, const void* scene, const float* depth, uint8_t* shadow, uint32_t width, uint32_t height,
-                              const NvMeshDraw* draws, uint32_t drawCount, const NvMaterial* materials, uint32_t materialCount, const NvTextureDesc* textures,
-                              uint32_t textureCount, const uint32_t* texels, unsigned long long texelWords, uint32_t maxBlocks);
-int launch_bloom_extract(hipStream_t, const uint32_t* gbuffer0, uint32_t width, uint32_t height, uint32_t* bloom, const NvBloomDesc& desc, uint32_t maxBlocks);
-int launch_bloom_downsample(hipStream_t, uint32_t* bloom, const NvBloomDesc& desc, uint32_t level);
-int launch_bloom_upsample(hipStream_t, uint32_t* bloom, const NvBloomDesc& desc, uint32_t level, float radius);
-uint32_t bloom_tail_first(const NvBloomDesc& desc);
-int launch_bloom_tail(hipStream_t, uint32_t* bloom, const NvBloomDesc& desc, uint32_t first, float radius);
-int launch_visibility_merge(hipStream_t, unsigned long long* dst, const unsigned long long* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks);
-int launch_rasterindexed(hipStream_t, RasterIndexedArgs a, void* scratch, uint32_t gridBlocks, bool nearClip);
-size_t rasterindexed_scratch_bytes(uint32_t drawCount);
-int launch_meshlet_bounds(hipStream_t, const NvVertex* vertices, const uint32_t* data, NvMeshlet* meshlets, uint32_t count, float* out8, uint32_t gridBlocks);
-uint64_t tlas_plan(uint64_t staticBytes, uint32_t maxDraws, TlasPlan* plan);
-int launch_tlas_build(hipStream_t, void* scene, const TlasPlan& plan, const NvMeshDraw* draws, uint32_t drawCount);
-int rt_pack_blob(const RtHeader& src, const RtBlas* table, const RtNode* tlas, uint32_t tlasNodes, const RtInstance* inst, uint32_t instances,
-                 const RtNode* blas, const RtF4* tris, float padOrigin, uint32_t drawCount, void* out, uint64_t* bytes);
-
-} // namespace nv
+#include "launch.h"
 
 struct ProfRecord
 {
@@ -94,65 +32,66 @@ struct ProfRecord
 // flight) use ONE instance, so that three contexts do not hold three identical 480 MB mirrors.  Reference-counted.
 struct nv_scene
 {
-	std::atomic<int> refs;
-	int device;
+	std::atomic<int> refs{ 1 };
+	int device = 0;
 	// SoA mirror of the meshlet cull bytes
-	const NvMeshlet* mirroredFrom;
-	uint32_t mirroredCount;
-	uint2* soaBounds;
-	uint32_t* soaCones;
-	uint32_t* poolWords; // 2 x u32 (largest |centre component| / |radius| as fp16 bits) + 2 x float {3 Vmax, Rmax}: clustercull.hip pool_bounds_kernel
-	uint4* blockBounds;  // one 16-B record per 64 meshlets of the mirror (soaCapacity / 64): filtermath.h block_record, clustercull.hip block_bounds_kernel
-	uint32_t soaCapacity;
+	const NvMeshlet* mirroredFrom = nullptr;
+	uint32_t mirroredCount = 0;
+	uint2* soaBounds = nullptr;
+	uint32_t* soaCones = nullptr;
+	uint32_t* poolWords = nullptr; // 2 x u32 (largest |centre component| / |radius| as fp16 bits) + 2 x float {3 Vmax, Rmax}: clustercull.hip pool_bounds_kernel
+	uint4* blockBounds = nullptr; // one 16-B record per 64 meshlets of the mirror (soaCapacity / 64): filtermath.h block_record, clustercull.hip block_bounds_kernel
+	uint32_t soaCapacity = 0;
 	// SoA mirror of the MeshDraw fields a draw decision reads (nv_upload_draws)
-	const NvMeshDraw* drawsFrom;
-	const NvMesh* drawsMeshes; // the Mesh table whose centres / radii are folded into the mirror
-	uint32_t drawsCount;
-	float4* soaWorld;
-	uint2* soaScaleMesh;
-	uint32_t* soaPostPass;
-	uint32_t drawsCapacity;
+	const NvMeshDraw* drawsFrom = nullptr;
+	const NvMesh* drawsMeshes = nullptr; // the Mesh table whose centres / radii are folded into the mirror
+	uint32_t drawsCount = 0;
+	float4* soaWorld = nullptr;
+	uint2* soaScaleMesh = nullptr;
+	uint32_t* soaPostPass = nullptr;
+	uint32_t drawsCapacity = 0;
 	// Mesh table registered by nv_upload_meshes (pointer identity + count): lets drawcull stage it in LDS
-	const NvMesh* meshesFrom;
-	uint32_t meshCount;
+	const NvMesh* meshesFrom = nullptr;
+	uint32_t meshCount = 0;
 };
 
+// nv_create value-initialises it: a field without an initialiser starts at zero
 struct nv_context
 {
 	int device;
 	int numCUs;
-	uint64_t* masks; // per-command ballots between the two clustercull launches
-	nv::ClusterCounts* tileCounts;
-	uint4* candList; // late pass with HiZ: the commands with survivors (cull kernel -> occlusion stage)
+	uint64_t* masks = nullptr; // per-command ballots between the two clustercull launches
+	nv::ClusterCounts* tileCounts = nullptr;
+	uint4* candList = nullptr; // late pass with HiZ: the commands with survivors (cull kernel -> occlusion stage)
 	uint32_t listStride; // room per sub-list (entries)
-	uint32_t listSharers, listMinPer; // occlusion stage: blocks per sub-list, listed commands per block at least
+	uint32_t listSharers = 4, listMinPer = 8; // occlusion stage: blocks per sub-list, listed commands per block at least
 	// drawcull: per-draw result bytes between its two launches, and its own per-tile counts
-	uint8_t* drawResults;
+	uint8_t* drawResults = nullptr;
 	size_t drawResultsCapacity;
-	nv::ClusterCounts* drawTileCounts;
-	unsigned long long* totalsPartials; // nv_trianglecull / nv_cluster_expand / nv_rasterdepth(_indexed): per-workgroup partial totals (up to 4 x u64 x grid)
+	nv::ClusterCounts* drawTileCounts = nullptr;
+	unsigned long long* totalsPartials = nullptr; // nv_trianglecull / nv_cluster_expand / nv_rasterdepth(_indexed): per-workgroup partial totals (up to 4 x u64 x grid)
 	// nv_rasterdepth_indexed: per-command chunk prefixes + the count launch's per-workgroup sums (rasterindexed.hip), sized like drawResults
-	void* rasterScratch;
+	void* rasterScratch = nullptr;
 	uint32_t rasterScratchDraws;
-	nv_scene* scene; // mirrors + registrations (shared between contexts by nv_share_scene)
+	nv_scene* scene = nullptr; // mirrors + registrations (shared between contexts by nv_share_scene)
 	// launch shape of the cull kernel (workgroups per CU) and the dealing's start-delay compensation in percent; constants
 	// in the product, environment-tunable (with the NV_DEBUG_MODE bit mask) only in the NV_EXPERIMENTS build
 	uint32_t debugMode;
-	uint32_t ccBlocksPerCU;
-	uint32_t dealScale;
-	uint32_t scatterTilesPerCU;
-	uint32_t scatterWaves; // NV_OPT_SCATTER_WAVES: waves per workgroup of the cluster scatter launch (16; 4 / 8)
+	uint32_t ccBlocksPerCU = 6;
+	uint32_t dealScale = 100;
+	uint32_t scatterTilesPerCU = 1;
+	uint32_t scatterWaves = 16; // NV_OPT_SCATTER_WAVES: waves per workgroup of the cluster scatter launch (16; 4 / 8)
 	uint32_t scatterTilesAbs; // experiments: absolute number of scatter tiles (0 = per CU)
-	uint32_t directPercent; // share of commands passing the filter above which the next launch skips the filter pass
-	uint32_t bitsBlocksPerCU; // cluster_bits_kernel: grid (blocks per CU)
+	uint32_t directPercent = 35; // share of commands passing the filter above which the next launch skips the filter pass (measured crossover, config 3A geometry at several densities: ~36 %)
+	uint32_t bitsBlocksPerCU = 4; // cluster_bits_kernel: grid (blocks per CU)
 	uint32_t taskcullOneLaunch; // experiments: nv_taskcull's early pass as the one-command-per-wave kernel (the round-1 form)
-	int forceDirect;        // NV_OPT_CULL_FORM: -1 = by the previous launch's statistic, 0 / 1 = always filter / always direct, 2 = direct and never the bit-expanding early form
-	int forceVisFirst;      // NV_OPT_DRAW_RECORDS: -1 = by the statistic of the last TASK pass, 0 / 1 = records with / after the visibility words in drawcull's early pass
-	int forceTaskList;      // NV_OPT_TASK_EMIT: -1 = by the statistic of earlier TASK passes, 0 / 1 = per-draw / list form of drawcull's TASK scatter
-	int forceShallow;       // NV_OPT_CULL_RING: -1 = by the previous launch's command count, 0 / 1 = always the 8-deep / the 4-deep ring
+	int forceDirect = -1;   // NV_OPT_CULL_FORM: -1 = by the previous launch's statistic, 0 / 1 = always filter / always direct, 2 = direct and never the bit-expanding early form
+	int forceVisFirst = -1; // NV_OPT_DRAW_RECORDS: -1 = by the statistic of the last TASK pass, 0 / 1 = records with / after the visibility words in drawcull's early pass
+	int forceTaskList = -1; // NV_OPT_TASK_EMIT: -1 = by the statistic of earlier TASK passes, 0 / 1 = per-draw / list form of drawcull's TASK scatter
+	int forceShallow = -1;  // NV_OPT_CULL_RING: -1 = by the previous launch's command count, 0 / 1 = always the 8-deep / the 4-deep ring
 	// command count of the previous clustercull launch, written by its kernel into mapped host memory (tuning hint)
-	volatile uint32_t* hintHost;
-	uint32_t* hintDevice;
+	volatile uint32_t* hintHost = nullptr;
+	uint32_t* hintDevice = nullptr;
 	// the command buffer the last nv_drawcull(task) of this context wrote: a cluster pass over it runs on the commands of draws the draw-level cull
 	// already found visible — nothing for the conservative filter to remove — so, while no launch has left a filter statistic yet (a fresh
 	// context's first frames: the hint words lag the launches that fill them), such a pass takes the direct / lane forms instead of the filter form
@@ -162,17 +101,17 @@ struct nv_context
 	uint64_t* countsSink; // nv_set_counts_sink
 	// nv_profile_*: event pairs recorded on the launch stream, drained by nv_profile_read
 	int profiling;
-	std::vector<ProfRecord>* prof;
-	float* timing; // NV_DEBUG_MODE bit 3: 8 x u64 stamps per wave of the last clustercull
+	std::vector<ProfRecord>* prof = nullptr;
+	float* timing = nullptr; // NV_DEBUG_MODE bit 3: 8 x u64 stamps per wave of the last clustercull
 	size_t timingWaves; // its room, in waves
 	uint32_t variants[NV_VARIANT_SLOTS]; // nv_profile_variants: launches per kernel variant since the last read
-	uint32_t rasterSmallLimit; // NV_OPT_RASTER_SMALL_LIMIT
+	uint32_t rasterSmallLimit = 16; // NV_OPT_RASTER_SMALL_LIMIT
 	uint32_t rasterNearClip;   // NV_OPT_RASTER_NEAR_CLIP: 1 = the clipping instantiations of both depth rasterisers
 	uint32_t rasterStableIds;  // NV_OPT_RASTER_VISIBILITY_ID: 1 = nv_rasterdepth writes the stable form of the visibility word
 	uint32_t bloomFusedTail;   // NV_OPT_BLOOM_FUSED_TAIL: 1 = nv_bloom runs the levels that fit one workgroup's LDS as one launch
 	uint32_t resolvePerPixel;  // experiments: nv_visibility_resolve without the per-run de-duplication
 	uint32_t attributesPerPixel; // experiments: nv_visibility_attributes without the per-run set-up
-	void* rtScene;               // nv_rt_scene_upload: the device copy of the validated scene blob nv_shadow_trace walks
+	void* rtScene = nullptr;     // nv_rt_scene_upload: the device copy of the validated scene blob nv_shadow_trace walks
 	uint64_t rtSceneBytes;       // of the static blob (a dynamic reservation's allocation is rtPlan.bytes)
 	uint32_t rtSceneFlags;       // the uploaded blob's header flags (RT_FLAG_*): a rebuild and a re-housing keep them
 	nv::TlasPlan rtPlan;         // nv_rt_scene_reserve_dynamic: where the dynamic sections and the rebuild's scratch lie; maxDraws == 0 = static
@@ -198,6 +137,12 @@ struct DeviceGuard
 };
 
 uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
+
+// ---- what the entry points refuse, said one way
+bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; } // (NULL is aligned: optional pointers pass)
+
+// every image of the library: n = width * height fits 32 bits with room for the launchers' rounding
+bool image_size_ok(uint32_t width, uint32_t height) { return width != 0 && height != 0 && width <= 16384 && height <= 16384; }
 
 // Library-owned device memory goes through these two.  Product: hipMalloc / hipFree.  Experiments build (tests with
 // NV_LIBRARY_PATH = libniagara_vis_exp.so, tools/): every block sits between two 4 KiB canary zones (0xC5) that
@@ -270,6 +215,23 @@ void scratch_free(void* p)
 #endif
 }
 
+// frees a library-owned block and forgets it
+template <class T>
+void scratch_reset(T*& p)
+{
+	scratch_free(p);
+	p = nullptr;
+}
+
+#ifdef NV_EXPERIMENTS
+// an environment variable of the experiments build as atoi reads it, parsed once; `unset` when it is not there
+uint32_t env_u32(const char* name, uint32_t unset)
+{
+	const char* v = getenv(name);
+	return v ? (uint32_t)atoi(v) : unset;
+}
+#endif
+
 // profiling: returns an event recorded on `stream` now, or nullptr when profiling is off
 hipEvent_t prof_mark(nv_context* ctx, hipStream_t stream)
 {
@@ -306,9 +268,7 @@ int reserve_draw_results(nv_context* ctx, uint32_t drawCount)
 	hipError_t e = hipDeviceSynchronize(); // a drawcull still in flight on any stream may be reading the old scratch
 	if (e != hipSuccess)
 		return (int)e;
-	if (ctx->drawResults)
-		scratch_free(ctx->drawResults);
-	ctx->drawResults = nullptr;
+	scratch_reset(ctx->drawResults);
 	ctx->drawResultsCapacity = 0;
 	const size_t cap = need < (size_t(1) << 21) ? (size_t(1) << 21) : need;
 	if (scratch_alloc(&ctx->drawResults, cap) != hipSuccess)
@@ -326,9 +286,7 @@ int reserve_raster_scratch(nv_context* ctx, uint32_t drawCount)
 	hipError_t e = hipDeviceSynchronize(); // a raster still in flight on any stream may be reading the old scratch
 	if (e != hipSuccess)
 		return (int)e;
-	if (ctx->rasterScratch)
-		scratch_free(ctx->rasterScratch);
-	ctx->rasterScratch = nullptr;
+	scratch_reset(ctx->rasterScratch);
 	ctx->rasterScratchDraws = 0;
 	const uint32_t cap = drawCount < (1u << 20) ? (1u << 20) : drawCount;
 	char* p = nullptr;
@@ -342,26 +300,29 @@ int reserve_raster_scratch(nv_context* ctx, uint32_t drawCount)
 nv_scene* scene_new(int device)
 {
 	nv_scene* sc = new (std::nothrow) nv_scene();
-	if (!sc)
-		return nullptr;
-	sc->refs.store(1);
-	sc->device = device;
-	sc->mirroredFrom = nullptr;
-	sc->mirroredCount = 0;
-	sc->soaBounds = nullptr;
-	sc->soaCones = nullptr;
-	sc->blockBounds = nullptr;
-	sc->soaCapacity = 0;
-	sc->drawsFrom = nullptr;
-	sc->drawsMeshes = nullptr;
-	sc->drawsCount = 0;
-	sc->soaWorld = nullptr;
-	sc->soaScaleMesh = nullptr;
-	sc->soaPostPass = nullptr;
-	sc->drawsCapacity = 0;
-	sc->meshesFrom = nullptr;
-	sc->meshCount = 0;
+	if (sc)
+		sc->device = device;
 	return sc;
+}
+
+// the meshlet mirror (nv_upload_meshlets); the pool words are sized once and stay
+void scene_drop_meshlet_mirror(nv_scene* sc)
+{
+	scratch_reset(sc->soaBounds);
+	scratch_reset(sc->soaCones);
+	scratch_reset(sc->blockBounds);
+	sc->soaCapacity = 0;
+	sc->mirroredFrom = nullptr;
+}
+
+// the draw mirror (nv_upload_draws)
+void scene_drop_draw_mirror(nv_scene* sc)
+{
+	scratch_reset(sc->soaWorld);
+	scratch_reset(sc->soaScaleMesh);
+	scratch_reset(sc->soaPostPass);
+	sc->drawsCapacity = 0;
+	sc->drawsFrom = nullptr;
 }
 
 // drops one reference; the last one frees the mirrors (the caller has made the owning device current)
@@ -369,21 +330,21 @@ void scene_release(nv_scene* sc)
 {
 	if (!sc || sc->refs.fetch_sub(1) != 1)
 		return;
-	if (sc->soaBounds)
-		scratch_free(sc->soaBounds);
-	if (sc->soaCones)
-		scratch_free(sc->soaCones);
-	if (sc->blockBounds)
-		scratch_free(sc->blockBounds);
-	if (sc->poolWords)
-		scratch_free(sc->poolWords);
-	if (sc->soaWorld)
-		scratch_free(sc->soaWorld);
-	if (sc->soaScaleMesh)
-		scratch_free(sc->soaScaleMesh);
-	if (sc->soaPostPass)
-		scratch_free(sc->soaPostPass);
+	scene_drop_meshlet_mirror(sc);
+	scratch_reset(sc->poolWords);
+	scene_drop_draw_mirror(sc);
 	delete sc;
+}
+
+// Whether [d_draws, d_draws + count) is a sub-range of the registered draw buffer that starts on a record, and at which record (a pass over a
+// shard of the draws, an update of some of them).  On byte differences: a pointer between two records is no NvMeshDraw* to subtract.
+bool registered_draw_range(const nv_scene* sc, const NvMeshDraw* d_draws, uint32_t count, size_t* offset)
+{
+	const uintptr_t from = reinterpret_cast<uintptr_t>(sc->drawsFrom), at = reinterpret_cast<uintptr_t>(d_draws);
+	if (!sc->drawsFrom || at < from || (at - from) % sizeof(NvMeshDraw) != 0)
+		return false;
+	*offset = (at - from) / sizeof(NvMeshDraw);
+	return *offset + count <= sc->drawsCount;
 }
 
 // one scatter workgroup per CU, capped by the per-tile count table
@@ -454,7 +415,6 @@ int nv_create(nv_context** out_ctx, int device)
 	nv_context* ctx = new (std::nothrow) nv_context();
 	if (!ctx)
 		return NV_ENOMEM;
-	memset(ctx, 0, sizeof(*ctx));
 	ctx->device = device;
 	ctx->scene = scene_new(device);
 	if (!ctx->scene)
@@ -472,54 +432,26 @@ int nv_create(nv_context** out_ctx, int device)
 		return (int)e;
 	}
 	ctx->numCUs = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-	ctx->ccBlocksPerCU = 6;
-	ctx->dealScale = 100;
-	ctx->scatterTilesPerCU = 1;
-	ctx->scatterWaves = 16;
-	ctx->rasterSmallLimit = 16;
-	ctx->rasterNearClip = 0;
-	ctx->rasterStableIds = 0;
-	ctx->bloomFusedTail = 0;
-	ctx->directPercent = 35; // measured crossover (config 3A geometry at several densities): ~36 % of the commands passing the filter
-	ctx->forceDirect = -1;
-	ctx->bitsBlocksPerCU = 4;
-	ctx->taskcullOneLaunch = 0;
-	ctx->forceShallow = -1;
-	ctx->forceTaskList = -1;
-	ctx->forceVisFirst = -1;
 	ctx->listStride = nv::clustercull_list_stride();
-	ctx->listSharers = 4;
-	ctx->listMinPer = 8;
 #ifdef NV_EXPERIMENTS
-	if (const char* v = getenv("NV_RESOLVE_PER_PIXEL"))
-		ctx->resolvePerPixel = (uint32_t)atoi(v);
-	if (const char* v = getenv("NV_ATTRIBUTES_PER_PIXEL"))
-		ctx->attributesPerPixel = (uint32_t)atoi(v);
-	if (const char* v = getenv("NV_DIRECT"))
-		ctx->forceDirect = atoi(v);
-	if (const char* v = getenv("NV_TASKCULL_ONE_LAUNCH"))
-		ctx->taskcullOneLaunch = (uint32_t)atoi(v);
-	if (const char* v = getenv("NV_BITS_BLOCKS"))
-		ctx->bitsBlocksPerCU = (uint32_t)atoi(v);
-	if (const char* v = getenv("NV_DIRECT_PERCENT"))
-		ctx->directPercent = (uint32_t)atoi(v);
-	if (const char* v = getenv("NV_SCATTER_TILES_PER_CU"))
-		ctx->scatterTilesPerCU = (uint32_t)atoi(v) ? (uint32_t)atoi(v) : 1;
-	if (const char* v = getenv("NV_SCATTER_TILES"))
-		ctx->scatterTilesAbs = (uint32_t)atoi(v);
 	// the experiments build only (tools/): the product library reads no environment variable
-	if (const char* v = getenv("NV_DEBUG_MODE"))
-		ctx->debugMode = (uint32_t)atoi(v);
-	if (const char* v = getenv("NV_HIZ_LIST_STRIDE")) // a small value forces the occlusion stage's scan fallback (tests)
-		ctx->listStride = (uint32_t)atoi(v) < nv::clustercull_list_stride() ? (uint32_t)atoi(v) : nv::clustercull_list_stride();
-	if (const char* v = getenv("NV_HIZ_SHARERS"))
-		ctx->listSharers = (uint32_t)atoi(v) ? (uint32_t)atoi(v) : 4;
-	if (const char* v = getenv("NV_HIZ_MIN_PER"))
-		ctx->listMinPer = (uint32_t)atoi(v) >= 4 && (uint32_t)atoi(v) <= 64 ? (uint32_t)atoi(v) : 8;
-	if (const char* v = getenv("NV_DEAL_SCALE"))
-		ctx->dealScale = (uint32_t)atoi(v);
-	if (const char* v = getenv("NV_CC_BLOCKS_PER_CU"))
-		ctx->ccBlocksPerCU = (uint32_t)atoi(v) ? ((uint32_t)atoi(v) > 8 ? 8u : (uint32_t)atoi(v)) : 6; // (the stamp buffer holds 8 per CU)
+	ctx->resolvePerPixel = env_u32("NV_RESOLVE_PER_PIXEL", ctx->resolvePerPixel);
+	ctx->attributesPerPixel = env_u32("NV_ATTRIBUTES_PER_PIXEL", ctx->attributesPerPixel);
+	ctx->forceDirect = (int)env_u32("NV_DIRECT", (uint32_t)ctx->forceDirect);
+	ctx->taskcullOneLaunch = env_u32("NV_TASKCULL_ONE_LAUNCH", ctx->taskcullOneLaunch);
+	ctx->bitsBlocksPerCU = env_u32("NV_BITS_BLOCKS", ctx->bitsBlocksPerCU);
+	ctx->directPercent = env_u32("NV_DIRECT_PERCENT", ctx->directPercent);
+	ctx->scatterTilesPerCU = std::max(env_u32("NV_SCATTER_TILES_PER_CU", 1), 1u);
+	ctx->scatterTilesAbs = env_u32("NV_SCATTER_TILES", ctx->scatterTilesAbs);
+	ctx->debugMode = env_u32("NV_DEBUG_MODE", ctx->debugMode);
+	ctx->listStride = std::min(env_u32("NV_HIZ_LIST_STRIDE", ctx->listStride), ctx->listStride); // a small value forces the occlusion stage's scan fallback (tests)
+	if (const uint32_t v = env_u32("NV_HIZ_SHARERS", 0))
+		ctx->listSharers = v;
+	if (const uint32_t v = env_u32("NV_HIZ_MIN_PER", 0); v >= 4 && v <= 64)
+		ctx->listMinPer = v;
+	ctx->dealScale = env_u32("NV_DEAL_SCALE", ctx->dealScale);
+	if (const uint32_t v = env_u32("NV_CC_BLOCKS_PER_CU", 0))
+		ctx->ccBlocksPerCU = std::min(v, 8u); // (the stamp buffer holds 8 per CU)
 #endif
 
 	if (scratch_alloc(&ctx->masks, nv::clustercull_mask_bytes()) != hipSuccess || scratch_alloc(&ctx->tileCounts, sizeof(nv::ClusterCounts)) != hipSuccess ||
@@ -561,25 +493,16 @@ void nv_destroy(nv_context* ctx)
 	DeviceGuard guard(ctx->device);
 	if (ctx->hintHost)
 		(void)hipHostFree(const_cast<uint32_t*>(ctx->hintHost));
-	if (ctx->drawResults)
-		scratch_free(ctx->drawResults);
-	if (ctx->drawTileCounts)
-		scratch_free(ctx->drawTileCounts);
-	if (ctx->totalsPartials)
-		scratch_free(ctx->totalsPartials);
-	if (ctx->rasterScratch)
-		scratch_free(ctx->rasterScratch);
-	if (ctx->masks)
-		scratch_free(ctx->masks);
-	if (ctx->tileCounts)
-		scratch_free(ctx->tileCounts);
-	if (ctx->candList)
-		scratch_free(ctx->candList);
+	scratch_reset(ctx->drawResults);
+	scratch_reset(ctx->drawTileCounts);
+	scratch_reset(ctx->totalsPartials);
+	scratch_reset(ctx->rasterScratch);
+	scratch_reset(ctx->masks);
+	scratch_reset(ctx->tileCounts);
+	scratch_reset(ctx->candList);
 	scene_release(ctx->scene);
-	if (ctx->timing)
-		scratch_free(ctx->timing);
-	if (ctx->rtScene)
-		scratch_free(ctx->rtScene);
+	scratch_reset(ctx->timing);
+	scratch_reset(ctx->rtScene);
 	delete ctx->prof;
 	delete ctx;
 }
@@ -771,17 +694,7 @@ int nv_upload_meshlets(nv_context* ctx, void* stream, const NvMeshlet* d_meshlet
 		hipError_t e = hipDeviceSynchronize();
 		if (e != hipSuccess)
 			return (int)e;
-		if (ctx->scene->soaBounds)
-			scratch_free(ctx->scene->soaBounds);
-		if (ctx->scene->soaCones)
-			scratch_free(ctx->scene->soaCones);
-		if (ctx->scene->blockBounds)
-			scratch_free(ctx->scene->blockBounds);
-		ctx->scene->soaBounds = nullptr;
-		ctx->scene->soaCones = nullptr;
-		ctx->scene->blockBounds = nullptr;
-		ctx->scene->soaCapacity = 0;
-		ctx->scene->mirroredFrom = nullptr;
+		scene_drop_meshlet_mirror(ctx->scene);
 		if (scratch_alloc(&ctx->scene->soaBounds, (size_t)padded * sizeof(uint2)) != hipSuccess ||
 		    scratch_alloc(&ctx->scene->soaCones, (size_t)padded * sizeof(uint32_t)) != hipSuccess ||
 		    scratch_alloc(&ctx->scene->blockBounds, (size_t)(padded / 64) * sizeof(uint4)) != hipSuccess)
@@ -843,17 +756,7 @@ int nv_upload_draws(nv_context* ctx, void* stream, const NvMeshDraw* d_draws, ui
 		hipError_t e = hipDeviceSynchronize();
 		if (e != hipSuccess)
 			return (int)e;
-		if (ctx->scene->soaWorld)
-			scratch_free(ctx->scene->soaWorld);
-		if (ctx->scene->soaScaleMesh)
-			scratch_free(ctx->scene->soaScaleMesh);
-		if (ctx->scene->soaPostPass)
-			scratch_free(ctx->scene->soaPostPass);
-		ctx->scene->soaWorld = nullptr;
-		ctx->scene->soaScaleMesh = nullptr;
-		ctx->scene->soaPostPass = nullptr;
-		ctx->scene->drawsCapacity = 0;
-		ctx->scene->drawsFrom = nullptr;
+		scene_drop_draw_mirror(ctx->scene);
 		const size_t cap = (size_t)drawCount + 64;
 		if (scratch_alloc(&ctx->scene->soaWorld, cap * sizeof(float4)) != hipSuccess || scratch_alloc(&ctx->scene->soaScaleMesh, cap * sizeof(uint2)) != hipSuccess ||
 		    scratch_alloc(&ctx->scene->soaPostPass, cap * sizeof(uint32_t)) != hipSuccess)
@@ -873,9 +776,10 @@ int nv_update_draws(nv_context* ctx, void* stream, const NvMeshDraw* d_draws, ui
 {
 	if (!ctx || !d_draws)
 		return NV_EINVAL;
-	if (!ctx->scene->drawsFrom || d_draws < ctx->scene->drawsFrom || d_draws >= ctx->scene->drawsFrom + ctx->scene->drawsCount || ctx->scene->drawsFrom + (d_draws - ctx->scene->drawsFrom) != d_draws)
+	size_t base = 0;
+	if (!registered_draw_range(ctx->scene, d_draws, 1, &base))
 		return NV_OK; // nothing registered for this buffer: the passes read it in place anyway
-	const size_t base = (size_t)(d_draws - ctx->scene->drawsFrom) + first;
+	base += first;
 	if (base > ctx->scene->drawsCount || count > ctx->scene->drawsCount - base)
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
@@ -902,9 +806,9 @@ int nv_drawcull(nv_context* ctx, void* stream, const NvCullData* cull, int late,
 	a.pyr = pyramid ? *pyramid : null_pyramid();
 	a.draws = d_draws;
 	// the mirror serves the registered buffer and any sub-range of it that starts on a record (a pass over a shard of the draws)
-	const size_t drawOffset = ctx->scene->drawsFrom && d_draws >= ctx->scene->drawsFrom ? (size_t)(d_draws - ctx->scene->drawsFrom) : ~size_t(0);
-	const bool mirrored = ctx->scene->soaWorld && drawOffset != ~size_t(0) && ctx->scene->drawsFrom + drawOffset == d_draws &&
-	                      drawOffset + cull->drawCount <= ctx->scene->drawsCount && ctx->scene->drawsMeshes == d_meshes; // (the mirror folds THAT table's bounds in)
+	size_t drawOffset = 0;
+	const bool mirrored = ctx->scene->soaWorld && registered_draw_range(ctx->scene, d_draws, cull->drawCount, &drawOffset) &&
+	                      ctx->scene->drawsMeshes == d_meshes; // (the mirror folds THAT table's bounds in)
 	a.soaWorld = mirrored ? ctx->scene->soaWorld + drawOffset : nullptr;
 	a.soaScaleMesh = mirrored ? ctx->scene->soaScaleMesh + drawOffset : nullptr;
 	a.soaPostPass = mirrored ? ctx->scene->soaPostPass + drawOffset : nullptr;
@@ -1030,11 +934,8 @@ int nv_clustercull(nv_context* ctx, void* stream, const NvCullData* cull, int la
 		// room for the cull launch at any NV_OPT_CULL_WORKGROUPS_PER_CU (4 waves per workgroup) AND for the occlusion stage's grid (bit 28:
 		// listSharers x CC_LISTS blocks of 4 waves — more than the cull launch's on a small part or with NV_HIZ_SHARERS raised)
 		const size_t timingWaves = std::max((size_t)persistent_grid(ctx, 8) * 4, (size_t)ctx->listSharers * nv::CC_LISTS * 4);
-		if (ctx->timing && ctx->timingWaves < timingWaves)
-		{
-			scratch_free(ctx->timing);
-			ctx->timing = nullptr;
-		}
+		if (ctx->timingWaves < timingWaves)
+			scratch_reset(ctx->timing);
 		if (!ctx->timing && scratch_alloc(&ctx->timing, timingWaves * 8 * sizeof(unsigned long long)) == hipSuccess)
 			ctx->timingWaves = timingWaves;
 		a.probeOut = ctx->timing;
@@ -1106,9 +1007,16 @@ int nv_cluster_expand(nv_context* ctx, void* stream, const NvMeshTaskCommand* d_
 	if (!ctx || !d_commands || !d_meshlets || !d_clusterIndices || !d_clusterCount4 || !d_totals3 || (!d_records && recordCapacity))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
-	const uint32_t grid = persistent_grid(ctx, 8);
-	return nv::launch_cluster_expand((hipStream_t)stream, d_commands, d_meshlets, d_clusterIndices, d_clusterCount4, d_records, recordCapacity,
-	                                 d_totals3, ctx->totalsPartials, grid);
+	nv::ClusterExpandArgs a;
+	a.commands = d_commands;
+	a.meshlets = d_meshlets;
+	a.clusterIndices = d_clusterIndices;
+	a.cc4 = d_clusterCount4;
+	a.records = d_records;
+	a.capacity = recordCapacity;
+	a.totals = reinterpret_cast<unsigned long long*>(d_totals3);
+	a.partials = ctx->totalsPartials;
+	return nv::launch_cluster_expand((hipStream_t)stream, a, persistent_grid(ctx, 8));
 }
 
 int nv_trianglecull(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshTaskCommand* d_commands, const NvMeshDraw* d_draws,
@@ -1141,8 +1049,7 @@ int nv_rasterdepth(nv_context* ctx, void* stream, const NvGlobals* globals, cons
                    const uint32_t* d_clusterCount4, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_visibility, uint64_t* d_totals4)
 {
 	if (!ctx || !globals || !d_commands || !d_draws || !d_meshlets || !d_meshletData || !d_vertices || !d_clusterIndices || !d_clusterCount4 ||
-	    !d_depth || width == 0 || height == 0 || width > 16384 || height > 16384 || globals->screenWidth != (float)width ||
-	    globals->screenHeight != (float)height)
+	    !d_depth || !image_size_ok(width, height) || globals->screenWidth != (float)width || globals->screenHeight != (float)height)
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	nv::RasterArgs a;
@@ -1168,8 +1075,8 @@ int nv_rasterdepth_indexed(nv_context* ctx, void* stream, const NvGlobals* globa
                            const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices, uint32_t indexCapacity,
                            const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_totals4)
 {
-	if (!ctx || !globals || !d_commands || !d_count || !d_draws || !d_indices || !d_vertices || !d_depth || width == 0 || height == 0 ||
-	    width > 16384 || height > 16384 || globals->screenWidth != (float)width || globals->screenHeight != (float)height)
+	if (!ctx || !globals || !d_commands || !d_count || !d_draws || !d_indices || !d_vertices || !d_depth || !image_size_ok(width, height) ||
+	    globals->screenWidth != (float)width || globals->screenHeight != (float)height)
 		return NV_EINVAL;
 	if (drawCount > ctx->rasterScratchDraws)
 		return NV_ENOMEM; // nv_reserve(ctx, maxDraws, ...) first: a pass never allocates
@@ -1200,9 +1107,8 @@ int nv_meshlet_bounds(nv_context* ctx, void* stream, const NvVertex* d_vertices,
 	if (!ctx || (meshletCount && (!d_vertices || !d_meshletData || !d_meshlets)))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
-	const uint32_t blocks = (meshletCount + 3) / 4;
-	const uint32_t cap = persistent_grid(ctx, 16);
-	int rc = nv::launch_meshlet_bounds((hipStream_t)stream, d_vertices, d_meshletData, d_meshlets, meshletCount, d_bounds8, blocks < cap ? blocks : cap);
+	int rc = nv::launch_meshlet_bounds((hipStream_t)stream, d_vertices, d_meshletData, d_meshlets, meshletCount, d_bounds8,
+	                                   nv::capped_grid(meshletCount, 4, persistent_grid(ctx, 16)));
 	// a mirror built from these records is stale now (its registration is by pointer, its contents a snapshot)
 	if (rc == 0 && ctx->scene->mirroredFrom == d_meshlets)
 		ctx->scene->mirroredFrom = nullptr;
@@ -1223,11 +1129,10 @@ int nv_depthreduce(nv_context* ctx, void* stream, const float* d_depth, uint32_t
 
 int nv_depth_merge(nv_context* ctx, void* stream, float* d_dst, const float* const* d_srcs, uint32_t sources, uint32_t width, uint32_t height)
 {
-	if (!ctx || !d_dst || !d_srcs || sources == 0 || width == 0 || height == 0 || width > 16384 || height > 16384 ||
-	    (reinterpret_cast<uintptr_t>(d_dst) & 3u))
+	if (!ctx || !d_dst || !d_srcs || sources == 0 || !image_size_ok(width, height) || misaligned(d_dst, 3u))
 		return NV_EINVAL;
 	for (uint32_t i = 0; i < sources; ++i)
-		if (!d_srcs[i] || d_srcs[i] == d_dst || (reinterpret_cast<uintptr_t>(d_srcs[i]) & 3u))
+		if (!d_srcs[i] || d_srcs[i] == d_dst || misaligned(d_srcs[i], 3u))
 			return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	return nv::launch_depth_merge((hipStream_t)stream, d_dst, d_srcs, sources, width * height, persistent_grid(ctx, 8));
@@ -1237,14 +1142,55 @@ int nv_visibility_resolve(nv_context* ctx, void* stream, const NvCullData* cull,
                           const NvMeshDraw* d_draws, uint32_t drawCount, const NvMesh* d_meshes, uint32_t meshCount, NvVisRecord* d_records,
                           uint32_t* d_meshletSeen, uint32_t* d_drawPixels, uint64_t* d_totals4)
 {
-	if (!ctx || !cull || !d_visibility || width == 0 || height == 0 || width > 16384 || height > 16384 || (drawCount && !d_draws) ||
-	    (meshCount && !d_meshes) || (reinterpret_cast<uintptr_t>(d_visibility) & 7u) || (reinterpret_cast<uintptr_t>(d_records) & 15u) ||
-	    (reinterpret_cast<uintptr_t>(d_totals4) & 7u))
+	if (!ctx || !cull || !d_visibility || !image_size_ok(width, height) || (drawCount && !d_draws) || (meshCount && !d_meshes) ||
+	    misaligned(d_visibility, 7u) || misaligned(d_records, 15u) || misaligned(d_totals4, 7u))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
-	return nv::launch_visibility_resolve((hipStream_t)stream, *cull, reinterpret_cast<const unsigned long long*>(d_visibility), width * height, d_draws,
-	                                     drawCount, d_meshes, meshCount, d_records, d_meshletSeen, d_drawPixels,
-	                                     reinterpret_cast<unsigned long long*>(d_totals4), persistent_grid(ctx, 8), ctx->resolvePerPixel != 0);
+	nv::VisResolveArgs a;
+	a.cd = *cull;
+	a.visibility = reinterpret_cast<const unsigned long long*>(d_visibility);
+	a.n = width * height;
+	a.draws = d_draws;
+	a.drawCount = drawCount;
+	a.meshes = d_meshes;
+	a.meshCount = meshCount;
+	a.records = reinterpret_cast<uint4*>(d_records);
+	a.meshletSeen = d_meshletSeen;
+	a.drawPixels = d_drawPixels;
+	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
+	return nv::launch_visibility_resolve((hipStream_t)stream, a, persistent_grid(ctx, 8), ctx->resolvePerPixel != 0);
+}
+
+// The part nv_visibility_attributes and nv_visibility_attributes_textured share (the parameters are the entry points' first twenty, in their
+// order): the refusals both have, then the caller-facing fields of the launch.  Each entry point adds its own rule for the material table.
+static int fill_attribute_args(nv::VisAttrArgs& a, nv_context* ctx, const NvGlobals* globals, const NvVisRecord* d_records, uint32_t width, uint32_t height,
+                               const NvMeshDraw* d_draws, uint32_t drawCount, const NvMeshlet* d_meshlets, uint32_t meshletCount, const uint32_t* d_meshletData,
+                               uint32_t meshletDataWords, const NvVertex* d_vertices, uint32_t vertexCount, const NvMaterial* d_materials, uint32_t materialCount,
+                               NvPixelAttributes* d_attributes, uint32_t* d_gbuffer0, uint32_t* d_gbuffer1, uint64_t* d_totals4)
+{
+	if (!ctx || !globals || !d_records || !image_size_ok(width, height) || globals->screenWidth != (float)width || globals->screenHeight != (float)height ||
+	    (drawCount && !d_draws) || (meshletCount && !d_meshlets) || (meshletDataWords && !d_meshletData) || (vertexCount && !d_vertices) ||
+	    misaligned(d_records, 15u) || misaligned(d_attributes, 15u) || misaligned(d_draws, 15u) || misaligned(d_vertices, 15u) || misaligned(d_materials, 15u) ||
+	    misaligned(d_totals4, 7u) || misaligned(d_meshlets, 3u) || misaligned(d_meshletData, 3u) || misaligned(d_gbuffer0, 3u) || misaligned(d_gbuffer1, 3u))
+		return NV_EINVAL;
+	a.globals = *globals;
+	a.records = reinterpret_cast<const nv::va_u4*>(d_records);
+	a.width = width;
+	a.draws = d_draws;
+	a.drawCount = drawCount;
+	a.meshlets = d_meshlets;
+	a.meshletCount = meshletCount;
+	a.meshletData = d_meshletData;
+	a.dataWords = meshletDataWords;
+	a.vertices = d_vertices;
+	a.vertexCount = vertexCount;
+	a.materials = d_materials;
+	a.materialCount = materialCount;
+	a.attributes = reinterpret_cast<uint4*>(d_attributes);
+	a.gbuffer0 = d_gbuffer0;
+	a.gbuffer1 = d_gbuffer1;
+	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
+	return NV_OK;
 }
 
 int nv_visibility_attributes(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisRecord* d_records, uint32_t width, uint32_t height,
@@ -1253,17 +1199,13 @@ int nv_visibility_attributes(nv_context* ctx, void* stream, const NvGlobals* glo
                              const NvMaterial* d_materials, uint32_t materialCount, NvPixelAttributes* d_attributes, uint32_t* d_gbuffer0,
                              uint32_t* d_gbuffer1, uint64_t* d_totals4)
 {
-	const auto misaligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
-	if (!ctx || !globals || !d_records || width == 0 || height == 0 || width > 16384 || height > 16384 || globals->screenWidth != (float)width ||
-	    globals->screenHeight != (float)height || (drawCount && !d_draws) || (meshletCount && !d_meshlets) || (meshletDataWords && !d_meshletData) ||
-	    (vertexCount && !d_vertices) || (materialCount && !d_materials) || ((d_gbuffer0 || d_gbuffer1) && !d_materials) || misaligned(d_records, 15u) ||
-	    misaligned(d_attributes, 15u) || misaligned(d_draws, 15u) || misaligned(d_vertices, 15u) || misaligned(d_materials, 15u) ||
-	    misaligned(d_totals4, 7u) || misaligned(d_meshlets, 3u) || misaligned(d_meshletData, 3u) || misaligned(d_gbuffer0, 3u) || misaligned(d_gbuffer1, 3u))
+	nv::VisAttrArgs a;
+	if (fill_attribute_args(a, ctx, globals, d_records, width, height, d_draws, drawCount, d_meshlets, meshletCount, d_meshletData, meshletDataWords, d_vertices,
+	                        vertexCount, d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1, d_totals4) != NV_OK ||
+	    (materialCount && !d_materials) || ((d_gbuffer0 || d_gbuffer1) && !d_materials))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
-	return nv::launch_visibility_attributes((hipStream_t)stream, *globals, d_records, width, height, d_draws, drawCount, d_meshlets, meshletCount, d_meshletData,
-	                                        meshletDataWords, d_vertices, vertexCount, d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1,
-	                                        reinterpret_cast<unsigned long long*>(d_totals4), persistent_grid(ctx, 8), ctx->attributesPerPixel != 0);
+	return nv::launch_visibility_attributes((hipStream_t)stream, a, height, persistent_grid(ctx, 8), ctx->attributesPerPixel != 0);
 }
 
 // ---- material textures (texdecode.hip, visattr_tex.hip)
@@ -1274,27 +1216,24 @@ int nv_visibility_attributes_textured(nv_context* ctx, void* stream, const NvGlo
                                       uint32_t* d_gbuffer0, uint32_t* d_gbuffer1, uint64_t* d_totals4, const NvTextureDesc* d_textures,
                                       uint32_t textureCount, const uint32_t* d_texels, uint64_t texelWords)
 {
-	const auto misaligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
-	if (!ctx || !globals || !d_records || width == 0 || height == 0 || width > 16384 || height > 16384 || globals->screenWidth != (float)width ||
-	    globals->screenHeight != (float)height || (drawCount && !d_draws) || (meshletCount && !d_meshlets) || (meshletDataWords && !d_meshletData) ||
-	    (vertexCount && !d_vertices) || !d_materials || (textureCount && (!d_textures || !d_texels)) || misaligned(d_records, 15u) ||
-	    misaligned(d_attributes, 15u) || misaligned(d_draws, 15u) || misaligned(d_vertices, 15u) || misaligned(d_materials, 15u) ||
-	    misaligned(d_totals4, 7u) || misaligned(d_meshlets, 3u) || misaligned(d_meshletData, 3u) || misaligned(d_gbuffer0, 3u) || misaligned(d_gbuffer1, 3u) ||
-	    misaligned(d_textures, 15u) || misaligned(d_texels, 3u))
+	nv::VisAttrTexArgs a;
+	if (fill_attribute_args(a, ctx, globals, d_records, width, height, d_draws, drawCount, d_meshlets, meshletCount, d_meshletData, meshletDataWords, d_vertices,
+	                        vertexCount, d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1, d_totals4) != NV_OK ||
+	    !d_materials || (textureCount && (!d_textures || !d_texels)) || misaligned(d_textures, 15u) || misaligned(d_texels, 3u))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
-	return nv::launch_visibility_attributes_textured((hipStream_t)stream, *globals, d_records, width, height, d_draws, drawCount, d_meshlets, meshletCount,
-	                                                 d_meshletData, meshletDataWords, d_vertices, vertexCount, d_materials, materialCount, d_attributes,
-	                                                 d_gbuffer0, d_gbuffer1, reinterpret_cast<unsigned long long*>(d_totals4), d_textures,
-	                                                 d_textures ? textureCount : 0u, d_texels, texelWords, persistent_grid(ctx, 8));
+	a.tx.descs = reinterpret_cast<const uint4*>(d_textures);
+	a.tx.count = d_textures ? textureCount : 0u;
+	a.tx.texels = d_texels;
+	a.tx.texelWords = texelWords;
+	return nv::launch_visibility_attributes_textured((hipStream_t)stream, a, height, persistent_grid(ctx, 8));
 }
 
 int nv_texture_decode(nv_context* ctx, void* stream, const void* d_blocks, uint32_t format, uint32_t width, uint32_t height, uint32_t levels,
                       uint32_t* d_texels, const NvTextureDesc* desc)
 {
-	if (!ctx || !d_blocks || !d_texels || !desc || width == 0 || height == 0 || levels == 0 || width > 16384 || height > 16384 ||
-	    levels > NV_TEXTURE_MAX_LEVELS || desc->width != width || desc->height != height || desc->levels != levels ||
-	    (reinterpret_cast<uintptr_t>(d_blocks) & 7u) || (reinterpret_cast<uintptr_t>(d_texels) & 3u))
+	if (!ctx || !d_blocks || !d_texels || !desc || !image_size_ok(width, height) || levels == 0 || levels > NV_TEXTURE_MAX_LEVELS ||
+	    desc->width != width || desc->height != height || desc->levels != levels || misaligned(d_blocks, 7u) || misaligned(d_texels, 3u))
 		return NV_EINVAL;
 	if (format == NV_FORMAT_BC4 || format == NV_FORMAT_BC5 || format == NV_FORMAT_BC6H)
 		return NV_ETEXFORMAT;
@@ -1305,11 +1244,9 @@ int nv_texture_decode(nv_context* ctx, void* stream, const void* d_blocks, uint3
 }
 
 // ---- the shading end of the frame (shade.hip)
-static bool shade_size_ok(uint32_t width, uint32_t height) { return width != 0 && height != 0 && width <= 16384 && height <= 16384; }
-
 int nv_shadow_fill(nv_context* ctx, void* stream, uint8_t* d_shadow, const float* d_depth, uint32_t width, uint32_t height, int checkerboard)
 {
-	if (!ctx || !d_shadow || !d_depth || !shade_size_ok(width, height) || (reinterpret_cast<uintptr_t>(d_depth) & 3u))
+	if (!ctx || !d_shadow || !d_depth || !image_size_ok(width, height) || misaligned(d_depth, 3u))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	return nv::launch_shadow_fill((hipStream_t)stream, d_shadow, d_depth, width, height, checkerboard, persistent_grid(ctx, 8));
@@ -1318,23 +1255,41 @@ int nv_shadow_fill(nv_context* ctx, void* stream, uint8_t* d_shadow, const float
 int nv_shadow_blur(nv_context* ctx, void* stream, uint8_t* d_out, const uint8_t* d_shadow, const float* d_depth, uint32_t width, uint32_t height,
                    int direction, float znear)
 {
-	if (!ctx || !d_out || !d_shadow || !d_depth || d_out == d_shadow || !shade_size_ok(width, height) || (direction != 0 && direction != 1) ||
-	    (reinterpret_cast<uintptr_t>(d_depth) & 3u))
+	if (!ctx || !d_out || !d_shadow || !d_depth || d_out == d_shadow || !image_size_ok(width, height) || (direction != 0 && direction != 1) ||
+	    misaligned(d_depth, 3u))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	return nv::launch_shadow_blur((hipStream_t)stream, d_out, d_shadow, d_depth, width, height, direction == 1, znear);
 }
 
+// what nv_shade_final and nv_shade_final_bloom share: the refusals, then the caller-facing fields of the launch (a.bloom stays nullptr)
+static int fill_shade_args(nv::ShadeFinalBloomArgs& a, nv_context* ctx, const NvShadeData* shade, const uint32_t* d_gbuffer0, const uint32_t* d_gbuffer1,
+                           const float* d_depth, const uint8_t* d_shadow, uint32_t* d_color, uint32_t width, uint32_t height)
+{
+	if (!ctx || !shade || !d_gbuffer0 || !d_gbuffer1 || !d_depth || !d_color || !image_size_ok(width, height) || shade->imageSize[0] != (float)width ||
+	    shade->imageSize[1] != (float)height || (shade->shadowsEnabled == 1 && !d_shadow) || misaligned(d_gbuffer0, 3u) || misaligned(d_gbuffer1, 3u) ||
+	    misaligned(d_depth, 3u) || misaligned(d_color, 3u))
+		return NV_EINVAL;
+	a.sd = *shade;
+	a.gbuffer0 = d_gbuffer0;
+	a.gbuffer1 = d_gbuffer1;
+	a.depth = d_depth;
+	a.shadow = d_shadow;
+	a.color = d_color;
+	a.width = width;
+	a.bloom = nullptr;
+	a.bloomWidth = a.bloomHeight = 0;
+	return NV_OK;
+}
+
 int nv_shade_final(nv_context* ctx, void* stream, const NvShadeData* shade, const uint32_t* d_gbuffer0, const uint32_t* d_gbuffer1, const float* d_depth,
                    const uint8_t* d_shadow, uint32_t* d_color, uint32_t width, uint32_t height)
 {
-	const auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
-	if (!ctx || !shade || !d_gbuffer0 || !d_gbuffer1 || !d_depth || !d_color || !shade_size_ok(width, height) || shade->imageSize[0] != (float)width ||
-	    shade->imageSize[1] != (float)height || (shade->shadowsEnabled == 1 && !d_shadow) || misaligned(d_gbuffer0) || misaligned(d_gbuffer1) ||
-	    misaligned(d_depth) || misaligned(d_color))
+	nv::ShadeFinalBloomArgs a;
+	if (fill_shade_args(a, ctx, shade, d_gbuffer0, d_gbuffer1, d_depth, d_shadow, d_color, width, height) != NV_OK)
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
-	return nv::launch_shade_final((hipStream_t)stream, *shade, d_gbuffer0, d_gbuffer1, d_depth, d_shadow, d_color, width, height, persistent_grid(ctx, 8), nullptr, 0, 0);
+	return nv::launch_shade_final((hipStream_t)stream, a, height, persistent_grid(ctx, 8));
 }
 
 // ---- ray-traced sun shadows (shadowtrace.hip, rtbuild.cpp)
@@ -1435,7 +1390,7 @@ int nv_rt_scene_reserve_dynamic(nv_context* ctx, void* stream, uint32_t maxDraws
 int nv_rt_tlas_build(nv_context* ctx, void* stream, const NvMeshDraw* d_draws, uint32_t drawCount)
 {
 	if (!ctx || !ctx->rtScene || ctx->rtPlan.maxDraws == 0 || drawCount > ctx->rtPlan.maxDraws || (drawCount && !d_draws) ||
-	    (reinterpret_cast<uintptr_t>(d_draws) & 3u))
+	    misaligned(d_draws, 3u))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	return nv::launch_tlas_build((hipStream_t)stream, ctx->rtScene, ctx->rtPlan, d_draws, drawCount);
@@ -1444,7 +1399,7 @@ int nv_rt_tlas_build(nv_context* ctx, void* stream, const NvMeshDraw* d_draws, u
 // Test and tooling accessor (synchronises): the context's current scene as a canonical blob
 int nv_rt_scene_download(nv_context* ctx, void* stream, void* out, uint64_t* bytes)
 {
-	if (!ctx || !ctx->rtScene || !bytes || (reinterpret_cast<uintptr_t>(out) & 15u))
+	if (!ctx || !ctx->rtScene || !bytes || misaligned(out, 15u))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	hipError_t e = hipStreamSynchronize((hipStream_t)stream);
@@ -1479,14 +1434,30 @@ int nv_rt_scene_download(nv_context* ctx, void* stream, void* out, uint64_t* byt
 	}
 }
 
+// what nv_shadow_trace and nv_shadow_trace_textured share: the refusals, then the caller-facing fields of the opaque launch
+static int fill_trace_args(nv::ShadowTraceArgs& a, nv_context* ctx, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width,
+                           uint32_t height, int quality)
+{
+	if (!ctx || !ctx->rtScene || !shadow || !d_depth || !d_shadow || !image_size_ok(width, height) || shadow->imageSize[0] != (float)width ||
+	    shadow->imageSize[1] != (float)height || quality < 0 || quality > 1 || misaligned(d_depth, 3u))
+		return NV_EINVAL;
+	a.sd = *shadow;
+	a.scene = static_cast<const unsigned char*>(ctx->rtScene);
+	a.depth = d_depth;
+	a.shadow = d_shadow;
+	a.width = width;
+	a.height = height;
+	return NV_OK;
+}
+
 int nv_shadow_trace(nv_context* ctx, void* stream, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width, uint32_t height,
                     int quality)
 {
-	if (!ctx || !ctx->rtScene || !shadow || !d_depth || !d_shadow || !shade_size_ok(width, height) || shadow->imageSize[0] != (float)width ||
-	    shadow->imageSize[1] != (float)height || quality < 0 || quality > 1 || (reinterpret_cast<uintptr_t>(d_depth) & 3u))
+	nv::ShadowTraceArgs a;
+	if (fill_trace_args(a, ctx, shadow, d_depth, d_shadow, width, height, quality) != NV_OK)
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
-	return nv::launch_shadow_trace((hipStream_t)stream, *shadow, ctx->rtScene, d_depth, d_shadow, width, height, quality, persistent_grid(ctx, 8));
+	return nv::launch_shadow_trace((hipStream_t)stream, a, quality, persistent_grid(ctx, 8));
 }
 
 // the alpha-tested trace (shadowtrace_alpha.hip); quality 0 has no alpha test and is nv_shadow_trace's launch
@@ -1494,22 +1465,33 @@ int nv_shadow_trace_textured(nv_context* ctx, void* stream, const NvShadowData* 
                              int quality, const NvMeshDraw* d_draws, uint32_t drawCount, const NvMaterial* d_materials, uint32_t materialCount,
                              const NvTextureDesc* d_textures, uint32_t textureCount, const uint32_t* d_texels, uint64_t texelWords)
 {
-	const auto misaligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
-	if (!ctx || !ctx->rtScene || !shadow || !d_depth || !d_shadow || !shade_size_ok(width, height) || shadow->imageSize[0] != (float)width ||
-	    shadow->imageSize[1] != (float)height || quality < 0 || quality > 1 || misaligned(d_depth, 3u) || !(ctx->rtSceneFlags & nv::RT_FLAG_TEXCOORDS) ||
+	nv::ShadowTraceArgs opaque;
+	if (fill_trace_args(opaque, ctx, shadow, d_depth, d_shadow, width, height, quality) != NV_OK || !(ctx->rtSceneFlags & nv::RT_FLAG_TEXCOORDS) ||
 	    (drawCount && !d_draws) || (materialCount && !d_materials) || (textureCount && !d_textures) || (texelWords && !d_texels) || misaligned(d_draws, 15u) ||
 	    misaligned(d_materials, 15u) || misaligned(d_textures, 15u) || misaligned(d_texels, 3u))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	if (quality == 0)
-		return nv::launch_shadow_trace((hipStream_t)stream, *shadow, ctx->rtScene, d_depth, d_shadow, width, height, 0, persistent_grid(ctx, 8));
-	return nv::launch_shadow_trace_alpha((hipStream_t)stream, *shadow, ctx->rtScene, d_depth, d_shadow, width, height, d_draws, drawCount, d_materials,
-	                                     materialCount, d_textures, textureCount, d_texels, texelWords, persistent_grid(ctx, 8));
+		return nv::launch_shadow_trace((hipStream_t)stream, opaque, 0, persistent_grid(ctx, 8));
+	nv::ShadowTraceAlphaArgs a;
+	a.sd = opaque.sd;
+	a.in.draws = d_draws;
+	a.in.materials = d_materials;
+	a.in.textures = reinterpret_cast<const nv::TxDesc*>(d_textures);
+	a.in.texels = d_texels;
+	a.in.texelWords = texelWords;
+	a.in.drawCount = drawCount;
+	a.in.materialCount = materialCount;
+	a.in.textureCount = textureCount;
+	a.scene = opaque.scene;
+	a.depth = d_depth;
+	a.shadow = d_shadow;
+	a.width = width;
+	a.height = height;
+	return nv::launch_shadow_trace_alpha((hipStream_t)stream, a, persistent_grid(ctx, 8));
 }
 
 // ---- bloom (bloom.hip)
-static bool misaligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
-
 // desc is what nv_bloom_desc_init gives for a width x height image
 static bool bloom_desc_ok(const NvBloomDesc* desc, uint32_t width, uint32_t height)
 {
@@ -1525,7 +1507,7 @@ static bool bloom_desc_ok(const NvBloomDesc* desc)
 
 int nv_bloom_extract(nv_context* ctx, void* stream, const uint32_t* d_gbuffer0, uint32_t width, uint32_t height, uint32_t* d_bloom, const NvBloomDesc* desc)
 {
-	if (!ctx || !d_gbuffer0 || !d_bloom || !shade_size_ok(width, height) || !bloom_desc_ok(desc, width, height) || misaligned4(d_gbuffer0) || misaligned4(d_bloom))
+	if (!ctx || !d_gbuffer0 || !d_bloom || !image_size_ok(width, height) || !bloom_desc_ok(desc, width, height) || misaligned(d_gbuffer0, 3u) || misaligned(d_bloom, 3u))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	return nv::launch_bloom_extract((hipStream_t)stream, d_gbuffer0, width, height, d_bloom, *desc, persistent_grid(ctx, 8));
@@ -1533,7 +1515,7 @@ int nv_bloom_extract(nv_context* ctx, void* stream, const uint32_t* d_gbuffer0, 
 
 int nv_bloom_downsample(nv_context* ctx, void* stream, uint32_t* d_bloom, const NvBloomDesc* desc, uint32_t level)
 {
-	if (!ctx || !d_bloom || !bloom_desc_ok(desc) || level < 1u || level >= desc->levels || misaligned4(d_bloom))
+	if (!ctx || !d_bloom || !bloom_desc_ok(desc) || level < 1u || level >= desc->levels || misaligned(d_bloom, 3u))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	return nv::launch_bloom_downsample((hipStream_t)stream, d_bloom, *desc, level);
@@ -1542,7 +1524,7 @@ int nv_bloom_downsample(nv_context* ctx, void* stream, uint32_t* d_bloom, const 
 int nv_bloom_upsample(nv_context* ctx, void* stream, uint32_t* d_bloom, const NvBloomDesc* desc, uint32_t level, float radius)
 {
 	// (level + 2 > levels would wrap for a level near 2^32 and let it through)
-	if (!ctx || !d_bloom || !bloom_desc_ok(desc) || desc->levels < 2u || level > desc->levels - 2u || !(radius >= 0.0f) || !(radius <= 3.402823466e38f) || misaligned4(d_bloom))
+	if (!ctx || !d_bloom || !bloom_desc_ok(desc) || desc->levels < 2u || level > desc->levels - 2u || !(radius >= 0.0f) || !(radius <= 3.402823466e38f) || misaligned(d_bloom, 3u))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	return nv::launch_bloom_upsample((hipStream_t)stream, d_bloom, *desc, level, radius);
@@ -1550,7 +1532,7 @@ int nv_bloom_upsample(nv_context* ctx, void* stream, uint32_t* d_bloom, const Nv
 
 int nv_bloom(nv_context* ctx, void* stream, const uint32_t* d_gbuffer0, uint32_t width, uint32_t height, uint32_t* d_bloom, const NvBloomDesc* desc)
 {
-	if (!ctx || !d_gbuffer0 || !d_bloom || !shade_size_ok(width, height) || !bloom_desc_ok(desc, width, height) || misaligned4(d_gbuffer0) || misaligned4(d_bloom))
+	if (!ctx || !d_gbuffer0 || !d_bloom || !image_size_ok(width, height) || !bloom_desc_ok(desc, width, height) || misaligned(d_gbuffer0, 3u) || misaligned(d_bloom, 3u))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	// src/niagara.cpp:1873-1901
@@ -1576,23 +1558,23 @@ int nv_bloom(nv_context* ctx, void* stream, const uint32_t* d_gbuffer0, uint32_t
 int nv_shade_final_bloom(nv_context* ctx, void* stream, const NvShadeData* shade, const uint32_t* d_gbuffer0, const uint32_t* d_gbuffer1, const float* d_depth,
                          const uint8_t* d_shadow, uint32_t* d_color, uint32_t width, uint32_t height, const uint32_t* d_bloom, const NvBloomDesc* desc)
 {
-	if (!ctx || !shade || !d_gbuffer0 || !d_gbuffer1 || !d_depth || !d_color || !d_bloom || !shade_size_ok(width, height) ||
-	    shade->imageSize[0] != (float)width || shade->imageSize[1] != (float)height || (shade->shadowsEnabled == 1 && !d_shadow) ||
-	    !bloom_desc_ok(desc, width, height) || misaligned4(d_gbuffer0) || misaligned4(d_gbuffer1) || misaligned4(d_depth) || misaligned4(d_color) ||
-	    misaligned4(d_bloom))
+	nv::ShadeFinalBloomArgs a;
+	if (fill_shade_args(a, ctx, shade, d_gbuffer0, d_gbuffer1, d_depth, d_shadow, d_color, width, height) != NV_OK || !d_bloom ||
+	    !bloom_desc_ok(desc, width, height) || misaligned(d_bloom, 3u))
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
-	return nv::launch_shade_final((hipStream_t)stream, *shade, d_gbuffer0, d_gbuffer1, d_depth, d_shadow, d_color, width, height, persistent_grid(ctx, 8),
-	                              d_bloom + desc->levelOffset[0], desc->width, desc->height);
+	a.bloom = d_bloom + desc->levelOffset[0];
+	a.bloomWidth = desc->width;
+	a.bloomHeight = desc->height;
+	return nv::launch_shade_final((hipStream_t)stream, a, height, persistent_grid(ctx, 8));
 }
 
 int nv_visibility_merge(nv_context* ctx, void* stream, uint64_t* d_dst, const uint64_t* const* d_srcs, uint32_t sources, uint32_t width, uint32_t height)
 {
-	if (!ctx || !d_dst || !d_srcs || sources == 0 || width == 0 || height == 0 || width > 16384 || height > 16384 ||
-	    (reinterpret_cast<uintptr_t>(d_dst) & 7u))
+	if (!ctx || !d_dst || !d_srcs || sources == 0 || !image_size_ok(width, height) || misaligned(d_dst, 7u))
 		return NV_EINVAL;
 	for (uint32_t i = 0; i < sources; ++i)
-		if (!d_srcs[i] || d_srcs[i] == d_dst || (reinterpret_cast<uintptr_t>(d_srcs[i]) & 7u))
+		if (!d_srcs[i] || d_srcs[i] == d_dst || misaligned(d_srcs[i], 7u))
 			return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	return nv::launch_visibility_merge((hipStream_t)stream, reinterpret_cast<unsigned long long*>(d_dst),
@@ -1675,9 +1657,7 @@ int nv_probe_cluster_scalars(nv_context* ctx, void* stream, const NvCullData* cu
 	DeviceGuard guard(ctx->device);
 	a.commandCountOverride = commandCount;
 	a.probeOut = d_out16;
-	uint32_t blocks = (commandCount + 3) / 4;
-	uint32_t cap = (uint32_t)ctx->numCUs * 8;
-	return nv::launch_probe((hipStream_t)stream, a, a.soaBounds != nullptr, blocks < cap ? blocks : cap);
+	return nv::launch_probe((hipStream_t)stream, a, a.soaBounds != nullptr, nv::capped_grid(commandCount, 4, persistent_grid(ctx, 8)));
 }
 
 } // extern "C"

@@ -1,4 +1,5 @@
-// depthmerge.hip — the depth composite of a sharded frame for gfx950.
+// depthmerge.hip — the composites of a sharded frame for gfx950: nv_depth_merge and nv_visibility_merge, ONE kernel text for the
+// two word types.
 //
 // Every shard of a frame rasterises its own draws into its own depth target; the frame's target is the element-wise maximum of the
 // shards' (reverse-Z in [0, 1]: the maximum of the floats is the unsigned maximum of their bits, the rule the rasterisers' atomics
@@ -13,181 +14,107 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch.h"
+
 namespace nv
 {
 
-constexpr int DEPTH_MERGE_MAX = 8; // sources per launch: the host folds longer lists in groups (the destination accumulates)
+// nv_visibility_merge is the same composite for the stable-ID visibility buffer: dst[i] = max(dst[i], src_0[i], ...,
+// src_{K-1}[i]) on unsigned 64-bit words.  Every shard writes the same word for the same sample (NV_OPT_RASTER_VISIBILITY_ID 1), so the maximum
+// over the shards is the word one pass over all draws leaves.  Twice the bytes per element: a thread owns a PAIR of words per 16-B group.
 
-struct DepthMergeArgs
+constexpr int MERGE_MAX = 8; // sources per launch: the host folds longer lists in groups (the destination accumulates)
+
+// W = uint32_t (depth bits) or unsigned long long (visibility words)
+template <typename W>
+struct MergeArgs
 {
-	uint32_t* dst;
-	const uint32_t* src[DEPTH_MERGE_MAX];
-	uint32_t n4; // whole 16-B groups (0 when a pointer is not 16-B aligned: everything goes through the scalar loop)
-	uint32_t n;  // texels, <= 16384 * 16384
-};
-
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
-
-template <int K>
-__global__ __launch_bounds__(256) void depth_merge_kernel(DepthMergeArgs a)
-{
-	const uint32_t stride = gridDim.x * 256u;
-	const uint32_t first = blockIdx.x * 256u + threadIdx.x;
-	for (uint32_t i = first; i < a.n4; i += stride)
-	{
-		v4u s[K];
-#pragma unroll
-		for (int k = 0; k < K; ++k)
-			s[k] = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(a.src[k]) + i);
-		v4u d = reinterpret_cast<const v4u*>(a.dst)[i];
-#pragma unroll
-		for (int k = 0; k < K; ++k)
-		{
-			d.x = umax(d.x, s[k].x);
-			d.y = umax(d.y, s[k].y);
-			d.z = umax(d.z, s[k].z);
-			d.w = umax(d.w, s[k].w);
-		}
-		reinterpret_cast<v4u*>(a.dst)[i] = d;
-	}
-	// the ragged end (at most 3 texels), or the whole buffer when a pointer is not 16-B aligned
-	for (uint32_t i = a.n4 * 4u + first; i < a.n; i += stride)
-	{
-		uint32_t d = a.dst[i];
-#pragma unroll
-		for (int k = 0; k < K; ++k)
-			d = umax(d, a.src[k][i]);
-		a.dst[i] = d;
-	}
-}
-
-template <int K>
-static void launch_k(hipStream_t stream, const DepthMergeArgs& a, uint32_t grid)
-{
-	hipLaunchKernelGGL(depth_merge_kernel<K>, dim3(grid), dim3(256), 0, stream, a);
-}
-
-int launch_depth_merge(hipStream_t stream, float* dst, const float* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks)
-{
-	for (uint32_t at = 0; at < sources; at += DEPTH_MERGE_MAX)
-	{
-		const uint32_t k = sources - at < (uint32_t)DEPTH_MERGE_MAX ? sources - at : (uint32_t)DEPTH_MERGE_MAX;
-		DepthMergeArgs a;
-		a.dst = reinterpret_cast<uint32_t*>(dst);
-		uintptr_t bits = reinterpret_cast<uintptr_t>(dst);
-		for (uint32_t i = 0; i < (uint32_t)DEPTH_MERGE_MAX; ++i)
-		{
-			a.src[i] = reinterpret_cast<const uint32_t*>(srcs[at + (i < k ? i : 0)]);
-			bits |= reinterpret_cast<uintptr_t>(a.src[i]);
-		}
-		a.n = n;
-		a.n4 = (bits & 15u) ? 0u : n / 4u;
-		const uint32_t work = a.n4 ? a.n4 + 3u : n; // threads that have something to do
-		uint32_t grid = (work + 255u) / 256u;
-		grid = grid < maxBlocks ? grid : maxBlocks;
-		switch (k)
-		{
-		case 1: launch_k<1>(stream, a, grid); break;
-		case 2: launch_k<2>(stream, a, grid); break;
-		case 3: launch_k<3>(stream, a, grid); break;
-		case 4: launch_k<4>(stream, a, grid); break;
-		case 5: launch_k<5>(stream, a, grid); break;
-		case 6: launch_k<6>(stream, a, grid); break;
-		case 7: launch_k<7>(stream, a, grid); break;
-		default: launch_k<8>(stream, a, grid); break;
-		}
-	}
-	return (int)hipGetLastError();
-}
-
-// ---- nv_visibility_merge: the same composite for the stable-ID visibility buffer
-//
-// dst[i] = max(dst[i], src_0[i], ..., src_{K-1}[i]) on unsigned 64-bit words.  Every shard writes the same word for the same sample
-// (NV_OPT_RASTER_VISIBILITY_ID 1), so the maximum over the shards is the word one pass over all draws leaves.  The shape of the depth merge
-// with twice the bytes per element: one thread owns a PAIR of words (16-B loads and stores), no atomics, a scalar tail for an odd count.
-
-struct VisMergeArgs
-{
-	unsigned long long* dst;
-	const unsigned long long* src[DEPTH_MERGE_MAX];
-	uint32_t n2; // whole 16-B pairs (0 when a pointer is not 16-B aligned)
+	W* dst;
+	const W* src[MERGE_MAX];
+	uint32_t nv; // whole 16-B groups (0 when a pointer is not 16-B aligned: everything goes through the scalar loop)
 	uint32_t n;  // words, <= 16384 * 16384
 };
 
-typedef unsigned long long v2ull __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned long long umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
-
-template <int K>
-__global__ __launch_bounds__(256) void visibility_merge_kernel(VisMergeArgs a)
+template <typename W, int K>
+__global__ __launch_bounds__(256) void merge_kernel(MergeArgs<W> a)
 {
+	constexpr uint32_t PER = 16u / sizeof(W); // words of a 16-B group
+	typedef W vec __attribute__((ext_vector_type(PER)));
 	const uint32_t stride = gridDim.x * 256u;
 	const uint32_t first = blockIdx.x * 256u + threadIdx.x;
-	for (uint32_t i = first; i < a.n2; i += stride)
+	for (uint32_t i = first; i < a.nv; i += stride)
 	{
-		v2ull s[K];
+		vec s[K];
 #pragma unroll
 		for (int k = 0; k < K; ++k)
-			s[k] = __builtin_nontemporal_load(reinterpret_cast<const v2ull*>(a.src[k]) + i);
-		v2ull d = reinterpret_cast<const v2ull*>(a.dst)[i];
+			s[k] = __builtin_nontemporal_load(reinterpret_cast<const vec*>(a.src[k]) + i);
+		vec d = reinterpret_cast<const vec*>(a.dst)[i];
 #pragma unroll
 		for (int k = 0; k < K; ++k)
-		{
-			d.x = umax64(d.x, s[k].x);
-			d.y = umax64(d.y, s[k].y);
-		}
-		reinterpret_cast<v2ull*>(a.dst)[i] = d;
+#pragma unroll
+			for (uint32_t j = 0; j < PER; ++j)
+				d[j] = d[j] > s[k][j] ? d[j] : s[k][j];
+		reinterpret_cast<vec*>(a.dst)[i] = d;
 	}
-	// the odd last word, or the whole buffer when a pointer is not 16-B aligned
-	for (uint32_t i = a.n2 * 2u + first; i < a.n; i += stride)
+	// the ragged end (fewer words than a group), or the whole buffer when a pointer is not 16-B aligned
+	for (uint32_t i = a.nv * PER + first; i < a.n; i += stride)
 	{
-		unsigned long long d = a.dst[i];
+		W d = a.dst[i];
 #pragma unroll
 		for (int k = 0; k < K; ++k)
-			d = umax64(d, a.src[k][i]);
+			d = d > a.src[k][i] ? d : a.src[k][i];
 		a.dst[i] = d;
 	}
 }
 
-template <int K>
-static void launch_vk(hipStream_t stream, const VisMergeArgs& a, uint32_t grid)
+template <typename W, int K>
+static void launch_k(hipStream_t stream, const MergeArgs<W>& a, uint32_t grid)
 {
-	hipLaunchKernelGGL(visibility_merge_kernel<K>, dim3(grid), dim3(256), 0, stream, a);
+	hipLaunchKernelGGL((merge_kernel<W, K>), dim3(grid), dim3(256), 0, stream, a);
 }
 
-int launch_visibility_merge(hipStream_t stream, unsigned long long* dst, const unsigned long long* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks)
+template <typename W>
+static int launch_merge(hipStream_t stream, W* dst, const W* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks)
 {
-	for (uint32_t at = 0; at < sources; at += DEPTH_MERGE_MAX)
+	constexpr uint32_t PER = 16u / sizeof(W);
+	for (uint32_t at = 0; at < sources; at += MERGE_MAX)
 	{
-		const uint32_t k = sources - at < (uint32_t)DEPTH_MERGE_MAX ? sources - at : (uint32_t)DEPTH_MERGE_MAX;
-		VisMergeArgs a;
+		const uint32_t k = sources - at < (uint32_t)MERGE_MAX ? sources - at : (uint32_t)MERGE_MAX;
+		MergeArgs<W> a;
 		a.dst = dst;
 		uintptr_t bits = reinterpret_cast<uintptr_t>(dst);
-		for (uint32_t i = 0; i < (uint32_t)DEPTH_MERGE_MAX; ++i)
+		for (uint32_t i = 0; i < (uint32_t)MERGE_MAX; ++i)
 		{
 			a.src[i] = srcs[at + (i < k ? i : 0)];
 			bits |= reinterpret_cast<uintptr_t>(a.src[i]);
 		}
 		a.n = n;
-		a.n2 = (bits & 15u) ? 0u : n / 2u;
-		const uint32_t work = a.n2 ? a.n2 + 1u : n; // threads that have something to do
-		uint32_t grid = (work + 255u) / 256u;
-		grid = grid < maxBlocks ? grid : maxBlocks;
+		a.nv = (bits & 15u) ? 0u : n / PER;
+		const uint32_t work = a.nv ? a.nv + (PER - 1u) : n; // threads that have something to do
+		const uint32_t grid = capped_grid(work, 256u, maxBlocks);
 		switch (k)
 		{
-		case 1: launch_vk<1>(stream, a, grid); break;
-		case 2: launch_vk<2>(stream, a, grid); break;
-		case 3: launch_vk<3>(stream, a, grid); break;
-		case 4: launch_vk<4>(stream, a, grid); break;
-		case 5: launch_vk<5>(stream, a, grid); break;
-		case 6: launch_vk<6>(stream, a, grid); break;
-		case 7: launch_vk<7>(stream, a, grid); break;
-		default: launch_vk<8>(stream, a, grid); break;
+		case 1: launch_k<W, 1>(stream, a, grid); break;
+		case 2: launch_k<W, 2>(stream, a, grid); break;
+		case 3: launch_k<W, 3>(stream, a, grid); break;
+		case 4: launch_k<W, 4>(stream, a, grid); break;
+		case 5: launch_k<W, 5>(stream, a, grid); break;
+		case 6: launch_k<W, 6>(stream, a, grid); break;
+		case 7: launch_k<W, 7>(stream, a, grid); break;
+		default: launch_k<W, 8>(stream, a, grid); break;
 		}
 	}
 	return (int)hipGetLastError();
+}
+
+int launch_depth_merge(hipStream_t stream, float* dst, const float* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks)
+{
+	return launch_merge(stream, reinterpret_cast<uint32_t*>(dst), reinterpret_cast<const uint32_t* const*>(srcs), sources, n, maxBlocks);
+}
+
+int launch_visibility_merge(hipStream_t stream, unsigned long long* dst, const unsigned long long* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks)
+{
+	return launch_merge(stream, dst, srcs, sources, n, maxBlocks);
 }
 
 } // namespace nv

@@ -12,6 +12,7 @@
 // Level 0 from a depth target that is not exactly 2x the pyramid (e.g. 1024x768 -> 512x512) goes through the
 // generic sampler kernel first.
 #include "cullmath.h"
+#include "launch.h"
 
 namespace nv
 {

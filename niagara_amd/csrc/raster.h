@@ -6,7 +6,7 @@
 #pragma once
 
 #include "cullmath.h"
-#include "args.h"
+#include "launch.h"
 
 namespace nv
 {
@@ -237,8 +237,5 @@ NV_DEV bool rd_sample(const RdTri& t, int32_t px, int32_t py, uint32_t W, uint32
 	}
 	return true;
 }
-
-// adds the per-workgroup partial sums of a launch (4 x u64 per workgroup) to the caller's four totals (one workgroup; rasterdepth.hip)
-int launch_raster_totals(hipStream_t stream, const unsigned long long* partials, uint32_t blocks, unsigned long long* totals);
 
 } // namespace nv

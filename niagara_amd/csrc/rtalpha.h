@@ -16,17 +16,6 @@
 namespace nv
 {
 
-// what the alpha test reads besides the blob: the caller's buffers, every index checked against its count before the load
-struct RtAlphaInputs
-{
-	const NvMeshDraw* draws;
-	const NvMaterial* materials;
-	const TxDesc* textures; // == NvTextureDesc; entry 0 is "no texture"
-	const uint32_t* texels;
-	uint64_t texelWords;
-	uint32_t drawCount, materialCount, textureCount;
-};
-
 // the fp16 of the low 16 bits, exact (rtbuild.cpp's half_to_float)
 NV_RT float rt_half(uint32_t h)
 {

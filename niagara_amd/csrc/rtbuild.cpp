@@ -14,6 +14,7 @@
 #include "rtalpha.h"
 #include "rtmath.h"
 #include "rttlas.h"
+#include "launch.h"
 
 namespace
 {

@@ -9,6 +9,8 @@
 
 #include <stdint.h>
 
+#include "../../include/niagara_vis.h"
+
 #if defined(__HIPCC__)
 #define NV_RT __host__ __device__ inline __attribute__((always_inline))
 #else
@@ -21,6 +23,19 @@ namespace nv
 struct rt3
 {
 	float x, y, z;
+};
+
+// what the alpha test of rtalpha.h reads besides the blob: the caller's buffers, every index checked against its count before the load.  Here,
+// not there: it is a field of the alpha trace's kernel arguments (args.h), which do not need the test's text
+struct TxDesc; // texmath.h
+struct RtAlphaInputs
+{
+	const NvMeshDraw* draws;
+	const NvMaterial* materials;
+	const TxDesc* textures; // == NvTextureDesc; entry 0 is "no texture"
+	const uint32_t* texels;
+	uint64_t texelWords;
+	uint32_t drawCount, materialCount, textureCount;
 };
 
 struct __attribute__((aligned(16))) RtF4 // one 16-byte load

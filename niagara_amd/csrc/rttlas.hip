@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rttlas.h"
+#include "launch.h"
 
 namespace nv
 {

@@ -15,6 +15,7 @@
 #include "cullmath.h"
 #include "bloommath.h"
 #include "rtmath.h"
+#include "launch.h"
 
 namespace nv
 {
@@ -139,24 +140,7 @@ __global__ __launch_bounds__(SH_THREADS) void shadow_blur_kernel(uint8_t* __rest
 
 // ---------------------------------------------------------------------------------------------------------------- final shade
 
-struct ShadeFinalArgs
-{
-	NvShadeData sd;
-	const uint32_t* __restrict__ gbuffer0;
-	const uint32_t* __restrict__ gbuffer1;
-	const float* __restrict__ depth;
-	const uint8_t* __restrict__ shadow; // read only by the SHADOW = true instantiation
-	uint32_t* __restrict__ color;
-	uint32_t width, n;
-};
-
-// the kernel argument of the BLOOM = true instantiations; the others keep ShadeFinalArgs, and with it their code
-struct ShadeFinalBloomArgs : ShadeFinalArgs
-{
-	const uint32_t* __restrict__ bloom; // level 0 of the bloom target
-	uint32_t bloomWidth, bloomHeight;
-};
-
+// the kernel argument by instantiation (args.h): BLOOM = false keeps ShadeFinalArgs, and with it its code
 template <bool BLOOM>
 struct ShadeFinalArgsOf
 {
@@ -264,9 +248,7 @@ int launch_shadow_fill(hipStream_t stream, uint8_t* shadow, const float* depth, 
 {
 	const uint32_t halfWidth = (width + 1u) / 2u; // src/niagara.cpp:1797,1833
 	const uint32_t n = halfWidth * height;
-	uint32_t grid = (n + SH_THREADS - 1u) / SH_THREADS;
-	grid = grid < maxBlocks ? grid : maxBlocks;
-	hipLaunchKernelGGL(shadow_fill_kernel, dim3(grid), dim3(SH_THREADS), 0, stream, shadow, depth, width, height, halfWidth, n, (uint32_t)checkerboard);
+	hipLaunchKernelGGL(shadow_fill_kernel, dim3(capped_grid(n, SH_THREADS, maxBlocks)), dim3(SH_THREADS), 0, stream, shadow, depth, width, height, halfWidth, n, (uint32_t)checkerboard);
 	return (int)hipGetLastError();
 }
 
@@ -283,32 +265,18 @@ int launch_shadow_blur(hipStream_t stream, uint8_t* out, const uint8_t* shadow, 
 	return (int)hipGetLastError();
 }
 
-int launch_shade_final(hipStream_t stream, const NvShadeData& sd, const uint32_t* gbuffer0, const uint32_t* gbuffer1, const float* depth,
-                       const uint8_t* shadow, uint32_t* color, uint32_t width, uint32_t height, uint32_t maxBlocks, const uint32_t* bloom, uint32_t bloomWidth,
-                       uint32_t bloomHeight)
+int launch_shade_final(hipStream_t stream, ShadeFinalBloomArgs a, uint32_t height, uint32_t maxBlocks)
 {
-	ShadeFinalBloomArgs a;
-	a.sd = sd;
-	a.gbuffer0 = gbuffer0;
-	a.gbuffer1 = gbuffer1;
-	a.depth = depth;
-	a.shadow = shadow;
-	a.color = color;
-	a.width = width;
-	a.n = width * height;
-	a.bloom = bloom;
-	a.bloomWidth = bloomWidth;
-	a.bloomHeight = bloomHeight;
-	uint32_t grid = (a.n + SH_THREADS - 1u) / SH_THREADS;
-	grid = grid < maxBlocks ? grid : maxBlocks;
-	if (bloom)
+	a.n = a.width * height;
+	const uint32_t grid = capped_grid(a.n, SH_THREADS, maxBlocks);
+	if (a.bloom)
 	{
-		if (sd.shadowsEnabled == 1)
+		if (a.sd.shadowsEnabled == 1)
 			hipLaunchKernelGGL((shade_final_kernel<true, true>), dim3(grid), dim3(SH_THREADS), 0, stream, a);
 		else
 			hipLaunchKernelGGL((shade_final_kernel<false, true>), dim3(grid), dim3(SH_THREADS), 0, stream, a);
 	}
-	else if (sd.shadowsEnabled == 1)
+	else if (a.sd.shadowsEnabled == 1)
 		hipLaunchKernelGGL((shade_final_kernel<true, false>), dim3(grid), dim3(SH_THREADS), 0, stream, static_cast<const ShadeFinalArgs&>(a));
 	else
 		hipLaunchKernelGGL((shade_final_kernel<false, false>), dim3(grid), dim3(SH_THREADS), 0, stream, static_cast<const ShadeFinalArgs&>(a));

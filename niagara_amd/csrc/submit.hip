@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/niagara_vis.h"
+#include "launch.h"
 
 namespace nv
 {
@@ -160,12 +161,10 @@ int launch_totals3(hipStream_t stream, const unsigned long long* partials, uint3
 	return (int)hipGetLastError();
 }
 
-int launch_cluster_expand(hipStream_t stream, const NvMeshTaskCommand* commands, const NvMeshlet* meshlets, const uint32_t* clusterIndices,
-                          const uint32_t* cc4, NvClusterRecord* records, uint32_t capacity, uint64_t* totals, unsigned long long* partials,
-                          uint32_t gridBlocks)
+int launch_cluster_expand(hipStream_t stream, const ClusterExpandArgs& a, uint32_t gridBlocks)
 {
-	hipLaunchKernelGGL(cluster_expand_kernel, dim3(gridBlocks), dim3(256), 0, stream, commands, meshlets, clusterIndices, cc4, records, capacity, partials);
-	return launch_totals3(stream, partials, gridBlocks, reinterpret_cast<unsigned long long*>(totals));
+	hipLaunchKernelGGL(cluster_expand_kernel, dim3(gridBlocks), dim3(256), 0, stream, a.commands, a.meshlets, a.clusterIndices, a.cc4, a.records, a.capacity, a.partials);
+	return launch_totals3(stream, a.partials, gridBlocks, a.totals);
 }
 
 int launch_tasksubmit(hipStream_t stream, uint32_t* count4, NvMeshTaskCommand* commands)

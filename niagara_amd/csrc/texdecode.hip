@@ -10,6 +10,7 @@
 
 #include "../../include/niagara_vis.h"
 #include "texmath.h"
+#include "launch.h"
 
 namespace nv
 {

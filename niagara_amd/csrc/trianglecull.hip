@@ -15,7 +15,7 @@
 // Algorithmic bytes per slot = 4 + 20 + 48 + 24 + refs (2 or 4 B x vertexCount) + 3 B x triangleCount + 8 B x vertexCount (position half
 // of the 16-B vertex) + 16 B out.
 #include "cullmath.h"
-#include "args.h"
+#include "launch.h"
 
 namespace nv
 {
@@ -376,8 +376,6 @@ __global__ __launch_bounds__(TC_THREADS) void trianglecull_kernel(TriangleArgs a
 		a.partials[(size_t)blockIdx.x * 3 + threadIdx.x] = t;
 	}
 }
-
-int launch_totals3(hipStream_t stream, const unsigned long long* partials, uint32_t blocks, unsigned long long* totals); // submit.hip
 
 int launch_trianglecull(hipStream_t stream, const TriangleArgs& a, uint32_t gridBlocks)
 {

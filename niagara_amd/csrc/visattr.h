@@ -1,9 +1,11 @@
 // visattr.h — the attribute pass of the visibility buffer as ONE text for its two entry points: visattr.hip
 // instantiates visibility_attributes_kernel<RUNS> (nv_visibility_attributes: the fragment stage from the material's factors) and
-// visattr_tex.hip visibility_attributes_kernel<true, true, VisAttrTexArgs> (nv_visibility_attributes_textured: the complete fragment stage).  Run detection, set-up, barycentrics and varyings are shared; TEX only
-// adds statements under `if constexpr (TEX)`, so the untextured kernels keep their instruction streams.
+// visattr_tex.hip visibility_attributes_kernel<true, true, VisAttrTexArgs> (nv_visibility_attributes_textured: the complete fragment stage); the
+// argument structs are args.h's.  Run detection, set-up, barycentrics and varyings are shared; TEX only adds statements under
+// `if constexpr (TEX)`, so the untextured kernels keep their instruction streams.
 #pragma once
 #include "raster.h"
+#include "launch.h"
 #define NV_TX_SAMPLER_ONLY // (the pass decodes no blocks: keep the BC tables out of its code objects)
 #include "texmath.h"
 
@@ -11,29 +13,6 @@ namespace nv
 {
 
 constexpr int VA_THREADS = 256;
-typedef uint32_t va_u4 __attribute__((ext_vector_type(4))); // (a native vector: what the non-temporal load builtin takes)
-
-struct VisAttrArgs
-{
-	NvGlobals globals;
-	const va_u4* __restrict__ records;
-	uint32_t width, n; // n = width * height <= 16384 * 16384
-	float fw, fh;      // (float)width, (float)height
-	const NvMeshDraw* __restrict__ draws;
-	uint32_t drawCount;
-	const NvMeshlet* __restrict__ meshlets;
-	uint32_t meshletCount;
-	const uint32_t* __restrict__ meshletData;
-	uint32_t dataWords;
-	const NvVertex* __restrict__ vertices;
-	uint32_t vertexCount;
-	const NvMaterial* __restrict__ materials; // optional
-	uint32_t materialCount;
-	uint4* __restrict__ attributes;           // optional
-	uint32_t* __restrict__ gbuffer0;          // optional
-	uint32_t* __restrict__ gbuffer1;          // optional
-	unsigned long long* totals;               // optional
-};
 
 // one corner of the triangle after the vertex stage
 struct VaCorner
@@ -166,15 +145,6 @@ NV_DEV uint32_t va_unorm(float x, float scale)
 	return (uint32_t)__builtin_rintf(v * scale);
 }
 
-// the texture set of the textured pass (§4.18); all zero in the untextured kernels, which never read it
-struct VaTextures
-{
-	const uint4* __restrict__ descs; // NvTextureDesc, entry 0 reserved
-	uint32_t count;
-	const uint32_t* __restrict__ texels;
-	unsigned long long texelWords;
-};
-
 // homogeneous barycentrics of the set-up triangle at the point (fx, fy) in pixels (row 0 at the top), the pixel's own statements again for
 // the two neighbouring centres of the textured pass; returns §4.13's `degen`
 NV_DEV bool va_bary(const VaSetup& s, float fx, float fy, float fw, float fh, float& l0, float& l1, float& l2)
@@ -204,12 +174,6 @@ NV_DEV bool va_texture(const VaTextures& tx, uint32_t id, float u, float v, floa
 	c = tx_sample(tx.texels, d, u, v, dudx, dvdx, dudy, dvdy);
 	return true;
 }
-
-// VisAttrArgs plus the texture set: the argument of the textured kernel
-struct VisAttrTexArgs : VisAttrArgs
-{
-	VaTextures tx;
-};
 
 // ARGS = VisAttrArgs (TEX = false) or VisAttrTexArgs (TEX = true)
 template <bool RUNS, bool TEX = false, typename ARGS = VisAttrArgs>
@@ -401,35 +365,13 @@ __global__ __launch_bounds__(VA_THREADS) void visibility_attributes_kernel(ARGS 
 	}
 }
 
-
-// the kernel arguments of both entry points
-inline VisAttrArgs va_make_args(const NvGlobals& globals, const void* records, uint32_t width, uint32_t height, const NvMeshDraw* draws, uint32_t drawCount,
-                                const NvMeshlet* meshlets, uint32_t meshletCount, const uint32_t* meshletData, uint32_t dataWords, const NvVertex* vertices,
-                                uint32_t vertexCount, const NvMaterial* materials, uint32_t materialCount, void* attributes, uint32_t* gbuffer0,
-                                uint32_t* gbuffer1, unsigned long long* totals)
+// the fields both launchers derive from the image size, and their grid
+inline uint32_t va_complete(VisAttrArgs& a, uint32_t height, uint32_t maxBlocks)
 {
-	VisAttrArgs a;
-	a.globals = globals;
-	a.records = static_cast<const va_u4*>(records);
-	a.width = width;
-	a.n = width * height;
-	a.fw = (float)width;
+	a.n = a.width * height;
+	a.fw = (float)a.width;
 	a.fh = (float)height;
-	a.draws = draws;
-	a.drawCount = drawCount;
-	a.meshlets = meshlets;
-	a.meshletCount = meshletCount;
-	a.meshletData = meshletData;
-	a.dataWords = dataWords;
-	a.vertices = vertices;
-	a.vertexCount = vertexCount;
-	a.materials = materials;
-	a.materialCount = materialCount;
-	a.attributes = static_cast<uint4*>(attributes);
-	a.gbuffer0 = gbuffer0;
-	a.gbuffer1 = gbuffer1;
-	a.totals = totals;
-	return a;
+	return capped_grid(a.n, VA_THREADS, maxBlocks);
 }
 
 } // namespace nv

@@ -12,22 +12,9 @@
 namespace nv
 {
 
-int launch_visibility_attributes_textured(hipStream_t stream, const NvGlobals& globals, const void* records, uint32_t width, uint32_t height,
-                                          const NvMeshDraw* draws, uint32_t drawCount, const NvMeshlet* meshlets, uint32_t meshletCount,
-                                          const uint32_t* meshletData, uint32_t dataWords, const NvVertex* vertices, uint32_t vertexCount,
-                                          const NvMaterial* materials, uint32_t materialCount, void* attributes, uint32_t* gbuffer0, uint32_t* gbuffer1,
-                                          unsigned long long* totals, const void* textures, uint32_t textureCount, const uint32_t* texels,
-                                          unsigned long long texelWords, uint32_t maxBlocks)
+int launch_visibility_attributes_textured(hipStream_t stream, VisAttrTexArgs a, uint32_t height, uint32_t maxBlocks)
 {
-	VisAttrTexArgs a;
-	static_cast<VisAttrArgs&>(a) = va_make_args(globals, records, width, height, draws, drawCount, meshlets, meshletCount, meshletData, dataWords, vertices, vertexCount,
-	                                   materials, materialCount, attributes, gbuffer0, gbuffer1, totals);
-	a.tx.descs = static_cast<const uint4*>(textures);
-	a.tx.count = textureCount;
-	a.tx.texels = texels;
-	a.tx.texelWords = texelWords;
-	uint32_t grid = (a.n + VA_THREADS - 1u) / VA_THREADS;
-	grid = grid < maxBlocks ? grid : maxBlocks;
+	const uint32_t grid = va_complete(a, height, maxBlocks);
 	hipLaunchKernelGGL((visibility_attributes_kernel<true, true, VisAttrTexArgs>), dim3(grid), dim3(VA_THREADS), 0, stream, a);
 	return (int)hipGetLastError();
 }

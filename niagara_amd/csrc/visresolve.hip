@@ -18,28 +18,13 @@
 // RUNS = false (experiments build, NV_RESOLVE_PER_PIXEL=1) is the kernel without the runs — every named pixel searches and adds for itself —
 // kept for the measurement that justifies the runs (profiles/r10_visibility.md).
 #include "cullmath.h"
-#include "args.h"
+#include "launch.h"
 
 namespace nv
 {
 
 constexpr int VR_THREADS = 256;
 constexpr uint32_t VR_ID_BITS = 34;
-
-struct VisResolveArgs
-{
-	NvCullData cd;
-	const unsigned long long* __restrict__ visibility;
-	uint32_t n; // pixels, <= 16384 * 16384
-	const NvMeshDraw* __restrict__ draws;
-	uint32_t drawCount;
-	const NvMesh* __restrict__ meshes;
-	uint32_t meshCount;
-	uint4* __restrict__ records;        // optional
-	uint32_t* meshletSeen;              // optional
-	uint32_t* drawPixels;               // optional
-	unsigned long long* totals;         // optional
-};
 
 // {drawId or ~0 when mvi names no meshlet, meshletIndex} of the cluster with meshlet-visibility index mvi
 NV_DEV uint2 vr_lookup(const VisResolveArgs& a, uint32_t mvi)
@@ -177,24 +162,9 @@ __global__ __launch_bounds__(VR_THREADS) void visibility_resolve_kernel(VisResol
 	}
 }
 
-int launch_visibility_resolve(hipStream_t stream, const NvCullData& cd, const unsigned long long* visibility, uint32_t n, const NvMeshDraw* draws,
-                              uint32_t drawCount, const NvMesh* meshes, uint32_t meshCount, void* records, uint32_t* meshletSeen, uint32_t* drawPixels,
-                              unsigned long long* totals, uint32_t maxBlocks, bool perPixel)
+int launch_visibility_resolve(hipStream_t stream, VisResolveArgs a, uint32_t maxBlocks, bool perPixel)
 {
-	VisResolveArgs a;
-	a.cd = cd;
-	a.visibility = visibility;
-	a.n = n;
-	a.draws = draws;
-	a.drawCount = drawCount;
-	a.meshes = meshes;
-	a.meshCount = meshCount;
-	a.records = static_cast<uint4*>(records);
-	a.meshletSeen = meshletSeen;
-	a.drawPixels = drawPixels;
-	a.totals = totals;
-	uint32_t grid = (n + VR_THREADS - 1u) / VR_THREADS;
-	grid = grid < maxBlocks ? grid : maxBlocks;
+	const uint32_t grid = capped_grid(a.n, VR_THREADS, maxBlocks);
 	if (perPixel)
 		hipLaunchKernelGGL(visibility_resolve_kernel<false>, dim3(grid), dim3(VR_THREADS), 0, stream, a);
 	else

@@ -13,7 +13,7 @@ import torch
 from . import host
 from . import synth
 from . import layouts as L
-from ._lib import VARIANT_NAMES, NvError, PyramidDesc, check, lib
+from ._lib import PROF_NAMES, VARIANT_NAMES, NvError, PyramidDesc, check, lib
 
 
 def _ptr(t):
@@ -90,11 +90,10 @@ class Context:
         check(lib.nv_profile_enable(self.h, int(enabled)), "nv_profile_enable")
 
     def profile_read(self):
-        """{slot: (total_ms, launches)} for cluster_cull, cluster_scatter, drawcull, depthreduce, cluster_hiz"""
-        ms, cnt = (C.c_float * 5)(), (C.c_uint32 * 5)()
+        """{slot: (total_ms, launches)} for every slot of _lib.PROF_NAMES"""
+        ms, cnt = (C.c_float * len(PROF_NAMES))(), (C.c_uint32 * len(PROF_NAMES))()
         check(lib.nv_profile_read(self.h, C.byref(ms), C.byref(cnt)), "nv_profile_read")
-        names = ("cluster_cull", "cluster_scatter", "drawcull", "depthreduce", "cluster_hiz")
-        return {n: (float(ms[i]), int(cnt[i])) for i, n in enumerate(names)}
+        return {n: (float(ms[i]), int(cnt[i])) for i, n in enumerate(PROF_NAMES)}
 
     VARIANTS = VARIANT_NAMES
 
