@@ -598,7 +598,7 @@ typedef struct NvPixelAttributes
  * (mesh.frag.glsl:57-89) is evaluated from the material's factors — this entry point samples no textures (nv_visibility_attributes_textured
  * does); a material with a texture index > 0 is shaded from its factors and its pixels are counted — and packed: d_gbuffer0 R8G8B8A8_UNORM {tosrgb(albedo).rgb, log2(1 + emissivef) / 5},
  * d_gbuffer1 A2B10G10R10_UNORM_PACK32 {encodeOct(nrm) * 0.5 + 0.5 + deband * (0.5 / 1023), specgloss.a, 0} (src/niagara.cpp:634-637), UNORM =
- * clamp to [0, 1] with NaN -> 0, times 2^bits - 1, rounded half to even.  The POST alpha discard (:88) is coverage and is not modelled.
+ * clamp to [0, 1] with NaN -> 0, times 2^bits - 1, rounded half to even.  The POST alpha discard (:88) is coverage: nv_rasterdepth_textured applies it, this pass does not.
  * Every fp32 operation is one IEEE operation in a fixed order; pow and log2 (gbuffer0 only) are the device's.
  * A record with drawId == 0xFFFFFFFF (no sample, unresolved) writes the no-sample attributes and 0 into both G-buffer words.  A record is
  * INVALID — counted, written like no sample — when drawId >= drawCount, meshletIndex >= meshletCount, triangle >= min(triangleCount, 96), an
@@ -699,6 +699,37 @@ int nv_visibility_attributes_textured(nv_context* ctx, void* stream, const NvGlo
                                       NvPixelAttributes* d_attributes /* optional */, uint32_t* d_gbuffer0 /* optional */,
                                       uint32_t* d_gbuffer1 /* optional */, uint64_t* d_totals4 /* optional */, const NvTextureDesc* d_textures,
                                       uint32_t textureCount, const uint32_t* d_texels, uint64_t texelWords);
+
+/* ---- depth raster with the POST alpha discard as coverage ----
+ * nv_rasterdepth whose covered samples of a post-pass launch also pass the fragment's alpha test (mesh.frag.glsl:88,
+ * `if (POST > 0 && albedo.a < 0.5) discard;`) before they touch d_depth or d_visibility.  The first fifteen parameters, the options
+ * (NV_OPT_RASTER_SMALL_LIMIT, NV_OPT_RASTER_NEAR_CLIP, NV_OPT_RASTER_VISIBILITY_ID) and every rule of coverage and depth are nv_rasterdepth's.
+ * The test applies only when globals->cullData.postPass != 0 and d_materials is given; otherwise the call writes exactly nv_rasterdepth's bits
+ * and totals, and both alpha totals stay as they are.  Per slot (cluster) the draw's materialIndex selects materials[materialIndex]:
+ *   - materialIndex >= materialCount: the slot is opaque (nv_rasterdepth's road); its covered samples are counted as unevaluated;
+ *   - albedoTexture == 0: albedo.a = diffuseFactor.a for every sample of the slot;
+ *   - albedoTexture >= textureCount, or d_textures[albedoTexture] does not describe a chain inside texelWords (nv_visibility_attributes_textured's
+ *     descriptor rule): the texture is treated as absent, albedo.a = diffuseFactor.a, and the covered samples are counted as unevaluated;
+ *   - otherwise albedo.a = diffuseFactor.a * texture(albedo, uv).a per covered sample, with uv and its per-pixel steps taken from the ORIGINAL
+ *     triangle (with NV_OPT_RASTER_NEAR_CLIP 1 too: not from the piece) at the pixel centre exactly as nv_visibility_attributes_textured takes them
+ *     for the same triangle and pixel, and the same sampler (REPEAT, trilinear, the level of detail's log2 is the device's).
+ * A covered sample with albedo.a < 0.5 is dropped: no load, no atomic on either target.  A NaN albedo.a keeps the sample.  Every texel index
+ * stays inside d_texels for every bit pattern of the texcoords.  The depth bias of the post pass stays unmodelled.
+ * d_totals4 words 0-2 are nv_rasterdepth's; word 3 counts the samples KEPT.  d_alphaTotals2 (optional, accumulated: zero it first): samples
+ * dropped, samples unevaluated.  Word 3 + dropped = nv_rasterdepth's word 3 on the same inputs; every total is independent of the order of the
+ * GPU's work (alpha is evaluated for every covered sample of an alpha-tested slot, whether or not it could still raise the targets).
+ * NV_EINVAL, nothing launched: nv_rasterdepth's refusals; d_commands / d_clusterIndices / d_clusterCount4 / d_depth / d_meshlets /
+ * d_meshletData / d_texels not 4-byte aligned, d_visibility / d_totals4 / d_alphaTotals2 not 8-byte aligned, d_draws / d_vertices / d_materials /
+ * d_textures not 16-byte aligned; d_textures without d_texels or the reverse; textureCount != 0 without d_textures; d_materials with
+ * materialCount == 0.  NV_ENOMEM: d_alphaTotals2 while the context holds no partial sums for it (nv_create reserves them). */
+int nv_rasterdepth_textured(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshTaskCommand* d_commands,
+                            const NvMeshDraw* d_draws, const NvMeshlet* d_meshlets, const uint32_t* d_meshletData,
+                            const NvVertex* d_vertices, const uint32_t* d_clusterIndices, const uint32_t* d_clusterCount4,
+                            float* d_depth, uint32_t width, uint32_t height,
+                            uint64_t* d_visibility /* optional, width*height */, uint64_t* d_totals4 /* optional */,
+                            const NvMaterial* d_materials /* optional */, uint32_t materialCount,
+                            const NvTextureDesc* d_textures /* optional */, uint32_t textureCount,
+                            const uint32_t* d_texels /* optional */, uint64_t texelWords, uint64_t* d_alphaTotals2 /* optional */);
 
 /* ---- the shading end of the frame (replaces shadowfill.comp.glsl, shadowblur.comp.glsl and final.comp.glsl) ----
  * Three of niagara's compute passes behind the G-buffer.  All images are linear buffers with row 0 at the top, as the raster target is:

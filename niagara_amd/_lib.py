@@ -99,6 +99,7 @@ _SIGS = {
     "nv_cluster_expand": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "nv_trianglecull": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "nv_rasterdepth": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "nv_rasterdepth_textured": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _u32, _vp, C.c_uint64, _vp]),
     "nv_rasterdepth_indexed": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp]),
     "nv_depthreduce": (_i, [_vp, _vp, _vp, _u32, _u32, C.POINTER(PyramidDesc)]),
     "nv_depth_merge": (_i, [_vp, _vp, _vp, C.POINTER(_vp), _u32, _u32, _u32]),

@@ -338,6 +338,16 @@ struct VaTextures
 	unsigned long long texelWords;
 };
 
+// nv_rasterdepth_textured (rasterdepth.h, rasterdepth_alpha.hip): RasterArgs plus the material table, the texture set and the alpha totals
+struct RasterAlphaArgs : RasterArgs
+{
+	const NvMaterial* __restrict__ materials; // optional
+	uint32_t materialCount;
+	VaTextures tx;
+	unsigned long long* __restrict__ alphaTotals;   // optional: {dropped, unevaluated}
+	unsigned long long* __restrict__ alphaPartials; // library scratch: 2 counters per workgroup of the launch (set whenever alphaTotals is)
+};
+
 // nv_visibility_attributes_textured (visattr.h, visattr_tex.hip): VisAttrArgs plus the texture set
 struct VisAttrTexArgs : VisAttrArgs
 {

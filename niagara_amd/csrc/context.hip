@@ -69,6 +69,7 @@ struct nv_context
 	uint8_t* drawResults = nullptr;
 	size_t drawResultsCapacity;
 	nv::ClusterCounts* drawTileCounts = nullptr;
+	unsigned long long* alphaPartials = nullptr;  // nv_rasterdepth_textured: per-workgroup {dropped, unevaluated} (2 x u64 x grid)
 	unsigned long long* totalsPartials = nullptr; // nv_trianglecull / nv_cluster_expand / nv_rasterdepth(_indexed): per-workgroup partial totals (up to 4 x u64 x grid)
 	// nv_rasterdepth_indexed: per-command chunk prefixes + the count launch's per-workgroup sums (rasterindexed.hip), sized like drawResults
 	void* rasterScratch = nullptr;
@@ -460,7 +461,8 @@ int nv_create(nv_context** out_ctx, int device)
 	    scratch_alloc(&ctx->drawTileCounts, sizeof(nv::ClusterCounts)) != hipSuccess ||
 	    hipMemset(ctx->drawTileCounts, 0, sizeof(nv::ClusterCounts)) != hipSuccess || reserve_draw_results(ctx, 1u << 20) != NV_OK ||
 	    reserve_raster_scratch(ctx, 1u << 20) != NV_OK ||
-	    scratch_alloc(&ctx->totalsPartials, (size_t)persistent_grid(ctx, 8) * 4 * sizeof(unsigned long long)) != hipSuccess)
+	    scratch_alloc(&ctx->totalsPartials, (size_t)persistent_grid(ctx, 8) * 4 * sizeof(unsigned long long)) != hipSuccess ||
+	    scratch_alloc(&ctx->alphaPartials, (size_t)persistent_grid(ctx, 8) * 2 * sizeof(unsigned long long)) != hipSuccess)
 	{
 		nv_destroy(ctx);
 		return NV_ENOMEM;
@@ -496,6 +498,7 @@ void nv_destroy(nv_context* ctx)
 	scratch_reset(ctx->drawResults);
 	scratch_reset(ctx->drawTileCounts);
 	scratch_reset(ctx->totalsPartials);
+	scratch_reset(ctx->alphaPartials);
 	scratch_reset(ctx->rasterScratch);
 	scratch_reset(ctx->masks);
 	scratch_reset(ctx->tileCounts);
@@ -1069,6 +1072,50 @@ int nv_rasterdepth(nv_context* ctx, void* stream, const NvGlobals* globals, cons
 	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
 	a.partials = ctx->totalsPartials;
 	return nv::launch_rasterdepth((hipStream_t)stream, a, persistent_grid(ctx, 8), ctx->rasterNearClip != 0, ctx->rasterStableIds != 0);
+}
+
+int nv_rasterdepth_textured(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshTaskCommand* d_commands, const NvMeshDraw* d_draws,
+                            const NvMeshlet* d_meshlets, const uint32_t* d_meshletData, const NvVertex* d_vertices, const uint32_t* d_clusterIndices,
+                            const uint32_t* d_clusterCount4, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_visibility, uint64_t* d_totals4,
+                            const NvMaterial* d_materials, uint32_t materialCount, const NvTextureDesc* d_textures, uint32_t textureCount,
+                            const uint32_t* d_texels, uint64_t texelWords, uint64_t* d_alphaTotals2)
+{
+	if (!ctx || !globals || !d_commands || !d_draws || !d_meshlets || !d_meshletData || !d_vertices || !d_clusterIndices || !d_clusterCount4 ||
+	    !d_depth || !image_size_ok(width, height) || globals->screenWidth != (float)width || globals->screenHeight != (float)height ||
+	    misaligned(d_commands, 3u) || misaligned(d_clusterIndices, 3u) || misaligned(d_clusterCount4, 3u) || misaligned(d_depth, 3u) ||
+	    misaligned(d_meshlets, 3u) || misaligned(d_meshletData, 3u) || misaligned(d_texels, 3u) || misaligned(d_visibility, 7u) ||
+	    misaligned(d_totals4, 7u) || misaligned(d_alphaTotals2, 7u) || misaligned(d_draws, 15u) || misaligned(d_vertices, 15u) ||
+	    misaligned(d_materials, 15u) || misaligned(d_textures, 15u) || (d_textures != nullptr) != (d_texels != nullptr) || (textureCount && !d_textures) ||
+	    (d_materials && materialCount == 0))
+		return NV_EINVAL;
+	if (d_alphaTotals2 && !ctx->alphaPartials)
+		return NV_ENOMEM; // (nv_create reserves them: a pass never allocates)
+	DeviceGuard guard(ctx->device);
+	nv::RasterAlphaArgs a;
+	a.globals = *globals;
+	a.commands = d_commands;
+	a.draws = d_draws;
+	a.meshlets = d_meshlets;
+	a.meshletData = d_meshletData;
+	a.vertices = d_vertices;
+	a.clusterIndices = d_clusterIndices;
+	a.cc4 = d_clusterCount4;
+	a.depth = reinterpret_cast<uint32_t*>(d_depth);
+	a.visibility = reinterpret_cast<unsigned long long*>(d_visibility);
+	a.width = width;
+	a.height = height;
+	a.smallLimit = ctx->rasterSmallLimit;
+	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
+	a.partials = ctx->totalsPartials;
+	a.materials = d_materials;
+	a.materialCount = d_materials ? materialCount : 0u;
+	a.tx.descs = reinterpret_cast<const uint4*>(d_textures);
+	a.tx.count = d_textures ? textureCount : 0u;
+	a.tx.texels = d_texels;
+	a.tx.texelWords = d_texels ? texelWords : 0u;
+	a.alphaTotals = reinterpret_cast<unsigned long long*>(d_alphaTotals2);
+	a.alphaPartials = d_alphaTotals2 ? ctx->alphaPartials : nullptr;
+	return nv::launch_rasterdepth_alpha((hipStream_t)stream, a, persistent_grid(ctx, 8), ctx->rasterNearClip != 0, ctx->rasterStableIds != 0);
 }
 
 int nv_rasterdepth_indexed(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshDrawCommand* d_commands, const uint32_t* d_count,

@@ -210,18 +210,22 @@ NV_DEV bool rd_setup(const int4* vtx, uint32_t ia, uint32_t ib, uint32_t ic, uin
 constexpr uint32_t RD_STABLE_SHIFT = 34;
 constexpr uint32_t RD_STABLE_MVI_END = (1u << 27) - 1u;
 
-// One pixel centre: coverage, depth, and the atomics (vis: optional).  Returns whether the sample is covered.  STABLE = false: the word is
-// bits(z) << 32 | id (ID = uint32_t, slot << 7 | triangle); STABLE = true: bits(z) << 34 | id (ID = 64 bits, id34).
-template <bool STABLE = false, class ID = uint32_t>
-NV_DEV bool rd_sample(const RdTri& t, int32_t px, int32_t py, uint32_t W, uint32_t* __restrict__ depth, unsigned long long* __restrict__ vis, ID id)
+// One pixel centre, first half: coverage by the edge functions and the top-left rule; wb, wc: the edge values the depth is interpolated with
+NV_DEV bool rd_covered(const RdTri& t, int32_t px, int32_t py, int64_t& wb, int64_t& wc)
 {
 	const int32_t sx = px * 256 + 128, sy = py * 256 + 128;
 	const int64_t wa = rd_edge(t.bx, t.by, t.cx, t.cy, sx, sy);
-	const int64_t wb = rd_edge(t.cx, t.cy, t.ax, t.ay, sx, sy);
-	const int64_t wc = rd_edge(t.ax, t.ay, t.bx, t.by, sx, sy);
-	const bool covered = (wa > 0 || (wa == 0 && (t.topLeft & 2u))) && (wb > 0 || (wb == 0 && (t.topLeft & 4u))) && (wc > 0 || (wc == 0 && (t.topLeft & 1u)));
-	if (!covered)
-		return false;
+	wb = rd_edge(t.cx, t.cy, t.ax, t.ay, sx, sy);
+	wc = rd_edge(t.ax, t.ay, t.bx, t.by, sx, sy);
+	return (wa > 0 || (wa == 0 && (t.topLeft & 2u))) && (wb > 0 || (wb == 0 && (t.topLeft & 4u))) && (wc > 0 || (wc == 0 && (t.topLeft & 1u)));
+}
+
+// One pixel centre, second half: the depth of a covered sample and the atomics (vis: optional).  STABLE = false: the word is
+// bits(z) << 32 | id (ID = uint32_t, slot << 7 | triangle); STABLE = true: bits(z) << 34 | id (ID = 64 bits, id34).
+template <bool STABLE = false, class ID = uint32_t>
+NV_DEV void rd_write(const RdTri& t, int64_t wb, int64_t wc, int32_t px, int32_t py, uint32_t W, uint32_t* __restrict__ depth, unsigned long long* __restrict__ vis,
+                     ID id)
+{
 	float z = (t.za + ((float)wb * t.inv) * t.dzb) + ((float)wc * t.inv) * t.dzc;
 	z = z > 0.0f ? z : 0.0f; // (NaN -> 0)
 	z = z < 1.0f ? z : 1.0f;
@@ -235,6 +239,16 @@ NV_DEV bool rd_sample(const RdTri& t, int32_t px, int32_t py, uint32_t W, uint32
 		if (v > vis[at])
 			atomicMax(vis + at, v);
 	}
+}
+
+// One pixel centre: rd_covered, then rd_write.  Returns whether the sample is covered.
+template <bool STABLE = false, class ID = uint32_t>
+NV_DEV bool rd_sample(const RdTri& t, int32_t px, int32_t py, uint32_t W, uint32_t* __restrict__ depth, unsigned long long* __restrict__ vis, ID id)
+{
+	int64_t wb, wc;
+	if (!rd_covered(t, px, py, wb, wc))
+		return false;
+	rd_write<STABLE>(t, wb, wc, px, py, W, depth, vis, id);
 	return true;
 }
 

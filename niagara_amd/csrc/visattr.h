@@ -6,19 +6,16 @@
 #pragma once
 #include "raster.h"
 #include "launch.h"
-#define NV_TX_SAMPLER_ONLY // (the pass decodes no blocks: keep the BC tables out of its code objects)
-#include "texmath.h"
+#include "fragalpha.h" // the corner's clip x, y, w and uv, the barycentrics, the texture read: shared with the alpha-tested raster (§4.20)
 
 namespace nv
 {
 
 constexpr int VA_THREADS = 256;
 
-// one corner of the triangle after the vertex stage
-struct VaCorner
+// one corner of the triangle after the vertex stage: fragalpha.h's clip x, y, w and packed uv, plus what the other varyings need
+struct VaCorner : FaCorner
 {
-	float cx, cy, cw; // clip x, y, w
-	uint32_t uv;      // tu | tv << 16, fp16 bits (the conversion is exact: done after the hand-over)
 	f3 n;             // rotateQuat(normal)
 	f3 t;             // rotateQuat(tangent.xyz)
 	float tw;         // tangent.w
@@ -133,9 +130,7 @@ NV_DEV void va_from(VaCorner& c, uint32_t lane)
 	c.n = va_from(c.n, lane), c.t = va_from(c.t, lane), c.tw = va_from(c.tw, lane), c.w = va_from(c.w, lane);
 }
 
-NV_DEV float va_mix(float l0, float l1, float l2, float a0, float a1, float a2) { return (l0 * a0 + l1 * a1) + l2 * a2; }
 NV_DEV float va_fract(float x) { return x - __builtin_floorf(x); }
-NV_DEV bool va_finite(float x) { return __builtin_fabsf(x) < __builtin_inff(); }
 
 // UNORM pack of one channel: clamp to [0, 1] with NaN -> 0, scale, round half to even
 NV_DEV uint32_t va_unorm(float x, float scale)
@@ -145,31 +140,12 @@ NV_DEV uint32_t va_unorm(float x, float scale)
 	return (uint32_t)__builtin_rintf(v * scale);
 }
 
-// homogeneous barycentrics of the set-up triangle at the point (fx, fy) in pixels (row 0 at the top), the pixel's own statements again for
-// the two neighbouring centres of the textured pass; returns §4.13's `degen`
-NV_DEV bool va_bary(const VaSetup& s, float fx, float fy, float fw, float fh, float& l0, float& l1, float& l2)
-{
-	const float nx = (fx / fw) * 2.0f - 1.0f, ny = 1.0f - (fy / fh) * 2.0f;
-	const float d0x = s.a.cx - nx * s.a.cw, d0y = s.a.cy - ny * s.a.cw;
-	const float d1x = s.b.cx - nx * s.b.cw, d1y = s.b.cy - ny * s.b.cw;
-	const float d2x = s.c.cx - nx * s.c.cw, d2y = s.c.cy - ny * s.c.cw;
-	const float b0 = d1x * d2y - d1y * d2x, b1 = d2x * d0y - d2y * d0x, b2 = d0x * d1y - d0y * d1x;
-	const float sum = (b0 + b1) + b2;
-	l0 = b0 / sum, l1 = b1 / sum, l2 = b2 / sum;
-	const bool degen = sum == 0.0f || !va_finite(l0) || !va_finite(l1) || !va_finite(l2);
-	l0 = degen ? 1.0f : l0, l1 = degen ? 0.0f : l1, l2 = degen ? 0.0f : l2;
-	return degen;
-}
-
 // texture(SAMP(id), uv) of the textured pass.  false: textures[id] was not sampled — id is past the table or its descriptor's chain does not
 // lie inside texelWords — and nothing was loaded from the texel buffer; the caller shades from the factors and counts the pixel.
 NV_DEV bool va_texture(const VaTextures& tx, uint32_t id, float u, float v, float dudx, float dvdx, float dudy, float dvdy, TxF4& c)
 {
-	if (id >= tx.count)
-		return false;
-	const uint4 w = tx.descs[id];
-	const TxDesc d = { w.x, w.y, w.z, w.w };
-	if (!tx_desc_ok(d, tx.texelWords))
+	TxDesc d;
+	if (!fa_texture_desc(tx, id, d))
 		return false;
 	c = tx_sample(tx.texels, d, u, v, dudx, dvdx, dudy, dvdy);
 	return true;
@@ -195,7 +171,7 @@ __global__ __launch_bounds__(VA_THREADS) void visibility_attributes_kernel(ARGS 
 
 		VaSetup s;
 		s.ok = 0u, s.materialIndex = 0u;
-		s.a = VaCorner{ 0.0f, 0.0f, 0.0f, 0u, f3{ 0.0f, 0.0f, 0.0f }, f3{ 0.0f, 0.0f, 0.0f }, 0.0f, f3{ 0.0f, 0.0f, 0.0f } };
+		s.a = VaCorner{ FaCorner{ 0.0f, 0.0f, 0.0f, 0u }, f3{ 0.0f, 0.0f, 0.0f }, f3{ 0.0f, 0.0f, 0.0f }, 0.0f, f3{ 0.0f, 0.0f, 0.0f } };
 		s.b = s.a, s.c = s.a;
 		if (RUNS)
 		{
@@ -223,7 +199,7 @@ __global__ __launch_bounds__(VA_THREADS) void visibility_attributes_kernel(ARGS 
 			// ---- homogeneous barycentrics at the pixel centre (row 0 at the top)
 			const uint32_t py = i / a.width, px = i - py * a.width;
 			const float fx = (float)px + 0.5f, fy = (float)py + 0.5f;
-			// (written out, not va_bary(): through the function the compiler orders the untextured kernels' instructions differently, and they keep theirs)
+			// (written out, not fa_bary(): through the function the compiler orders the untextured kernels' instructions differently, and they keep theirs)
 			const float nx = (fx / a.fw) * 2.0f - 1.0f, ny = 1.0f - (fy / a.fh) * 2.0f;
 			const float d0x = s.a.cx - nx * s.a.cw, d0y = s.a.cy - ny * s.a.cw;
 			const float d1x = s.b.cx - nx * s.b.cw, d1y = s.b.cy - ny * s.b.cw;
@@ -260,20 +236,15 @@ __global__ __launch_bounds__(VA_THREADS) void visibility_attributes_kernel(ARGS 
 				if constexpr (TEX)
 				{
 					// ---- uv's derivatives per pixel step: the same set-up at the centres of (px + 1, py) and (px, py + 1); nothing is loaded there
-					const float ua = half_bits_to_float(s.a.uv & 0xffffu), ub = half_bits_to_float(s.b.uv & 0xffffu), uc = half_bits_to_float(s.c.uv & 0xffffu);
-					const float va = half_bits_to_float(s.a.uv >> 16), vb = half_bits_to_float(s.b.uv >> 16), vc = half_bits_to_float(s.c.uv >> 16);
-					float m0, m1, m2;
-					const bool degenX = va_bary(s, (float)(px + 1u) + 0.5f, fy, a.fw, a.fh, m0, m1, m2);
-					const float dudx = degenX ? 0.0f : va_mix(m0, m1, m2, ua, ub, uc) - u, dvdx = degenX ? 0.0f : va_mix(m0, m1, m2, va, vb, vc) - v;
-					const bool degenY = va_bary(s, fx, (float)(py + 1u) + 0.5f, a.fw, a.fh, m0, m1, m2);
-					const float dudy = degenY ? 0.0f : va_mix(m0, m1, m2, ua, ub, uc) - u, dvdy = degenY ? 0.0f : va_mix(m0, m1, m2, va, vb, vc) - v;
+					float dudx, dvdx, dudy, dvdy;
+					fa_uv_steps(s.a, s.b, s.c, px, py, fx, fy, a.fw, a.fh, u, v, dudx, dvdx, dudy, dvdy);
 					// :62-76, one texture after the other (8 taps each): the taps of one are consumed before the next one's are issued
 					bool missing = false;
 					TxF4 c;
 					if (tex.x != 0u)
 					{
 						if (va_texture(a.tx, tex.x, u, v, dudx, dvdx, dudy, dvdy, c))
-							albedo = make_float4(albedo.x * __builtin_powf(c.x, 2.2f), albedo.y * __builtin_powf(c.y, 2.2f), albedo.z * __builtin_powf(c.z, 2.2f), albedo.w * c.w);
+							albedo = make_float4(albedo.x * __builtin_powf(c.x, 2.2f), albedo.y * __builtin_powf(c.y, 2.2f), albedo.z * __builtin_powf(c.z, 2.2f), fa_alpha(albedo.w, c.w));
 						else
 							missing = true;
 					}

@@ -177,6 +177,17 @@ class Context:
         check(lib.nv_rasterdepth(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(dcb), _ptr(db), _ptr(mlb), _ptr(meshlet_data), _ptr(vertices),
                                  _ptr(cib), _ptr(ccb), _ptr(depth), int(width), int(height), _ptr(visibility), _ptr(totals4)), "nv_rasterdepth")
 
+    def rasterdepth_textured(self, globals_, dcb, db, mlb, meshlet_data, vertices, cib, ccb, depth, width, height, visibility=None, totals4=None,
+                             materials=None, material_count=0, textures=None, texture_count=0, texels=None, texel_words=0, alpha_totals2=None):
+        """rasterdepth whose covered samples of a post-pass launch (globals' postPass != 0, with `materials`) also pass the fragment's alpha
+        test against the albedo texture (nv_rasterdepth_textured, mesh.frag.glsl:88): a sample with albedo.a < 0.5 touches neither target.
+        materials = a device table of layouts.MATERIAL, textures / texels = texture_decode's set; totals4[3] counts the samples kept,
+        alpha_totals2 (optional, accumulated): samples dropped, samples unevaluated"""
+        check(lib.nv_rasterdepth_textured(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(dcb), _ptr(db), _ptr(mlb), _ptr(meshlet_data),
+                                          _ptr(vertices), _ptr(cib), _ptr(ccb), _ptr(depth), int(width), int(height), _ptr(visibility), _ptr(totals4),
+                                          _ptr(materials), int(material_count), _ptr(textures), int(texture_count), _ptr(texels), int(texel_words),
+                                          _ptr(alpha_totals2)), "nv_rasterdepth_textured")
+
     def rasterdepth_indexed(self, globals_, dcb, dccb, db, draw_count, ib, index_capacity, vertices, vertex_capacity, depth, width, height,
                             totals4=None):
         """depth-only raster of the indexed draws dcb[0, min(dccb[0], draw_count)) (vkCmdDrawIndexedIndirectCount with maxDrawCount = draw_count)
@@ -488,9 +499,12 @@ class VisibilityPipeline:
     def build_pyramid(self, depth):
         self.ctx.depthreduce(depth, self.depth_w, self.depth_h, self.pyramid.desc)
 
-    def render_depth(self, cull_data, late, post_pass=0, visibility=None, totals4=None):
+    def render_depth(self, cull_data, late, post_pass=0, visibility=None, totals4=None, textures=False, materials=None, alpha_totals2=None):
         """the raster of render() (src/niagara.cpp:1582-1611): the clusters of the last render_clusters into self.depth.  The early pass
-        clears the target first (LOAD_OP_CLEAR, depthClear = 0), the late and post passes load it"""
+        clears the target first (LOAD_OP_CLEAR, depthClear = 0), the late and post passes load it.  textures=True: the raster is
+        nv_rasterdepth_textured over set_textures()'s set and `materials` (a host array of layouts.MATERIAL or a device tensor of them): the
+        covered samples of a post pass also pass the alpha test of mesh.frag.glsl:88 (a pass with post_pass = 0 writes the same bits either way);
+        alpha_totals2 (optional): samples dropped, samples unevaluated"""
         if self.mdb is None:
             raise NvError("render_depth needs the scene's geometry: VisibilityPipeline(..., meshlet_data=, vertices=)")
         if not late:
@@ -500,6 +514,16 @@ class VisibilityPipeline:
         pass_data = cull_data.copy()
         pass_data["postPass"] = post_pass
         g = synth.make_globals(pass_data, (self.depth_w, self.depth_h))
+        if textures:
+            missing = [what for what, absent in (("set_textures()", getattr(self, "texture_table", None) is None),
+                                                 ("a material table (materials=)", materials is None)) if absent]
+            if missing:
+                raise NvError("render_depth(textures=True) needs " + ", ".join(missing))
+            mat = to_device(np.ascontiguousarray(materials, L.MATERIAL), self.ctx.device) if isinstance(materials, np.ndarray) else materials
+            self.ctx.rasterdepth_textured(g, self.dcb, self.db, self.mlb, self.mdb, self.vb, self.cib, self.ccb, self.depth, self.depth_w, self.depth_h,
+                                          visibility, totals4, mat, mat.numel() * mat.element_size() // L.MATERIAL.itemsize, self.texture_table,
+                                          len(self.texture_descs), self.texels, self.texels.numel(), alpha_totals2)
+            return
         self.ctx.rasterdepth(g, self.dcb, self.db, self.mlb, self.mdb, self.vb, self.cib, self.ccb, self.depth, self.depth_w, self.depth_h,
                              visibility, totals4)
 
@@ -694,12 +718,16 @@ class VisibilityPipeline:
             self.ctx.shade_final(sd, gbuffer0, gbuffer1, self.depth, shadow, color, w, h)
         return color
 
-    def frame(self, cull_data, post_pass=False, on_phase=None, task=True, visibility=None):
+    def frame(self, cull_data, post_pass=False, on_phase=None, task=True, visibility=None, textures=False, materials=None):
         """one frame of src/niagara.cpp:1765-1788 with the raster in place of the graphics passes: early cull -> clusters -> raster ->
         pyramid -> late cull -> clusters -> raster (-> post cull -> clusters -> raster).  task=False runs the classic path instead (no mesh
         shading): every cull writes MeshDrawCommands, render_draws rasterises them, and clusterOcclusionEnabled is 0 (src/niagara.cpp:1516).
         on_phase(name) is called after each phase's raster ("early", "late", "post").  visibility (stable_ids=True, task=True): a u64
-        target of the depth target's size that the three rasters share (cleared before the early one); resolve() reads it"""
+        target of the depth target's size that the three rasters share (cleared before the early one); resolve() reads it.  textures=True
+        (task=True, after set_textures, with `materials`): the post phase's raster is render_depth(textures=True), the alpha-tested one; the early
+        and late phases stay on nv_rasterdepth (their bits are the same through either entry point)"""
+        if textures and not task:
+            raise NvError("frame(textures=True) needs the cluster path (task=True): nv_rasterdepth_indexed has no alpha-tested form")
         if visibility is not None and not (self.stable_ids and task):
             raise NvError("frame(visibility=) needs stable ids and the cluster path: VisibilityPipeline(..., stable_ids=True), task=True "
                           "(the slot index of the default visibility word does not outlive a pass)")
@@ -713,7 +741,10 @@ class VisibilityPipeline:
             self.cull(cull_data, late=late, task=task, post_pass=pp)
             if task:
                 self.render_clusters(cull_data, late=late, post_pass=pp)
-                self.render_depth(cull_data, late=late, post_pass=pp, visibility=visibility)
+                if textures and pp:
+                    self.render_depth(cull_data, late=late, post_pass=pp, visibility=visibility, textures=True, materials=materials)
+                else:
+                    self.render_depth(cull_data, late=late, post_pass=pp, visibility=visibility)
             else:
                 self.render_draws(cull_data, late=late, post_pass=pp)
             if on_phase is not None:
@@ -803,7 +834,9 @@ class ShardedVisibilityPipeline(VisibilityPipeline):
     def render_clusters(self, cull_data, late, post_pass=0):
         super().render_clusters(self._local(cull_data), late, post_pass)
 
-    def render_depth(self, cull_data, late, post_pass=0, visibility=None, totals4=None):
+    def render_depth(self, cull_data, late, post_pass=0, visibility=None, totals4=None, textures=False, **kw):
+        if textures:
+            raise NvError("render_depth(textures=True) is not available on a sharded pipeline")
         if visibility is not None and not self.stable_ids:
             raise NvError("a sharded frame has no visibility buffer: the slot index nv_rasterdepth writes is rank-local")
         super().render_depth(self._local(cull_data), late, post_pass, visibility, totals4)
@@ -838,10 +871,12 @@ class ShardedVisibilityPipeline(VisibilityPipeline):
         if visibility is not None:
             shard.composite_visibility(visibility, self.group)
 
-    def frame(self, cull_data, post_pass=False, on_phase=None, task=True, visibility=None, composite_last=True, on_raster=None):
+    def frame(self, cull_data, post_pass=False, on_phase=None, task=True, visibility=None, composite_last=True, on_raster=None, textures=False):
         """VisibilityPipeline.frame for this rank's draws, with the depth composite after each phase's raster.  on_raster(name) is called
         between a phase's raster and its composite (the rank's own depth), on_phase(name) after the composite.  composite_last=False skips
         the composite after the last phase: the rank's target then holds the earlier composites plus its own last raster"""
+        if textures:
+            raise NvError("frame(textures=True) is not available on a sharded pipeline")
         if visibility is not None and not (self.stable_ids and task):
             raise NvError("a sharded frame has no visibility buffer: the slot index nv_rasterdepth writes is rank-local "
                           "(ShardedVisibilityPipeline(..., stable_ids=True) and task=True name clusters by a frame-stable id instead)")
@@ -895,8 +930,10 @@ class LocalShards:
     def new_visibility(self):
         return [p.new_visibility() for p in self.pipes]
 
-    def frame(self, cull_data, post_pass=False, on_phase=None, task=True, composite_last=True, on_raster=None, visibility=None):
+    def frame(self, cull_data, post_pass=False, on_phase=None, task=True, composite_last=True, on_raster=None, visibility=None, textures=False):
         """visibility: a list with one u64 target per shard (new_visibility()); needs local_shards(..., stable_ids=True)"""
+        if textures:
+            raise NvError("frame(textures=True) is not available on a sharded pipeline")
         names = ["early", "late"] + (["post"] if post_pass else [])
         for name in names:
             for k, p in enumerate(self.pipes):

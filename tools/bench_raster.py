@@ -8,7 +8,12 @@ synth.occluder_scene (VisibilityPipeline.frame) against the same frame reduced f
 --near-clip: the same workloads with NV_OPT_RASTER_NEAR_CLIP 1 (triangles crossing the near plane are clipped, not dropped).  --only loop also
 times synth.interior_scene (the camera inside the geometry) with and without clipping, whatever the switch.
 
-    python tools/bench_raster.py [--iters N] [--only raster|loop|indexed] [--limits 0,16,...] [--near-clip]
+--only alpha: nv_rasterdepth_textured against nv_rasterdepth, alternated on one context: the post-phase launch of the cut-out
+occluder scene at 1920 x 1080 (the wall alone: large triangles, the wave path) with a 64-texel set (magnified) and a 1024-texel set (minified,
+two levels blended), and 512 distant instances of the wall (triangles of a few pixels) at NV_OPT_RASTER_SMALL_LIMIT 16 (a lane walks its own
+triangle: divergent taps) and 0 (every triangle through the wave path).
+
+    python tools/bench_raster.py [--iters N] [--only raster|loop|indexed|alpha] [--limits 0,16,...] [--near-clip]
 Kernel-trace times: rocprofv3 --kernel-trace --stats -d OUT -o raster -- python tools/bench_raster.py --only raster
 Prints one JSON object."""
 import argparse
@@ -316,10 +321,74 @@ def bench_indexed(iters, near_clip=False):
     return out
 
 
+def bench_alpha(iters):
+    import raster_alpha_ref as RA
+    ctx = P.Context()
+    dev = ctx.device
+    ctx.set_option(P.NV_OPT_RASTER_VISIBILITY_ID, 1)  # the frame's post phase writes the stable word
+    w, h = 1920, 1080
+    out = {}
+
+    def case(name, s, list_draws, size, limit):
+        t = synth.with_textures(s, size=size, cutout=True)
+        draws = t["draws"].copy()
+        draws["postPass"][list_draws] = 1
+        draws["materialIndex"][list_draws] = 0
+        t["draws"] = draws
+        commands, cib_h, cc4_h = RA.draw_list(t, list_draws)
+        cd = t["cull"].copy()
+        cd["postPass"] = 1
+        g = synth.make_globals(cd, (w, h))
+        descs, texels = ctx.texture_decode(t["textures"])
+        dev_args = [P.to_device(a, dev) for a in (commands, draws, t["meshlets"], t["data"], t["vertices"], cib_h, cc4_h)]
+        mat, table = P.to_device(t["materials"], dev), P.to_device(descs, dev)
+        depth = torch.zeros((h, w), dtype=torch.float32, device=dev)
+        vis = torch.zeros((h, w), dtype=torch.int64, device=dev)
+        tot, alpha = torch.zeros(4, dtype=torch.int64, device=dev), torch.zeros(2, dtype=torch.int64, device=dev)
+        tex = dict(materials=mat, material_count=len(t["materials"]), textures=table, texture_count=len(descs), texels=texels, texel_words=texels.numel())
+        plain = lambda totals=None: ctx.rasterdepth(g, *dev_args, depth, w, h, vis, totals)
+        textured = lambda totals=None, a2=None: ctx.rasterdepth_textured(g, *dev_args, depth, w, h, vis, totals, alpha_totals2=a2, **tex)
+
+        def reset():  # every launch starts from cleared targets
+            depth.zero_()
+            vis.zero_()
+        ctx.set_option(P.NV_OPT_RASTER_SMALL_LIMIT, limit)
+        rounds = [(_time(plain, iters, reset), _time(textured, iters, reset)) for _ in range(3)]  # alternated
+        reset()
+        plain(tot)
+        p = [int(x) for x in tot.cpu().numpy()]
+        tot.zero_()
+        reset()
+        textured(tot, alpha)
+        k, a2 = [int(x) for x in tot.cpu().numpy()], [int(x) for x in alpha.cpu().numpy()]
+        ctx.status()
+        ctx.set_option(P.NV_OPT_RASTER_SMALL_LIMIT, 16)
+        out[name] = dict(texture_side=size, small_limit=limit, clusters=p[0], triangles=p[1], rasterised=p[2], samples=p[3], kept=k[3], dropped=a2[0],
+                         unevaluated=a2[1], plain_us_median=[r[0][0] for r in rounds], textured_us_median=[r[1][0] for r in rounds],
+                         plain_us_min=min(r[0][1] for r in rounds), textured_us_min=min(r[1][1] for r in rounds))
+
+    wall = synth.occluder_scene(viewport=(w, h), box_scale=3.0, meshlet_bounds=oracle.meshlet_bounds)
+    case("wall_1080p_64", wall, wall["wall"], 64, 16)
+    case("wall_1080p_1024", wall, wall["wall"], 1024, 16)
+    # 512 instances of the wall, far away and small: triangles of a few pixels
+    far = dict(wall)
+    rng = np.random.default_rng(5)
+    d = np.zeros(512, L.MESHDRAW)
+    d["orientation"], d["scale"], d["meshIndex"] = (0.0, 0.0, 0.0, 1.0), wall["draws"]["scale"][0], 0
+    dist = rng.uniform(200.0, 300.0, 512)
+    d["position"] = np.stack([rng.uniform(-1.2, 1.2, 512) * dist, rng.uniform(-0.7, 0.7, 512) * dist, -dist], 1)
+    far["draws"] = d
+    host.assign_visibility_offsets(far["draws"], far["meshes"])
+    for limit in (16, 0):
+        case("far_walls_limit_%d" % limit, far, list(range(512)), 256, limit)
+    ctx.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--only", choices=("raster", "loop", "indexed"), default=None)
+    ap.add_argument("--only", choices=("raster", "loop", "indexed", "alpha"), default=None)
     ap.add_argument("--limits", default="0,4,9,16,32,64,%d" % INT_MAX)
     ap.add_argument("--no-split", action="store_true")
     ap.add_argument("--near-clip", action="store_true", help="NV_OPT_RASTER_NEAR_CLIP 1 on every context")
@@ -334,6 +403,8 @@ def main():
         res["loop"] = bench_loop(a.iters, a.near_clip)
     if a.only in (None, "indexed"):
         res["indexed"] = bench_indexed(a.iters, a.near_clip)
+    if a.only == "alpha":
+        res["alpha"] = bench_alpha(a.iters)
     print(json.dumps(res))
 
 

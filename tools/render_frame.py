@@ -8,6 +8,7 @@
     python3 tools/render_frame.py --traced-shadows                      # the mask is ray traced (nv_shadow_trace)
     python3 tools/render_frame.py --traced-shadows --animate 8          # 8 images, one box on a circle: its shadow follows (§4.17)
     python3 tools/render_frame.py --alpha-shadows                       # the wall is a cut-out in the post pass: its shadow has holes (§4.19)
+    python3 tools/render_frame.py --alpha-coverage --alpha-shadows      # and so has the wall: the boxes behind it show through (§4.20)
 
 Writes a binary PPM (P6, R G B from the R8G8B8A8 colour words) and prints one JSON line with the passes' times by HIP events (one run
 each after a warm-up frame: launch gaps included, an upper bound of the kernel time; profiles/r13_shade.md has the kernel trace).
@@ -246,6 +247,9 @@ def main():
     ap.add_argument("--traced-shadows", action="store_true", help="ray trace the shadow mask (the default stays the synthetic mask)")
     ap.add_argument("--alpha-shadows", action="store_true", help="--traced-shadows --textures with the wall in the post pass and a cut-out albedo: the trace "
                     "runs the alpha test (nv_shadow_trace_textured, DESIGN.md §4.19) and the wall's shadow has the checker's holes")
+    ap.add_argument("--alpha-coverage", action="store_true", help="--textures with the wall in the post pass and a cut-out albedo: the post phase's raster runs the "
+                    "fragment's alpha test (nv_rasterdepth_textured, DESIGN.md §4.20) and the boxes behind the wall's holes are in the image; alone or "
+                    "with --alpha-shadows")
     ap.add_argument("--quality", type=int, default=1, help="--traced-shadows: 0 = opaque draws cast, 1 = post-pass draws too")
     ap.add_argument("--animate", type=int, default=0, help="--traced-shadows: write N images (out_000.ppm ...) with one draw displaced along a circle "
                     "per frame through move_draws, which rebuilds the TLAS on the device")
@@ -254,6 +258,9 @@ def main():
     args = ap.parse_args()
     if args.alpha_shadows:
         args.traced_shadows = args.textures = True
+    if args.alpha_coverage:
+        args.textures = True
+    cutout = args.alpha_shadows or args.alpha_coverage
     if args.passes == "shadow_trace":
         if not args.traced_shadows:
             ap.error("--passes shadow_trace times the ray-traced pass: give --traced-shadows")
@@ -289,10 +296,10 @@ def main():
     textures = None
     if args.textures:
         from niagara_amd import synth
-        t = synth.with_textures(dict(vertices=v, draws=draws, materials=materials), cutout=args.alpha_shadows)  # planar texcoords, the four maps, materials that name them
+        t = synth.with_textures(dict(vertices=v, draws=draws, materials=materials), cutout=cutout)  # planar texcoords, the four maps, materials that name them
         v, materials, textures = t["vertices"], t["materials"], t["textures"]
-    if args.alpha_shadows:
-        draws["postPass"][s["wall"]] = 1  # the alpha test sees post-pass instances only (src/scenert.cpp:516)
+    if cutout:
+        draws["postPass"][s["wall"]] = 1  # both alpha tests see post-pass draws only (src/scenert.cpp:516, mesh.frag.glsl:88)
     pipe = P.VisibilityPipeline(s["meshes"], s["meshlets"], draws, (w, h), fused=True, vertices=v, meshlet_data=s["data"], stable_ids=True)
     if textures:
         pipe.set_textures(textures)
@@ -306,7 +313,7 @@ def main():
 
     def frame(events):
         vis = pipe.new_visibility()
-        _timed(events, "frame", lambda: pipe.frame(s["cull"], post_pass=True, visibility=vis))
+        _timed(events, "frame", lambda: pipe.frame(s["cull"], post_pass=True, visibility=vis, textures=args.alpha_coverage, materials=mat))
         res = _timed(events, "resolve", lambda: pipe.resolve(s["cull"], vis))
         att = _timed(events, "attributes", lambda: pipe.attributes(s["cull"], res["records"], mat, attributes=False, textures=args.textures))
         shadow = None if args.no_shadow else "trace" if args.traced_shadows else torch.from_numpy(mask.copy()).to(pipe.ctx.device)
@@ -320,7 +327,7 @@ def main():
             f.write(b"P6\n%d %d\n255\n" % (w, h))
             f.write(rgb.tobytes())
         print(json.dumps(dict(out=path, viewport=[w, h], shadow=not args.no_shadow, traced=bool(args.traced_shadows and not args.no_shadow), bloom=args.bloom,
-                              covered=int((pipe.depth > 0).sum().item()), mean_rgb=[round(float(c), 2) for c in rgb.reshape(-1, 3).mean(0)],
+                              covered=int((pipe.depth > 0).sum().item()), alpha_coverage=bool(args.alpha_coverage), mean_rgb=[round(float(c), 2) for c in rgb.reshape(-1, 3).mean(0)],
                               us={name: round(a.elapsed_time(b) * 1e3, 1) for name, a, b in events}, **extra)))
     frame([])  # warm-up (and the visibility bits of the closed loop)
     if args.animate > 0:
