@@ -700,6 +700,64 @@ int nv_visibility_attributes_textured(nv_context* ctx, void* stream, const NvGlo
                                       uint32_t* d_gbuffer1 /* optional */, uint64_t* d_totals4 /* optional */, const NvTextureDesc* d_textures,
                                       uint32_t textureCount, const uint32_t* d_texels, uint64_t texelWords);
 
+/* ---- block-resident texture sets ----
+ * A second residency for a texture set: the device buffer holds the DDS payloads verbatim (8 bytes per 16 texels for BC1, 16 for BC2 / BC3 /
+ * BC7, against 64 decoded) and the sampler decodes each tap's texel from its block when it fetches it.  A tap decoded from its block is the
+ * RGBA8 code nv_texture_decode stores, and everything after the fetch is the decoded sampler's text: the results are the decoded entry
+ * points', bit for bit.  Opt-in: the decoded entry points are untouched.
+ *
+ * One block-resident texture: its payload — level after level exactly as the file has them (NvDdsInfo.levelOffset) — lies from byte
+ * 16 * offset of the set's block buffer.  Level l is a grid of ceil(w_l / 4) x ceil(h_l / 4) blocks, row-major; texel (x, y) is texel
+ * (y & 3) * 4 + (x & 3) of block (x >> 2, y >> 2).  16 bytes, fixed (niagara_amd/layouts.py TEXTUREBLOCKDESC). */
+typedef struct NvTextureBlockDesc
+{
+	uint32_t offset;       /* in 16-byte units: every 16-byte block stays aligned, a set can reach 64 GiB */
+	uint32_t width, height;
+	uint32_t levelsFormat; /* the level count in bits 0-7, NV_FORMAT_* in bits 8-15, bits 16-31 zero */
+} NvTextureBlockDesc;
+
+/* nv_texture_block_layout: nv_texture_set_layout for the block form, a pure function.  descs has count + 1 entries (entry 0 reserved, all
+ * zero; entry i + 1 belongs to infos[i]); each payload is rounded up to 16 bytes; *units16 = the 16-byte units the caller allocates.
+ * Uploading is a plain copy of infos[i]'s payload to byte 16 * descs[i + 1].offset: no kernel.  Refuses what nv_texture_set_layout refuses,
+ * with its codes; NV_EINVAL also for a total of 2^32 units or more. */
+int nv_texture_block_layout(const NvDdsInfo* infos, uint32_t count, NvTextureBlockDesc* descs, uint64_t* units16);
+
+/* the RGBA8 code of texel (x, y) of `level`, decoded from its block on the CPU (csrc/texmath.h, the text the kernels run): the word
+ * nv_texture_decode_host stores there.  blocks: the set's block buffer, units16 units.  NV_EINVAL: a NULL pointer, a descriptor the check in
+ * front of every block load refuses (shape, format, levelsFormat's upper bits, a chain past units16), level, x or y outside the texture. */
+int nv_texture_block_fetch_host(const NvTextureBlockDesc* desc, const void* blocks, uint64_t units16, uint32_t level, uint32_t x, uint32_t y,
+                                uint32_t* rgba);
+
+/* nv_texture_sample_host over a block-resident set: the same bits */
+int nv_texture_block_sample_host(const NvTextureBlockDesc* descs, uint32_t textureCount, const void* blocks, uint64_t units16, uint32_t id,
+                                 const float uv[2], const float duvdx[2], const float duvdy[2], float out_rgba[4]);
+
+/* test accessors of the per-block decode: out_alpha[t] = the alpha-only decode of texel t, out_split[t] = the RGBA8 code through the BC7
+ * header / per-texel split (the plain decode for the other formats), of the block {lo, hi} of a decodable format (NV_EINVAL otherwise) */
+int nv_texture_block_decode_host(uint32_t format, uint64_t lo, uint64_t hi, uint32_t out_alpha[16], uint32_t out_split[16]);
+
+/* nv_visibility_attributes_blocks: nv_visibility_attributes_textured over a block-resident set.  Its arguments, outputs, d_totals4[3] rule
+ * and errors; d_textures: NvTextureBlockDesc, d_blocks: the block buffer (16-byte aligned), units16 its size.  Before any block load the index
+ * is checked against textureCount and the descriptor against units16 (shape, format, whole chain, in 64 bits).  Outputs equal
+ * nv_visibility_attributes_textured's over the decoded form of the same set bit for bit.  One launch, capturable. */
+int nv_visibility_attributes_blocks(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisRecord* d_records, uint32_t width,
+                                    uint32_t height, const NvMeshDraw* d_draws, uint32_t drawCount, const NvMeshlet* d_meshlets,
+                                    uint32_t meshletCount, const uint32_t* d_meshletData, uint32_t meshletDataWords, const NvVertex* d_vertices,
+                                    uint32_t vertexCount, const NvMaterial* d_materials, uint32_t materialCount,
+                                    NvPixelAttributes* d_attributes /* optional */, uint32_t* d_gbuffer0 /* optional */,
+                                    uint32_t* d_gbuffer1 /* optional */, uint64_t* d_totals4 /* optional */, const NvTextureBlockDesc* d_textures,
+                                    uint32_t textureCount, const void* d_blocks, uint64_t units16);
+
+/* nv_rasterdepth_blocks: nv_rasterdepth_textured (below) over a block-resident set — its parameters, rules, counters and errors, with
+ * NvTextureBlockDesc descriptors, d_blocks (16-byte aligned) and units16.  Depth, visibility, d_totals4 and d_alphaTotals2 equal
+ * nv_rasterdepth_textured's over the decoded form of the same set bit for bit. */
+int nv_rasterdepth_blocks(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshTaskCommand* d_commands, const NvMeshDraw* d_draws,
+                          const NvMeshlet* d_meshlets, const uint32_t* d_meshletData, const NvVertex* d_vertices, const uint32_t* d_clusterIndices,
+                          const uint32_t* d_clusterCount4, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_visibility /* optional */,
+                          uint64_t* d_totals4 /* optional */, const NvMaterial* d_materials /* optional */, uint32_t materialCount,
+                          const NvTextureBlockDesc* d_textures /* optional */, uint32_t textureCount, const void* d_blocks /* optional */,
+                          uint64_t units16, uint64_t* d_alphaTotals2 /* optional */);
+
 /* ---- depth raster with the POST alpha discard as coverage ----
  * nv_rasterdepth whose covered samples of a post-pass launch also pass the fragment's alpha test (mesh.frag.glsl:88,
  * `if (POST > 0 && albedo.a < 0.5) discard;`) before they touch d_depth or d_visibility.  The first fifteen parameters, the options
@@ -934,6 +992,15 @@ int nv_shadow_trace_textured(nv_context* ctx, void* stream, const NvShadowData* 
                              uint32_t materialCount, const NvTextureDesc* d_textures, uint32_t textureCount, const uint32_t* d_texels,
                              uint64_t texelWords);
 
+/* nv_shadow_trace_blocks: nv_shadow_trace_textured (the shadow passes, below) over a block-resident set — its parameters, rules and errors,
+ * with NvTextureBlockDesc descriptors, d_blocks (16-byte aligned) and units16; the four alpha taps of a candidate are decoded from their
+ * blocks, alpha alone.  The mask equals nv_shadow_trace_textured's over the decoded form of the same set byte for byte. */
+int nv_shadow_trace_blocks(nv_context* ctx, void* stream, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width,
+                           uint32_t height, int quality, const NvMeshDraw* d_draws, uint32_t drawCount, const NvMaterial* d_materials,
+                           uint32_t materialCount, const NvTextureBlockDesc* d_textures, uint32_t textureCount, const void* d_blocks,
+                           uint64_t units16);
+
+
 /* ---- the TLAS rebuilt for moving draws (niagara_amd/csrc/rttlas.h is the definition) ----
  * The rebuilt TLAS is a function of the blob's BLAS side and the current draw array alone: the instances are the draws that cast by the rule
  * above (re-derived at every rebuild), each with nv_rt_scene_build's fp64 box; they are ordered by (key, drawId), key the 30-bit Morton code of
@@ -1076,6 +1143,7 @@ static_assert(sizeof(NvRtSceneStats) == 40, "NvRtSceneStats is mirrored by niaga
 static_assert(sizeof(NvBloomDesc) == 48 && offsetof(NvBloomDesc, levels) == 8 && offsetof(NvBloomDesc, levelOffset) == 12 &&
               offsetof(NvBloomDesc, totalTexels) == 44, "NvBloomDesc is mirrored by niagara_amd/_lib.py and niagara_amd/layouts.py");
 static_assert(sizeof(NvTextureDesc) == 16 && offsetof(NvTextureDesc, width) == 4 && offsetof(NvTextureDesc, levels) == 12, "NvTextureDesc is mirrored by niagara_amd/layouts.py");
+static_assert(sizeof(NvTextureBlockDesc) == 16 && offsetof(NvTextureBlockDesc, width) == 4 && offsetof(NvTextureBlockDesc, height) == 8 && offsetof(NvTextureBlockDesc, levelsFormat) == 12, "NvTextureBlockDesc is mirrored by niagara_amd/layouts.py");
 static_assert(sizeof(NvDdsInfo) == 152 && offsetof(NvDdsInfo, payloadBytes) == 24 && offsetof(NvDdsInfo, levelOffset) == 32, "NvDdsInfo is mirrored by niagara_amd/_lib.py");
 static_assert(sizeof(NvSceneCacheInfo) == 208, "NvSceneCacheInfo is mirrored by niagara_amd/_lib.py");
 #endif

@@ -109,6 +109,14 @@ _SIGS = {
     "nv_visibility_attributes_textured": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp,
                                                _vp, _u32, _vp, C.c_uint64]),
     "nv_dds_parse": (_i, [_vp, C.c_uint64, C.POINTER(DdsInfo)]),
+    "nv_visibility_attributes_blocks": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp,
+                                             _vp, _u32, _vp, C.c_uint64]),
+    "nv_rasterdepth_blocks": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _u32, _vp, C.c_uint64, _vp]),
+    "nv_shadow_trace_blocks": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _i, _vp, _u32, _vp, _u32, _vp, _u32, _vp, C.c_uint64]),
+    "nv_texture_block_layout": (_i, [C.POINTER(DdsInfo), _u32, _vp, C.POINTER(C.c_uint64)]),
+    "nv_texture_block_fetch_host": (_i, [_vp, _vp, C.c_uint64, _u32, _u32, _u32, _vp]),
+    "nv_texture_block_sample_host": (_i, [_vp, _u32, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp]),
+    "nv_texture_block_decode_host": (_i, [_u32, C.c_uint64, C.c_uint64, _vp, _vp]),
     "nv_texture_set_layout": (_i, [C.POINTER(DdsInfo), _u32, _vp, C.POINTER(C.c_uint64)]),
     "nv_texture_decode_host": (_i, [C.POINTER(DdsInfo), _vp, _vp, _vp, C.c_uint64]),
     "nv_texture_decode": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, C.POINTER(TextureDesc)]),

@@ -30,7 +30,7 @@
 
 #include "../../include/niagara_vis.h"
 #include "dealing.h"
-#include "rtmath.h" // RtAlphaInputs (ShadowTraceAlphaArgs)
+#include "rtmath.h" // RtAlphaInputs (ShadowTraceAlphaArgs), RtAlphaBlockInputs (ShadowTraceBlockArgs)
 
 // Tuning experiments (wave stamps, partial passes, alternative dealing ...) exist only in a separate build
 // (-DNV_EXPERIMENTS -> libniagara_vis_exp.so, tools/): the product library carries no switch that could change a result
@@ -354,6 +354,21 @@ struct VisAttrTexArgs : VisAttrArgs
 	VaTextures tx;
 };
 
+// the block-resident texture set
+struct VaBlockTextures
+{
+	const uint4* __restrict__ descs; // NvTextureBlockDesc, entry 0 reserved
+	uint32_t count;
+	const void* __restrict__ blocks; // the DDS payloads, 16-byte aligned
+	unsigned long long units16;
+};
+
+// nv_visibility_attributes_blocks (visattr.h, visattr_blocks.hip): VisAttrArgs plus the block-resident set
+struct VisAttrBlockArgs : VisAttrArgs
+{
+	VaBlockTextures tx;
+};
+
 // nv_shade_final (shade.hip)
 struct ShadeFinalArgs
 {
@@ -396,6 +411,29 @@ struct ShadowTraceAlphaArgs
 	uint32_t width, height;
 	uint32_t invocationsX; // as ShadowTraceArgs
 	uint32_t tilesX, tiles;
+};
+
+// nv_shadow_trace_blocks at quality 1 (shadowtrace.h, shadowtrace_blocks.hip)
+struct ShadowTraceBlockArgs
+{
+	NvShadowData sd;
+	RtAlphaBlockInputs in;
+	const unsigned char* __restrict__ scene;
+	const float* __restrict__ depth;
+	uint8_t* __restrict__ shadow;
+	uint32_t width, height;
+	uint32_t invocationsX; // as ShadowTraceArgs
+	uint32_t tilesX, tiles;
+};
+
+// nv_rasterdepth_blocks (rasterdepth.h, rasterdepth_blocks.hip): RasterAlphaArgs with the block-resident set
+struct RasterBlockArgs : RasterArgs
+{
+	const NvMaterial* __restrict__ materials; // optional
+	uint32_t materialCount;
+	VaBlockTextures tx;
+	unsigned long long* __restrict__ alphaTotals;   // optional: {dropped, unevaluated}
+	unsigned long long* __restrict__ alphaPartials; // library scratch: 2 counters per workgroup of the launch (set whenever alphaTotals is)
 };
 
 } // namespace nv

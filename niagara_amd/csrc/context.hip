@@ -1118,6 +1118,51 @@ int nv_rasterdepth_textured(nv_context* ctx, void* stream, const NvGlobals* glob
 	return nv::launch_rasterdepth_alpha((hipStream_t)stream, a, persistent_grid(ctx, 8), ctx->rasterNearClip != 0, ctx->rasterStableIds != 0);
 }
 
+// the same pass over a block-resident set (rasterdepth_blocks.hip)
+int nv_rasterdepth_blocks(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshTaskCommand* d_commands, const NvMeshDraw* d_draws,
+                          const NvMeshlet* d_meshlets, const uint32_t* d_meshletData, const NvVertex* d_vertices, const uint32_t* d_clusterIndices,
+                          const uint32_t* d_clusterCount4, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_visibility, uint64_t* d_totals4,
+                          const NvMaterial* d_materials, uint32_t materialCount, const NvTextureBlockDesc* d_textures, uint32_t textureCount,
+                          const void* d_blocks, uint64_t units16, uint64_t* d_alphaTotals2)
+{
+	if (!ctx || !globals || !d_commands || !d_draws || !d_meshlets || !d_meshletData || !d_vertices || !d_clusterIndices || !d_clusterCount4 ||
+	    !d_depth || !image_size_ok(width, height) || globals->screenWidth != (float)width || globals->screenHeight != (float)height ||
+	    misaligned(d_commands, 3u) || misaligned(d_clusterIndices, 3u) || misaligned(d_clusterCount4, 3u) || misaligned(d_depth, 3u) ||
+	    misaligned(d_meshlets, 3u) || misaligned(d_meshletData, 3u) || misaligned(d_blocks, 15u) || misaligned(d_visibility, 7u) ||
+	    misaligned(d_totals4, 7u) || misaligned(d_alphaTotals2, 7u) || misaligned(d_draws, 15u) || misaligned(d_vertices, 15u) ||
+	    misaligned(d_materials, 15u) || misaligned(d_textures, 15u) || (d_textures != nullptr) != (d_blocks != nullptr) || (textureCount && !d_textures) ||
+	    (d_materials && materialCount == 0))
+		return NV_EINVAL;
+	if (d_alphaTotals2 && !ctx->alphaPartials)
+		return NV_ENOMEM; // (nv_create reserves them: a pass never allocates)
+	DeviceGuard guard(ctx->device);
+	nv::RasterBlockArgs a;
+	a.globals = *globals;
+	a.commands = d_commands;
+	a.draws = d_draws;
+	a.meshlets = d_meshlets;
+	a.meshletData = d_meshletData;
+	a.vertices = d_vertices;
+	a.clusterIndices = d_clusterIndices;
+	a.cc4 = d_clusterCount4;
+	a.depth = reinterpret_cast<uint32_t*>(d_depth);
+	a.visibility = reinterpret_cast<unsigned long long*>(d_visibility);
+	a.width = width;
+	a.height = height;
+	a.smallLimit = ctx->rasterSmallLimit;
+	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
+	a.partials = ctx->totalsPartials;
+	a.materials = d_materials;
+	a.materialCount = d_materials ? materialCount : 0u;
+	a.tx.descs = reinterpret_cast<const uint4*>(d_textures);
+	a.tx.count = d_textures ? textureCount : 0u;
+	a.tx.blocks = d_blocks;
+	a.tx.units16 = d_blocks ? units16 : 0u;
+	a.alphaTotals = reinterpret_cast<unsigned long long*>(d_alphaTotals2);
+	a.alphaPartials = d_alphaTotals2 ? ctx->alphaPartials : nullptr;
+	return nv::launch_rasterdepth_blocks((hipStream_t)stream, a, persistent_grid(ctx, 8), ctx->rasterNearClip != 0, ctx->rasterStableIds != 0);
+}
+
 int nv_rasterdepth_indexed(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshDrawCommand* d_commands, const uint32_t* d_count,
                            const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices, uint32_t indexCapacity,
                            const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_totals4)
@@ -1274,6 +1319,27 @@ int nv_visibility_attributes_textured(nv_context* ctx, void* stream, const NvGlo
 	a.tx.texels = d_texels;
 	a.tx.texelWords = texelWords;
 	return nv::launch_visibility_attributes_textured((hipStream_t)stream, a, height, persistent_grid(ctx, 8));
+}
+
+// the same pass over a block-resident set (visattr_blocks.hip)
+int nv_visibility_attributes_blocks(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisRecord* d_records, uint32_t width,
+                                    uint32_t height, const NvMeshDraw* d_draws, uint32_t drawCount, const NvMeshlet* d_meshlets,
+                                    uint32_t meshletCount, const uint32_t* d_meshletData, uint32_t meshletDataWords, const NvVertex* d_vertices,
+                                    uint32_t vertexCount, const NvMaterial* d_materials, uint32_t materialCount, NvPixelAttributes* d_attributes,
+                                    uint32_t* d_gbuffer0, uint32_t* d_gbuffer1, uint64_t* d_totals4, const NvTextureBlockDesc* d_textures,
+                                    uint32_t textureCount, const void* d_blocks, uint64_t units16)
+{
+	nv::VisAttrBlockArgs a;
+	if (fill_attribute_args(a, ctx, globals, d_records, width, height, d_draws, drawCount, d_meshlets, meshletCount, d_meshletData, meshletDataWords, d_vertices,
+	                        vertexCount, d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1, d_totals4) != NV_OK ||
+	    !d_materials || (textureCount && (!d_textures || !d_blocks)) || misaligned(d_textures, 15u) || misaligned(d_blocks, 15u))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	a.tx.descs = reinterpret_cast<const uint4*>(d_textures);
+	a.tx.count = d_textures ? textureCount : 0u;
+	a.tx.blocks = d_blocks;
+	a.tx.units16 = units16;
+	return nv::launch_visibility_attributes_blocks((hipStream_t)stream, a, height, persistent_grid(ctx, 8));
 }
 
 int nv_texture_decode(nv_context* ctx, void* stream, const void* d_blocks, uint32_t format, uint32_t width, uint32_t height, uint32_t levels,
@@ -1536,6 +1602,37 @@ int nv_shadow_trace_textured(nv_context* ctx, void* stream, const NvShadowData* 
 	a.width = width;
 	a.height = height;
 	return nv::launch_shadow_trace_alpha((hipStream_t)stream, a, persistent_grid(ctx, 8));
+}
+
+// the same over a block-resident set (shadowtrace_blocks.hip)
+int nv_shadow_trace_blocks(nv_context* ctx, void* stream, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width, uint32_t height,
+                           int quality, const NvMeshDraw* d_draws, uint32_t drawCount, const NvMaterial* d_materials, uint32_t materialCount,
+                           const NvTextureBlockDesc* d_textures, uint32_t textureCount, const void* d_blocks, uint64_t units16)
+{
+	nv::ShadowTraceArgs opaque;
+	if (fill_trace_args(opaque, ctx, shadow, d_depth, d_shadow, width, height, quality) != NV_OK || !(ctx->rtSceneFlags & nv::RT_FLAG_TEXCOORDS) ||
+	    (drawCount && !d_draws) || (materialCount && !d_materials) || (textureCount && !d_textures) || (units16 && !d_blocks) || misaligned(d_draws, 15u) ||
+	    misaligned(d_materials, 15u) || misaligned(d_textures, 15u) || misaligned(d_blocks, 15u))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	if (quality == 0)
+		return nv::launch_shadow_trace((hipStream_t)stream, opaque, 0, persistent_grid(ctx, 8));
+	nv::ShadowTraceBlockArgs a;
+	a.sd = opaque.sd;
+	a.in.draws = d_draws;
+	a.in.materials = d_materials;
+	a.in.textures = reinterpret_cast<const nv::TxBlockDesc*>(d_textures);
+	a.in.blocks = d_blocks;
+	a.in.units16 = units16;
+	a.in.drawCount = drawCount;
+	a.in.materialCount = materialCount;
+	a.in.textureCount = textureCount;
+	a.scene = opaque.scene;
+	a.depth = d_depth;
+	a.shadow = d_shadow;
+	a.width = width;
+	a.height = height;
+	return nv::launch_shadow_trace_blocks((hipStream_t)stream, a, persistent_grid(ctx, 8));
 }
 
 // ---- bloom (bloom.hip)

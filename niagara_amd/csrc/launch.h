@@ -69,6 +69,8 @@ int launch_trianglecull(hipStream_t, const TriangleArgs& a, uint32_t gridBlocks)
 // rasterdepth.hip, rasterindexed.hip
 int launch_rasterdepth(hipStream_t, const RasterArgs& a, uint32_t gridBlocks, bool nearClip, bool stableIds);
 int launch_rasterdepth_alpha(hipStream_t, const RasterAlphaArgs& a, uint32_t gridBlocks, bool nearClip, bool stableIds);
+int launch_rasterdepth_blocks(hipStream_t, const RasterBlockArgs& a, uint32_t gridBlocks, bool nearClip, bool stableIds);
+int launch_raster_alpha_totals(hipStream_t, const unsigned long long* partials, uint32_t blocks, unsigned long long* totals); // (rasterdepth_alpha.hip)
 int launch_raster_totals(hipStream_t, const unsigned long long* partials, uint32_t blocks, unsigned long long* totals); // (rasterindexed.hip's too)
 int launch_rasterindexed(hipStream_t, RasterIndexedArgs a, void* scratch, uint32_t gridBlocks, bool nearClip);
 size_t rasterindexed_scratch_bytes(uint32_t drawCount);
@@ -79,6 +81,7 @@ int launch_visibility_merge(hipStream_t, unsigned long long* dst, const unsigned
 int launch_visibility_resolve(hipStream_t, VisResolveArgs a, uint32_t maxBlocks, bool perPixel);
 int launch_visibility_attributes(hipStream_t, VisAttrArgs a, uint32_t height, uint32_t maxBlocks, bool perPixel);
 int launch_visibility_attributes_textured(hipStream_t, VisAttrTexArgs a, uint32_t height, uint32_t maxBlocks);
+int launch_visibility_attributes_blocks(hipStream_t, VisAttrBlockArgs a, uint32_t height, uint32_t maxBlocks);
 int launch_texture_decode(hipStream_t, const void* blocks, uint32_t format, uint32_t width, uint32_t height, uint32_t levels, uint32_t* texels);
 // shade.hip
 int launch_shadow_fill(hipStream_t, uint8_t* shadow, const float* depth, uint32_t width, uint32_t height, int checkerboard, uint32_t maxBlocks);
@@ -87,6 +90,7 @@ int launch_shade_final(hipStream_t, ShadeFinalBloomArgs a, uint32_t height, uint
 // shadowtrace.hip, shadowtrace_alpha.hip, rttlas.hip
 int launch_shadow_trace(hipStream_t, ShadowTraceArgs a, int quality, uint32_t maxBlocks);
 int launch_shadow_trace_alpha(hipStream_t, ShadowTraceAlphaArgs a, uint32_t maxBlocks);
+int launch_shadow_trace_blocks(hipStream_t, ShadowTraceBlockArgs a, uint32_t maxBlocks);
 int launch_tlas_build(hipStream_t, void* scene, const TlasPlan& plan, const NvMeshDraw* draws, uint32_t drawCount);
 // bloom.hip
 int launch_bloom_extract(hipStream_t, const uint32_t* gbuffer0, uint32_t width, uint32_t height, uint32_t* bloom, const NvBloomDesc& desc, uint32_t maxBlocks);

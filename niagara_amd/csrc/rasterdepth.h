@@ -1,7 +1,7 @@
-// rasterdepth.h — the kernel of the depth rasteriser of the visible clusters as ONE text for its two entry points:
+// rasterdepth.h — the kernel of the depth rasteriser of the visible clusters as ONE text for its entry points:
 // rasterdepth.hip instantiates rasterdepth_kernel<CLIP, STABLE> (nv_rasterdepth) and rasterdepth_alpha.hip
 // rasterdepth_kernel<CLIP, STABLE, true, RasterAlphaArgs> (nv_rasterdepth_textured: covered samples of a post-pass launch also pass the
-// fragment's alpha test).  ALPHA only adds statements under `if constexpr (ALPHA)`, so the four kernels of nv_rasterdepth keep their
+// fragment's alpha test; rasterdepth_blocks.hip the same with RasterBlockArgs, over a block-resident texture set, §4.21).  ALPHA only adds statements under `if constexpr (ALPHA)`, so the four kernels of nv_rasterdepth keep their
 // instruction streams.  rasterdepth.hip's header describes the shape.
 #pragma once
 #include "raster.h"
@@ -36,11 +36,16 @@ struct RdAlphaSlot
 {
 	uint32_t mode; // RD_A_*; 0: albedo.a = diffuseFactor.a >= 0.5 (or NaN), or the launch does not test
 	float factor;  // diffuseFactor.a
-	TxDesc desc;   // RD_A_TEXTURED: the albedo texture's descriptor, accepted by tx_desc_ok
+	TxDesc desc;   // RD_A_TEXTURED: the albedo texture's descriptor, accepted by tx_desc_ok (the block set: TxBlockDesc's four words, by tx_block_desc_ok)
 };
 
+// the albedo texture's descriptor of a slot; false as fa_texture_desc.  (The block set's overload is rasterdepth_blocks.hip's.)
+NV_DEV bool rd_slot_desc(const VaTextures& tx, uint32_t id, TxDesc& d) { return fa_texture_desc(tx, id, d); }
+
 // The slot record of a draw's material.  Every load is behind the check that keeps it inside the caller's tables.
-NV_DEV void rd_alpha_slot(const RasterAlphaArgs& a, uint32_t materialIndex, uint32_t& mode, float& factor, uint4& desc)
+// ARGS = RasterAlphaArgs or RasterBlockArgs
+template <typename ARGS>
+NV_DEV void rd_alpha_slot(const ARGS& a, uint32_t materialIndex, uint32_t& mode, float& factor, uint4& desc)
 {
 	mode = RD_A_UNEVALUATED;
 	if (materialIndex >= a.materialCount)
@@ -52,7 +57,7 @@ NV_DEV void rd_alpha_slot(const RasterAlphaArgs& a, uint32_t materialIndex, uint
 	if (albedoTexture != 0u) // mesh.frag.glsl:63
 	{
 		TxDesc d;
-		if (fa_texture_desc(a.tx, albedoTexture, d))
+		if (rd_slot_desc(a.tx, albedoTexture, d))
 		{
 			mode = RD_A_TEXTURED;
 			desc = make_uint4(d.offset, d.width, d.height, d.levels);
@@ -63,10 +68,25 @@ NV_DEV void rd_alpha_slot(const RasterAlphaArgs& a, uint32_t materialIndex, uint
 	mode |= fa_discard(factor) ? RD_A_DROP_ALL : 0u;
 }
 
+// the slot's albedo texture at (u, v) from the decoded set (the block set's overload, over its bytes, is rasterdepth_blocks.hip's)
+NV_DEV TxF4 rd_texture(const uint32_t* texels, const TxDesc& desc, float u, float v, float dudx, float dvdx, float dudy, float dvdy)
+{
+	return tx_sample(texels, desc, u, v, dudx, dvdx, dudy, dvdy);
+}
+
+// What the kernel hands rd_sample_alpha as the texel buffer: the decoded set's words (the block set: its bytes, a specialisation of
+// rasterdepth_blocks.hip's)
+template <typename ARGS>
+struct RdTexels
+{
+	typedef uint32_t type;
+	static NV_DEV const type* of(const ARGS& a) { return a.tx.texels; }
+};
+
 // rd_sample with the fragment's alpha test between the coverage and the atomics: the attribute pass's arithmetic (fragalpha.h) for the
 // ORIGINAL triangle's corners (ca, cb, cc: stored order) at this pixel.  A dropped sample loads, compares and writes nothing.
-template <bool STABLE, class ID>
-NV_DEV void rd_sample_alpha(const RdTri& t, const RdAlphaSlot& m, const uint32_t* __restrict__ texels, const FaCorner& ca, const FaCorner& cb, const FaCorner& cc,
+template <bool STABLE, class ID, class TEXEL>
+NV_DEV void rd_sample_alpha(const RdTri& t, const RdAlphaSlot& m, const TEXEL* __restrict__ texels, const FaCorner& ca, const FaCorner& cb, const FaCorner& cc,
                             int32_t px, int32_t py, uint32_t W, float fw, float fh, uint32_t* __restrict__ depth, unsigned long long* __restrict__ vis, ID id,
                             unsigned long long& kept, unsigned long long& dropped, unsigned long long& unevaluated)
 {
@@ -83,7 +103,7 @@ NV_DEV void rd_sample_alpha(const RdTri& t, const RdAlphaSlot& m, const uint32_t
 		const float v = va_mix(l0, l1, l2, half_bits_to_float(ca.uv >> 16), half_bits_to_float(cb.uv >> 16), half_bits_to_float(cc.uv >> 16));
 		float dudx, dvdx, dudy, dvdy;
 		fa_uv_steps(ca, cb, cc, (uint32_t)px, (uint32_t)py, fx, fy, fw, fh, u, v, dudx, dvdx, dudy, dvdy);
-		const TxF4 c = tx_sample(texels, m.desc, u, v, dudx, dvdx, dudy, dvdy);
+		const TxF4 c = rd_texture(texels, m.desc, u, v, dudx, dvdx, dudy, dvdy);
 		drop = fa_discard(fa_alpha(m.factor, c.w));
 	}
 	if (!drop)
@@ -128,14 +148,14 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(ARGS a)
 	float4* attr = nullptr;
 	bool alphaOn = false;
 	float fw = 0.0f, fh = 0.0f;
-	const uint32_t* texels = nullptr;
+	const typename RdTexels<ARGS>::type* texels = nullptr;
 	unsigned long long dropped = 0, unevaluated = 0; // per lane
 	if constexpr (ALPHA)
 	{
 		attr = s_attr[wave];
 		alphaOn = bothFaces && a.materials != nullptr;
 		fw = (float)a.width, fh = (float)a.height;
-		texels = a.tx.texels;
+		texels = RdTexels<ARGS>::of(a);
 	}
 
 	uint32_t clusters = 0, triangles = 0; // wave-uniform

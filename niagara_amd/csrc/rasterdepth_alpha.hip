@@ -40,6 +40,13 @@ __global__ __launch_bounds__(256) void rasterdepth_alpha_totals_kernel(const uns
 		totals[threadIdx.x] += s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
 }
 
+// the launch of the kernel above, for nv_rasterdepth_blocks' launcher too
+int launch_raster_alpha_totals(hipStream_t stream, const unsigned long long* partials, uint32_t blocks, unsigned long long* totals)
+{
+	hipLaunchKernelGGL(rasterdepth_alpha_totals_kernel, dim3(1), dim3(256), 0, stream, partials, blocks, totals);
+	return (int)hipGetLastError();
+}
+
 int launch_rasterdepth_alpha(hipStream_t stream, const RasterAlphaArgs& a, uint32_t gridBlocks, bool nearClip, bool stableIds)
 {
 	gridBlocks = gridBlocks / 8 * RD_BLOCKS_PER_CU; // the caller passes 8 workgroups per CU, the size of `partials` and `alphaPartials`
@@ -58,10 +65,7 @@ int launch_rasterdepth_alpha(hipStream_t stream, const RasterAlphaArgs& a, uint3
 	if (e == hipSuccess && a.totals)
 		e = (hipError_t)launch_raster_totals(stream, a.partials, gridBlocks, a.totals);
 	if (e == hipSuccess && a.alphaTotals)
-	{
-		hipLaunchKernelGGL(rasterdepth_alpha_totals_kernel, dim3(1), dim3(256), 0, stream, a.alphaPartials, gridBlocks, a.alphaTotals);
-		e = hipGetLastError();
-	}
+		e = (hipError_t)launch_raster_alpha_totals(stream, a.alphaPartials, gridBlocks, a.alphaTotals);
 	return (int)e;
 }
 

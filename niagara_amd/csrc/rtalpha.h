@@ -101,22 +101,42 @@ NV_RT float rt_alpha_lod0(const uint32_t* texels, const TxDesc& t, float u, floa
 	return tx_lerp(tx_lerp(a00, a01, ax), tx_lerp(a10, a11, ax), ay);
 }
 
-// the alpha of an accepted triangle at the hit (shadow.comp.glsl:110-117); w0, w1, w2: the corners' packed texcoord bits tu | tv << 16
-NV_RT float rt_hit_alpha(const uint32_t* texels, const TxDesc& t, const RtHit& hit, uint32_t w0, uint32_t w1, uint32_t w2)
+// uv of an accepted triangle at the hit (shadow.comp.glsl:110-116); w0, w1, w2: the corners' packed texcoord bits tu | tv << 16
+struct RtUv
+{
+	float u, v;
+};
+NV_RT RtUv rt_hit_uv(const RtHit& hit, uint32_t w0, uint32_t w1, uint32_t w2)
 {
 	const float b1 = hit.V / hit.det, b2 = hit.W / hit.det;
 	const float b0 = (1.0f - b1) - b2;
 	const float u = (rt_half(w0 & 0xffffu) * b0 + rt_half(w1 & 0xffffu) * b1) + rt_half(w2 & 0xffffu) * b2;
 	const float v = (rt_half(w0 >> 16) * b0 + rt_half(w1 >> 16) * b1) + rt_half(w2 >> 16) * b2;
-	return rt_alpha_lod0(texels, t, u, v);
+	return RtUv{ u, v };
+}
+
+// the alpha of an accepted triangle at the hit (:117)
+NV_RT float rt_hit_alpha(const uint32_t* texels, const TxDesc& t, const RtHit& hit, uint32_t w0, uint32_t w1, uint32_t w2)
+{
+	const RtUv at = rt_hit_uv(hit, w0, w1, w2);
+	return rt_alpha_lod0(texels, t, at.u, at.v);
+}
+
+// what rt_occluded_alpha asks of its inputs, for the decoded set: the descriptor of "no texture yet" and the alpha at a hit.  The block set's
+// three (rt_alpha_texture, rt_alpha_none, rt_hit_alpha over RtAlphaBlockInputs) are shadowtrace_blocks.hip's.
+NV_RT TxDesc rt_alpha_none(const RtAlphaInputs&) { return TxDesc{ 0u, 1u, 1u, 1u }; }
+NV_RT float rt_hit_alpha(const RtAlphaInputs& in, const TxDesc& t, const RtHit& hit, uint32_t w0, uint32_t w1, uint32_t w2)
+{
+	return rt_hit_alpha(in.texels, t, hit, w0, w1, w2);
 }
 
 // rt_occluded(..., 1) whose hits are CONFIRMED: a triangle of a postPass == 0 instance always (FORCE_OPAQUE, src/scenert.cpp:516), one of a
 // postPass == 1 instance when its alpha is >= 0.5 (a NaN does not confirm).  The instance's texture is resolved once, where its BLAS is
 // entered; an instance without one confirms unconditionally and leaves at its first accepted triangle, as rt_occluded does.  The result is an OR
 // over the accepted triangles: it does not depend on the order of the walk.  The blob has passed nv_rt_scene_validate and carries
-// RT_FLAG_TEXCOORDS.
-NV_RT bool rt_occluded_alpha(const unsigned char* blob, const RtAlphaInputs& in, rt3 o, rt3 d, float tmin, float tmax)
+// RT_FLAG_TEXCOORDS.  INPUTS = RtAlphaInputs or RtAlphaBlockInputs: one text for both residencies of the texture set.
+template <typename INPUTS>
+NV_RT bool rt_occluded_alpha(const unsigned char* blob, const INPUTS& in, rt3 o, rt3 d, float tmin, float tmax)
 {
 	if (!(rt_finite(o.x) && rt_finite(o.y) && rt_finite(o.z) && rt_finite(d.x) && rt_finite(d.y) && rt_finite(d.z)))
 		return false;
@@ -150,7 +170,7 @@ NV_RT bool rt_occluded_alpha(const unsigned char* blob, const RtAlphaInputs& in,
 		const uint32_t postPass = rt_bits(i2.y);
 		if (postPass > 1u)
 			continue;
-		TxDesc tex = { 0u, 1u, 1u, 1u };
+		auto tex = rt_alpha_none(in);
 		const bool tested = postPass == 1u && rt_alpha_texture(in, rt_bits(i2.x), &tex);
 		const float position[3] = { i0.x, i0.y, i0.z }, orientation[4] = { i1.x, i1.y, i1.z, i1.w };
 		rt3 o2, d2;
@@ -189,7 +209,7 @@ NV_RT bool rt_occluded_alpha(const unsigned char* blob, const RtAlphaInputs& in,
 					continue;
 				if (!tested)
 					return true;
-				if (rt_hit_alpha(in.texels, tex, hit, rt_bits(v0.w), rt_bits(v1.w), rt_bits(v2.w)) >= 0.5f) // :118; a NaN does not confirm
+				if (rt_hit_alpha(in, tex, hit, rt_bits(v0.w), rt_bits(v1.w), rt_bits(v2.w)) >= 0.5f) // :118; a NaN does not confirm
 					return true;
 			}
 		}

@@ -38,6 +38,18 @@ struct RtAlphaInputs
 	uint32_t drawCount, materialCount, textureCount;
 };
 
+// the same over a block-resident texture set (shadowtrace_blocks.hip)
+struct TxBlockDesc; // texmath.h
+struct RtAlphaBlockInputs
+{
+	const NvMeshDraw* draws;
+	const NvMaterial* materials;
+	const TxBlockDesc* textures; // == NvTextureBlockDesc; entry 0 is "no texture"
+	const void* blocks;          // the DDS payloads, 16-byte aligned
+	uint64_t units16;
+	uint32_t drawCount, materialCount, textureCount;
+};
+
 struct __attribute__((aligned(16))) RtF4 // one 16-byte load
 {
 	float x, y, z, w;

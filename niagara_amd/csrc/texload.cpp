@@ -9,7 +9,8 @@
 #include "texmath.h"
 
 static_assert(sizeof(nv::TxDesc) == sizeof(NvTextureDesc), "TxDesc is NvTextureDesc");
-static_assert(NV_FORMAT_BC1 == nv::TX_BC1 && NV_FORMAT_BC2 == nv::TX_BC2 && NV_FORMAT_BC3 == nv::TX_BC3 && NV_FORMAT_BC7 == nv::TX_BC7, "formats");
+static_assert(sizeof(nv::TxBlockDesc) == sizeof(NvTextureBlockDesc), "TxBlockDesc is NvTextureBlockDesc");
+static_assert(NV_FORMAT_BC1 ==nv::TX_BC1 && NV_FORMAT_BC2 == nv::TX_BC2 && NV_FORMAT_BC3 == nv::TX_BC3 && NV_FORMAT_BC7 == nv::TX_BC7, "formats");
 static_assert(NV_TEXTURE_MAX_LEVELS == nv::TX_MAX_LEVELS, "levels");
 
 namespace
@@ -188,6 +189,69 @@ int nv_texture_sample_host(const NvTextureDesc* descs, uint32_t textureCount, co
 		return NV_EINVAL;
 	const nv::TxF4 c = nv::tx_sample(texels, d, uv[0], uv[1], duvdx[0], duvdx[1], duvdy[0], duvdy[1]);
 	out_rgba[0] = c.x, out_rgba[1] = c.y, out_rgba[2] = c.z, out_rgba[3] = c.w;
+	return NV_OK;
+}
+
+// ---- block-resident sets
+int nv_texture_block_layout(const NvDdsInfo* infos, uint32_t count, NvTextureBlockDesc* descs, uint64_t* units16)
+{
+	if ((count && !infos) || !descs || !units16)
+		return NV_EINVAL;
+	descs[0] = NvTextureBlockDesc{ 0u, 0u, 0u, 0u };
+	uint64_t units = 0;
+	for (uint32_t i = 0; i < count; ++i)
+	{
+		const NvDdsInfo& t = infos[i];
+		if (!shape_ok(t.width, t.height, t.levels))
+			return NV_EINVAL;
+		if (!nv::tx_decodable(t.format))
+			return t.format == NV_FORMAT_BC4 || t.format == NV_FORMAT_BC5 || t.format == NV_FORMAT_BC6H ? NV_ETEXFORMAT : NV_EINVAL;
+		descs[i + 1] = NvTextureBlockDesc{ (uint32_t)units, t.width, t.height, t.levels | t.format << 8 };
+		units += (nv::tx_chain_block_bytes(t.width, t.height, t.levels, t.format) + 15u) / 16u; // == payloadBytes rounded up (nv_dds_parse)
+		if (units >> 32)
+			return NV_EINVAL;
+	}
+	*units16 = units;
+	return NV_OK;
+}
+
+int nv_texture_block_fetch_host(const NvTextureBlockDesc* desc, const void* blocks, uint64_t units16, uint32_t level, uint32_t x, uint32_t y, uint32_t* rgba)
+{
+	if (!desc || !blocks || !rgba)
+		return NV_EINVAL;
+	const nv::TxBlockDesc d = { desc->offset, desc->width, desc->height, desc->levelsFormat };
+	if (!nv::tx_block_desc_ok(d, units16))
+		return NV_EINVAL;
+	const nv::TxBlockSource src = nv::tx_block_source(blocks, d);
+	if (level >= src.levels || x >= nv::tx_level_side(src.width, level) || y >= nv::tx_level_side(src.height, level))
+		return NV_EINVAL;
+	*rgba = src.fetch(level, x, y);
+	return NV_OK;
+}
+
+int nv_texture_block_sample_host(const NvTextureBlockDesc* descs, uint32_t textureCount, const void* blocks, uint64_t units16, uint32_t id,
+                                 const float uv[2], const float duvdx[2], const float duvdy[2], float out_rgba[4])
+{
+	if (!descs || !blocks || !uv || !duvdx || !duvdy || !out_rgba || id == 0u || id >= textureCount)
+		return NV_EINVAL;
+	const nv::TxBlockDesc d = { descs[id].offset, descs[id].width, descs[id].height, descs[id].levelsFormat };
+	if (!nv::tx_block_desc_ok(d, units16))
+		return NV_EINVAL;
+	const nv::TxF4 c = nv::tx_sample(nv::tx_block_source(blocks, d), uv[0], uv[1], duvdx[0], duvdx[1], duvdy[0], duvdy[1]);
+	out_rgba[0] = c.x, out_rgba[1] = c.y, out_rgba[2] = c.z, out_rgba[3] = c.w;
+	return NV_OK;
+}
+
+int nv_texture_block_decode_host(uint32_t format, uint64_t lo, uint64_t hi, uint32_t out_alpha[16], uint32_t out_split[16])
+{
+	if (!nv::tx_decodable(format) || !out_alpha || !out_split)
+		return NV_EINVAL;
+	const nv::TxBc7Header h = nv::tx_bc7_header(lo, hi);
+	for (uint32_t t = 0; t < 16u; ++t)
+	{
+		out_alpha[t] = nv::tx_decode_alpha(format, lo, hi, t);
+		out_split[t] = format == NV_FORMAT_BC7 ? nv::tx_bc7_texel_h(lo, hi, h, t) : nv::tx_decode_texel(format, lo, hi, t);
+	}
 	return NV_OK;
 }
 

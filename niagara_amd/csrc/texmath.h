@@ -1,7 +1,8 @@
 // texmath.h — the material textures of DESIGN.md §4.18 in ONE text that compiles for the device (hipcc) and for the host (g++): the decode of
 // one texel of a BC1 / BC2 / BC3 / BC7 block to RGBA8, the UNORM fetch, and `textureSampler` (niagara.cpp:627, resources.cpp:294-310: LINEAR min
 // and mag, mipmap LINEAR, REPEAT, lod 0..16) as a software sampler over a decoded RGBA8 mip chain.  texdecode.hip, visattr_tex.hip and the
-// host entry points of texload.cpp run the same text; tests/texture_ref.c restates it independently.
+// host entry points of texload.cpp run the same text; tests/texture_ref.c restates it independently.  The same sampler also runs over a texel
+// SOURCE, and TxBlockSource is the source that decodes each tap from its BC block (block-resident sets).
 //
 // Build with -ffp-contract=off: every fp32 operation of the sampler is one IEEE operation in the order written (log2 excepted, §4.18).
 //
@@ -15,8 +16,10 @@
 
 #if defined(__HIPCC__)
 #define NV_TX __host__ __device__ inline __attribute__((always_inline))
+#define NV_TXM __host__ __device__ inline __attribute__((always_inline)) // (a member function)
 #else
 #define NV_TX static inline
+#define NV_TXM inline
 #endif
 // constant data of both sides: the host reads the variable itself, device code gets a copy in the constant address space (a constexpr
 // variable is usable from device code as it stands; a __constant__ one would read as zeros on the host)
@@ -336,5 +339,328 @@ NV_TX TxF4 tx_sample(const uint32_t* texels, const TxDesc& t, float u, float v, 
 
 // textureLod(sampler2D, uv, 0) (shadow.comp.glsl:117 reads its .w): the same sampler at lambda = 0
 NV_TX TxF4 tx_sample_lod0(const uint32_t* texels, const TxDesc& t, float u, float v) { return tx_sample_lod(texels, t, u, v, 0.0f); }
+
+// ---- the same sampler over a texel SOURCE.  The functions above are the decoded source and keep their text; these overloads
+// run the same operations in the same order on the RGBA8 codes a source hands out, so a source that returns the codes of the decoded chain gives
+// the decoded sampler's bits.  SRC has width, height, levels (accepted by its own *_desc_ok), level_bases(d, d1, b0, b1) — where levels d and
+// d1 start, in the source's own unit — and quad(base, w, h, x0, x1, y0, y1, c00, c01, c10, c11): the codes of the four taps of one level.
+NV_TX TxF4 tx_unorm(uint32_t c)
+{
+	return TxF4{ (float)(c & 255u) / 255.0f, (float)(c >> 8 & 255u) / 255.0f, (float)(c >> 16 & 255u) / 255.0f, (float)(c >> 24) / 255.0f };
+}
+
+template <typename SRC>
+NV_TX TxF4 tx_bilinear(const SRC& src, uint64_t base, uint32_t w, uint32_t h, float u, float v)
+{
+	uint32_t x0, x1, y0, y1;
+	float ax, ay;
+	tx_axis(u, w, x0, x1, ax);
+	tx_axis(v, h, y0, y1, ay);
+	uint32_t c00, c01, c10, c11;
+	src.quad(base, w, h, x0, x1, y0, y1, c00, c01, c10, c11);
+	const TxF4 top = tx_lerp(tx_unorm(c00), tx_unorm(c01), ax);
+	const TxF4 bottom = tx_lerp(tx_unorm(c10), tx_unorm(c11), ax);
+	return tx_lerp(top, bottom, ay);
+}
+
+template <typename SRC>
+NV_TX TxF4 tx_sample_lod(const SRC& src, float u, float v, float lod)
+{
+	const float top = (float)(src.levels - 1u);
+	const float low = lod > 0.0f ? lod : 0.0f;
+	const float lambda = low < top ? low : top;
+	const float fl = __builtin_floorf(lambda);
+	const float f = lambda - fl;
+	uint32_t d = (uint32_t)tx_to_int(fl);
+	d = d < src.levels ? d : src.levels - 1u;
+	const uint32_t d1 = d + 1u < src.levels ? d + 1u : src.levels - 1u;
+	uint64_t b0, b1;
+	src.level_bases(d, d1, b0, b1);
+	const TxF4 lo = tx_bilinear(src, b0, tx_level_side(src.width, d), tx_level_side(src.height, d), u, v);
+	const TxF4 hi = tx_bilinear(src, b1, tx_level_side(src.width, d1), tx_level_side(src.height, d1), u, v);
+	return tx_lerp(lo, hi, f);
+}
+
+template <typename SRC>
+NV_TX TxF4 tx_sample(const SRC& src, float u, float v, float dudx, float dvdx, float dudy, float dvdy)
+{
+	return tx_sample_lod(src, u, v, tx_lambda(dudx, dvdx, dudy, dvdy, src.width, src.height, src.levels));
+}
+
+template <typename SRC>
+NV_TX TxF4 tx_sample_lod0(const SRC& src, float u, float v) { return tx_sample_lod(src, u, v, 0.0f); }
+
+#ifndef NV_TX_SAMPLER_ONLY
+// ---- the block source (§4.21): the set's buffer holds the DDS payloads verbatim and a tap decodes its texel from its block.
+
+// BC7 in two parts: what a block says once (the mode's fields, the bases of its bit fields, the partition word and its anchors) and what one
+// texel adds.  tx_bc7_texel above keeps its text; tx_bc7_texel_h(lo, hi, tx_bc7_header(lo, hi), t) is held equal to it on every fixture block.
+struct TxBc7Header
+{
+	uint32_t fields;  // ns | cb << 4 | ab << 8 | ib << 12 | ib2 << 16 | rotation << 20 | isb << 24 | (uniqueP ? 1 : sharedP ? 2 : 0) << 28; 0: RESERVED
+	uint32_t bases;   // colourBase | alphaBase << 8 | pBase << 16 | indexBase << 24 (each < 128)
+	uint32_t part;    // TX_P2 / TX_P3 of the partition (ns = 2 / 3)
+	uint32_t anchors; // a1 | a2 << 8 (16: no such anchor)
+};
+
+NV_TX TxBc7Header tx_bc7_header(uint64_t lo, uint64_t hi)
+{
+	const uint32_t byte0 = (uint32_t)lo & 255u;
+	if (byte0 == 0u)
+		return TxBc7Header{ 0u, 0u, 0u, 0u };
+	const uint32_t mode = (uint32_t)__builtin_ctz(byte0);
+	const uint32_t ns = tx_nibble(0x21112323u, mode), pb = tx_nibble(0x60006664u, mode), rb = tx_nibble(0x00220000u, mode);
+	const uint32_t cb = tx_nibble(0x57757564u, mode), ab = tx_nibble(0x57860000u, mode), ib = tx_nibble(0x24222233u, mode);
+	const uint32_t ib2 = tx_nibble(0x00230000u, mode);
+	const bool uniqueP = mode == 0u || mode == 3u || mode == 6u || mode == 7u, sharedP = mode == 1u;
+	const uint32_t ne = ns * 2u;
+	uint32_t pos = mode + 1u;
+	const uint32_t partition = tx_bits(lo, hi, pos, pb);
+	pos += pb;
+	const uint32_t rotation = tx_bits(lo, hi, pos, rb);
+	pos += rb;
+	const uint32_t isb = mode == 4u ? tx_bits(lo, hi, pos, 1u) : 0u;
+	pos += mode == 4u ? 1u : 0u;
+	const uint32_t colourBase = pos, alphaBase = colourBase + 3u * ne * cb, pBase = alphaBase + ne * ab;
+	const uint32_t indexBase = pBase + (uniqueP ? ne : sharedP ? 2u : 0u);
+	const uint32_t anchors = TX_ANCHOR[partition];
+	const uint32_t a1 = ns == 1u ? 16u : ns == 2u ? anchors & 15u : anchors >> 4 & 15u;
+	const uint32_t a2 = ns == 3u ? anchors >> 8 & 15u : 16u;
+	TxBc7Header h;
+	h.fields = ns | cb << 4 | ab << 8 | ib << 12 | ib2 << 16 | rotation << 20 | isb << 24 | (uniqueP ? 1u : sharedP ? 2u : 0u) << 28;
+	h.bases = colourBase | alphaBase << 8 | pBase << 16 | indexBase << 24;
+	h.part = ns == 2u ? (uint32_t)TX_P2[partition] : ns == 3u ? TX_P3[partition] : 0u;
+	h.anchors = a1 | a2 << 8;
+	return h;
+}
+
+// what both per-texel parts start with: the texel's subset, its two index weights and its endpoints' p-bits
+struct TxBc7Tap
+{
+	uint32_t e0, wc, wa, p0, p1;
+	bool hasP;
+};
+
+NV_TX TxBc7Tap tx_bc7_tap(uint64_t lo, uint64_t hi, const TxBc7Header& h, uint32_t t)
+{
+	const uint32_t ns = h.fields & 15u, ib = h.fields >> 12 & 15u, ib2 = h.fields >> 16 & 15u, isb = h.fields >> 24 & 1u, pkind = h.fields >> 28;
+	const uint32_t pBase = h.bases >> 16 & 255u, indexBase = h.bases >> 24;
+	const uint32_t a1 = h.anchors & 255u, a2 = h.anchors >> 8;
+	const uint32_t subset = ns == 1u ? 0u : ns == 2u ? h.part >> t & 1u : h.part >> (2u * t) & 3u;
+	const bool anchor = t == 0u || t == a1 || t == a2;
+	const uint32_t index = tx_bits(lo, hi, indexBase + t * ib - (t > 0u ? 1u : 0u) - (t > a1 ? 1u : 0u) - (t > a2 ? 1u : 0u), anchor ? ib - 1u : ib);
+	const uint32_t index2Base = indexBase + 16u * ib - ns;
+	const uint32_t index2 = ib2 ? tx_bits(lo, hi, index2Base + t * ib2 - (t > 0u ? 1u : 0u), t == 0u ? ib2 - 1u : ib2) : 0u;
+	const bool uniqueP = pkind == 1u, sharedP = pkind == 2u;
+	TxBc7Tap k;
+	k.e0 = subset * 2u;
+	k.p0 = uniqueP ? tx_bits(lo, hi, pBase + k.e0, 1u) : sharedP ? tx_bits(lo, hi, pBase + subset, 1u) : 0u;
+	k.p1 = uniqueP ? tx_bits(lo, hi, pBase + k.e0 + 1u, 1u) : k.p0;
+	k.hasP = uniqueP || sharedP;
+	const uint32_t wp = tx_bc7_weight(ib, index), ws = ib2 ? tx_bc7_weight(ib2, index2) : wp;
+	k.wc = isb ? ws : wp, k.wa = ib2 ? (isb ? wp : ws) : wp;
+	return k;
+}
+
+// texel t of the BC7 block {lo, hi} whose header is h: tx_bc7_texel(lo, hi, t)
+NV_TX uint32_t tx_bc7_texel_h(uint64_t lo, uint64_t hi, const TxBc7Header& h, uint32_t t)
+{
+	if (h.fields == 0u)
+		return 0u;
+	const uint32_t ne = (h.fields & 15u) * 2u, cb = h.fields >> 4 & 15u, ab = h.fields >> 8 & 15u, rotation = h.fields >> 20 & 15u;
+	const uint32_t colourBase = h.bases & 255u, alphaBase = h.bases >> 8 & 255u;
+	const TxBc7Tap k = tx_bc7_tap(lo, hi, h, t);
+	const uint32_t e0 = k.e0, e1 = e0 + 1u;
+	const uint32_t r0 = tx_bc7_endpoint(lo, hi, colourBase + e0 * cb, cb, k.hasP, k.p0), r1 = tx_bc7_endpoint(lo, hi, colourBase + e1 * cb, cb, k.hasP, k.p1);
+	const uint32_t g0 = tx_bc7_endpoint(lo, hi, colourBase + (ne + e0) * cb, cb, k.hasP, k.p0), g1 = tx_bc7_endpoint(lo, hi, colourBase + (ne + e1) * cb, cb, k.hasP, k.p1);
+	const uint32_t b0 = tx_bc7_endpoint(lo, hi, colourBase + (2u * ne + e0) * cb, cb, k.hasP, k.p0), b1 = tx_bc7_endpoint(lo, hi, colourBase + (2u * ne + e1) * cb, cb, k.hasP, k.p1);
+	const uint32_t al0 = ab ? tx_bc7_endpoint(lo, hi, alphaBase + e0 * ab, ab, k.hasP, k.p0) : 255u, al1 = ab ? tx_bc7_endpoint(lo, hi, alphaBase + e1 * ab, ab, k.hasP, k.p1) : 255u;
+	uint32_t r = tx_bc7_mix(r0, r1, k.wc), g = tx_bc7_mix(g0, g1, k.wc), b = tx_bc7_mix(b0, b1, k.wc), a = tx_bc7_mix(al0, al1, k.wa);
+	// (selects, where tx_bc7_texel branches: the rotation differs between the lanes of a wave)
+	const uint32_t s = a;
+	a = rotation == 1u ? r : rotation == 2u ? g : rotation == 3u ? b : a;
+	r = rotation == 1u ? s : r, g = rotation == 2u ? s : g, b = rotation == 3u ? s : b;
+	return (a & 255u) << 24 | (b & 255u) << 16 | (g & 255u) << 8 | (r & 255u);
+}
+
+// the alpha of texel t alone: tx_bc7_texel(lo, hi, t) >> 24.  Without rotation the alpha endpoints and the alpha weight; with it the colour
+// channel the rotation swapped into alpha, with the colour weight.
+NV_TX uint32_t tx_bc7_alpha_h(uint64_t lo, uint64_t hi, const TxBc7Header& h, uint32_t t)
+{
+	if (h.fields == 0u)
+		return 0u;
+	const uint32_t ne = (h.fields & 15u) * 2u, cb = h.fields >> 4 & 15u, ab = h.fields >> 8 & 15u, rotation = h.fields >> 20 & 15u;
+	const uint32_t colourBase = h.bases & 255u, alphaBase = h.bases >> 8 & 255u;
+	if (rotation == 0u && ab == 0u)
+		return 255u;
+	const TxBc7Tap k = tx_bc7_tap(lo, hi, h, t);
+	const uint32_t bits = rotation ? cb : ab;
+	const uint32_t at = rotation ? colourBase + ((rotation - 1u) * ne + k.e0) * cb : alphaBase + k.e0 * ab;
+	const uint32_t v0 = tx_bc7_endpoint(lo, hi, at, bits, k.hasP, k.p0), v1 = tx_bc7_endpoint(lo, hi, at + bits, bits, k.hasP, k.p1);
+	return tx_bc7_mix(v0, v1, rotation ? k.wc : k.wa) & 255u;
+}
+
+// the alpha of texel t of a block of a decodable format: tx_decode_texel(format, lo, hi, t) >> 24, for the two consumers that read .w only.
+// BC1: the index and the endpoint order; BC2 / BC3: the alpha half; BC7: tx_bc7_alpha_h.
+NV_TX uint32_t tx_decode_alpha(uint32_t format, uint64_t lo, uint64_t hi, uint32_t t)
+{
+	if (format == TX_BC1)
+	{
+		const uint32_t c0 = (uint32_t)lo & 0xffffu, c1 = (uint32_t)(lo >> 16) & 0xffffu, idx = (uint32_t)(lo >> (32u + 2u * t)) & 3u;
+		return idx == 3u && c0 <= c1 ? 0u : 255u;
+	}
+	if (format == TX_BC2)
+		return ((uint32_t)(lo >> (4u * t)) & 15u) * 17u;
+	if (format == TX_BC3)
+		return tx_bc3_alpha(lo, t);
+	return tx_bc7_alpha_h(lo, hi, tx_bc7_header(lo, hi), t);
+}
+
+// the descriptor of one block-resident texture (== NvTextureBlockDesc): its payload — level after level as the file has them — lies from byte
+// 16 * offset of the block buffer; levelsFormat = levels | format << 8
+struct TxBlockDesc
+{
+	uint32_t offset, width, height, levelsFormat;
+};
+
+NV_TX uint32_t tx_level_blocks_x(uint32_t width, uint32_t level) { return (tx_level_side(width, level) + 3u) >> 2; }
+
+// bytes of the first `levels` levels' blocks
+NV_TX uint64_t tx_chain_block_bytes(uint32_t width, uint32_t height, uint32_t levels, uint32_t format)
+{
+	uint64_t n = 0;
+	for (uint32_t l = 0; l < levels; ++l)
+		n += (uint64_t)tx_level_blocks_x(width, l) * tx_level_blocks_x(height, l);
+	return n * tx_block_bytes(format);
+}
+
+// the check in front of every block load: tx_desc_ok's shape limits, a decodable format, nothing but levels and format in levelsFormat, and
+// the whole chain (rounded up to 16 bytes, as the layout places it) inside the caller's `units16`, in 64 bits
+NV_TX bool tx_block_desc_ok(const TxBlockDesc& d, uint64_t units16)
+{
+	const uint32_t levels = d.levelsFormat & 255u, format = d.levelsFormat >> 8 & 255u;
+	if (d.width == 0u || d.height == 0u || d.width > TX_MAX_SIDE || d.height > TX_MAX_SIDE || levels == 0u || levels > TX_MAX_LEVELS)
+		return false;
+	if (!tx_decodable(format) || (d.levelsFormat >> 16) != 0u)
+		return false;
+	return (uint64_t)d.offset + (tx_chain_block_bytes(d.width, d.height, levels, format) + 15u) / 16u <= units16;
+}
+
+// one block in registers: its bytes (BC1: lo only) and, for BC7, its header
+struct TxBlock
+{
+	uint64_t lo, hi;
+	TxBc7Header h;
+};
+
+// the source: a texture tx_block_desc_ok accepted.  Bases are byte offsets into `blocks`.
+struct TxBlockSource
+{
+	const void* blocks;
+	uint64_t byteBase; // 16 * offset
+	uint32_t width, height, levels, format;
+
+	NV_TXM void level_bases(uint32_t d, uint32_t d1, uint64_t& b0, uint64_t& b1) const
+	{
+		const uint32_t bb = tx_block_bytes(format);
+		uint64_t base = byteBase;
+		b0 = base, b1 = base;
+		for (uint32_t l = 0; l < levels; ++l)
+		{
+			b0 = l == d ? base : b0;
+			b1 = l == d1 ? base : b1;
+			base += (uint64_t)tx_level_blocks_x(width, l) * tx_level_blocks_x(height, l) * bb;
+		}
+	}
+
+	// block `index` of the level at `base`: 8 bytes (BC1) or 16 bytes in one load, parsed once
+	NV_TXM TxBlock load(uint64_t base, uint32_t index) const
+	{
+		TxBlock b;
+		b.h = TxBc7Header{ 0u, 0u, 0u, 0u };
+		if (format == TX_BC1)
+		{
+			const unsigned char* p = static_cast<const unsigned char*>(blocks) + base + (uint64_t)index * 8u;
+#if defined(__HIP_DEVICE_COMPILE__)
+			p = static_cast<const unsigned char*>(__builtin_assume_aligned(p, 8));
+#endif
+			__builtin_memcpy(&b.lo, p, 8);
+			b.hi = 0u;
+		}
+		else
+		{
+			const unsigned char* p = static_cast<const unsigned char*>(blocks) + base + (uint64_t)index * 16u;
+#if defined(__HIP_DEVICE_COMPILE__)
+			p = static_cast<const unsigned char*>(__builtin_assume_aligned(p, 16)); // (the entry points refuse a misaligned buffer; offsets are 16-byte units)
+#endif
+			uint64_t q[2];
+			__builtin_memcpy(q, p, 16);
+			b.lo = q[0], b.hi = q[1];
+			if (format == TX_BC7)
+				b.h = tx_bc7_header(b.lo, b.hi);
+		}
+		return b;
+	}
+
+	NV_TXM uint32_t texel(const TxBlock& b, uint32_t t) const
+	{
+		return format == TX_BC7 ? tx_bc7_texel_h(b.lo, b.hi, b.h, t) : tx_decode_texel(format, b.lo, b.hi, t);
+	}
+	NV_TXM uint32_t alpha(const TxBlock& b, uint32_t t) const
+	{
+		return format == TX_BC7 ? tx_bc7_alpha_h(b.lo, b.hi, b.h, t) : tx_decode_alpha(format, b.lo, b.hi, t);
+	}
+
+	// The four taps of one level, each block loaded and parsed once: the walk goes 00 -> 01 -> 11 -> 10 when x0 and x1 share a block column
+	// and 00 -> 10 -> 11 -> 01 otherwise, so a step that changes the block is taken once per distinct block (1 for 9 of 16 texel positions,
+	// 2 across one edge, 4 at a corner); a step inside the block keeps it.  ALPHA: the codes' top bytes only, in bits 24-31.
+	template <bool ALPHA>
+	NV_TXM void walk(uint64_t base, uint32_t w, uint32_t x0, uint32_t x1, uint32_t y0, uint32_t y1, uint32_t& c00, uint32_t& c01, uint32_t& c10, uint32_t& c11) const
+	{
+		const uint32_t bw = (w + 3u) >> 2;
+		const bool xfirst = (x0 >> 2) == (x1 >> 2);
+		const uint32_t xa = xfirst ? x1 : x0, ya = xfirst ? y0 : y1; // the second tap
+		const uint32_t xb = xfirst ? x0 : x1, yb = xfirst ? y1 : y0; // the fourth
+		uint32_t cur = (y0 >> 2) * bw + (x0 >> 2);
+		TxBlock b = load(base, cur);
+		c00 = ALPHA ? alpha(b, (y0 & 3u) * 4u + (x0 & 3u)) << 24 : texel(b, (y0 & 3u) * 4u + (x0 & 3u));
+		uint32_t at = (ya >> 2) * bw + (xa >> 2);
+		if (at != cur)
+			b = load(base, at), cur = at;
+		const uint32_t ca = ALPHA ? alpha(b, (ya & 3u) * 4u + (xa & 3u)) << 24 : texel(b, (ya & 3u) * 4u + (xa & 3u));
+		at = (y1 >> 2) * bw + (x1 >> 2);
+		if (at != cur)
+			b = load(base, at), cur = at;
+		c11 = ALPHA ? alpha(b, (y1 & 3u) * 4u + (x1 & 3u)) << 24 : texel(b, (y1 & 3u) * 4u + (x1 & 3u));
+		at = (yb >> 2) * bw + (xb >> 2);
+		if (at != cur)
+			b = load(base, at), cur = at;
+		const uint32_t cb = ALPHA ? alpha(b, (yb & 3u) * 4u + (xb & 3u)) << 24 : texel(b, (yb & 3u) * 4u + (xb & 3u));
+		c01 = xfirst ? ca : cb;
+		c10 = xfirst ? cb : ca;
+	}
+
+	NV_TXM void quad(uint64_t base, uint32_t w, uint32_t h, uint32_t x0, uint32_t x1, uint32_t y0, uint32_t y1, uint32_t& c00, uint32_t& c01, uint32_t& c10, uint32_t& c11) const
+	{
+		(void)h;
+		walk<false>(base, w, x0, x1, y0, y1, c00, c01, c10, c11);
+	}
+
+	// the RGBA8 code of texel (x, y) of `level` (level < levels, x and y inside the level)
+	NV_TXM uint32_t fetch(uint32_t level, uint32_t x, uint32_t y) const
+	{
+		uint64_t b0, b1;
+		level_bases(level, level, b0, b1);
+		const TxBlock b = load(b0, (y >> 2) * tx_level_blocks_x(width, level) + (x >> 2));
+		return texel(b, (y & 3u) * 4u + (x & 3u));
+	}
+};
+
+// the source of a descriptor tx_block_desc_ok accepted
+NV_TX TxBlockSource tx_block_source(const void* blocks, const TxBlockDesc& d)
+{
+	return TxBlockSource{ blocks, (uint64_t)d.offset * 16u, d.width, d.height, d.levelsFormat & 255u, d.levelsFormat >> 8 & 255u };
+}
+#endif // NV_TX_SAMPLER_ONLY
 
 } // namespace nv

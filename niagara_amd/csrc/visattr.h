@@ -1,6 +1,7 @@
-// visattr.h — the attribute pass of the visibility buffer as ONE text for its two entry points: visattr.hip
+// visattr.h — the attribute pass of the visibility buffer as ONE text for its entry points: visattr.hip
 // instantiates visibility_attributes_kernel<RUNS> (nv_visibility_attributes: the fragment stage from the material's factors) and
-// visattr_tex.hip visibility_attributes_kernel<true, true, VisAttrTexArgs> (nv_visibility_attributes_textured: the complete fragment stage); the
+// visattr_tex.hip visibility_attributes_kernel<true, true, VisAttrTexArgs> (nv_visibility_attributes_textured: the complete fragment stage;
+// visattr_blocks.hip the same with VisAttrBlockArgs, over a block-resident texture set, §4.21); the
 // argument structs are args.h's.  Run detection, set-up, barycentrics and varyings are shared; TEX only adds statements under
 // `if constexpr (TEX)`, so the untextured kernels keep their instruction streams.
 #pragma once

@@ -255,6 +255,60 @@ def texture_sample_host(descs, texels, tex_id, uv, duvdx=(0.0, 0.0), duvdy=(0.0,
     return out
 
 
+def texture_block_layout(files):
+    """nv_texture_block_layout over DDS file images: (descs, units16, infos) — descs a layouts.TEXTUREBLOCKDESC array of len(files) + 1 entries
+    (entry 0 reserved), units16 the size of the set's block buffer in 16-byte units"""
+    from ._lib import DdsInfo
+    infos = (DdsInfo * max(1, len(files)))()
+    for i, data in enumerate(files):
+        infos[i] = _dds_info(data)
+    descs = np.zeros(len(files) + 1, L.TEXTUREBLOCKDESC)
+    units = C.c_uint64(0)
+    check(lib.nv_texture_block_layout(infos, len(files), _p(descs), C.byref(units)), "nv_texture_block_layout")
+    return descs, int(units.value), infos
+
+
+def texture_blocks_host(files):
+    """the block-resident form of a set on the CPU: (descs, blocks uint8 array of 16 * units16 bytes) — each file's payload copied verbatim to
+    byte 16 * offset"""
+    descs, units, infos = texture_block_layout(files)
+    blocks = np.zeros(max(1, units) * 16, np.uint8)
+    for i, data in enumerate(files):
+        at = int(descs[i + 1]["offset"]) * 16
+        payload = np.frombuffer(bytes(data), np.uint8)[infos[i].payloadOffset:]
+        blocks[at:at + len(payload)] = payload
+    return descs, blocks[:units * 16] if units else blocks[:0]
+
+
+def texture_block_fetch_host(desc, blocks, level, x, y, units16=None):
+    """the RGBA8 code of one texel decoded from its block (nv_texture_block_fetch_host)"""
+    d = np.ascontiguousarray(desc, L.TEXTUREBLOCKDESC).reshape(1)
+    blocks = np.ascontiguousarray(blocks, np.uint8)
+    out = np.zeros(1, np.uint32)
+    check(lib.nv_texture_block_fetch_host(_p(d), _p(blocks), len(blocks) // 16 if units16 is None else int(units16), int(level), int(x), int(y), _p(out)),
+          "nv_texture_block_fetch_host")
+    return int(out[0])
+
+
+def texture_block_sample_host(descs, blocks, tex_id, uv, duvdx=(0.0, 0.0), duvdy=(0.0, 0.0)):
+    """texture_sample_host over a block-resident set (nv_texture_block_sample_host): the same four float32, bit for bit"""
+    descs = np.ascontiguousarray(descs, L.TEXTUREBLOCKDESC)
+    blocks = np.ascontiguousarray(blocks, np.uint8)
+    a, b, c = (np.asarray(v, np.float32).copy() for v in (uv, duvdx, duvdy))
+    out = np.zeros(4, np.float32)
+    check(lib.nv_texture_block_sample_host(_p(descs), len(descs), _p(blocks), len(blocks) // 16, int(tex_id), _p(a), _p(b), _p(c), _p(out)),
+          "nv_texture_block_sample_host")
+    return out
+
+
+def texture_block_decode_host(fmt, lo, hi):
+    """(alpha, split): per texel of one block the alpha-only decode and the RGBA8 code through the BC7 header / per-texel split
+    (nv_texture_block_decode_host); 16 uint32 each"""
+    alpha, split = np.zeros(16, np.uint32), np.zeros(16, np.uint32)
+    check(lib.nv_texture_block_decode_host(int(fmt), int(lo), int(hi), _p(alpha), _p(split)), "nv_texture_block_decode_host")
+    return alpha, split
+
+
 def scenecache_read(path):
     """(info, meshes, meshlets, draws) of a niagara .cache file; the arrays are the raw struct arrays of the file"""
     info = scenecache_info(path)

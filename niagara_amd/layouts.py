@@ -58,6 +58,10 @@ BLOOM_MAX_LEVELS = 8
 TEXTUREDESC = np.dtype([("offset", "<u4"), ("width", "<u4"), ("height", "<u4"), ("levels", "<u4")])
 assert TEXTUREDESC.itemsize == 16
 TEXTURE_MAX_LEVELS = 15
+# NvTextureBlockDesc: one block-resident texture of a set — the offset of its DDS payload in the set's block buffer in 16-byte
+# units, level 0's size, and the level count (bits 0-7) with the format (layouts.FORMAT_*, bits 8-15).  Entry 0 is the reserved entry
+TEXTUREBLOCKDESC = np.dtype([("offset", "<u4"), ("width", "<u4"), ("height", "<u4"), ("levelsFormat", "<u4")])
+assert TEXTUREBLOCKDESC.itemsize == 16
 FORMAT_BC1, FORMAT_BC2, FORMAT_BC3, FORMAT_BC4, FORMAT_BC5, FORMAT_BC6H, FORMAT_BC7 = 1, 2, 3, 4, 5, 6, 7
 VIS_ID_BITS = 34  # the stable form of the visibility word: bits(z) << 34 | ((mvi << 7 | triangle) + 1)
 

@@ -242,6 +242,34 @@ class Context:
                                                     _ptr(gbuffer1), _ptr(totals4), _ptr(textures), int(texture_count), _ptr(texels), int(texel_words)),
               "nv_visibility_attributes_textured")
 
+    def rasterdepth_blocks(self, globals_, dcb, db, mlb, meshlet_data, vertices, cib, ccb, depth, width, height, visibility=None, totals4=None,
+                           materials=None, material_count=0, textures=None, texture_count=0, blocks=None, units16=0, alpha_totals2=None):
+        """rasterdepth_textured over a block-resident set (nv_rasterdepth_blocks): textures = a device table of
+        layouts.TEXTUREBLOCKDESC, blocks = texture_blocks' buffer of units16 16-byte units.  The same targets and counters bit for bit"""
+        check(lib.nv_rasterdepth_blocks(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(dcb), _ptr(db), _ptr(mlb), _ptr(meshlet_data),
+                                        _ptr(vertices), _ptr(cib), _ptr(ccb), _ptr(depth), int(width), int(height), _ptr(visibility), _ptr(totals4),
+                                        _ptr(materials), int(material_count), _ptr(textures), int(texture_count), _ptr(blocks), int(units16),
+                                        _ptr(alpha_totals2)), "nv_rasterdepth_blocks")
+
+    def shadow_trace_blocks(self, shadow_data, depth, shadow, width, height, quality, draws, draw_count, materials, material_count, textures,
+                            texture_count, blocks, units16):
+        """shadow_trace_textured over a block-resident set (nv_shadow_trace_blocks): the same mask byte for byte"""
+        check(lib.nv_shadow_trace_blocks(self.h, _stream(), C.c_void_p(shadow_data.ctypes.data) if shadow_data is not None else None, _ptr(depth),
+                                         _ptr(shadow), int(width), int(height), int(quality), _ptr(draws), int(draw_count), _ptr(materials),
+                                         int(material_count), _ptr(textures), int(texture_count), _ptr(blocks), int(units16)),
+              "nv_shadow_trace_blocks")
+
+    def visibility_attributes_blocks(self, globals_, records, width, height, db, draw_count, mlb, meshlet_count, meshlet_data, data_words, vertices,
+                                     vertex_count, materials, material_count, attributes=None, gbuffer0=None, gbuffer1=None, totals4=None,
+                                     textures=None, texture_count=0, blocks=None, units16=0):
+        """visibility_attributes_textured over a block-resident set (nv_visibility_attributes_blocks): textures = a device table
+        of layouts.TEXTUREBLOCKDESC (entry 0 reserved), blocks = texture_blocks' buffer of units16 16-byte units.  The same outputs bit for bit"""
+        check(lib.nv_visibility_attributes_blocks(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(records), int(width), int(height), _ptr(db),
+                                                  int(draw_count), _ptr(mlb), int(meshlet_count), _ptr(meshlet_data), int(data_words), _ptr(vertices),
+                                                  int(vertex_count), _ptr(materials), int(material_count), _ptr(attributes), _ptr(gbuffer0),
+                                                  _ptr(gbuffer1), _ptr(totals4), _ptr(textures), int(texture_count), _ptr(blocks), int(units16)),
+              "nv_visibility_attributes_blocks")
+
     # ---- material textures (DESIGN.md §4.18); the three host functions need no device and are host.py's
     dds_parse = staticmethod(host.dds_parse)
     texture_set_layout = staticmethod(host.texture_set_layout)
@@ -261,6 +289,15 @@ class Context:
             check(lib.nv_texture_decode(self.h, _stream(), _ptr(blocks), info.format, info.width, info.height, info.levels, _ptr(texels), C.byref(d)),
                   "nv_texture_decode")
         return descs, texels
+
+    texture_block_layout = staticmethod(host.texture_block_layout)
+
+    def texture_blocks(self, files):
+        """the block-resident form of a texture set: files = DDS file images (bytes).  Returns (descs: host
+        layouts.TEXTUREBLOCKDESC array with the reserved entry 0, blocks: uint8 device tensor of 16 * units16 bytes holding the payloads verbatim).
+        A plain copy: no kernel and no decode launch"""
+        descs, blocks = host.texture_blocks_host(files)
+        return descs, to_device(blocks if len(blocks) else np.zeros(16, np.uint8), self.device)
 
     def shadow_fill(self, shadow, depth, width, height, checkerboard):
         """shadowfill.comp.glsl in place (nv_shadow_fill): the texels of one checkerboard parity of the u8 shadow image become the
@@ -520,6 +557,11 @@ class VisibilityPipeline:
             if missing:
                 raise NvError("render_depth(textures=True) needs " + ", ".join(missing))
             mat = to_device(np.ascontiguousarray(materials, L.MATERIAL), self.ctx.device) if isinstance(materials, np.ndarray) else materials
+            if getattr(self, "texture_resident", "decoded") == "blocks":
+                self.ctx.rasterdepth_blocks(g, self.dcb, self.db, self.mlb, self.mdb, self.vb, self.cib, self.ccb, self.depth, self.depth_w, self.depth_h,
+                                            visibility, totals4, mat, mat.numel() * mat.element_size() // L.MATERIAL.itemsize, self.texture_table,
+                                            len(self.texture_descs), self.texture_block_buffer, self.texture_block_buffer.numel() // 16, alpha_totals2)
+                return
             self.ctx.rasterdepth_textured(g, self.dcb, self.db, self.mlb, self.mdb, self.vb, self.cib, self.ccb, self.depth, self.depth_w, self.depth_h,
                                           visibility, totals4, mat, mat.numel() * mat.element_size() // L.MATERIAL.itemsize, self.texture_table,
                                           len(self.texture_descs), self.texels, self.texels.numel(), alpha_totals2)
@@ -560,10 +602,14 @@ class VisibilityPipeline:
                                     out["records"], out["meshlet_seen"], out["draw_pixels"], out["totals"])
         return out
 
-    def set_textures(self, files):
+    def set_textures(self, files, resident="decoded"):
         """the scene's material textures, once per scene: a list of DDS file images (bytes) or paths, in texturePaths order — textures[i + 1]
-        is files[i], as niagara binds them (src/niagara.cpp:934).  Decoded on the device to RGBA8 mip chains; attributes(textures=True) samples
-        them"""
+        is files[i], as niagara binds them (src/niagara.cpp:934).  resident="decoded": decoded on the device to RGBA8 mip chains;
+        attributes(textures=True) samples them.  resident="blocks" (DESIGN.md §4.21): the DDS payloads stay as they are (4-8 x smaller) and
+        attributes(textures=True), render_depth / frame(textures=True) and shade(shadow="trace", textures=True) decode each tap from its block,
+        to the same bits.  texture_resident_bytes: the bytes of the set's device buffer"""
+        if resident not in ("decoded", "blocks"):
+            raise NvError("set_textures: resident is \"decoded\" or \"blocks\"")
         data = []
         for f in files:
             if isinstance(f, (bytes, bytearray, memoryview)):
@@ -571,7 +617,15 @@ class VisibilityPipeline:
             else:
                 with open(f, "rb") as fh:
                     data.append(fh.read())
-        descs, self.texels = self.ctx.texture_decode(data)
+        self.texture_resident = resident
+        if resident == "blocks":
+            descs, self.texture_block_buffer = self.ctx.texture_blocks(data)
+            self.texels = None
+            self.texture_resident_bytes = int(self.texture_block_buffer.numel()) if len(data) else 0
+        else:
+            descs, self.texels = self.ctx.texture_decode(data)
+            self.texture_block_buffer = None
+            self.texture_resident_bytes = int(self.texels.numel()) * 4 if len(data) else 0
         self.texture_descs = descs
         self.texture_table = to_device(descs, self.ctx.device)
 
@@ -604,6 +658,13 @@ class VisibilityPipeline:
                 raise NvError("attributes(textures=True) samples set_textures()'s set: call set_textures first")
             if mat is None:
                 raise NvError("attributes(textures=True) needs the material table")
+            if getattr(self, "texture_resident", "decoded") == "blocks":
+                self.ctx.visibility_attributes_blocks(g, records, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws, self.mlb,
+                                                      self.meshlet_count, self.mdb, self.mdb.numel() * self.mdb.element_size() // 4, self.vb,
+                                                      self.vertex_count, mat, n_mat, out["attributes"], out["gbuffer0"], out["gbuffer1"], out["totals"],
+                                                      self.texture_table, len(self.texture_descs), self.texture_block_buffer,
+                                                      self.texture_block_buffer.numel() // 16)
+                return out
             self.ctx.visibility_attributes_textured(g, records, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws, self.mlb,
                                                     self.meshlet_count, self.mdb, self.mdb.numel() * self.mdb.element_size() // 4, self.vb,
                                                     self.vertex_count, mat, n_mat, out["attributes"], out["gbuffer0"], out["gbuffer1"], out["totals"],
@@ -690,9 +751,14 @@ class VisibilityPipeline:
                 if missing:
                     raise NvError("shade(shadow=\"trace\", textures=True) needs " + ", ".join(missing))
                 mat = to_device(np.ascontiguousarray(materials, L.MATERIAL), dev) if isinstance(materials, np.ndarray) else materials
-                self.ctx.shadow_trace_textured(sh, self.depth, shadow, w, h, quality, self.db, self.draw_count, mat,
-                                               mat.numel() * mat.element_size() // L.MATERIAL.itemsize, self.texture_table, len(self.texture_descs),
-                                               self.texels, self.texels.numel())
+                if getattr(self, "texture_resident", "decoded") == "blocks":
+                    self.ctx.shadow_trace_blocks(sh, self.depth, shadow, w, h, quality, self.db, self.draw_count, mat,
+                                                 mat.numel() * mat.element_size() // L.MATERIAL.itemsize, self.texture_table, len(self.texture_descs),
+                                                 self.texture_block_buffer, self.texture_block_buffer.numel() // 16)
+                else:
+                    self.ctx.shadow_trace_textured(sh, self.depth, shadow, w, h, quality, self.db, self.draw_count, mat,
+                                                   mat.numel() * mat.element_size() // L.MATERIAL.itemsize, self.texture_table,
+                                                   len(self.texture_descs), self.texels, self.texels.numel())
             else:
                 self.ctx.shadow_trace(sh, self.depth, shadow, w, h, quality)
         if shadow is not None:

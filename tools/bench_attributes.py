@@ -15,7 +15,13 @@ timing loop: the run to put under a kernel trace.
 --textures gives the occluder scene synth.with_textures' four 1024 x 1024 BC1 textures (--texture-size) and times, on the same records,
 nv_visibility_attributes (outputs "all") and nv_visibility_attributes_textured, cache-cold: a buffer larger than the last-level cache is
 overwritten between the timed launches (one launch per sample, not a batch), as the untextured rows of this mode are too.  It then times
-nv_texture_decode per format on a 2048 x 2048 chain and prints GB/s of RGBA8 written."""
+nv_texture_decode per format on a 2048 x 2048 chain and prints GB/s of RGBA8 written.
+
+    python3 tools/bench_attributes.py --textures --blocks --sizes 1920x1080 [--random-format 7]
+
+--blocks adds nv_visibility_attributes_blocks over the block-resident form of the same set: its samples alternate with the decoded entry
+point's (decoded, blocks, decoded, ...; each cache-cold), the outputs of the two are compared byte for byte, and the resident bytes of both
+forms are printed.  --random-format fills the four maps with random blocks of one format (BC7: every mode), to time that format's decode."""
 import argparse
 import json
 import os
@@ -52,6 +58,9 @@ def main():
     ap.add_argument("--sizes", default="1920x1080,4096x4096")
     ap.add_argument("--textures", action="store_true")
     ap.add_argument("--texture-size", type=int, default=1024)
+    ap.add_argument("--blocks", action="store_true", help="with --textures: also time nv_visibility_attributes_blocks, alternating with the decoded entry point")
+    ap.add_argument("--random-format", type=int, default=0, choices=(0, 1, 2, 3, 7),
+                    help="with --textures: replace the four maps by random blocks of this NV_FORMAT_* (0: keep synth.with_textures' BC1 images)")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -135,6 +144,25 @@ def timed_cold(fn, repeats, flush):
     return dict(us_median=round(statistics.median(out), 2), us_min=round(min(out), 2), us_max=round(max(out), 2))
 
 
+def alternated_cold(fns, names, repeats, flush):
+    """timed_cold for several launches whose samples alternate (a, b, a, b, ...): a drift of the machine lands on all of them alike"""
+    import torch
+    for fn in fns:
+        fn()
+    out = {n: [] for n in names}
+    for k in range(repeats):
+        for n, fn in zip(names, fns):
+            flush.fill_(k)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            out[n].append(a.elapsed_time(b) * 1e3)
+    return {n + "_us": dict(median=round(statistics.median(v), 2), min=round(min(v), 2), max=round(max(v), 2)) for n, v in out.items()}
+
+
 def textures_mode(args, bounds):
     import ctypes as C
 
@@ -155,6 +183,21 @@ def textures_mode(args, bounds):
         v["tu"], v["tv"] = ((rng.random(len(v)) * 4).astype(np.float16).view(np.uint16) for _ in range(2))
         s["vertices"] = v
         s = synth.with_textures(s, size=args.texture_size)
+        if args.random_format:
+            fmt = args.random_format
+            side, levels = args.texture_size, args.texture_size.bit_length()
+            code = {1: 71, 2: 74, 3: 77, 7: 98}[fmt]
+            files = []
+            for _ in range(4):
+                head = np.zeros(37, np.uint32)
+                head[0], head[1], head[3], head[4], head[7], head[19], head[20], head[21] = 0x20534444, 124, side, side, levels, 32, 4, 0x30315844
+                head[32], head[33], head[35] = code, 3, 1
+                nbytes = sum(((max(1, side >> l) + 3) // 4) ** 2 for l in range(levels)) * (8 if fmt == 1 else 16)
+                payload = rng.integers(0, 256, nbytes, dtype=np.uint8)
+                if fmt == 7:
+                    payload[0::16] |= 1 << 7  # a mode bit in every first byte: modes 0..7 by the lowest set bit, none reserved
+                files.append(head.tobytes() + payload.tobytes())
+            s["textures"] = files
         mats = s["materials"]
         pipe = P.VisibilityPipeline(s["meshes"], s["meshlets"], s["draws"], s["viewport"], task_capacity=4096, cluster_capacity=4096 * 64, fused=True,
                                     vertices=v, meshlet_data=s["data"], stable_ids=True)
@@ -183,6 +226,23 @@ def textures_mode(args, bounds):
             rec = dict(what=name, scene="occluder, textured", viewport=[w, h], shaded=int(t[0]), unsampled=int(t[3]), texture_size=args.texture_size, cold=True)
             if not args.once:
                 rec.update(timed_cold(fn, args.repeats, flush))
+            print(json.dumps(rec), flush=True)
+        if args.blocks:
+            bdescs, blocks = c.texture_blocks(s["textures"])
+            btable = P.to_device(bdescs, dev)
+            decoded = rows[1][1]
+            block_fn = lambda: c.visibility_attributes_blocks(*args_, btable, len(bdescs), blocks, blocks.numel() // 16)
+            outs = []
+            for fn in (decoded, block_fn):
+                for t_ in (attr, g0, g1, tot):
+                    t_.zero_()
+                fn()
+                c.status()
+                outs.append([t_.cpu().numpy().tobytes() for t_ in (attr, g0, g1, tot)])
+            rec = dict(what="blocks against decoded", scene="occluder, textured", viewport=[w, h], texture_size=args.texture_size, random_format=args.random_format,
+                       outputs_equal=outs[0] == outs[1], decoded_bytes=int(texels.numel()) * 4, block_bytes=int(blocks.numel()), cold=True)
+            if not args.once:
+                rec.update(alternated_cold([decoded, block_fn], ["decoded", "blocks"], args.repeats, flush))
             print(json.dumps(rec), flush=True)
         if not args.once:
             side, levels = 2048, 12

@@ -348,12 +348,17 @@ def bench_alpha(iters):
         tex = dict(materials=mat, material_count=len(t["materials"]), textures=table, texture_count=len(descs), texels=texels, texel_words=texels.numel())
         plain = lambda totals=None: ctx.rasterdepth(g, *dev_args, depth, w, h, vis, totals)
         textured = lambda totals=None, a2=None: ctx.rasterdepth_textured(g, *dev_args, depth, w, h, vis, totals, alpha_totals2=a2, **tex)
+        # the same pass over the block-resident form of the set
+        bdescs, bbuf = ctx.texture_blocks(t["textures"])
+        btex = dict(materials=mat, material_count=len(t["materials"]), textures=P.to_device(bdescs, dev), texture_count=len(bdescs), blocks=bbuf,
+                    units16=bbuf.numel() // 16)
+        blocks = lambda totals=None, a2=None: ctx.rasterdepth_blocks(g, *dev_args, depth, w, h, vis, totals, alpha_totals2=a2, **btex)
 
         def reset():  # every launch starts from cleared targets
             depth.zero_()
             vis.zero_()
         ctx.set_option(P.NV_OPT_RASTER_SMALL_LIMIT, limit)
-        rounds = [(_time(plain, iters, reset), _time(textured, iters, reset)) for _ in range(3)]  # alternated
+        rounds = [(_time(plain, iters, reset), _time(textured, iters, reset), _time(blocks, iters, reset)) for _ in range(3)]  # alternated
         reset()
         plain(tot)
         p = [int(x) for x in tot.cpu().numpy()]
@@ -361,11 +366,19 @@ def bench_alpha(iters):
         reset()
         textured(tot, alpha)
         k, a2 = [int(x) for x in tot.cpu().numpy()], [int(x) for x in alpha.cpu().numpy()]
+        want = (depth.cpu().numpy().tobytes(), vis.cpu().numpy().tobytes(), k, a2)
+        tot.zero_()
+        alpha.zero_()
+        reset()
+        blocks(tot, alpha)
+        same = want == (depth.cpu().numpy().tobytes(), vis.cpu().numpy().tobytes(), [int(x) for x in tot.cpu().numpy()], [int(x) for x in alpha.cpu().numpy()])
         ctx.status()
         ctx.set_option(P.NV_OPT_RASTER_SMALL_LIMIT, 16)
         out[name] = dict(texture_side=size, small_limit=limit, clusters=p[0], triangles=p[1], rasterised=p[2], samples=p[3], kept=k[3], dropped=a2[0],
                          unevaluated=a2[1], plain_us_median=[r[0][0] for r in rounds], textured_us_median=[r[1][0] for r in rounds],
-                         plain_us_min=min(r[0][1] for r in rounds), textured_us_min=min(r[1][1] for r in rounds))
+                         blocks_us_median=[r[2][0] for r in rounds], plain_us_min=min(r[0][1] for r in rounds), textured_us_min=min(r[1][1] for r in rounds),
+                         blocks_us_min=min(r[2][1] for r in rounds), blocks_equal_textured=same, decoded_bytes=int(texels.numel()) * 4,
+                         block_bytes=int(bbuf.numel()))
 
     wall = synth.occluder_scene(viewport=(w, h), box_scale=3.0, meshlet_bounds=oracle.meshlet_bounds)
     case("wall_1080p_64", wall, wall["wall"], 64, 16)

@@ -215,11 +215,17 @@ def alpha_passes(args, s, pipe):
     runs = dict(opaque=lambda: ctx.shadow_trace(sd, pipe.depth, mask, w, h, 1),
                 alpha=lambda: ctx.shadow_trace_textured(sd, pipe.depth, mask, w, h, 1, db, len(draws), mat, len(t["materials"]), pipe.texture_table,
                                                         len(pipe.texture_descs), pipe.texels, pipe.texels.numel()))
+    if args.block_textures:  # the same trace over the block-resident form of the set, in the same alternation
+        bdescs, blocks = ctx.texture_blocks(t["textures"])
+        btable = P.to_device(bdescs, dev)
+        runs["blocks"] = lambda: ctx.shadow_trace_blocks(sd, pipe.depth, mask, w, h, 1, db, len(draws), mat, len(t["materials"]), btable, len(bdescs), blocks,
+                                                         blocks.numel() // 16)
     line = dict(size="%dx%d" % (w, h), covered=int((pipe.depth > 0).sum().item()), scene=host.rt_scene_stats(blob))
     times = {name: [] for name in runs}
     for name, run in runs.items():
         run()  # warm-up
         line["occluded_" + name] = int((mask == 0).sum().item())
+        line["mask_sum_" + name] = int(mask.sum(dtype=torch.int64).item())
     for _ in range(args.repeats):
         for name, run in runs.items():
             flush.add_(1)
@@ -244,6 +250,8 @@ def main():
     ap.add_argument("--bloom", action="store_true", help="two materials emit; run the bloom chain and final's bloom term")
     ap.add_argument("--textures", action="store_true", help="synth.with_textures' checker albedo, bump normal map, specular and emissive maps through "
                     "nv_visibility_attributes_textured (DESIGN.md §4.18)")
+    ap.add_argument("--block-textures", action="store_true", help="--textures with the set block-resident (set_textures(resident=\"blocks\"), DESIGN.md §4.21): every "
+                    "textured pass decodes its taps from the BC blocks; the image equals the decoded run's byte for byte")
     ap.add_argument("--traced-shadows", action="store_true", help="ray trace the shadow mask (the default stays the synthetic mask)")
     ap.add_argument("--alpha-shadows", action="store_true", help="--traced-shadows --textures with the wall in the post pass and a cut-out albedo: the trace "
                     "runs the alpha test (nv_shadow_trace_textured, DESIGN.md §4.19) and the wall's shadow has the checker's holes")
@@ -258,7 +266,7 @@ def main():
     args = ap.parse_args()
     if args.alpha_shadows:
         args.traced_shadows = args.textures = True
-    if args.alpha_coverage:
+    if args.alpha_coverage or args.block_textures:
         args.textures = True
     cutout = args.alpha_shadows or args.alpha_coverage
     if args.passes == "shadow_trace":
@@ -302,7 +310,7 @@ def main():
         draws["postPass"][s["wall"]] = 1  # both alpha tests see post-pass draws only (src/scenert.cpp:516, mesh.frag.glsl:88)
     pipe = P.VisibilityPipeline(s["meshes"], s["meshlets"], draws, (w, h), fused=True, vertices=v, meshlet_data=s["data"], stable_ids=True)
     if textures:
-        pipe.set_textures(textures)
+        pipe.set_textures(textures, resident="blocks" if args.block_textures else "decoded")
     x, y = np.meshgrid(np.arange(w), np.arange(h))
     r = np.hypot(x - 0.45 * w, y - 0.5 * h) / (0.3 * h)
     mask = np.clip(np.rint(255.0 * np.clip((r - 0.8) / 0.4, 0.0, 1.0)), 0, 255).astype(np.uint8)
