@@ -86,6 +86,34 @@ typedef struct NvMeshDraw
 	uint32_t materialIndex;
 } NvMeshDraw;
 
+/* src/scene.h:51-58; 32 B, align 16 */
+typedef struct NvLight
+{
+	float position[3];
+	float range;
+	float color[3];
+	float intensity;
+} NvLight;
+
+/* src/scene.h:119-124; 32 B; rotation is (x,y,z,w) like NvMeshDraw.orientation */
+typedef struct NvKeyframe
+{
+	float translation[3];
+	float scale;
+	float rotation[4];
+} NvKeyframe;
+
+/* src/scene.h:126-136; 24 B.  A negative drawIndex / lightIndex means "no such target" */
+typedef struct NvAnimation
+{
+	int32_t drawIndex;
+	int32_t lightIndex;
+	float startTime;
+	float period;
+	uint32_t keyframeOffset;
+	uint32_t keyframeCount;
+} NvAnimation;
+
 /* src/scene.h:68-75, src/shaders/mesh.h:53-60; 20 B */
 typedef struct NvMeshLod
 {
@@ -898,8 +926,9 @@ int nv_shade_final_bloom(nv_context* ctx, void* stream, const NvShadeData* shade
  * opacity micromaps.  For quality 0 the reference's outcome for non-opaque instances depends on its driver's
  * traversal order (one rayQueryProceedEXT, nothing confirmed): post-pass draws are defined as non-casters there.  Animation: when draws move,
  * nv_rt_tlas_build (below) rebuilds the TLAS on the device from the rewritten draw records, in place of the reference's
- * buildTLAS(MODE_UPDATE) (src/niagara.cpp:1396, :1482).  The mask does not depend on which TLAS is walked.  Not modelled: keyframe evaluation
- * (src/niagara.cpp:1386-1388: the caller writes the draws), a BLAS rebuild (geometry is static), lights. */
+ * buildTLAS(MODE_UPDATE) (src/niagara.cpp:1396, :1482).  The mask does not depend on which TLAS is walked.  The keyframe evaluation that
+ * rewrites them (src/niagara.cpp:1368-1409) is nv_animate_draws (below).  Not modelled: a BLAS rebuild (geometry is static),
+ * lights as shadow casters. */
 
 /* shadow.comp.glsl:26-35, src/niagara.cpp:269-278; 96 B (92 used), align 16.  inverseViewProjection is column-major */
 typedef struct NvShadowData
@@ -1027,6 +1056,61 @@ int nv_rt_tlas_build(nv_context* ctx, void* stream, const NvMeshDraw* d_draws, u
  * protocol of nv_rt_scene_build.  NV_EINVAL: no scene, a NULL bytes, a misaligned out, too little room. */
 int nv_rt_scene_download(nv_context* ctx, void* stream, void* out, uint64_t* bytes);
 
+/* ---- keyframe animation on the device (src/niagara.cpp:1368-1409; niagara_amd/csrc/animmath.h is the text) ----
+ * Per animation, in the reference's statements: index = (time - startTime) / period in fp64; index < 0 skips the animation; index =
+ * fmod(index, keyframeCount); index0 = int(index) % keyframeCount, index1 = (index0 + 1) % keyframeCount; t = float(index - floor(index)); with
+ * k0 / k1 = keyframes[keyframeOffset + index0 / index1]: position = mix(k0.translation, k1.translation, t), scale = mix(k0.scale, k1.scale, t),
+ * orientation = slerp(k0.rotation, k1.rotation, t) of the draw drawIndex >= 0, and position = mix(...) of the light lightIndex >= 0.
+ * mix(x, y, a) = x * (1 - a) + y * a.  slerp as glm publishes it: cosTheta = (x.w y.w + x.x y.x) + (x.y y.y + x.z y.z); z = cosTheta < 0 ? -y : y
+ * (and cosTheta = -cosTheta); cosTheta > 1 - FLT_EPSILON: the component-wise mix; otherwise (sin((1 - a) angle) x + sin(a angle) z) / sin(angle)
+ * with angle = acos(cosTheta).  Every fp32 operation is one IEEE operation in that order, no contraction: the device and nv_animate_draws_host
+ * compile the same text and agree bit for bit except in sinf / acosf, whose libraries differ (bound: DESIGN.md §4.22).  glm itself is not part
+ * of the reference's snapshot: the parity of mix / slerp is "glm's published definition", unpinned, as for nv_meshlet_bounds.
+ * Defined where the reference is not: an index that is not finite (time - startTime overflowing) skips the animation.
+ * ORDER: the reference applies the animations in array order, so of two that name the same draw (or light) the last one wins.  A lane per
+ * animation cannot keep that order, and loadScene never produces such a pair: duplicates are REFUSED by the validator instead. */
+enum
+{
+	NV_ANIM_OK = 0,
+	NV_ANIM_NO_KEYFRAMES = 1,    /* keyframeCount == 0 */
+	NV_ANIM_KEYFRAME_RANGE = 2,  /* keyframeOffset + keyframeCount beyond the table (or a keyframeCount above 2^31 - 1: int(index)) */
+	NV_ANIM_PERIOD = 3,          /* period not finite or <= 0 (the reference divides by it); startTime not finite */
+	NV_ANIM_DRAW_INDEX = 4,      /* drawIndex >= drawCount */
+	NV_ANIM_LIGHT_INDEX = 5,     /* lightIndex >= lightCount */
+	NV_ANIM_DUPLICATE_DRAW = 6,  /* two animations with the same drawIndex >= 0 */
+	NV_ANIM_DUPLICATE_LIGHT = 7  /* two animations with the same lightIndex >= 0 */
+};
+/* Host only.  NV_OK, or NV_EINVAL with *out_reason = the NV_ANIM_* reason and *out_index = the first animation it holds for (either may be
+ * NULL).  The reasons are tried in the order of the enum per animation, the duplicates after every animation has passed the others. */
+int nv_animation_validate_host(const NvAnimation* animations, uint32_t animationCount, uint32_t keyframeCount, uint32_t drawCount,
+                               uint32_t lightCount, uint32_t* out_reason, uint32_t* out_index);
+/* Host only: the time statements alone (tests), one sample per (animations[which[i]], times[i]), i < n: out_skipped[i] = 1 when the animation
+ * is skipped at that time, else 0 with the keyframe pair and t (the outputs of a skipped sample are left alone).  NV_EINVAL: a NULL pointer with
+ * n > 0, a non-finite time, a sampled animation with keyframeCount 0 or above 2^31 - 1. */
+int nv_animation_phase_host(const NvAnimation* animations, const uint32_t* which, const double* times, uint64_t n, uint8_t* out_skipped,
+                            uint32_t* out_index0, uint32_t* out_index1, float* out_t);
+/* The host twin of nv_animate_draws (the same text): validates like nv_upload_animations, then rewrites draws / lights in place.  draws or
+ * lights may be NULL (those targets are skipped; the indices are still validated against the counts).  NV_EINVAL: a refused table, a
+ * non-finite time, a NULL array with a non-zero animationCount. */
+int nv_animate_draws_host(double time, const NvAnimation* animations, uint32_t animationCount, const NvKeyframe* keyframes,
+                          uint32_t keyframeCount, NvMeshDraw* draws, uint32_t drawCount, NvLight* lights, uint32_t lightCount);
+/* Load time, like nv_rt_scene_upload (allocates, copies and synchronises the stream; a grow frees the old copies after a device synchronise,
+ * as nv_upload_draws does): validates the HOST arrays (nv_animation_validate_host; NV_EINVAL) and keeps context-owned device copies, the
+ * 24-byte records re-laid into one 16-byte and one 8-byte stream.  h_animations == NULL with animationCount 0 drops them (a non-NULL pointer
+ * with count 0 uploads an empty table).  drawCount / lightCount are the bounds
+ * the indices were checked against: nv_animate_draws refuses smaller buffers. */
+int nv_upload_animations(nv_context* ctx, void* stream, const NvAnimation* h_animations, uint32_t animationCount, const NvKeyframe* h_keyframes,
+                         uint32_t keyframeCount, uint32_t drawCount, uint32_t lightCount);
+/* One launch, a lane per uploaded animation: words 0-7 of the target draws of d_draws (two 16-byte stores; words 8-11 are never written) and,
+ * when d_lights is given, the 12 position bytes of the target lights (d_lights == NULL skips light targets).  When d_draws lies in the buffer
+ * registered by nv_upload_draws, the same lane also rewrites that draw's entry of the cull mirror (the statements of nv_update_draws, from the
+ * draw's own meshIndex word): no nv_update_draws is needed behind it.  Only enqueues (no allocation, no synchronisation: it can be captured);
+ * `time` travels BY VALUE in the launch, so a replayed graph repeats the captured time.  An uploaded table of 0 animations: NV_OK, nothing
+ * enqueued.  NV_EINVAL with nothing launched: a non-finite time, drawCount / lightCount (with d_lights) below the bounds given to
+ * nv_upload_animations, a NULL d_draws with a non-zero bound, d_draws not 16-byte aligned, d_lights not 4-byte aligned.  NV_ESTATE: no uploaded
+ * table (never uploaded, or dropped). */
+int nv_animate_draws(nv_context* ctx, void* stream, double time, NvMeshDraw* d_draws, uint32_t drawCount, NvLight* d_lights, uint32_t lightCount);
+
 /* ---- host helpers mirroring src/niagara.cpp / src/resources.cpp (no device work) ---- */
 uint32_t nv_previous_pow2(uint32_t v);                        /* src/niagara.cpp:439-447 */
 uint32_t nv_image_mip_levels(uint32_t width, uint32_t height); /* src/resources.cpp:280-292 */
@@ -1106,6 +1190,10 @@ int nv_scenecache_read(const char* path, const NvSceneCacheInfo* info, NvMesh* m
  * DDS file paths[i] names.  The records sit behind sections this reader does not size (lights, animations, opacity micromaps), so they are
  * taken from the END of the file; every record is NUL-terminated on return.  NV_EFORMAT: the file is too short to hold them. */
 int nv_scenecache_texture_paths(const char* path, const NvSceneCacheInfo* info, char (*paths)[256]);
+/* the info->lightCount Light, info->animationCount Animation and info->keyframeCount Keyframe records, three raw arrays that follow the draws
+ * directly (src/scenecache.cpp:183-186): they start at info->drawOffset + drawCount * 48.  Any destination may be NULL.  NV_EFORMAT: the
+ * file is too short to hold them; NV_EIO: it cannot be read. */
+int nv_scenecache_animations(const char* path, const NvSceneCacheInfo* info, NvLight* lights, NvAnimation* animations, NvKeyframe* keyframes);
 
 /* ---- verification probe (tests only): per-meshlet scalar intermediates of the cluster cull
  * (view-space centre xyz, radius, cone lhs, cone rhs, aabb[4], mip level, sampled depth,
@@ -1120,6 +1208,7 @@ int nv_probe_cluster_scalars(nv_context* ctx, void* stream, const NvCullData* cu
 
 static_assert(sizeof(NvMeshlet) == 24, "Meshlet layout (src/scene.h:10-23)");
 static_assert(sizeof(NvMeshDraw) == 48, "MeshDraw layout (src/scene.h:39-49)");
+static_assert(sizeof(NvLight) == 32 && sizeof(NvKeyframe) == 32 && sizeof(NvAnimation) == 24, "Light / Keyframe / Animation layouts (src/scene.h:51-58, 119-136)");
 static_assert(sizeof(NvMeshLod) == 20, "MeshLod layout (src/scene.h:68-75)");
 static_assert(sizeof(NvMesh) == 208, "Mesh layout (src/scene.h:77-93)");
 static_assert(offsetof(NvMesh, lods) == 48, "Mesh.lods offset");

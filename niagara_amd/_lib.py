@@ -161,6 +161,12 @@ _SIGS = {
     "nv_set_counts_sink": (_i, [_vp, _vp]),
     "nv_scenecache_info": (_i, [C.c_char_p, C.POINTER(SceneCacheInfo)]),
     "nv_scenecache_read": (_i, [C.c_char_p, C.POINTER(SceneCacheInfo), _vp, _vp, _vp]),
+    "nv_scenecache_animations": (_i, [C.c_char_p, C.POINTER(SceneCacheInfo), _vp, _vp, _vp]),
+    "nv_animation_validate_host": (_i, [_vp, _u32, _u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
+    "nv_animation_phase_host": (_i, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "nv_animate_draws_host": (_i, [C.c_double, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32]),
+    "nv_upload_animations": (_i, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32]),
+    "nv_animate_draws": (_i, [_vp, _vp, C.c_double, _vp, _u32, _vp, _u32]),
     "nv_probe_cluster_scalars": (_i, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, C.POINTER(PyramidDesc), _vp]),
 }
 EXPORTS = sorted(_SIGS)

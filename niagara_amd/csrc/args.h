@@ -436,4 +436,21 @@ struct RasterBlockArgs : RasterArgs
 	unsigned long long* __restrict__ alphaPartials; // library scratch: 2 counters per workgroup of the launch (set whenever alphaTotals is)
 };
 
+// nv_animate_draws (animmath.h, animate.hip).  No __restrict__ on the written buffers: the mirror instantiation reads the draw it wrote
+struct AnimateArgs
+{
+	double time;
+	const uint4* __restrict__ records;  // {drawIndex, lightIndex, keyframeOffset, keyframeCount} per animation (nv_upload_animations)
+	const float2* __restrict__ times;   // {startTime, period}
+	const float4* __restrict__ keyframes; // NvKeyframe as two 16-byte words
+	uint32_t count;
+	float4* draws;   // NvMeshDraw as three 16-byte words; words 8-11 are only read (mirror)
+	float* lights;   // NvLight as 8 floats; optional
+	// the mirror instantiation: the registered Mesh table and the mirror's streams at d_draws' first record
+	const NvMesh* __restrict__ meshes;
+	uint32_t meshCount;
+	float4* world;
+	uint2* scaleMesh;
+};
+
 } // namespace nv

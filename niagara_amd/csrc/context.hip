@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <math.h>
+#include <float.h>
 
 #include "../../include/niagara_vis.h"
 #include "cullmath.h"
@@ -116,6 +117,14 @@ struct nv_context
 	uint64_t rtSceneBytes;       // of the static blob (a dynamic reservation's allocation is rtPlan.bytes)
 	uint32_t rtSceneFlags;       // the uploaded blob's header flags (RT_FLAG_*): a rebuild and a re-housing keep them
 	nv::TlasPlan rtPlan;         // nv_rt_scene_reserve_dynamic: where the dynamic sections and the rebuild's scratch lie; maxDraws == 0 = static
+	// nv_upload_animations: the validated table as nv_animate_draws' kernel loads it (args.h AnimateArgs)
+	uint4* animRecords = nullptr;
+	float2* animTimes = nullptr;
+	float4* animKeyframes = nullptr;
+	uint32_t animCapacity, animKeyCapacity; // room, in animations / keyframes
+	uint32_t animCount;
+	uint32_t animDrawBound, animLightBound; // the counts the indices were validated against
+	bool animUploaded;
 };
 
 namespace
@@ -506,6 +515,9 @@ void nv_destroy(nv_context* ctx)
 	scene_release(ctx->scene);
 	scratch_reset(ctx->timing);
 	scratch_reset(ctx->rtScene);
+	scratch_reset(ctx->animRecords);
+	scratch_reset(ctx->animTimes);
+	scratch_reset(ctx->animKeyframes);
 	delete ctx->prof;
 	delete ctx;
 }
@@ -1507,6 +1519,108 @@ int nv_rt_tlas_build(nv_context* ctx, void* stream, const NvMeshDraw* d_draws, u
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	return nv::launch_tlas_build((hipStream_t)stream, ctx->rtScene, ctx->rtPlan, d_draws, drawCount);
+}
+
+// ---- keyframe animation on the device (animate.hip, animmath.h)
+// Load time, like nv_rt_scene_upload: validates, allocates, copies and synchronises.  Only a table nv_animation_validate_host accepts reaches
+// the device: every keyframe and target index the kernel follows stays inside the bounds kept here, and no two lanes share a target.
+int nv_upload_animations(nv_context* ctx, void* stream, const NvAnimation* h_animations, uint32_t animationCount, const NvKeyframe* h_keyframes,
+                         uint32_t keyframeCount, uint32_t drawCount, uint32_t lightCount)
+{
+	if (!ctx || (!h_animations && animationCount) || (!h_keyframes && keyframeCount))
+		return NV_EINVAL;
+	if (nv_animation_validate_host(h_animations, animationCount, keyframeCount, drawCount, lightCount, nullptr, nullptr) != NV_OK)
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	hipError_t e = hipStreamSynchronize((hipStream_t)stream); // a launch that still reads the old copy
+	if (e != hipSuccess)
+		return (int)e;
+	ctx->animUploaded = false;
+	ctx->animCount = 0;
+	if (!h_animations || animationCount > ctx->animCapacity || keyframeCount > ctx->animKeyCapacity)
+	{
+		if ((e = hipDeviceSynchronize()) != hipSuccess) // as nv_upload_draws: another stream may still be reading the old copies
+			return (int)e;
+		scratch_reset(ctx->animRecords);
+		scratch_reset(ctx->animTimes);
+		scratch_reset(ctx->animKeyframes);
+		ctx->animCapacity = ctx->animKeyCapacity = 0;
+		if (!h_animations)
+			return NV_OK; // dropped
+		if (scratch_alloc(&ctx->animRecords, (size_t)(animationCount ? animationCount : 1u) * sizeof(uint4)) != hipSuccess ||
+		    scratch_alloc(&ctx->animTimes, (size_t)(animationCount ? animationCount : 1u) * sizeof(float2)) != hipSuccess ||
+		    scratch_alloc(&ctx->animKeyframes, (size_t)(keyframeCount ? keyframeCount : 1u) * sizeof(NvKeyframe)) != hipSuccess)
+		{
+			scratch_reset(ctx->animRecords);
+			scratch_reset(ctx->animTimes);
+			scratch_reset(ctx->animKeyframes);
+			return NV_ENOMEM;
+		}
+		ctx->animCapacity = animationCount;
+		ctx->animKeyCapacity = keyframeCount;
+	}
+	if (animationCount)
+	{
+		// the 24-byte records as two streams a wave loads with one vector load each
+		std::vector<uint4> records;
+		std::vector<float2> times;
+		try
+		{
+			records.resize(animationCount);
+			times.resize(animationCount);
+		}
+		catch (...)
+		{
+			return NV_ENOMEM;
+		}
+		for (uint32_t i = 0; i < animationCount; ++i)
+		{
+			const NvAnimation& a = h_animations[i];
+			records[i] = make_uint4((uint32_t)a.drawIndex, (uint32_t)a.lightIndex, a.keyframeOffset, a.keyframeCount);
+			times[i] = make_float2(a.startTime, a.period);
+		}
+		if ((e = hipMemcpy(ctx->animRecords, records.data(), (size_t)animationCount * sizeof(uint4), hipMemcpyHostToDevice)) != hipSuccess ||
+		    (e = hipMemcpy(ctx->animTimes, times.data(), (size_t)animationCount * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess ||
+		    (e = hipMemcpy(ctx->animKeyframes, h_keyframes, (size_t)keyframeCount * sizeof(NvKeyframe), hipMemcpyHostToDevice)) != hipSuccess)
+			return (int)e;
+	}
+	ctx->animCount = animationCount;
+	ctx->animDrawBound = drawCount;
+	ctx->animLightBound = lightCount;
+	ctx->animUploaded = true;
+	return NV_OK;
+}
+
+// Only enqueues: one launch, `time` by value
+int nv_animate_draws(nv_context* ctx, void* stream, double time, NvMeshDraw* d_draws, uint32_t drawCount, NvLight* d_lights, uint32_t lightCount)
+{
+	if (!ctx || !(fabs(time) <= DBL_MAX))
+		return NV_EINVAL;
+	if (!ctx->animUploaded)
+		return NV_ESTATE;
+	if (drawCount < ctx->animDrawBound || (ctx->animDrawBound && !d_draws) || misaligned(d_draws, 15u) || (d_lights && lightCount < ctx->animLightBound) ||
+	    misaligned(d_lights, 3u))
+		return NV_EINVAL;
+	if (!ctx->animCount)
+		return NV_OK;
+	nv::AnimateArgs a;
+	a.time = time;
+	a.records = ctx->animRecords;
+	a.times = ctx->animTimes;
+	a.keyframes = ctx->animKeyframes;
+	a.count = ctx->animCount;
+	a.draws = reinterpret_cast<float4*>(d_draws);
+	a.lights = reinterpret_cast<float*>(d_lights);
+	// the draws the table can name lie in the registered buffer: the lane writes their mirror entries too (nv_update_draws' statements)
+	const nv_scene* sc = ctx->scene;
+	size_t base = 0;
+	const bool mirror = d_draws && sc->soaWorld && sc->drawsMeshes && registered_draw_range(sc, d_draws, ctx->animDrawBound, &base);
+	a.meshes = mirror ? sc->drawsMeshes : nullptr;
+	a.meshCount = mirror && sc->meshesFrom == sc->drawsMeshes ? sc->meshCount : 0u;
+	a.world = mirror ? sc->soaWorld + base : nullptr;
+	a.scaleMesh = mirror ? sc->soaScaleMesh + base : nullptr;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_animate((hipStream_t)stream, a, mirror);
 }
 
 // Test and tooling accessor (synchronises): the context's current scene as a canonical blob

@@ -20,6 +20,7 @@
 //                           draw): one LANE per output command; since round 6 fed by 16-byte records of the emitting draws that
 //                           K1 leaves per wave, so that K2 reads neither result bytes nor draw words nor the Mesh table.
 #include "cullmath.h"
+#include "drawmirror.h"
 #include "args.h"
 
 namespace nv
@@ -1283,15 +1284,9 @@ __global__ __launch_bounds__(256) void draw_split_kernel(const NvMeshDraw* __res
 	const float4* p = reinterpret_cast<const float4*>(draws + first + i);
 	const float4 d0 = p[0], d1 = p[1];
 	const uint4 ids = *reinterpret_cast<const uint4*>(p + 2);
-	// A draw the passes always skip (postPass mismatch, never visible) may carry any meshIndex: the decide kernel never reads
-	// its Mesh, so the mirror must not either.  With a registered table the index is clamped — the entry of such a
-	// draw is never used; a valid index is untouched.
-	const uint32_t mi = meshCount && ids.x >= meshCount ? 0u : ids.x;
-	const float4 cr = *reinterpret_cast<const float4*>(meshes + mi); // center.xyz, radius
-	const f3 r = rotate_quat(f3{ cr.x, cr.y, cr.z }, f3{ d1.x, d1.y, d1.z }, d1.w);
-	// the same three statements as sphere_center() (cullmath.h) before view_point()
-	world[first + i] = make_float4(r.x * d0.w + d0.x, r.y * d0.w + d0.y, r.z * d0.w + d0.z, cr.w * d0.w);
-	scaleMesh[first + i] = make_uint2(__float_as_uint(d0.w), ids.x);
+	const DrawMirrorEntry e = draw_mirror_entry(d0, d1, ids.x, meshes, meshCount); // drawmirror.h: nv_animate_draws writes the same entry
+	world[first + i] = e.world;
+	scaleMesh[first + i] = e.scaleMesh;
 	postPass[first + i] = ids.z;
 }
 

@@ -1,11 +1,16 @@
 // host.cpp — host-side helpers of the C ABI (no device work): the pieces of niagara's main() that prepare what the
 // cull passes consume.  Plain C++; arithmetic is fp32 in the order written so that results are reproducible.
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
+#include <vector>
+
 #include "../../include/niagara_vis.h"
+#include "animmath.h"
 
 extern "C" {
 
@@ -465,6 +470,164 @@ int nv_scenecache_read(const char* path, const NvSceneCacheInfo* info, NvMesh* m
 	}
 	fclose(f);
 	return rc;
+}
+
+// src/scenecache.cpp:183-186: Light, Animation and Keyframe records, raw, directly behind the draws
+int nv_scenecache_animations(const char* path, const NvSceneCacheInfo* info, NvLight* lights, NvAnimation* animations, NvKeyframe* keyframes)
+{
+	if (!path || !info)
+		return NV_EINVAL;
+	FILE* f = fopen(path, "rb");
+	if (!f)
+		return NV_EIO;
+	uint64_t fileSize = 0;
+	if (fseek(f, 0, SEEK_END) == 0)
+		fileSize = (uint64_t)ftell(f);
+	struct
+	{
+		void* dst;
+		uint64_t offset, bytes;
+	} parts[3] = { { lights, 0, (uint64_t)info->lightCount * sizeof(NvLight) },
+		           { animations, 0, (uint64_t)info->animationCount * sizeof(NvAnimation) },
+		           { keyframes, 0, (uint64_t)info->keyframeCount * sizeof(NvKeyframe) } };
+	uint64_t off = info->drawOffset + (uint64_t)info->drawCount * sizeof(NvMeshDraw);
+	for (int i = 0; i < 3; ++i)
+	{
+		parts[i].offset = off;
+		off += parts[i].bytes;
+	}
+	int rc = off > fileSize ? NV_EFORMAT : NV_OK; // truncated
+	for (int i = 0; i < 3 && rc == NV_OK; ++i)
+	{
+		if (!parts[i].dst || !parts[i].bytes)
+			continue;
+		if (fseek(f, (long)parts[i].offset, SEEK_SET) != 0 || fread(parts[i].dst, 1, parts[i].bytes, f) != parts[i].bytes)
+			rc = NV_EIO;
+	}
+	fclose(f);
+	return rc;
+}
+
+// ---- keyframe animation (src/niagara.cpp:1368-1409; animmath.h is the text) ----
+int nv_animation_validate_host(const NvAnimation* animations, uint32_t animationCount, uint32_t keyframeCount, uint32_t drawCount, uint32_t lightCount,
+                               uint32_t* out_reason, uint32_t* out_index)
+{
+	uint32_t reason = NV_ANIM_OK, at = 0;
+	if (!animations && animationCount)
+		return NV_EINVAL;
+	for (uint32_t i = 0; i < animationCount && reason == NV_ANIM_OK; ++i)
+	{
+		const NvAnimation& a = animations[i];
+		if (a.keyframeCount == 0)
+			reason = NV_ANIM_NO_KEYFRAMES;
+		else if (a.keyframeCount > 0x7fffffffu || a.keyframeOffset > keyframeCount || a.keyframeCount > keyframeCount - a.keyframeOffset)
+			reason = NV_ANIM_KEYFRAME_RANGE;
+		else if (!(a.period > 0.0f) || !(a.period <= FLT_MAX) || !(fabsf(a.startTime) <= FLT_MAX))
+			reason = NV_ANIM_PERIOD;
+		else if (a.drawIndex >= 0 && (uint32_t)a.drawIndex >= drawCount)
+			reason = NV_ANIM_DRAW_INDEX;
+		else if (a.lightIndex >= 0 && (uint32_t)a.lightIndex >= lightCount)
+			reason = NV_ANIM_LIGHT_INDEX;
+		at = i;
+	}
+	// duplicates: the smallest animation index that repeats an earlier one's target (sorted by (target, animation))
+	for (int pass = 0; pass < 2 && reason == NV_ANIM_OK; ++pass)
+	{
+		std::vector<uint64_t> keys;
+		try
+		{
+			for (uint32_t i = 0; i < animationCount; ++i)
+			{
+				const int32_t target = pass ? animations[i].lightIndex : animations[i].drawIndex;
+				if (target >= 0)
+					keys.push_back((uint64_t)(uint32_t)target << 32 | i);
+			}
+		}
+		catch (...)
+		{
+			return NV_ENOMEM;
+		}
+		std::sort(keys.begin(), keys.end());
+		uint32_t first = 0xffffffffu;
+		for (size_t k = 1; k < keys.size(); ++k)
+			if (keys[k] >> 32 == keys[k - 1] >> 32 && (uint32_t)keys[k] < first)
+				first = (uint32_t)keys[k];
+		if (first != 0xffffffffu)
+		{
+			reason = pass ? NV_ANIM_DUPLICATE_LIGHT : NV_ANIM_DUPLICATE_DRAW;
+			at = first;
+		}
+	}
+	if (out_reason)
+		*out_reason = reason;
+	if (out_index)
+		*out_index = reason == NV_ANIM_OK ? 0u : at;
+	return reason == NV_ANIM_OK ? NV_OK : NV_EINVAL;
+}
+
+int nv_animation_phase_host(const NvAnimation* animations, const uint32_t* which, const double* times, uint64_t n, uint8_t* out_skipped, uint32_t* out_index0,
+                            uint32_t* out_index1, float* out_t)
+{
+	if (n && (!animations || !which || !times || !out_skipped || !out_index0 || !out_index1 || !out_t))
+		return NV_EINVAL;
+	for (uint64_t i = 0; i < n; ++i)
+	{
+		const NvAnimation& a = animations[which[i]];
+		if (!(fabs(times[i]) <= DBL_MAX) || a.keyframeCount == 0 || a.keyframeCount > 0x7fffffffu)
+			return NV_EINVAL;
+		nv::AnimPhase ph;
+		out_skipped[i] = nv::anim_phase(times[i], a.startTime, a.period, a.keyframeCount, ph) ? 0 : 1;
+		if (out_skipped[i])
+			continue;
+		out_index0[i] = ph.index0;
+		out_index1[i] = ph.index1;
+		out_t[i] = ph.t;
+	}
+	return NV_OK;
+}
+
+int nv_animate_draws_host(double time, const NvAnimation* animations, uint32_t animationCount, const NvKeyframe* keyframes, uint32_t keyframeCount,
+                          NvMeshDraw* draws, uint32_t drawCount, NvLight* lights, uint32_t lightCount)
+{
+	if (!(fabs(time) <= DBL_MAX) || (animationCount && (!animations || !keyframes)))
+		return NV_EINVAL;
+	const int rc = nv_animation_validate_host(animations, animationCount, keyframeCount, drawCount, lightCount, nullptr, nullptr);
+	if (rc != NV_OK)
+		return rc;
+	for (uint32_t i = 0; i < animationCount; ++i)
+	{
+		const NvAnimation& a = animations[i];
+		nv::AnimPhase ph;
+		if (!nv::anim_phase(time, a.startTime, a.period, a.keyframeCount, ph))
+			continue;
+		const NvKeyframe& k0 = keyframes[(size_t)a.keyframeOffset + ph.index0];
+		const NvKeyframe& k1 = keyframes[(size_t)a.keyframeOffset + ph.index1];
+		const float t = ph.t;
+		const float px = nv::anim_mix(k0.translation[0], k1.translation[0], t), py = nv::anim_mix(k0.translation[1], k1.translation[1], t),
+		            pz = nv::anim_mix(k0.translation[2], k1.translation[2], t);
+		if (a.drawIndex >= 0 && draws)
+		{
+			NvMeshDraw& d = draws[a.drawIndex];
+			const nv::AnimQuat q = nv::anim_slerp(nv::AnimQuat{ k0.rotation[0], k0.rotation[1], k0.rotation[2], k0.rotation[3] },
+			                                      nv::AnimQuat{ k1.rotation[0], k1.rotation[1], k1.rotation[2], k1.rotation[3] }, t);
+			d.position[0] = px;
+			d.position[1] = py;
+			d.position[2] = pz;
+			d.scale = nv::anim_mix(k0.scale, k1.scale, t);
+			d.orientation[0] = q.x;
+			d.orientation[1] = q.y;
+			d.orientation[2] = q.z;
+			d.orientation[3] = q.w;
+		}
+		if (a.lightIndex >= 0 && lights)
+		{
+			NvLight& l = lights[a.lightIndex];
+			l.position[0] = px;
+			l.position[1] = py;
+			l.position[2] = pz;
+		}
+	}
+	return NV_OK;
 }
 
 // contiguous ranges, remainder spread over the first ranks

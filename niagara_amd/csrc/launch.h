@@ -92,6 +92,8 @@ int launch_shadow_trace(hipStream_t, ShadowTraceArgs a, int quality, uint32_t ma
 int launch_shadow_trace_alpha(hipStream_t, ShadowTraceAlphaArgs a, uint32_t maxBlocks);
 int launch_shadow_trace_blocks(hipStream_t, ShadowTraceBlockArgs a, uint32_t maxBlocks);
 int launch_tlas_build(hipStream_t, void* scene, const TlasPlan& plan, const NvMeshDraw* draws, uint32_t drawCount);
+// animate.hip
+int launch_animate(hipStream_t, const AnimateArgs& a, bool mirror);
 // bloom.hip
 int launch_bloom_extract(hipStream_t, const uint32_t* gbuffer0, uint32_t width, uint32_t height, uint32_t* bloom, const NvBloomDesc& desc, uint32_t maxBlocks);
 int launch_bloom_downsample(hipStream_t, uint32_t* bloom, const NvBloomDesc& desc, uint32_t level);

@@ -319,6 +319,58 @@ def scenecache_read(path):
     return info, meshes, meshlets, draws
 
 
+def scenecache_animations(path):
+    """(lights, animations, keyframes) of a niagara .cache file (layouts.LIGHT / ANIMATION / KEYFRAME): the three raw arrays behind its
+    draws (nv_scenecache_animations)"""
+    info = scenecache_info(path)
+    lights = np.zeros(info.lightCount, dtype=L.LIGHT)
+    animations = np.zeros(info.animationCount, dtype=L.ANIMATION)
+    keyframes = np.zeros(info.keyframeCount, dtype=L.KEYFRAME)
+    check(lib.nv_scenecache_animations(os.fsencode(path), C.byref(info), _p(lights), _p(animations), _p(keyframes)), "nv_scenecache_animations")
+    return lights, animations, keyframes
+
+
+ANIM_REASONS = ("ok", "no_keyframes", "keyframe_range", "period", "draw_index", "light_index", "duplicate_draw", "duplicate_light")  # NV_ANIM_*
+
+
+def animation_validate(animations, keyframe_count, draw_count, light_count=0):
+    """(reason, index) of nv_animation_validate_host: reason is one of ANIM_REASONS ("ok" for a table nv_upload_animations accepts), index the
+    first animation it holds for"""
+    a = np.ascontiguousarray(animations, L.ANIMATION)
+    reason, index = C.c_uint32(0), C.c_uint32(0)
+    rc = lib.nv_animation_validate_host(_p(a), len(a), int(keyframe_count), int(draw_count), int(light_count), C.byref(reason), C.byref(index))
+    if rc != 0 and reason.value == 0:
+        check(rc, "nv_animation_validate_host")
+    return ANIM_REASONS[reason.value], index.value
+
+
+def animation_phase(animations, which, times):
+    """the time statements of nv_animate_draws alone (nv_animation_phase_host), one sample per (animations[which[i]], times[i]): (skipped bool,
+    index0, index1, t float32); the entries of a skipped sample are zero"""
+    a = np.ascontiguousarray(animations, L.ANIMATION)
+    which, times = np.ascontiguousarray(which, np.uint32), np.ascontiguousarray(times, np.float64)
+    if len(which) != len(times) or (len(which) and int(which.max()) >= len(a)):
+        raise ValueError("animation_phase: one time per sampled animation, every index inside the table")
+    n = len(which)
+    skipped, i0, i1, t = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.float32)
+    check(lib.nv_animation_phase_host(_p(a), _p(which), _p(times), n, _p(skipped), _p(i0), _p(i1), _p(t)), "nv_animation_phase_host")
+    return skipped.astype(bool), i0, i1, t
+
+
+def animate_draws_host(time, animations, keyframes, draws, lights=None, draw_count=None, light_count=None):
+    """the host twin of Context.animate_draws (nv_animate_draws_host, the kernel's text): rewrites `draws` (layouts.MESHDRAW, or None) and
+    `lights` (layouts.LIGHT, or None) IN PLACE.  draw_count / light_count: the bounds the indices are validated against where the array is
+    None (its targets are then skipped)"""
+    a = np.ascontiguousarray(animations, L.ANIMATION)
+    k = np.ascontiguousarray(keyframes, L.KEYFRAME)
+    for arr, dt in ((draws, L.MESHDRAW), (lights, L.LIGHT)):
+        if arr is not None and not (arr.dtype == dt and arr.flags.c_contiguous and arr.flags.writeable):
+            raise ValueError("animate_draws_host rewrites its arrays in place: contiguous, writeable arrays of the layout's dtype")
+    check(lib.nv_animate_draws_host(float(time), _p(a), len(a), _p(k), len(k), None if draws is None else _p(draws), int(draw_count or 0) if draws is None else len(draws),
+                                    None if lights is None else _p(lights), int(light_count or 0) if lights is None else len(lights)),
+          "nv_animate_draws_host")
+
+
 def mesh_bounds(positions):
     """Mesh.center / Mesh.radius of src/scene.cpp:207-220 over an (n, 3) float32 array"""
     pos = np.ascontiguousarray(positions, np.float32)

@@ -10,6 +10,11 @@ MESHLET = np.dtype([("center", "<u2", 3), ("radius", "<u2"), ("cone_axis", "i1",
                     ("shortRefs", "u1"), ("padding", "u1")])
 MESHDRAW = np.dtype([("position", "<f4", 3), ("scale", "<f4"), ("orientation", "<f4", 4), ("meshIndex", "<u4"),
                      ("meshletVisibilityOffset", "<u4"), ("postPass", "<u4"), ("materialIndex", "<u4")])
+# src/scene.h:51-58, 119-136: the animation path (nv_upload_animations / nv_animate_draws); rotation is (x, y, z, w) like MESHDRAW.orientation
+LIGHT = np.dtype([("position", "<f4", 3), ("range", "<f4"), ("color", "<f4", 3), ("intensity", "<f4")])
+KEYFRAME = np.dtype([("translation", "<f4", 3), ("scale", "<f4"), ("rotation", "<f4", 4)])
+ANIMATION = np.dtype([("drawIndex", "<i4"), ("lightIndex", "<i4"), ("startTime", "<f4"), ("period", "<f4"), ("keyframeOffset", "<u4"),
+                      ("keyframeCount", "<u4")])
 MESHLOD = np.dtype([("indexOffset", "<u4"), ("indexCount", "<u4"), ("meshletOffset", "<u4"), ("meshletCount", "<u4"),
                     ("error", "<f4")])
 MESH = np.dtype([("center", "<f4", 3), ("radius", "<f4"), ("vertexOffset", "<u4"), ("vertexCount", "<u4"),

@@ -123,6 +123,27 @@ class Context:
         """re-transposes draws [first, first + count) after the caller rewrote them (animation, src/niagara.cpp:1385-1391)"""
         check(lib.nv_update_draws(self.h, _stream(), _ptr(db), first, count), "nv_update_draws")
 
+    def upload_animations(self, animations, keyframes, draw_count, light_count=0):
+        """validate the host tables (layouts.ANIMATION / KEYFRAME; host.animation_validate names a refusal's reason) and keep context-owned
+        device copies for animate_draws (nv_upload_animations: load time, synchronises).  draw_count / light_count: the bounds the target
+        indices are checked against.  animations=None drops the copies"""
+        if animations is None:
+            check(lib.nv_upload_animations(self.h, _stream(), None, 0, None, 0, 0, 0), "nv_upload_animations")
+            return
+        a = np.ascontiguousarray(animations, L.ANIMATION)
+        k = np.ascontiguousarray(keyframes, L.KEYFRAME)
+        keep = np.zeros(1, L.KEYFRAME)  # an empty table is still a table: a non-NULL pointer with count 0
+        check(lib.nv_upload_animations(self.h, _stream(), C.c_void_p(a.ctypes.data if len(a) else keep.ctypes.data), len(a),
+                                       C.c_void_p(k.ctypes.data if len(k) else keep.ctypes.data), len(k), int(draw_count), int(light_count)),
+              "nv_upload_animations")
+
+    def animate_draws(self, time, db, draw_count, lights=None, light_count=0):
+        """src/niagara.cpp:1368-1409 on the device (nv_animate_draws): evaluates the uploaded animations at `time` and rewrites position, scale
+        and orientation of their target draws in the device buffer `db` (and the position of their target lights in `lights`, a device buffer
+        of layouts.LIGHT, when given); when `db` is the buffer registered by upload_draws the cull mirror is rewritten in the same launch.  One
+        launch, can be captured; `time` travels by value"""
+        check(lib.nv_animate_draws(self.h, _stream(), float(time), _ptr(db), int(draw_count), _ptr(lights), int(light_count)), "nv_animate_draws")
+
     def drawcull(self, cull, late, task, db, mb, dcb, dccb, dvb, pyramid=None):
         check(lib.nv_drawcull(self.h, _stream(), C.c_void_p(cull.ctypes.data), int(late), int(task), _ptr(db), _ptr(mb), _ptr(dcb),
                               _ptr(dccb), _ptr(dvb), None if pyramid is None else C.byref(pyramid)), "nv_drawcull")
@@ -715,6 +736,30 @@ class VisibilityPipeline:
         if getattr(self, "rt_dynamic", False):
             self.ctx.rt_tlas_build(self.db, self.draw_count)
 
+    def set_animations(self, animations, keyframes):
+        """upload the scene's animations (layouts.ANIMATION / KEYFRAME, e.g. host.scenecache_animations' or synth.orbit_animations') for
+        animate(); their drawIndex is checked against the pipeline's draw count, light targets are not driven here (light_count 0: an
+        animation with lightIndex >= 0 is refused).  None drops them"""
+        if isinstance(self, ShardedVisibilityPipeline):
+            raise NvError("set_animations is not available on a sharded pipeline")
+        self.ctx.upload_animations(animations, keyframes, self.draw_count, 0)
+
+    def animate(self, time):
+        """the animation path on the device (src/niagara.cpp:1362-1411, :1482): evaluates the uploaded animations at `time` into the device
+        draw buffer (nv_animate_draws: the cull mirror is rewritten in the same launch) and, with a dynamic ray-tracing scene, rebuilds its TLAS
+        (nv_rt_tlas_build).  All in stream order, nothing crosses the bus: the next frame() and shade(shadow="trace") see the moved draws.
+        draws_host is NOT rewritten and goes stale: it keeps only what move_draws needs from it, the visibility offsets (which no animation
+        changes); download_draws() returns the device records"""
+        if isinstance(self, ShardedVisibilityPipeline):
+            raise NvError("animate is not available on a sharded pipeline")
+        self.ctx.animate_draws(time, self.db, self.draw_count)
+        if getattr(self, "rt_dynamic", False):
+            self.ctx.rt_tlas_build(self.db, self.draw_count)
+
+    def download_draws(self):
+        """the device draw records (layouts.MESHDRAW) as animate() / move_draws left them (synchronises)"""
+        return from_device(self.db, L.MESHDRAW, self.draw_count).copy()
+
     def shade(self, cull_data, gbuffer0, gbuffer1, camera_position, sun_direction, shadow=None, blur=True, checkerboard=False, bloom=False, quality=1,
               textures=False, materials=None):
         """the shading end of the frame over attributes()'s G-buffer words and the pipeline's own depth target (src/niagara.cpp:1792-1850,
@@ -843,8 +888,8 @@ class ShardedVisibilityPipeline(VisibilityPipeline):
     visibility target is refused.
 
     Out of scope here: material textures (set_textures is refused; the textured pass is per pixel and works on any rank through the
-    Context) and moving draws.  move_draws and build_rt_scene(dynamic=True) (the TLAS rebuilt on the device) are
-    refused on a sharded pipeline: the ranks' draw buffers and mirrors would have to move together."""
+    Context) and moving draws.  move_draws, set_animations / animate and build_rt_scene(dynamic=True) (the TLAS rebuilt on
+    the device) are refused on a sharded pipeline: the ranks' draw buffers and mirrors would have to move together."""
 
     def set_textures(self, files):
         raise NvError("set_textures is not available on a sharded pipeline: decode the set with Context.texture_decode and run the textured "

@@ -545,3 +545,64 @@ def with_textures(scene, size=64, mips=True, cutout=False):
         v["tu"], v["tv"] = uv[:, 0].view(np.uint16), uv[:, 1].view(np.uint16)
         s["vertices"] = v
     return s
+
+
+def orbit_animations(draws, which, keyframes_per=8, seed=11, orbit=2.0, period=(0.25, 2.0), start=(0.0, 1.0)):
+    """(animations, keyframes), layouts.ANIMATION / KEYFRAME: one animation per draw index in `which` (no duplicates), `keyframes_per`
+    keyframes each (an int, or one count per animation).  Keyframe j of an animation places the draw on a circle of radius `orbit` x its scale
+    around its position in `draws`, in a random plane, with the draw's scale x U[0.75, 1.25] and a unit quaternion that turns by j / count
+    of a full turn about a random axis from the draw's own orientation; every fourth animation repeats a rotation in two neighbouring
+    keyframes (slerp's linear branch) and every third flips the sign of every other keyframe's quaternion (its negated-y path).  period and
+    startTime ~U[period], U[start].  For tests and tools: the reference reads its animations from glTF (src/scene.cpp)"""
+    rng = np.random.default_rng(seed)
+    which = np.asarray(which, np.int64).reshape(-1)
+    if len(np.unique(which)) != len(which):
+        raise ValueError("orbit_animations: a draw index appears twice (nv_upload_animations refuses duplicate targets)")
+    n = len(which)
+    counts = np.broadcast_to(np.asarray(keyframes_per, np.int64), (n,)).copy()
+    if n and counts.min() < 1:
+        raise ValueError("orbit_animations: every animation needs at least one keyframe")
+    anims = np.zeros(n, L.ANIMATION)
+    anims["drawIndex"] = which
+    anims["lightIndex"] = -1
+    anims["startTime"] = rng.uniform(start[0], start[1], n).astype(np.float32)
+    anims["period"] = rng.uniform(period[0], period[1], n).astype(np.float32)
+    anims["keyframeCount"] = counts
+    anims["keyframeOffset"] = np.concatenate([[0], np.cumsum(counts)[:-1]]) if n else 0
+    total = int(counts.sum())
+    keys = np.zeros(total, L.KEYFRAME)
+    if not total:
+        return anims, keys
+    owner = np.repeat(np.arange(n), counts)
+    j = np.arange(total) - np.repeat(anims["keyframeOffset"].astype(np.int64), counts)
+    phase = 2.0 * np.pi * j / counts[owner]
+
+    def unit(v):
+        return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+    u = unit(rng.normal(size=(n, 3)))
+    w = unit(np.cross(u, rng.normal(size=(n, 3))))
+    d = draws[which]
+    radius = orbit * d["scale"].astype(np.float64)
+    centre = d["position"].astype(np.float64)
+    keys["translation"] = (centre[owner] + radius[owner, None] * (np.cos(phase)[:, None] * u[owner] + np.sin(phase)[:, None] * w[owner])).astype(np.float32)
+    keys["scale"] = (d["scale"].astype(np.float64)[owner] * rng.uniform(0.75, 1.25, total)).astype(np.float32)
+    # rotation: q_draw * (axis sin(phase / 2), cos(phase / 2)), components (x, y, z, w)
+    axis = unit(rng.normal(size=(n, 3)))[owner]
+    held = (owner % 4 == 0) & (j % 2 == 1)  # repeats keyframe j - 1's rotation
+    half = 0.5 * np.where(held, 2.0 * np.pi * (j - 1) / counts[owner], phase)
+    b = axis * np.sin(half)[:, None]
+    bx, by, bz, bw = b[:, 0], b[:, 1], b[:, 2], np.cos(half)
+    q = d["orientation"].astype(np.float64)[owner]
+    norm = np.linalg.norm(q, axis=1)
+    q = np.where(norm[:, None] > 0, q / np.where(norm > 0, norm, 1.0)[:, None], np.array([0.0, 0.0, 0.0, 1.0]))
+    ax, ay, az, aw = q.T
+    r = np.stack([aw * bx + ax * bw + ay * bz - az * by,
+                  aw * by - ax * bz + ay * bw + az * bx,
+                  aw * bz + ax * by - ay * bx + az * bw,
+                  aw * bw - ax * bx - ay * by - az * bz], axis=1)
+    r = unit(r)
+    flip = (owner % 3 == 0) & (j % 2 == 1)
+    r[flip] = -r[flip]
+    keys["rotation"] = r.astype(np.float32)
+    return anims, keys

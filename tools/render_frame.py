@@ -261,6 +261,8 @@ def main():
     ap.add_argument("--quality", type=int, default=1, help="--traced-shadows: 0 = opaque draws cast, 1 = post-pass draws too")
     ap.add_argument("--animate", type=int, default=0, help="--traced-shadows: write N images (out_000.ppm ...) with one draw displaced along a circle "
                     "per frame through move_draws, which rebuilds the TLAS on the device")
+    ap.add_argument("--keyframes", action="store_true", help="--animate: the circle as N keyframes of one animation, evaluated on the device by "
+                    "animate(time) (nv_animate_draws, DESIGN.md §4.22) instead of records written on the host")
     ap.add_argument("--passes", default=None, help="WxH[,WxH...], or shadow_trace (with --traced-shadows)")
     ap.add_argument("--repeats", type=int, default=9)
     args = ap.parse_args()
@@ -344,12 +346,26 @@ def main():
         which = s["beside"][0]  # a box next to the wall, carried around the wall's edge: its shadow crosses the boxes behind
         home = draws[which:which + 1].copy()
         stem, ext = os.path.splitext(args.out)
-        for k in range(args.animate):
+
+        def circle(k):
             a = 2.0 * np.pi * k / args.animate
             rec = home.copy()
             rec["position"][0] = home["position"][0] + np.array([6.0 * np.cos(a) - 6.0, 6.0 * np.sin(a), 0.0], np.float32)
+            return rec
+        if args.keyframes:  # one keyframe per image, period 1: image k is the keyframe instant `time = k`
+            keys = np.zeros(args.animate, L.KEYFRAME)
+            for k in range(args.animate):
+                keys["translation"][k], keys["scale"][k], keys["rotation"][k] = circle(k)["position"][0], home["scale"][0], home["orientation"][0]
+            anim = np.zeros(1, L.ANIMATION)
+            anim["drawIndex"], anim["lightIndex"], anim["period"], anim["keyframeCount"] = which, -1, 1.0, args.animate
+            pipe.set_animations(anim, keys)
+        for k in range(args.animate):
+            rec = circle(k)
             events = []
-            _timed(events, "move_draws", lambda: pipe.move_draws(which, rec))
+            if args.keyframes:
+                _timed(events, "animate", lambda: pipe.animate(float(k)))
+            else:
+                _timed(events, "move_draws", lambda: pipe.move_draws(which, rec))
             frame(events)  # the closed loop's visibility bits follow the move one frame late, as niagara's do
             color = frame(events)
             torch.cuda.synchronize()
