@@ -136,6 +136,26 @@ def textured_fuzz_scene(instances=FUZZ["instances"], seed=FUZZ["seed"], radius=F
     return s, tset
 
 
+def textured_aligned_scene():
+    """(scene, set): shadow_ref.aligned_scene with random texcoords, its boxes in the post pass (postPass 1, 0, 1), a material per draw and
+    three random clear / solid textures: on edges and vertices T takes its fp64 branch and the barycentrics come from its values"""
+    rng = np.random.default_rng(21)
+    s = with_texcoords(SH.aligned_scene(), rng)
+    s["draws"] = s["draws"].copy()
+    s["draws"]["postPass"] = (1, 0, 1)
+    s["draws"]["materialIndex"] = (0, 1, 2)
+    t = texture_set(random_textures(rng, 3))
+    s["materials"] = np.zeros(3, L.MATERIAL)
+    s["materials"]["albedoTexture"] = (1, 2, 3)
+    return s, t
+
+
+def reference_masks(aref, scene, tset, launches, quality=1):
+    """(masks, rejected), each (launches, n, n): the restatement's pass over a poisoned mask for every launch of shadow_ref.degenerate_launches"""
+    out = SH.in_threads(lambda l: aref.shadow_trace(l[1], scene, tset, l[2], np.full(l[2].shape, SH.POISON, np.uint8), quality), launches)
+    return np.stack([m for m, _ in out]), np.stack([r for _, r in out])
+
+
 def layered_scene(box=False):
     """(scene, set): a cut-out wall (postPass 1, an 8 x 8 alpha checker; the wall mesh is 4 x 4 quads with texcoords (x, y) * 0.5 + 0.5, so a
     checker cell is half a quad and a BLAS leaf's triangles straddle opaque and clear cells) at z = 6 above an opaque wall (postPass 0) that

@@ -140,6 +140,12 @@ static RaySetup ray_setup(vec3 o, vec3 d)
 	return r;
 }
 
+/* test infrastructure only: the rays for which T took its fp64 branch against a casting triangle before the ray was decided (an input
+ * condition of the degenerate-ray tests; no result depends on it), and those among them for which the branch turned an fp32 zero of U, V or W
+ * into a number with a sign: the rays its extra precision can decide */
+static _Thread_local int fp64_flag, fp64_decided_flag;
+static uint64_t fp64_rays, fp64_decided_rays;
+
 static int triangle_test(const RaySetup* r, vec3 v0, vec3 v1, vec3 v2, float tmin, float tmax)
 {
 	vec3 A = { v0.x - r->o.x, v0.y - r->o.y, v0.z - r->o.z };
@@ -152,9 +158,13 @@ static int triangle_test(const RaySetup* r, vec3 v0, vec3 v1, vec3 v2, float tmi
 	float det, T, t;
 	if (U == 0.0f || V == 0.0f || W == 0.0f)
 	{
+		const float U32 = U, V32 = V, W32 = W;
+		fp64_flag = 1;
 		U = (float)((double)Cx * (double)By - (double)Cy * (double)Bx);
 		V = (float)((double)Ax * (double)Cy - (double)Ay * (double)Cx);
 		W = (float)((double)Bx * (double)Ay - (double)By * (double)Ax);
+		if ((U32 == 0.0f && U != 0.0f) || (V32 == 0.0f && V != 0.0f) || (W32 == 0.0f && W != 0.0f))
+			fp64_decided_flag = 1;
 	}
 	if ((U < 0.0f || V < 0.0f || W < 0.0f) && (U > 0.0f || V > 0.0f || W > 0.0f))
 		return 0;
@@ -230,6 +240,23 @@ static int occluded(const Mesh* meshes, uint32_t meshCount, const uint32_t* indi
 	return 0;
 }
 
+static int occluded_counted(const Mesh* meshes, uint32_t meshCount, const uint32_t* indices, uint32_t indexCapacity, const Vertex* vertices,
+                            uint32_t vertexCapacity, const MeshDraw* draws, uint32_t drawCount, vec3 o, vec3 d, float tmin, float tmax, int quality)
+{
+	int hit;
+	fp64_flag = fp64_decided_flag = 0;
+	hit = occluded(meshes, meshCount, indices, indexCapacity, vertices, vertexCapacity, draws, drawCount, o, d, tmin, tmax, quality);
+	if (fp64_flag)
+		__atomic_fetch_add(&fp64_rays, 1, __ATOMIC_RELAXED);
+	if (fp64_decided_flag)
+		__atomic_fetch_add(&fp64_decided_rays, 1, __ATOMIC_RELAXED);
+	return hit;
+}
+
+/* the counts since the last call */
+uint64_t shr_fp64_rays(void) { return __atomic_exchange_n(&fp64_rays, 0, __ATOMIC_RELAXED); }
+uint64_t shr_fp64_decided_rays(void) { return __atomic_exchange_n(&fp64_decided_rays, 0, __ATOMIC_RELAXED); }
+
 /* the rays of the full-resolution image (no checkerboard): origins / dirs are w * h * 3 floats */
 void shr_rays(const ShadowData* sd, const float* depth, uint32_t w, uint32_t h, float* origins, float* dirs)
 {
@@ -253,7 +280,7 @@ void shr_trace(const Mesh* meshes, uint32_t meshCount, const uint32_t* indices, 
 	for (i = 0; i < n; ++i)
 	{
 		vec3 o = { origins[3 * i], origins[3 * i + 1], origins[3 * i + 2] }, d = { dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2] };
-		out[i] = occluded(meshes, meshCount, indices, indexCapacity, vertices, vertexCapacity, draws, drawCount, o, d, tmin, tmax, quality) ? 0 : 255;
+		out[i] = occluded_counted(meshes, meshCount, indices, indexCapacity, vertices, vertexCapacity, draws, drawCount, o, d, tmin, tmax, quality) ? 0 : 255;
 	}
 }
 
@@ -274,6 +301,6 @@ void shr_shadow_trace(const ShadowData* sd, const Mesh* meshes, uint32_t meshCou
 			pixel_ray(sd, (uint32_t)px, gy, z, &o, &d);
 			if (px < (int64_t)w) /* a store outside the image is dropped */
 				shadow[(size_t)gy * w + (size_t)px] =
-				    occluded(meshes, meshCount, indices, indexCapacity, vertices, vertexCapacity, draws, drawCount, o, d, 1e-2f, 1e3f, quality) ? 0 : 255;
+				    occluded_counted(meshes, meshCount, indices, indexCapacity, vertices, vertexCapacity, draws, drawCount, o, d, 1e-2f, 1e3f, quality) ? 0 : 255;
 		}
 }

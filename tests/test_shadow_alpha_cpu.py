@@ -214,17 +214,35 @@ def test_fuzz_equals_the_restatement_and_exercises_the_loop(fuzz, aref, shref):
 
 def test_degenerate_rays_equal_the_restatement(aref):
     """the aligned scene's rays on edges and vertices: U, V or W is 0, T takes its fp64 branch and the barycentrics come from its values"""
-    rng = np.random.default_rng(21)
-    s = SA.with_texcoords(SH.aligned_scene(), rng)
-    s["draws"] = s["draws"].copy()
-    s["draws"]["postPass"] = (1, 0, 1)
-    s["draws"]["materialIndex"] = (0, 1, 2)
-    t = SA.texture_set(SA.random_textures(rng, 3))
-    s["materials"] = np.zeros(3, L.MATERIAL)
-    s["materials"]["albedoTexture"] = (1, 2, 3)
+    s, t = SA.textured_aligned_scene()
     o, d = SH.degenerate_rays(s)
     want, rejected = _same("degenerate", aref, s, t, o, d)
     assert int((rejected > 0).sum()) >= 200 and int((want == 0).sum()) >= 200
+
+
+def test_degenerate_launches_equal_the_restatement(aref, shref):
+    """every launch of shadow_ref.degenerate_launches around the textured aligned scene (tests/test_shadow_degenerate_gpu.py hands the same
+    launches to the device kernels): the host twin against the restatement on the rays of the pass, zero differences"""
+    s, t = SA.textured_aligned_scene()
+    blob = _build(s)
+    assert host.rt_scene_validate(blob)
+    launches = SH.degenerate_launches(s)
+    o, d, fam = SH.launch_rays(shref, launches)
+    want, rejected = aref.trace(s, t, o, d, 1)
+    got = _host(blob, s, t, o, d)
+    diff = int((want != got).sum())
+    print("degenerate launches: %d launches, %d rays, %d occluded, %d with a rejected candidate, %d differences" % (len(launches), len(want), int((want == 0).sum()),
+                                                                                                            int((rejected > 0).sum()), diff))
+    assert diff == 0 and set(np.unique(want).tolist()) == {0, 255}
+    assert int((rejected > 0).sum()) >= 200 and int((want == 0).sum()) >= 200
+    finite = np.isfinite(o).all(1) & np.isfinite(d).all(1)
+    assert (~finite).sum() >= 100 and (want[~finite] == 255).all() and (want[fam == "suns"] == 255).all()
+    # the restatement of the pass is the per-ray trace over its rays; quality 0 is the opaque trace
+    some = launches[::37]
+    full, _ = SA.reference_masks(aref, s, t, some, 1)
+    assert full.reshape(-1).tobytes() == np.concatenate([want[256 * i:256 * i + 256] for i in range(0, len(launches), 37)]).tobytes()
+    q0 = _host(blob, s, t, o, d, quality=0)
+    assert q0.tobytes() == shref.trace(s, o, d, 0).tobytes() == aref.trace(s, t, o, d, 0)[0].tobytes()
 
 
 def cutout_occluder():

@@ -335,6 +335,84 @@ def test_rule_cases_equal_the_brute_force(rule, shref):
         assert hits[1] < base_hits  # the rule removed casters
 
 
+# ---------------------------------------------------------------------------------------------------------------- the degenerate rays as launches
+
+def test_the_lattice_construction_is_exact(shref):
+    """shadow_ref.lattice_launch's hand-made matrix: the rays of the pass are the intended lattice and +-e_k, component for component.
+    tests/test_shadow_degenerate_gpu.py hands the same launches to the device kernels"""
+    base = SH.aligned_scene()
+    rays = 0
+    for scene in (base, dict(base, draws=SH.moved_exactly(base))):
+        for dr in scene["draws"]:
+            p, s = dr["position"].astype(np.float64), float(dr["scale"])
+            for k in range(3):
+                for sign in (1.0, -1.0):
+                    for start in SH.AXIS_STARTS:
+                        third = p[k] + sign * start * s
+                        o, d = shref.rays(*SH.lattice_launch(p, s, k, third, np.eye(3)[k] * sign))
+                        assert np.array_equal(o.astype(np.float64), SH.lattice_points(p, s, k, third))
+                        assert np.array_equal(d, np.broadcast_to((np.eye(3)[k] * sign).astype(np.float32), d.shape))
+                        rays += o.size // 3
+    print("lattice construction: %d rays, every component equal" % rays)
+    assert rays == 2 * 18432
+    # the comparison notices one ulp in any of the matrix's five entries
+    p, s, k, third = np.zeros(3), 1.0, 0, -3.0
+    want = SH.lattice_points(p, s, k, third)
+    sd, depth = SH.lattice_launch(p, s, k, third, (1.0, 0.0, 0.0))
+    entries = np.flatnonzero(sd["inverseViewProjection"][0])
+    assert entries.tolist() == [1, 6, 8, 13, 14, 15]
+    for e in entries[:-1]:
+        for toward in (np.inf, -np.inf):
+            bent = sd.copy()
+            bent["inverseViewProjection"][0, e] = np.nextafter(sd["inverseViewProjection"][0, e], np.float32(toward))
+            assert not np.array_equal(shref.rays(bent, depth)[0].astype(np.float64), want), (e, toward)
+
+
+@pytest.mark.parametrize("which", ["aligned", "extreme"])
+def test_degenerate_launches_equal_the_brute_force(which, shref):
+    """every launch of shadow_ref.degenerate_launches: the host twin of the kernel's traversal against the brute force on the rays of the
+    pass, both qualities, zero differences; the input conditions on the restatement alone"""
+    scene = SH.aligned_scene() if which == "aligned" else SH.extreme_scene()
+    blob = _build(scene)
+    assert host.rt_scene_validate(blob)
+    launches = SH.degenerate_launches(scene)
+    o, d, fam = SH.launch_rays(shref, launches)
+    masks = {}
+    shref.fp64_rays()
+    for q in (0, 1):
+        masks[q] = SH.in_chunks(lambda a, b: shref.trace(scene, a, b, q), o, d)
+        got = host.rt_scene_trace_host(blob, o, d, q)
+        diff = int((masks[q] != got).sum())
+        print("%s quality %d: %d launches, %d rays, %d occluded, %d differences" % (which, q, len(launches), len(o), int((masks[q] == 0).sum()), diff))
+        assert diff == 0
+    branch = shref.fp64_rays()
+    print("%s: %d rays took the fp64 branch of T against a casting triangle (both qualities)" % (which, branch))
+    assert branch >= 1000
+    SH.input_conditions(which, o, d, fam, masks)
+    # the graze family: rays for which the branch turns an fp32 zero of U, V or W into a sign, so that its precision decides texels (a
+    # device build whose branch ran in fp32 answers some of them differently: EXPERIMENTS.md)
+    shref.fp64_decided_rays()
+    graze = fam == "graze"
+    lit = int((shref.trace(scene, o[graze], d[graze], 1) == 255).sum())
+    decided = shref.fp64_decided_rays()
+    print("%s: graze family: %d rays, %d lit, the fp64 branch decides a zero in %d of them" % (which, int(graze.sum()), lit, decided))
+    assert decided >= 100 and lit >= 100 and graze.sum() - lit >= 100
+    # the restatement of the pass is the per-ray trace over its rays
+    some = launches[::37]
+    for q in (0, 1):
+        full = SH.reference_masks(shref, scene, some, q)
+        assert full.reshape(-1).tobytes() == np.concatenate([masks[q][256 * i:256 * i + 256] for i in range(0, len(launches), 37)]).tobytes()
+    alone, six = SH.closed_box_launches(scene)
+    SH.closed_box_property(which, SH.reference_masks(shref, alone, six, 0))
+    o6, d6, _ = SH.launch_rays(shref, six)
+    assert (host.rt_scene_trace_host(_build(alone), o6, d6, 0).reshape(6, 16, 16) == SH.reference_masks(shref, alone, six, 0)).all()
+    if which == "extreme":
+        import tlas_ref as TR
+        leaves = SH.infinite_leaves(TR.sections(blob)[1])
+        print("extreme: %d TLAS leaves with the infinite box" % len(leaves))
+        assert len(leaves) >= 1
+
+
 def test_the_standalone_program_runs_clean_under_the_host_sanitizers(tmp_path):
     """tools/rt_scene_check.cpp with rtbuild.cpp, host code only, its own main: AddressSanitizer and UBSan linked statically into the program itself"""
     exe = tmp_path / "rt_scene_check"

@@ -217,6 +217,33 @@ def test_degenerate_rays_on_the_rebuilt_aligned_scene_equal_the_brute_force(shre
     assert hits[0] > 1000 and hits[1] > hits[0]
 
 
+@pytest.mark.parametrize("which", ["aligned", "extreme"])
+def test_degenerate_launches_on_the_rebuilt_scene_equal_the_brute_force(which, shref):
+    """every launch of shadow_ref.degenerate_launches around the exactly-moved draws, on the TLAS the host twin rebuilds for them
+    (tests/test_shadow_degenerate_gpu.py hands the same launches to the device's rebuild); the input conditions on the restatement alone"""
+    sc = SH.aligned_scene() if which == "aligned" else SH.extreme_scene()
+    blob = host.rt_scene_build(sc["meshes"], sc["indices"], sc["vertices"], sc["draws"])
+    movedscene = dict(sc, draws=SH.moved_exactly(sc))
+    rebuilt = host.rt_tlas_build_host(blob, movedscene["draws"])
+    assert host.rt_scene_validate(rebuilt)
+    TR.check_blob(rebuilt)
+    launches = SH.degenerate_launches(movedscene)
+    o, d, fam = SH.launch_rays(shref, launches)
+    masks = {}
+    for q in (0, 1):
+        masks[q] = SH.in_chunks(lambda a, b: shref.trace(movedscene, a, b, q), o, d)
+        got = host.rt_scene_trace_host(rebuilt, o, d, q)
+        diff = int((masks[q] != got).sum())
+        print("moved %s quality %d: %d launches, %d rays, %d occluded, %d differences" % (which, q, len(launches), len(o), int((masks[q] == 0).sum()), diff))
+        assert diff == 0
+    SH.input_conditions("moved " + which, o, d, fam, masks)
+    stale = host.rt_scene_trace_host(blob, o, d, 1)
+    print("moved %s: the static blob answers %d of these rays differently" % (which, int((stale != masks[1]).sum())))
+    assert (stale != masks[1]).sum() >= 50  # the move matters (the bound of tests/test_tlas_build_gpu.py's moved draws)
+    if which == "extreme":
+        assert len(SH.infinite_leaves(TR.sections(blob)[1])) >= 1 and len(SH.infinite_leaves(TR.sections(rebuilt)[1])) >= 1
+
+
 def test_mixed_draws_equal_the_brute_force(base, shref):
     """clusters, duplicates, the infinite box and non-casters of every kind under the ray fuzz"""
     sc, blob = base
