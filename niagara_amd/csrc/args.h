@@ -30,7 +30,7 @@
 
 #include "../../include/niagara_vis.h"
 #include "dealing.h"
-#include "rtmath.h" // RtAlphaInputs (ShadowTraceAlphaArgs), RtAlphaBlockInputs (ShadowTraceBlockArgs)
+#include "rtmath.h" // RtAlphaInputs (ShadowTraceSetArgs)
 
 // Tuning experiments (wave stamps, partial passes, alternative dealing ...) exist only in a separate build
 // (-DNV_EXPERIMENTS -> libniagara_vis_exp.so, tools/): the product library carries no switch that could change a result
@@ -329,45 +329,53 @@ struct VisAttrArgs
 	unsigned long long* totals;               // optional
 };
 
-// the texture set of the textured pass
-struct VaTextures
+// The texture set of the attribute pass and of the alpha-tested raster: the descriptor table and the set's buffer.
+// SET is the set's residency, texmath.h's TxDecoded or TxBlocks (only named here: a translation unit that instantiates one of the templates
+// below has included texmath.h, a block one in full); the kernels reach the set through it alone.
+template <typename SET>
+struct TxTable
 {
-	const uint4* __restrict__ descs; // NvTextureDesc, entry 0 reserved
+	const uint4* __restrict__ descs; // NvTextureDesc / NvTextureBlockDesc, entry 0 reserved
 	uint32_t count;
-	const uint32_t* __restrict__ texels;
-	unsigned long long texelWords;
+	const typename SET::Unit* __restrict__ data; // the decoded texels / the DDS payloads, 16-byte aligned
+	unsigned long long extent;                   // texelWords / units16
+
+	// textures[id]'s descriptor.  false: id is past the table or SET::ok refused the descriptor (§4.18: the texture is treated as absent);
+	// nothing is ever loaded from the buffer through a descriptor this refused.
+	__device__ __forceinline__ bool desc(uint32_t id, typename SET::Desc& d) const
+	{
+		if (id >= count)
+			return false;
+		const uint4 w = descs[id];
+		d = typename SET::Desc{ w.x, w.y, w.z, w.w };
+		return SET::ok(d, extent);
+	}
 };
 
-// nv_rasterdepth_textured (rasterdepth.h, rasterdepth_alpha.hip): RasterArgs plus the material table, the texture set and the alpha totals
-struct RasterAlphaArgs : RasterArgs
+// nv_rasterdepth_textured, nv_rasterdepth_blocks (rasterdepth.h, rasterdepth_alpha.hip): RasterArgs plus the material table, the texture set and
+// the alpha totals
+template <typename SET>
+struct RasterSetArgs : RasterArgs
 {
+	typedef SET Set;
 	const NvMaterial* __restrict__ materials; // optional
 	uint32_t materialCount;
-	VaTextures tx;
+	TxTable<SET> tx;
 	unsigned long long* __restrict__ alphaTotals;   // optional: {dropped, unevaluated}
 	unsigned long long* __restrict__ alphaPartials; // library scratch: 2 counters per workgroup of the launch (set whenever alphaTotals is)
 };
+typedef RasterSetArgs<TxDecoded> RasterAlphaArgs;
+typedef RasterSetArgs<TxBlocks> RasterBlockArgs;
 
-// nv_visibility_attributes_textured (visattr.h, visattr_tex.hip): VisAttrArgs plus the texture set
-struct VisAttrTexArgs : VisAttrArgs
+// nv_visibility_attributes_textured, nv_visibility_attributes_blocks (visattr.h, visattr_tex.hip): VisAttrArgs plus the texture set
+template <typename SET>
+struct VisAttrSetArgs : VisAttrArgs
 {
-	VaTextures tx;
+	typedef SET Set;
+	TxTable<SET> tx;
 };
-
-// the block-resident texture set
-struct VaBlockTextures
-{
-	const uint4* __restrict__ descs; // NvTextureBlockDesc, entry 0 reserved
-	uint32_t count;
-	const void* __restrict__ blocks; // the DDS payloads, 16-byte aligned
-	unsigned long long units16;
-};
-
-// nv_visibility_attributes_blocks (visattr.h, visattr_blocks.hip): VisAttrArgs plus the block-resident set
-struct VisAttrBlockArgs : VisAttrArgs
-{
-	VaBlockTextures tx;
-};
+typedef VisAttrSetArgs<TxDecoded> VisAttrTexArgs;
+typedef VisAttrSetArgs<TxBlocks> VisAttrBlockArgs;
 
 // nv_shade_final (shade.hip)
 struct ShadeFinalArgs
@@ -400,11 +408,12 @@ struct ShadowTraceArgs
 	uint32_t tilesX, tiles;
 };
 
-// nv_shadow_trace_textured at quality 1 (shadowtrace.h, shadowtrace_alpha.hip)
-struct ShadowTraceAlphaArgs
+// nv_shadow_trace_textured, nv_shadow_trace_blocks at quality 1 (shadowtrace.h, shadowtrace_alpha.hip)
+template <typename SET>
+struct ShadowTraceSetArgs
 {
 	NvShadowData sd;
-	RtAlphaInputs in;
+	RtAlphaInputs<SET> in;
 	const unsigned char* __restrict__ scene;
 	const float* __restrict__ depth;
 	uint8_t* __restrict__ shadow;
@@ -412,29 +421,8 @@ struct ShadowTraceAlphaArgs
 	uint32_t invocationsX; // as ShadowTraceArgs
 	uint32_t tilesX, tiles;
 };
-
-// nv_shadow_trace_blocks at quality 1 (shadowtrace.h, shadowtrace_blocks.hip)
-struct ShadowTraceBlockArgs
-{
-	NvShadowData sd;
-	RtAlphaBlockInputs in;
-	const unsigned char* __restrict__ scene;
-	const float* __restrict__ depth;
-	uint8_t* __restrict__ shadow;
-	uint32_t width, height;
-	uint32_t invocationsX; // as ShadowTraceArgs
-	uint32_t tilesX, tiles;
-};
-
-// nv_rasterdepth_blocks (rasterdepth.h, rasterdepth_blocks.hip): RasterAlphaArgs with the block-resident set
-struct RasterBlockArgs : RasterArgs
-{
-	const NvMaterial* __restrict__ materials; // optional
-	uint32_t materialCount;
-	VaBlockTextures tx;
-	unsigned long long* __restrict__ alphaTotals;   // optional: {dropped, unevaluated}
-	unsigned long long* __restrict__ alphaPartials; // library scratch: 2 counters per workgroup of the launch (set whenever alphaTotals is)
-};
+typedef ShadowTraceSetArgs<TxDecoded> ShadowTraceAlphaArgs;
+typedef ShadowTraceSetArgs<TxBlocks> ShadowTraceBlockArgs;
 
 // nv_animate_draws (animmath.h, animate.hip).  No __restrict__ on the written buffers: the mirror instantiation reads the draw it wrote
 struct AnimateArgs

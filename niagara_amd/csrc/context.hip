@@ -20,6 +20,7 @@
 #include "../../include/niagara_vis.h"
 #include "cullmath.h"
 #include "filtermath.h"
+#include "texmath.h" // TxDecoded, TxBlocks: the residencies the texture-set argument structs are instantiated with
 #include "launch.h"
 
 struct ProfRecord
@@ -402,6 +403,166 @@ nv::CullForm launch_cull(nv_context* ctx, hipStream_t s, nv::ClusterArgs& a, boo
 	*rc = form.lanes ? nv::launch_cluster_bits(s, a, form.soa, persistent_grid(ctx, ctx->bitsBlocksPerCU))
 	                 : nv::launch_cluster_mask(s, a, form, persistent_grid(ctx, ctx->ccBlocksPerCU));
 	return form;
+}
+
+// ---- the argument checks and fills that the entry points of one pass share: every refusal here is made before anything is enqueued
+
+// What the three raster entry points share (the parameters are their first fifteen without the stream, in their order): the refusals all three
+// have, then the caller-facing fields of nv_rasterdepth's launch
+static int fill_raster_args(nv::RasterArgs& a, nv_context* ctx, const NvGlobals* globals, const NvMeshTaskCommand* d_commands, const NvMeshDraw* d_draws,
+                            const NvMeshlet* d_meshlets, const uint32_t* d_meshletData, const NvVertex* d_vertices, const uint32_t* d_clusterIndices,
+                            const uint32_t* d_clusterCount4, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_visibility, uint64_t* d_totals4)
+{
+	if (!ctx || !globals || !d_commands || !d_draws || !d_meshlets || !d_meshletData || !d_vertices || !d_clusterIndices || !d_clusterCount4 ||
+	    !d_depth || !image_size_ok(width, height) || globals->screenWidth != (float)width || globals->screenHeight != (float)height)
+		return NV_EINVAL;
+	a.globals = *globals;
+	a.commands = d_commands;
+	a.draws = d_draws;
+	a.meshlets = d_meshlets;
+	a.meshletData = d_meshletData;
+	a.vertices = d_vertices;
+	a.clusterIndices = d_clusterIndices;
+	a.cc4 = d_clusterCount4;
+	a.depth = reinterpret_cast<uint32_t*>(d_depth);
+	a.visibility = reinterpret_cast<unsigned long long*>(d_visibility);
+	a.width = width;
+	a.height = height;
+	a.smallLimit = ctx->rasterSmallLimit;
+	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
+	a.partials = ctx->totalsPartials;
+	return NV_OK;
+}
+
+// What nv_rasterdepth_textured and nv_rasterdepth_blocks add to fill_raster_args (rasterdepth_alpha.hip): the alignments
+// their kernels' loads need, the rules for the material table and the texture set, then the fields of the set.  d_buffer is the set's buffer —
+// the decoded texels, bufferMask 3, or the blocks, bufferMask 15 — and `extent` its size (texelWords or units16)
+template <typename SET>
+static int fill_raster_set_args(nv::RasterSetArgs<SET>& a, nv_context* ctx, const NvGlobals* globals, const NvMeshTaskCommand* d_commands,
+                                const NvMeshDraw* d_draws, const NvMeshlet* d_meshlets, const uint32_t* d_meshletData, const NvVertex* d_vertices,
+                                const uint32_t* d_clusterIndices, const uint32_t* d_clusterCount4, float* d_depth, uint32_t width, uint32_t height,
+                                uint64_t* d_visibility, uint64_t* d_totals4, const NvMaterial* d_materials, uint32_t materialCount, const void* d_textures,
+                                uint32_t textureCount, const void* d_buffer, uintptr_t bufferMask, uint64_t extent, uint64_t* d_alphaTotals2)
+{
+	if (fill_raster_args(a, ctx, globals, d_commands, d_draws, d_meshlets, d_meshletData, d_vertices, d_clusterIndices, d_clusterCount4, d_depth, width, height,
+	                     d_visibility, d_totals4) != NV_OK ||
+	    misaligned(d_commands, 3u) || misaligned(d_clusterIndices, 3u) || misaligned(d_clusterCount4, 3u) || misaligned(d_depth, 3u) ||
+	    misaligned(d_meshlets, 3u) || misaligned(d_meshletData, 3u) || misaligned(d_buffer, bufferMask) || misaligned(d_visibility, 7u) ||
+	    misaligned(d_totals4, 7u) || misaligned(d_alphaTotals2, 7u) || misaligned(d_draws, 15u) || misaligned(d_vertices, 15u) ||
+	    misaligned(d_materials, 15u) || misaligned(d_textures, 15u) || (d_textures != nullptr) != (d_buffer != nullptr) || (textureCount && !d_textures) ||
+	    (d_materials && materialCount == 0))
+		return NV_EINVAL;
+	if (d_alphaTotals2 && !ctx->alphaPartials)
+		return NV_ENOMEM; // (nv_create reserves them: a pass never allocates)
+	a.materials = d_materials;
+	a.materialCount = d_materials ? materialCount : 0u;
+	a.tx.descs = static_cast<const uint4*>(d_textures);
+	a.tx.count = d_textures ? textureCount : 0u;
+	a.tx.data = static_cast<const typename SET::Unit*>(d_buffer);
+	a.tx.extent = d_buffer ? extent : 0u;
+	a.alphaTotals = reinterpret_cast<unsigned long long*>(d_alphaTotals2);
+	a.alphaPartials = d_alphaTotals2 ? ctx->alphaPartials : nullptr;
+	return NV_OK;
+}
+
+// The part the three attribute entry points share (the parameters are the entry points' first twenty, in their
+// order): the refusals all three have, then the caller-facing fields of the launch.  The plain pass and the textured pair each add their own rule
+// for the material table.
+static int fill_attribute_args(nv::VisAttrArgs& a, nv_context* ctx, const NvGlobals* globals, const NvVisRecord* d_records, uint32_t width, uint32_t height,
+                               const NvMeshDraw* d_draws, uint32_t drawCount, const NvMeshlet* d_meshlets, uint32_t meshletCount, const uint32_t* d_meshletData,
+                               uint32_t meshletDataWords, const NvVertex* d_vertices, uint32_t vertexCount, const NvMaterial* d_materials, uint32_t materialCount,
+                               NvPixelAttributes* d_attributes, uint32_t* d_gbuffer0, uint32_t* d_gbuffer1, uint64_t* d_totals4)
+{
+	if (!ctx || !globals || !d_records || !image_size_ok(width, height) || globals->screenWidth != (float)width || globals->screenHeight != (float)height ||
+	    (drawCount && !d_draws) || (meshletCount && !d_meshlets) || (meshletDataWords && !d_meshletData) || (vertexCount && !d_vertices) ||
+	    misaligned(d_records, 15u) || misaligned(d_attributes, 15u) || misaligned(d_draws, 15u) || misaligned(d_vertices, 15u) || misaligned(d_materials, 15u) ||
+	    misaligned(d_totals4, 7u) || misaligned(d_meshlets, 3u) || misaligned(d_meshletData, 3u) || misaligned(d_gbuffer0, 3u) || misaligned(d_gbuffer1, 3u))
+		return NV_EINVAL;
+	a.globals = *globals;
+	a.records = reinterpret_cast<const nv::va_u4*>(d_records);
+	a.width = width;
+	a.draws = d_draws;
+	a.drawCount = drawCount;
+	a.meshlets = d_meshlets;
+	a.meshletCount = meshletCount;
+	a.meshletData = d_meshletData;
+	a.dataWords = meshletDataWords;
+	a.vertices = d_vertices;
+	a.vertexCount = vertexCount;
+	a.materials = d_materials;
+	a.materialCount = materialCount;
+	a.attributes = reinterpret_cast<uint4*>(d_attributes);
+	a.gbuffer0 = d_gbuffer0;
+	a.gbuffer1 = d_gbuffer1;
+	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
+	return NV_OK;
+}
+
+// What nv_visibility_attributes_textured and nv_visibility_attributes_blocks add to fill_attribute_args: their rule for the material table, the
+// texture set's refusals and fields.  d_buffer, bufferMask and extent as fill_raster_set_args'
+template <typename SET>
+static int fill_attribute_set_args(nv::VisAttrSetArgs<SET>& a, nv_context* ctx, const NvGlobals* globals, const NvVisRecord* d_records, uint32_t width,
+                                   uint32_t height, const NvMeshDraw* d_draws, uint32_t drawCount, const NvMeshlet* d_meshlets, uint32_t meshletCount,
+                                   const uint32_t* d_meshletData, uint32_t meshletDataWords, const NvVertex* d_vertices, uint32_t vertexCount,
+                                   const NvMaterial* d_materials, uint32_t materialCount, NvPixelAttributes* d_attributes, uint32_t* d_gbuffer0,
+                                   uint32_t* d_gbuffer1, uint64_t* d_totals4, const void* d_textures, uint32_t textureCount, const void* d_buffer,
+                                   uintptr_t bufferMask, uint64_t extent)
+{
+	if (fill_attribute_args(a, ctx, globals, d_records, width, height, d_draws, drawCount, d_meshlets, meshletCount, d_meshletData, meshletDataWords, d_vertices,
+	                        vertexCount, d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1, d_totals4) != NV_OK ||
+	    !d_materials || (textureCount && (!d_textures || !d_buffer)) || misaligned(d_textures, 15u) || misaligned(d_buffer, bufferMask))
+		return NV_EINVAL;
+	a.tx.descs = static_cast<const uint4*>(d_textures);
+	a.tx.count = d_textures ? textureCount : 0u;
+	a.tx.data = static_cast<const typename SET::Unit*>(d_buffer);
+	a.tx.extent = extent;
+	return NV_OK;
+}
+
+// what the three trace entry points share: the refusals, then the caller-facing fields of the opaque launch
+static int fill_trace_args(nv::ShadowTraceArgs& a, nv_context* ctx, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width,
+                           uint32_t height, int quality)
+{
+	if (!ctx || !ctx->rtScene || !shadow || !d_depth || !d_shadow || !image_size_ok(width, height) || shadow->imageSize[0] != (float)width ||
+	    shadow->imageSize[1] != (float)height || quality < 0 || quality > 1 || misaligned(d_depth, 3u))
+		return NV_EINVAL;
+	a.sd = *shadow;
+	a.scene = static_cast<const unsigned char*>(ctx->rtScene);
+	a.depth = d_depth;
+	a.shadow = d_shadow;
+	a.width = width;
+	a.height = height;
+	return NV_OK;
+}
+
+// What nv_shadow_trace_textured and nv_shadow_trace_blocks add to fill_trace_args (shadowtrace_alpha.hip): a scene with
+// texcoords, every count with its table, the alignments; then the alpha trace's arguments from the opaque launch's.  d_buffer, bufferMask and
+// extent as fill_raster_set_args'
+template <typename SET>
+static int fill_trace_alpha(nv::ShadowTraceSetArgs<SET>& a, nv::ShadowTraceArgs& opaque, nv_context* ctx, const NvShadowData* shadow, const float* d_depth,
+                            uint8_t* d_shadow, uint32_t width, uint32_t height, int quality, const NvMeshDraw* d_draws, uint32_t drawCount,
+                            const NvMaterial* d_materials, uint32_t materialCount, const void* d_textures, uint32_t textureCount, const void* d_buffer,
+                            uintptr_t bufferMask, uint64_t extent)
+{
+	if (fill_trace_args(opaque, ctx, shadow, d_depth, d_shadow, width, height, quality) != NV_OK || !(ctx->rtSceneFlags & nv::RT_FLAG_TEXCOORDS) ||
+	    (drawCount && !d_draws) || (materialCount && !d_materials) || (textureCount && !d_textures) || (extent && !d_buffer) || misaligned(d_draws, 15u) ||
+	    misaligned(d_materials, 15u) || misaligned(d_textures, 15u) || misaligned(d_buffer, bufferMask))
+		return NV_EINVAL;
+	a.sd = opaque.sd;
+	a.in.draws = d_draws;
+	a.in.materials = d_materials;
+	a.in.textures = static_cast<const typename SET::Desc*>(d_textures);
+	a.in.data = static_cast<const typename SET::Unit*>(d_buffer);
+	a.in.extent = extent;
+	a.in.drawCount = drawCount;
+	a.in.materialCount = materialCount;
+	a.in.textureCount = textureCount;
+	a.scene = opaque.scene;
+	a.depth = d_depth;
+	a.shadow = d_shadow;
+	a.width = width;
+	a.height = height;
+	return NV_OK;
 }
 
 } // namespace
@@ -1063,26 +1224,11 @@ int nv_rasterdepth(nv_context* ctx, void* stream, const NvGlobals* globals, cons
                    const NvMeshlet* d_meshlets, const uint32_t* d_meshletData, const NvVertex* d_vertices, const uint32_t* d_clusterIndices,
                    const uint32_t* d_clusterCount4, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_visibility, uint64_t* d_totals4)
 {
-	if (!ctx || !globals || !d_commands || !d_draws || !d_meshlets || !d_meshletData || !d_vertices || !d_clusterIndices || !d_clusterCount4 ||
-	    !d_depth || !image_size_ok(width, height) || globals->screenWidth != (float)width || globals->screenHeight != (float)height)
+	nv::RasterArgs a;
+	if (fill_raster_args(a, ctx, globals, d_commands, d_draws, d_meshlets, d_meshletData, d_vertices, d_clusterIndices, d_clusterCount4, d_depth, width, height,
+	                     d_visibility, d_totals4) != NV_OK)
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
-	nv::RasterArgs a;
-	a.globals = *globals;
-	a.commands = d_commands;
-	a.draws = d_draws;
-	a.meshlets = d_meshlets;
-	a.meshletData = d_meshletData;
-	a.vertices = d_vertices;
-	a.clusterIndices = d_clusterIndices;
-	a.cc4 = d_clusterCount4;
-	a.depth = reinterpret_cast<uint32_t*>(d_depth);
-	a.visibility = reinterpret_cast<unsigned long long*>(d_visibility);
-	a.width = width;
-	a.height = height;
-	a.smallLimit = ctx->rasterSmallLimit;
-	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
-	a.partials = ctx->totalsPartials;
 	return nv::launch_rasterdepth((hipStream_t)stream, a, persistent_grid(ctx, 8), ctx->rasterNearClip != 0, ctx->rasterStableIds != 0);
 }
 
@@ -1092,86 +1238,30 @@ int nv_rasterdepth_textured(nv_context* ctx, void* stream, const NvGlobals* glob
                             const NvMaterial* d_materials, uint32_t materialCount, const NvTextureDesc* d_textures, uint32_t textureCount,
                             const uint32_t* d_texels, uint64_t texelWords, uint64_t* d_alphaTotals2)
 {
-	if (!ctx || !globals || !d_commands || !d_draws || !d_meshlets || !d_meshletData || !d_vertices || !d_clusterIndices || !d_clusterCount4 ||
-	    !d_depth || !image_size_ok(width, height) || globals->screenWidth != (float)width || globals->screenHeight != (float)height ||
-	    misaligned(d_commands, 3u) || misaligned(d_clusterIndices, 3u) || misaligned(d_clusterCount4, 3u) || misaligned(d_depth, 3u) ||
-	    misaligned(d_meshlets, 3u) || misaligned(d_meshletData, 3u) || misaligned(d_texels, 3u) || misaligned(d_visibility, 7u) ||
-	    misaligned(d_totals4, 7u) || misaligned(d_alphaTotals2, 7u) || misaligned(d_draws, 15u) || misaligned(d_vertices, 15u) ||
-	    misaligned(d_materials, 15u) || misaligned(d_textures, 15u) || (d_textures != nullptr) != (d_texels != nullptr) || (textureCount && !d_textures) ||
-	    (d_materials && materialCount == 0))
-		return NV_EINVAL;
-	if (d_alphaTotals2 && !ctx->alphaPartials)
-		return NV_ENOMEM; // (nv_create reserves them: a pass never allocates)
-	DeviceGuard guard(ctx->device);
 	nv::RasterAlphaArgs a;
-	a.globals = *globals;
-	a.commands = d_commands;
-	a.draws = d_draws;
-	a.meshlets = d_meshlets;
-	a.meshletData = d_meshletData;
-	a.vertices = d_vertices;
-	a.clusterIndices = d_clusterIndices;
-	a.cc4 = d_clusterCount4;
-	a.depth = reinterpret_cast<uint32_t*>(d_depth);
-	a.visibility = reinterpret_cast<unsigned long long*>(d_visibility);
-	a.width = width;
-	a.height = height;
-	a.smallLimit = ctx->rasterSmallLimit;
-	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
-	a.partials = ctx->totalsPartials;
-	a.materials = d_materials;
-	a.materialCount = d_materials ? materialCount : 0u;
-	a.tx.descs = reinterpret_cast<const uint4*>(d_textures);
-	a.tx.count = d_textures ? textureCount : 0u;
-	a.tx.texels = d_texels;
-	a.tx.texelWords = d_texels ? texelWords : 0u;
-	a.alphaTotals = reinterpret_cast<unsigned long long*>(d_alphaTotals2);
-	a.alphaPartials = d_alphaTotals2 ? ctx->alphaPartials : nullptr;
+	const int rc = fill_raster_set_args(a, ctx, globals, d_commands, d_draws, d_meshlets, d_meshletData, d_vertices, d_clusterIndices, d_clusterCount4, d_depth,
+	                                    width, height, d_visibility, d_totals4, d_materials, materialCount, d_textures, textureCount, d_texels, 3u, texelWords,
+	                                    d_alphaTotals2);
+	if (rc != NV_OK)
+		return rc;
+	DeviceGuard guard(ctx->device);
 	return nv::launch_rasterdepth_alpha((hipStream_t)stream, a, persistent_grid(ctx, 8), ctx->rasterNearClip != 0, ctx->rasterStableIds != 0);
 }
 
-// the same pass over a block-resident set (rasterdepth_blocks.hip)
+// the same pass over a block-resident set
 int nv_rasterdepth_blocks(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshTaskCommand* d_commands, const NvMeshDraw* d_draws,
                           const NvMeshlet* d_meshlets, const uint32_t* d_meshletData, const NvVertex* d_vertices, const uint32_t* d_clusterIndices,
                           const uint32_t* d_clusterCount4, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_visibility, uint64_t* d_totals4,
                           const NvMaterial* d_materials, uint32_t materialCount, const NvTextureBlockDesc* d_textures, uint32_t textureCount,
                           const void* d_blocks, uint64_t units16, uint64_t* d_alphaTotals2)
 {
-	if (!ctx || !globals || !d_commands || !d_draws || !d_meshlets || !d_meshletData || !d_vertices || !d_clusterIndices || !d_clusterCount4 ||
-	    !d_depth || !image_size_ok(width, height) || globals->screenWidth != (float)width || globals->screenHeight != (float)height ||
-	    misaligned(d_commands, 3u) || misaligned(d_clusterIndices, 3u) || misaligned(d_clusterCount4, 3u) || misaligned(d_depth, 3u) ||
-	    misaligned(d_meshlets, 3u) || misaligned(d_meshletData, 3u) || misaligned(d_blocks, 15u) || misaligned(d_visibility, 7u) ||
-	    misaligned(d_totals4, 7u) || misaligned(d_alphaTotals2, 7u) || misaligned(d_draws, 15u) || misaligned(d_vertices, 15u) ||
-	    misaligned(d_materials, 15u) || misaligned(d_textures, 15u) || (d_textures != nullptr) != (d_blocks != nullptr) || (textureCount && !d_textures) ||
-	    (d_materials && materialCount == 0))
-		return NV_EINVAL;
-	if (d_alphaTotals2 && !ctx->alphaPartials)
-		return NV_ENOMEM; // (nv_create reserves them: a pass never allocates)
-	DeviceGuard guard(ctx->device);
 	nv::RasterBlockArgs a;
-	a.globals = *globals;
-	a.commands = d_commands;
-	a.draws = d_draws;
-	a.meshlets = d_meshlets;
-	a.meshletData = d_meshletData;
-	a.vertices = d_vertices;
-	a.clusterIndices = d_clusterIndices;
-	a.cc4 = d_clusterCount4;
-	a.depth = reinterpret_cast<uint32_t*>(d_depth);
-	a.visibility = reinterpret_cast<unsigned long long*>(d_visibility);
-	a.width = width;
-	a.height = height;
-	a.smallLimit = ctx->rasterSmallLimit;
-	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
-	a.partials = ctx->totalsPartials;
-	a.materials = d_materials;
-	a.materialCount = d_materials ? materialCount : 0u;
-	a.tx.descs = reinterpret_cast<const uint4*>(d_textures);
-	a.tx.count = d_textures ? textureCount : 0u;
-	a.tx.blocks = d_blocks;
-	a.tx.units16 = d_blocks ? units16 : 0u;
-	a.alphaTotals = reinterpret_cast<unsigned long long*>(d_alphaTotals2);
-	a.alphaPartials = d_alphaTotals2 ? ctx->alphaPartials : nullptr;
+	const int rc = fill_raster_set_args(a, ctx, globals, d_commands, d_draws, d_meshlets, d_meshletData, d_vertices, d_clusterIndices, d_clusterCount4, d_depth,
+	                                    width, height, d_visibility, d_totals4, d_materials, materialCount, d_textures, textureCount, d_blocks, 15u, units16,
+	                                    d_alphaTotals2);
+	if (rc != NV_OK)
+		return rc;
+	DeviceGuard guard(ctx->device);
 	return nv::launch_rasterdepth_blocks((hipStream_t)stream, a, persistent_grid(ctx, 8), ctx->rasterNearClip != 0, ctx->rasterStableIds != 0);
 }
 
@@ -1265,38 +1355,6 @@ int nv_visibility_resolve(nv_context* ctx, void* stream, const NvCullData* cull,
 	return nv::launch_visibility_resolve((hipStream_t)stream, a, persistent_grid(ctx, 8), ctx->resolvePerPixel != 0);
 }
 
-// The part nv_visibility_attributes and nv_visibility_attributes_textured share (the parameters are the entry points' first twenty, in their
-// order): the refusals both have, then the caller-facing fields of the launch.  Each entry point adds its own rule for the material table.
-static int fill_attribute_args(nv::VisAttrArgs& a, nv_context* ctx, const NvGlobals* globals, const NvVisRecord* d_records, uint32_t width, uint32_t height,
-                               const NvMeshDraw* d_draws, uint32_t drawCount, const NvMeshlet* d_meshlets, uint32_t meshletCount, const uint32_t* d_meshletData,
-                               uint32_t meshletDataWords, const NvVertex* d_vertices, uint32_t vertexCount, const NvMaterial* d_materials, uint32_t materialCount,
-                               NvPixelAttributes* d_attributes, uint32_t* d_gbuffer0, uint32_t* d_gbuffer1, uint64_t* d_totals4)
-{
-	if (!ctx || !globals || !d_records || !image_size_ok(width, height) || globals->screenWidth != (float)width || globals->screenHeight != (float)height ||
-	    (drawCount && !d_draws) || (meshletCount && !d_meshlets) || (meshletDataWords && !d_meshletData) || (vertexCount && !d_vertices) ||
-	    misaligned(d_records, 15u) || misaligned(d_attributes, 15u) || misaligned(d_draws, 15u) || misaligned(d_vertices, 15u) || misaligned(d_materials, 15u) ||
-	    misaligned(d_totals4, 7u) || misaligned(d_meshlets, 3u) || misaligned(d_meshletData, 3u) || misaligned(d_gbuffer0, 3u) || misaligned(d_gbuffer1, 3u))
-		return NV_EINVAL;
-	a.globals = *globals;
-	a.records = reinterpret_cast<const nv::va_u4*>(d_records);
-	a.width = width;
-	a.draws = d_draws;
-	a.drawCount = drawCount;
-	a.meshlets = d_meshlets;
-	a.meshletCount = meshletCount;
-	a.meshletData = d_meshletData;
-	a.dataWords = meshletDataWords;
-	a.vertices = d_vertices;
-	a.vertexCount = vertexCount;
-	a.materials = d_materials;
-	a.materialCount = materialCount;
-	a.attributes = reinterpret_cast<uint4*>(d_attributes);
-	a.gbuffer0 = d_gbuffer0;
-	a.gbuffer1 = d_gbuffer1;
-	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
-	return NV_OK;
-}
-
 int nv_visibility_attributes(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisRecord* d_records, uint32_t width, uint32_t height,
                              const NvMeshDraw* d_draws, uint32_t drawCount, const NvMeshlet* d_meshlets, uint32_t meshletCount,
                              const uint32_t* d_meshletData, uint32_t meshletDataWords, const NvVertex* d_vertices, uint32_t vertexCount,
@@ -1312,7 +1370,7 @@ int nv_visibility_attributes(nv_context* ctx, void* stream, const NvGlobals* glo
 	return nv::launch_visibility_attributes((hipStream_t)stream, a, height, persistent_grid(ctx, 8), ctx->attributesPerPixel != 0);
 }
 
-// ---- material textures (texdecode.hip, visattr_tex.hip, DESIGN.md §4.18)
+// ---- material textures (texdecode.hip, visattr_tex.hip, DESIGN.md §4.18, §4.21)
 int nv_visibility_attributes_textured(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisRecord* d_records, uint32_t width,
                                       uint32_t height, const NvMeshDraw* d_draws, uint32_t drawCount, const NvMeshlet* d_meshlets,
                                       uint32_t meshletCount, const uint32_t* d_meshletData, uint32_t meshletDataWords, const NvVertex* d_vertices,
@@ -1321,19 +1379,15 @@ int nv_visibility_attributes_textured(nv_context* ctx, void* stream, const NvGlo
                                       uint32_t textureCount, const uint32_t* d_texels, uint64_t texelWords)
 {
 	nv::VisAttrTexArgs a;
-	if (fill_attribute_args(a, ctx, globals, d_records, width, height, d_draws, drawCount, d_meshlets, meshletCount, d_meshletData, meshletDataWords, d_vertices,
-	                        vertexCount, d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1, d_totals4) != NV_OK ||
-	    !d_materials || (textureCount && (!d_textures || !d_texels)) || misaligned(d_textures, 15u) || misaligned(d_texels, 3u))
+	if (fill_attribute_set_args(a, ctx, globals, d_records, width, height, d_draws, drawCount, d_meshlets, meshletCount, d_meshletData, meshletDataWords,
+	                            d_vertices, vertexCount, d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1, d_totals4, d_textures, textureCount,
+	                            d_texels, 3u, texelWords) != NV_OK)
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
-	a.tx.descs = reinterpret_cast<const uint4*>(d_textures);
-	a.tx.count = d_textures ? textureCount : 0u;
-	a.tx.texels = d_texels;
-	a.tx.texelWords = texelWords;
 	return nv::launch_visibility_attributes_textured((hipStream_t)stream, a, height, persistent_grid(ctx, 8));
 }
 
-// the same pass over a block-resident set (visattr_blocks.hip)
+// the same pass over a block-resident set
 int nv_visibility_attributes_blocks(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisRecord* d_records, uint32_t width,
                                     uint32_t height, const NvMeshDraw* d_draws, uint32_t drawCount, const NvMeshlet* d_meshlets,
                                     uint32_t meshletCount, const uint32_t* d_meshletData, uint32_t meshletDataWords, const NvVertex* d_vertices,
@@ -1342,15 +1396,11 @@ int nv_visibility_attributes_blocks(nv_context* ctx, void* stream, const NvGloba
                                     uint32_t textureCount, const void* d_blocks, uint64_t units16)
 {
 	nv::VisAttrBlockArgs a;
-	if (fill_attribute_args(a, ctx, globals, d_records, width, height, d_draws, drawCount, d_meshlets, meshletCount, d_meshletData, meshletDataWords, d_vertices,
-	                        vertexCount, d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1, d_totals4) != NV_OK ||
-	    !d_materials || (textureCount && (!d_textures || !d_blocks)) || misaligned(d_textures, 15u) || misaligned(d_blocks, 15u))
+	if (fill_attribute_set_args(a, ctx, globals, d_records, width, height, d_draws, drawCount, d_meshlets, meshletCount, d_meshletData, meshletDataWords,
+	                            d_vertices, vertexCount, d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1, d_totals4, d_textures, textureCount,
+	                            d_blocks, 15u, units16) != NV_OK)
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
-	a.tx.descs = reinterpret_cast<const uint4*>(d_textures);
-	a.tx.count = d_textures ? textureCount : 0u;
-	a.tx.blocks = d_blocks;
-	a.tx.units16 = units16;
 	return nv::launch_visibility_attributes_blocks((hipStream_t)stream, a, height, persistent_grid(ctx, 8));
 }
 
@@ -1661,22 +1711,6 @@ int nv_rt_scene_download(nv_context* ctx, void* stream, void* out, uint64_t* byt
 	}
 }
 
-// what nv_shadow_trace and nv_shadow_trace_textured share: the refusals, then the caller-facing fields of the opaque launch
-static int fill_trace_args(nv::ShadowTraceArgs& a, nv_context* ctx, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width,
-                           uint32_t height, int quality)
-{
-	if (!ctx || !ctx->rtScene || !shadow || !d_depth || !d_shadow || !image_size_ok(width, height) || shadow->imageSize[0] != (float)width ||
-	    shadow->imageSize[1] != (float)height || quality < 0 || quality > 1 || misaligned(d_depth, 3u))
-		return NV_EINVAL;
-	a.sd = *shadow;
-	a.scene = static_cast<const unsigned char*>(ctx->rtScene);
-	a.depth = d_depth;
-	a.shadow = d_shadow;
-	a.width = width;
-	a.height = height;
-	return NV_OK;
-}
-
 int nv_shadow_trace(nv_context* ctx, void* stream, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width, uint32_t height,
                     int quality)
 {
@@ -1687,65 +1721,35 @@ int nv_shadow_trace(nv_context* ctx, void* stream, const NvShadowData* shadow, c
 	return nv::launch_shadow_trace((hipStream_t)stream, a, quality, persistent_grid(ctx, 8));
 }
 
-// the alpha-tested trace (shadowtrace_alpha.hip); quality 0 has no alpha test and is nv_shadow_trace's launch
+// the alpha-tested trace; quality 0 has no alpha test and is nv_shadow_trace's launch
 int nv_shadow_trace_textured(nv_context* ctx, void* stream, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width, uint32_t height,
                              int quality, const NvMeshDraw* d_draws, uint32_t drawCount, const NvMaterial* d_materials, uint32_t materialCount,
                              const NvTextureDesc* d_textures, uint32_t textureCount, const uint32_t* d_texels, uint64_t texelWords)
 {
 	nv::ShadowTraceArgs opaque;
-	if (fill_trace_args(opaque, ctx, shadow, d_depth, d_shadow, width, height, quality) != NV_OK || !(ctx->rtSceneFlags & nv::RT_FLAG_TEXCOORDS) ||
-	    (drawCount && !d_draws) || (materialCount && !d_materials) || (textureCount && !d_textures) || (texelWords && !d_texels) || misaligned(d_draws, 15u) ||
-	    misaligned(d_materials, 15u) || misaligned(d_textures, 15u) || misaligned(d_texels, 3u))
+	nv::ShadowTraceAlphaArgs a;
+	if (fill_trace_alpha(a, opaque, ctx, shadow, d_depth, d_shadow, width, height, quality, d_draws, drawCount, d_materials, materialCount, d_textures,
+	                     textureCount, d_texels, 3u, texelWords) != NV_OK)
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	if (quality == 0)
 		return nv::launch_shadow_trace((hipStream_t)stream, opaque, 0, persistent_grid(ctx, 8));
-	nv::ShadowTraceAlphaArgs a;
-	a.sd = opaque.sd;
-	a.in.draws = d_draws;
-	a.in.materials = d_materials;
-	a.in.textures = reinterpret_cast<const nv::TxDesc*>(d_textures);
-	a.in.texels = d_texels;
-	a.in.texelWords = texelWords;
-	a.in.drawCount = drawCount;
-	a.in.materialCount = materialCount;
-	a.in.textureCount = textureCount;
-	a.scene = opaque.scene;
-	a.depth = d_depth;
-	a.shadow = d_shadow;
-	a.width = width;
-	a.height = height;
 	return nv::launch_shadow_trace_alpha((hipStream_t)stream, a, persistent_grid(ctx, 8));
 }
 
-// the same over a block-resident set (shadowtrace_blocks.hip)
+// the same over a block-resident set
 int nv_shadow_trace_blocks(nv_context* ctx, void* stream, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width, uint32_t height,
                            int quality, const NvMeshDraw* d_draws, uint32_t drawCount, const NvMaterial* d_materials, uint32_t materialCount,
                            const NvTextureBlockDesc* d_textures, uint32_t textureCount, const void* d_blocks, uint64_t units16)
 {
 	nv::ShadowTraceArgs opaque;
-	if (fill_trace_args(opaque, ctx, shadow, d_depth, d_shadow, width, height, quality) != NV_OK || !(ctx->rtSceneFlags & nv::RT_FLAG_TEXCOORDS) ||
-	    (drawCount && !d_draws) || (materialCount && !d_materials) || (textureCount && !d_textures) || (units16 && !d_blocks) || misaligned(d_draws, 15u) ||
-	    misaligned(d_materials, 15u) || misaligned(d_textures, 15u) || misaligned(d_blocks, 15u))
+	nv::ShadowTraceBlockArgs a;
+	if (fill_trace_alpha(a, opaque, ctx, shadow, d_depth, d_shadow, width, height, quality, d_draws, drawCount, d_materials, materialCount, d_textures,
+	                     textureCount, d_blocks, 15u, units16) != NV_OK)
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	if (quality == 0)
 		return nv::launch_shadow_trace((hipStream_t)stream, opaque, 0, persistent_grid(ctx, 8));
-	nv::ShadowTraceBlockArgs a;
-	a.sd = opaque.sd;
-	a.in.draws = d_draws;
-	a.in.materials = d_materials;
-	a.in.textures = reinterpret_cast<const nv::TxBlockDesc*>(d_textures);
-	a.in.blocks = d_blocks;
-	a.in.units16 = units16;
-	a.in.drawCount = drawCount;
-	a.in.materialCount = materialCount;
-	a.in.textureCount = textureCount;
-	a.scene = opaque.scene;
-	a.depth = d_depth;
-	a.shadow = d_shadow;
-	a.width = width;
-	a.height = height;
 	return nv::launch_shadow_trace_blocks((hipStream_t)stream, a, persistent_grid(ctx, 8));
 }
 

@@ -1,11 +1,12 @@
 // fragalpha.h — what the fragment's albedo.a needs (mesh.frag.glsl:62-64, :88), in ONE text for its two users: the attribute pass (visattr.h,
 // DESIGN.md §4.13, §4.18) and the alpha-tested depth raster (rasterdepth.h with ALPHA, §4.20).  A corner as clip x, y, w plus its packed
-// texcoord, the homogeneous barycentrics with their degenerate rule, uv's steps to the two neighbouring pixel centres, the guarded texture
-// read and the alpha of a material.  Both stages feed it rd_clip_position's bits, so the same triangle at the same pixel gives the same alpha.
+// texcoord, the homogeneous barycentrics with their degenerate rule, uv's steps to the two neighbouring pixel centres and the alpha of a
+// material.  Both stages feed it rd_clip_position's bits, so the same triangle at the same pixel gives the same alpha.  The texture itself is
+// read through the set's residency type (texmath.h; args.h TxTable::desc is the guarded look-up).
 #pragma once
 #include "cullmath.h"
 #include "args.h"
-#define NV_TX_SAMPLER_ONLY // (neither user decodes blocks: keep the BC tables out of their code objects)
+#define NV_TX_SAMPLER_ONLY // (a block translation unit has included texmath.h in full ahead of this; the others keep the BC tables out of their code objects)
 #include "texmath.h"
 
 namespace nv
@@ -48,17 +49,6 @@ NV_DEV void fa_uv_steps(const FaCorner& a, const FaCorner& b, const FaCorner& c,
 	dudx = degenX ? 0.0f : va_mix(m0, m1, m2, ua, ub, uc) - u, dvdx = degenX ? 0.0f : va_mix(m0, m1, m2, va, vb, vc) - v;
 	const bool degenY = fa_bary(a, b, c, fx, (float)(py + 1u) + 0.5f, fw, fh, m0, m1, m2);
 	dudy = degenY ? 0.0f : va_mix(m0, m1, m2, ua, ub, uc) - u, dvdy = degenY ? 0.0f : va_mix(m0, m1, m2, va, vb, vc) - v;
-}
-
-// textures[id]'s descriptor.  false: id is past the table or the descriptor's chain does not lie inside texelWords (§4.18: the texture is
-// treated as absent); nothing is ever loaded from the texel buffer through a descriptor this refused.
-NV_DEV bool fa_texture_desc(const VaTextures& tx, uint32_t id, TxDesc& d)
-{
-	if (id >= tx.count)
-		return false;
-	const uint4 w = tx.descs[id];
-	d = TxDesc{ w.x, w.y, w.z, w.w };
-	return tx_desc_ok(d, tx.texelWords);
 }
 
 // albedo.a (:62-64): diffuseFactor.a, times the albedo texel's .a where the texture is sampled (fromsrgb leaves .a as it is)

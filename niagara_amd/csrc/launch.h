@@ -70,8 +70,7 @@ int launch_trianglecull(hipStream_t, const TriangleArgs& a, uint32_t gridBlocks)
 int launch_rasterdepth(hipStream_t, const RasterArgs& a, uint32_t gridBlocks, bool nearClip, bool stableIds);
 int launch_rasterdepth_alpha(hipStream_t, const RasterAlphaArgs& a, uint32_t gridBlocks, bool nearClip, bool stableIds);
 int launch_rasterdepth_blocks(hipStream_t, const RasterBlockArgs& a, uint32_t gridBlocks, bool nearClip, bool stableIds);
-int launch_raster_alpha_totals(hipStream_t, const unsigned long long* partials, uint32_t blocks, unsigned long long* totals); // (rasterdepth_alpha.hip)
-int launch_raster_totals(hipStream_t, const unsigned long long* partials, uint32_t blocks, unsigned long long* totals); // (rasterindexed.hip's too)
+int launch_raster_totals(hipStream_t, const unsigned long long* partials, uint32_t blocks, unsigned long long* totals, uint32_t counters); // (rasterindexed.hip's too)
 int launch_rasterindexed(hipStream_t, RasterIndexedArgs a, void* scratch, uint32_t gridBlocks, bool nearClip);
 size_t rasterindexed_scratch_bytes(uint32_t drawCount);
 // depthmerge.hip

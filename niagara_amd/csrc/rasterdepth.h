@@ -1,11 +1,13 @@
 // rasterdepth.h — the kernel of the depth rasteriser of the visible clusters as ONE text for its entry points:
-// rasterdepth.hip instantiates rasterdepth_kernel<CLIP, STABLE> (nv_rasterdepth) and rasterdepth_alpha.hip
-// rasterdepth_kernel<CLIP, STABLE, true, RasterAlphaArgs> (nv_rasterdepth_textured: covered samples of a post-pass launch also pass the
-// fragment's alpha test; rasterdepth_blocks.hip the same with RasterBlockArgs, over a block-resident texture set, §4.21).  ALPHA only adds statements under `if constexpr (ALPHA)`, so the four kernels of nv_rasterdepth keep their
-// instruction streams.  rasterdepth.hip's header describes the shape.
+// rasterdepth.hip instantiates rasterdepth_kernel<CLIP, STABLE> (nv_rasterdepth) and rasterdepth_alpha.hip and rasterdepth_blocks.hip
+// rasterdepth_kernel<CLIP, STABLE, true, RasterSetArgs<SET>> (nv_rasterdepth_textured, nv_rasterdepth_blocks: covered samples of a post-pass
+// launch also pass the fragment's alpha test against a texture set of residency SET, texmath.h's TxDecoded or TxBlocks, §4.21).  ALPHA only adds
+// statements under `if constexpr (ALPHA)`, so the four kernels of nv_rasterdepth keep their instruction streams.  rasterdepth.hip's header
+// describes the shape.  The launch of every instantiation is launch_rasterdepth_as below.
 #pragma once
 #include "raster.h"
 #include "fragalpha.h"
+#include "launch.h"
 
 namespace nv
 {
@@ -36,14 +38,11 @@ struct RdAlphaSlot
 {
 	uint32_t mode; // RD_A_*; 0: albedo.a = diffuseFactor.a >= 0.5 (or NaN), or the launch does not test
 	float factor;  // diffuseFactor.a
-	TxDesc desc;   // RD_A_TEXTURED: the albedo texture's descriptor, accepted by tx_desc_ok (the block set: TxBlockDesc's four words, by tx_block_desc_ok)
+	TxDesc desc;   // RD_A_TEXTURED: the albedo texture's descriptor, accepted by the set (TxTable::desc): its four words, whatever the set calls them
 };
 
-// the albedo texture's descriptor of a slot; false as fa_texture_desc.  (The block set's overload is rasterdepth_blocks.hip's.)
-NV_DEV bool rd_slot_desc(const VaTextures& tx, uint32_t id, TxDesc& d) { return fa_texture_desc(tx, id, d); }
-
 // The slot record of a draw's material.  Every load is behind the check that keeps it inside the caller's tables.
-// ARGS = RasterAlphaArgs or RasterBlockArgs
+// ARGS = RasterSetArgs<SET>
 template <typename ARGS>
 NV_DEV void rd_alpha_slot(const ARGS& a, uint32_t materialIndex, uint32_t& mode, float& factor, uint4& desc)
 {
@@ -56,11 +55,12 @@ NV_DEV void rd_alpha_slot(const ARGS& a, uint32_t materialIndex, uint32_t& mode,
 	mode = 0u;
 	if (albedoTexture != 0u) // mesh.frag.glsl:63
 	{
-		TxDesc d;
-		if (rd_slot_desc(a.tx, albedoTexture, d))
+		typename ARGS::Set::Desc d;
+		if (a.tx.desc(albedoTexture, d))
 		{
+			const auto& [w0, w1, w2, w3] = d;
 			mode = RD_A_TEXTURED;
-			desc = make_uint4(d.offset, d.width, d.height, d.levels);
+			desc = make_uint4(w0, w1, w2, w3);
 			return;
 		}
 		mode = RD_A_UNEVALUATED;
@@ -68,27 +68,13 @@ NV_DEV void rd_alpha_slot(const ARGS& a, uint32_t materialIndex, uint32_t& mode,
 	mode |= fa_discard(factor) ? RD_A_DROP_ALL : 0u;
 }
 
-// the slot's albedo texture at (u, v) from the decoded set (the block set's overload, over its bytes, is rasterdepth_blocks.hip's)
-NV_DEV TxF4 rd_texture(const uint32_t* texels, const TxDesc& desc, float u, float v, float dudx, float dvdx, float dudy, float dvdy)
-{
-	return tx_sample(texels, desc, u, v, dudx, dvdx, dudy, dvdy);
-}
-
-// What the kernel hands rd_sample_alpha as the texel buffer: the decoded set's words (the block set: its bytes, a specialisation of
-// rasterdepth_blocks.hip's)
-template <typename ARGS>
-struct RdTexels
-{
-	typedef uint32_t type;
-	static NV_DEV const type* of(const ARGS& a) { return a.tx.texels; }
-};
-
 // rd_sample with the fragment's alpha test between the coverage and the atomics: the attribute pass's arithmetic (fragalpha.h) for the
-// ORIGINAL triangle's corners (ca, cb, cc: stored order) at this pixel.  A dropped sample loads, compares and writes nothing.
-template <bool STABLE, class ID, class TEXEL>
-NV_DEV void rd_sample_alpha(const RdTri& t, const RdAlphaSlot& m, const TEXEL* __restrict__ texels, const FaCorner& ca, const FaCorner& cb, const FaCorner& cc,
-                            int32_t px, int32_t py, uint32_t W, float fw, float fh, uint32_t* __restrict__ depth, unsigned long long* __restrict__ vis, ID id,
-                            unsigned long long& kept, unsigned long long& dropped, unsigned long long& unevaluated)
+// ORIGINAL triangle's corners (ca, cb, cc: stored order) at this pixel, the albedo texture sampled from `texels`, the buffer of a set of
+// residency SET.  A dropped sample loads, compares and writes nothing.
+template <bool STABLE, class SET, class ID>
+NV_DEV void rd_sample_alpha(const RdTri& t, const RdAlphaSlot& m, const typename SET::Unit* __restrict__ texels, const FaCorner& ca, const FaCorner& cb,
+                            const FaCorner& cc, int32_t px, int32_t py, uint32_t W, float fw, float fh, uint32_t* __restrict__ depth,
+                            unsigned long long* __restrict__ vis, ID id, unsigned long long& kept, unsigned long long& dropped, unsigned long long& unevaluated)
 {
 	int64_t wb, wc;
 	if (!rd_covered(t, px, py, wb, wc))
@@ -103,7 +89,7 @@ NV_DEV void rd_sample_alpha(const RdTri& t, const RdAlphaSlot& m, const TEXEL* _
 		const float v = va_mix(l0, l1, l2, half_bits_to_float(ca.uv >> 16), half_bits_to_float(cb.uv >> 16), half_bits_to_float(cc.uv >> 16));
 		float dudx, dvdx, dudy, dvdy;
 		fa_uv_steps(ca, cb, cc, (uint32_t)px, (uint32_t)py, fx, fy, fw, fh, u, v, dudx, dvdx, dudy, dvdy);
-		const TxF4 c = rd_texture(texels, m.desc, u, v, dudx, dvdx, dudy, dvdy);
+		const TxF4 c = SET::sample(texels, typename SET::Desc{ m.desc.offset, m.desc.width, m.desc.height, m.desc.levels }, u, v, dudx, dvdx, dudy, dvdy);
 		drop = fa_discard(fa_alpha(m.factor, c.w));
 	}
 	if (!drop)
@@ -115,7 +101,7 @@ NV_DEV void rd_sample_alpha(const RdTri& t, const RdAlphaSlot& m, const TEXEL* _
 
 NV_DEV FaCorner rd_corner(float4 v) { return FaCorner{ v.x, v.y, v.z, __float_as_uint(v.w) }; }
 
-// ARGS = RasterArgs (ALPHA = false) or RasterAlphaArgs (ALPHA = true)
+// ARGS = RasterArgs (ALPHA = false) or RasterSetArgs<SET> (ALPHA = true)
 template <bool CLIP, bool STABLE, bool ALPHA = false, typename ARGS = RasterArgs>
 __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(ARGS a)
 {
@@ -148,14 +134,12 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(ARGS a)
 	float4* attr = nullptr;
 	bool alphaOn = false;
 	float fw = 0.0f, fh = 0.0f;
-	const typename RdTexels<ARGS>::type* texels = nullptr;
 	unsigned long long dropped = 0, unevaluated = 0; // per lane
 	if constexpr (ALPHA)
 	{
 		attr = s_attr[wave];
 		alphaOn = bothFaces && a.materials != nullptr;
 		fw = (float)a.width, fh = (float)a.height;
-		texels = RdTexels<ARGS>::of(a);
 	}
 
 	uint32_t clusters = 0, triangles = 0; // wave-uniform
@@ -294,8 +278,8 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(ARGS a)
 										ca = rd_corner(attr[ia]), cb = rd_corner(attr[ib]), cc = rd_corner(attr[ic]);
 									for (int32_t py = tri.y0; py <= tri.y1; ++py)
 										for (int32_t px = tri.x0; px <= tri.x1; ++px)
-											rd_sample_alpha<STABLE>(tri, slot, texels, ca, cb, cc, px, py, a.width, fw, fh, a.depth, STABLE ? vis : a.visibility, id, samples,
-											                        dropped, unevaluated);
+											rd_sample_alpha<STABLE, typename ARGS::Set>(tri, slot, a.tx.data, ca, cb, cc, px, py, a.width, fw, fh, a.depth,
+											                                            STABLE ? vis : a.visibility, id, samples, dropped, unevaluated);
 								}
 								else
 								{
@@ -352,8 +336,8 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(ARGS a)
 											ca = rd_corner(attr[ia]), cb = rd_corner(attr[ib]), cc = rd_corner(attr[ic]);
 										for (int32_t py = tri.y0; py <= tri.y1; ++py)
 											for (int32_t px = tri.x0; px <= tri.x1; ++px)
-												rd_sample_alpha<STABLE>(tri, slot, texels, ca, cb, cc, px, py, a.width, fw, fh, a.depth, STABLE ? vis : a.visibility, id,
-												                        samples, dropped, unevaluated);
+												rd_sample_alpha<STABLE, typename ARGS::Set>(tri, slot, a.tx.data, ca, cb, cc, px, py, a.width, fw, fh, a.depth,
+												                                            STABLE ? vis : a.visibility, id, samples, dropped, unevaluated);
 									}
 									else
 									{
@@ -412,8 +396,8 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(ARGS a)
 						if constexpr (ALPHA)
 						{
 							if (px <= tri.x1 && py <= tri.y1)
-								rd_sample_alpha<STABLE>(tri, slot, texels, ca, cb, cc, px, py, a.width, fw, fh, a.depth, STABLE ? vis : a.visibility, id, samples, dropped,
-								                        unevaluated);
+								rd_sample_alpha<STABLE, typename ARGS::Set>(tri, slot, a.tx.data, ca, cb, cc, px, py, a.width, fw, fh, a.depth,
+								                                            STABLE ? vis : a.visibility, id, samples, dropped, unevaluated);
 						}
 						else if (px <= tri.x1 && py <= tri.y1)
 							samples += rd_sample<STABLE>(tri, px, py, a.width, a.depth, STABLE ? vis : a.visibility, id) ? 1u : 0u;
@@ -423,7 +407,7 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(ARGS a)
 		}
 	}
 
-	// totals: per-workgroup partial sums, plain stores; rasterdepth_totals_kernel adds them up (ALPHA: two more, dropped and unevaluated samples)
+	// totals: per-workgroup partial sums, plain stores; rasterdepth_totals_kernel (rasterdepth.hip) adds them up (ALPHA: two more, dropped and unevaluated samples)
 	constexpr int TOTALS = ALPHA ? 6 : 4;
 	__shared__ unsigned long long s_tot[RD_WAVES][TOTALS];
 	unsigned long long d = drawn, smp = samples;
@@ -462,6 +446,32 @@ __global__ __launch_bounds__(RD_THREADS) void rasterdepth_kernel(ARGS a)
 			if (threadIdx.x >= 4 && a.alphaPartials)
 				a.alphaPartials[(size_t)blockIdx.x * 2 + (threadIdx.x - 4)] = t;
 	}
+}
+
+// The launch of one pass, for every ARGS: the kernel by near clip and id form, then the totals launches the caller asked for
+template <bool ALPHA, typename ARGS>
+int launch_rasterdepth_as(hipStream_t stream, const ARGS& a, uint32_t gridBlocks, bool nearClip, bool stableIds)
+{
+	gridBlocks = gridBlocks / 8 * RD_BLOCKS_PER_CU; // the caller passes 8 workgroups per CU, the size of `partials` and `alphaPartials`
+	// (the stable form differs only in the visibility word: without a visibility target the launch is the default kernel)
+	if (stableIds && a.visibility)
+	{
+		if (nearClip)
+			hipLaunchKernelGGL((rasterdepth_kernel<true, true, ALPHA, ARGS>), dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
+		else
+			hipLaunchKernelGGL((rasterdepth_kernel<false, true, ALPHA, ARGS>), dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
+	}
+	else if (nearClip)
+		hipLaunchKernelGGL((rasterdepth_kernel<true, false, ALPHA, ARGS>), dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
+	else
+		hipLaunchKernelGGL((rasterdepth_kernel<false, false, ALPHA, ARGS>), dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
+	hipError_t e = hipGetLastError();
+	if (e == hipSuccess && a.totals)
+		e = (hipError_t)launch_raster_totals(stream, a.partials, gridBlocks, a.totals, 4);
+	if constexpr (ALPHA)
+		if (e == hipSuccess && a.alphaTotals)
+			e = (hipError_t)launch_raster_totals(stream, a.alphaPartials, gridBlocks, a.alphaTotals, 2);
+	return (int)e;
 }
 
 } // namespace nv

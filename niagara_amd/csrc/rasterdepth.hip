@@ -23,8 +23,8 @@
 // meshlet-visibility index, fetched with the slot's header, instead of bits(z) << 32 | slot << 7 | triangle.  STABLE = false is the kernel
 // without it, instruction for instruction.
 //
-// The kernel's text is rasterdepth.h's (shared with rasterdepth_alpha.hip, which instantiates it with ALPHA: DESIGN.md §4.20); this file
-// instantiates the four kernels of nv_rasterdepth and holds the totals launch both entry points use.
+// The kernel's text and its launch are rasterdepth.h's (shared with rasterdepth_alpha.hip, which instantiates them with ALPHA: DESIGN.md §4.20); this
+// file instantiates the four kernels of nv_rasterdepth and holds the totals launch every raster entry point uses.
 #include "rasterdepth.h"
 
 namespace nv
@@ -52,31 +52,46 @@ __global__ __launch_bounds__(256) void rasterdepth_totals_kernel(const unsigned 
 		totals[threadIdx.x] += s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
 }
 
-int launch_raster_totals(hipStream_t stream, const unsigned long long* partials, uint32_t blocks, unsigned long long* totals)
+// The same for the two alpha totals {dropped, unevaluated} of an ALPHA launch.  Not the kernel above as a template over the number of counters: its
+// instantiation for two allocates other registers than this text does, and the kernels keep their code (profiles/texture_set_refactor.md)
+__global__ __launch_bounds__(256) void rasterdepth_alpha_totals_kernel(const unsigned long long* __restrict__ partials, uint32_t blocks,
+                                                                       unsigned long long* __restrict__ totals)
 {
-	hipLaunchKernelGGL(rasterdepth_totals_kernel, dim3(1), dim3(256), 0, stream, partials, blocks, totals);
+	__shared__ unsigned long long s_part[4][2];
+	unsigned long long t0 = 0, t1 = 0;
+	for (uint32_t i = threadIdx.x; i < blocks; i += 256)
+	{
+		t0 += partials[(size_t)i * 2];
+		t1 += partials[(size_t)i * 2 + 1];
+	}
+	for (int o = 32; o > 0; o >>= 1)
+	{
+		t0 += __shfl_xor(t0, o, 64);
+		t1 += __shfl_xor(t1, o, 64);
+	}
+	if ((threadIdx.x & 63u) == 0)
+	{
+		s_part[threadIdx.x >> 6][0] = t0;
+		s_part[threadIdx.x >> 6][1] = t1;
+	}
+	__syncthreads();
+	if (threadIdx.x < 2)
+		totals[threadIdx.x] += s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
+}
+
+// counters = 4 (the raster totals) or 2 (the alpha totals)
+int launch_raster_totals(hipStream_t stream, const unsigned long long* partials, uint32_t blocks, unsigned long long* totals, uint32_t counters)
+{
+	if (counters == 4u)
+		hipLaunchKernelGGL(rasterdepth_totals_kernel, dim3(1), dim3(256), 0, stream, partials, blocks, totals);
+	else
+		hipLaunchKernelGGL(rasterdepth_alpha_totals_kernel, dim3(1), dim3(256), 0, stream, partials, blocks, totals);
 	return (int)hipGetLastError();
 }
 
 int launch_rasterdepth(hipStream_t stream, const RasterArgs& a, uint32_t gridBlocks, bool nearClip, bool stableIds)
 {
-	gridBlocks = gridBlocks / 8 * RD_BLOCKS_PER_CU; // the caller passes 8 workgroups per CU, the size of `partials`
-	// (the stable form differs only in the visibility word: without a visibility target the launch is the default kernel)
-	if (stableIds && a.visibility)
-	{
-		if (nearClip)
-			hipLaunchKernelGGL((rasterdepth_kernel<true, true>), dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
-		else
-			hipLaunchKernelGGL((rasterdepth_kernel<false, true>), dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
-	}
-	else if (nearClip)
-		hipLaunchKernelGGL((rasterdepth_kernel<true, false>), dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
-	else
-		hipLaunchKernelGGL((rasterdepth_kernel<false, false>), dim3(gridBlocks), dim3(RD_THREADS), 0, stream, a);
-	hipError_t e = hipGetLastError();
-	if (e != hipSuccess || !a.totals)
-		return (int)e;
-	return launch_raster_totals(stream, a.partials, gridBlocks, a.totals);
+	return launch_rasterdepth_as<false>(stream, a, gridBlocks, nearClip, stableIds);
 }
 
 } // namespace nv

@@ -432,7 +432,7 @@ int launch_rasterindexed(hipStream_t stream, RasterIndexedArgs a, void* scratch,
 	hipError_t e = hipGetLastError();
 	if (e != hipSuccess || !a.totals)
 		return (int)e;
-	return launch_raster_totals(stream, a.partials, gridBlocks, a.totals);
+	return launch_raster_totals(stream, a.partials, gridBlocks, a.totals, 4);
 }
 
 } // namespace nv

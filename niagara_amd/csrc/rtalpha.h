@@ -1,7 +1,8 @@
 // rtalpha.h — the alpha-tested traversal of the ray-traced shadow pass in ONE place that compiles for the device (hipcc) and
 // for the host (g++): shadowTraceTransparent of shadow.comp.glsl:86-123.  The triangle test that hands back its U, V, W and det, the albedo
-// texture of an instance, the four alpha taps of textureLod(..., 0).w, and rt_occluded_alpha, rtmath.h's rt_occluded with the confirming loop.
-// shadowtrace_alpha.hip's kernel and nv_rt_scene_trace_host_textured_rays run the same text; tests/shadow_alpha_ref.c restates it without a BVH.
+// texture of an instance, and rt_occluded_alpha, rtmath.h's rt_occluded with the confirming loop.  The texture set is asked through its residency
+// type (texmath.h: TxDecoded or TxBlocks, RtAlphaInputs<SET>::Set), whose alpha_lod0 holds the four alpha taps of textureLod(..., 0).w.
+// shadowtrace_alpha.hip's kernels and nv_rt_scene_trace_host_textured_rays run the same text; tests/shadow_alpha_ref.c restates it without a BVH.
 //
 // Build with -ffp-contract=off.  rtmath.h's rt_triangle and rt_occluded are not touched: nv_shadow_trace's kernels keep their code.
 #pragma once
@@ -67,9 +68,10 @@ NV_RT bool rt_triangle_uvw(const RtRay& r, rt3 v0, rt3 v1, rt3 v2, float tmin, f
 }
 
 // The albedo texture the alpha test of draw `drawId` samples (shadow.comp.glsl:108-117): false = alpha is 1.  A draw, material or texture
-// index out of range, texture 0 (:116) and a descriptor whose chain does not lie inside texelWords are all "no texture": nothing is loaded
-// through an index that was not checked.
-NV_RT bool rt_alpha_texture(const RtAlphaInputs& in, uint32_t drawId, TxDesc* desc)
+// index out of range, texture 0 (:116) and a descriptor the set refuses (SET::ok: its chain does not lie inside the set's buffer) are all
+// "no texture": nothing is loaded through an index that was not checked.
+template <typename SET>
+NV_RT bool rt_albedo_desc(const RtAlphaInputs<SET>& in, uint32_t drawId, typename SET::Desc* desc)
 {
 	if (drawId >= in.drawCount)
 		return false;
@@ -80,25 +82,7 @@ NV_RT bool rt_alpha_texture(const RtAlphaInputs& in, uint32_t drawId, TxDesc* de
 	if (tex == 0u || tex >= in.textureCount)
 		return false;
 	*desc = in.textures[tex];
-	return tx_desc_ok(*desc, in.texelWords);
-}
-
-// tx_sample_lod0(texels, t, u, v).w with the four alpha taps of level 0 alone.  tx_sample_lod at lambda = 0 blends level 0 with weight 1 - 0
-// and level min(1, levels - 1) with weight 0: lo * 1 + hi * 0.  Every alpha is in [0, 1] or NaN, and a NaN comes from u, v alone (tx_axis), so
-// hi is NaN only where lo is: for a finite lo the blend is lo + 0 = lo (lo >= 0, never -0), for a NaN lo it is NaN like lo.  The taps of the
-// second level and the three colour channels change nothing and are left out; tests/test_shadow_alpha_cpu.py holds the two forms bit-identical
-// (a NaN for a NaN: its sign and payload are no result, the test that follows is alpha >= 0.5).
-// t has passed tx_desc_ok: tx_axis keeps every index inside level 0 for EVERY bit pattern of u, v.
-NV_RT float rt_alpha_lod0(const uint32_t* texels, const TxDesc& t, float u, float v)
-{
-	uint32_t x0, x1, y0, y1;
-	float ax, ay;
-	tx_axis(u, t.width, x0, x1, ax);
-	tx_axis(v, t.height, y0, y1, ay);
-	const uint64_t r0 = (uint64_t)t.offset + (uint64_t)y0 * t.width, r1 = (uint64_t)t.offset + (uint64_t)y1 * t.width;
-	const uint32_t c00 = texels[r0 + x0], c01 = texels[r0 + x1], c10 = texels[r1 + x0], c11 = texels[r1 + x1]; // the four loads together
-	const float a00 = (float)(c00 >> 24) / 255.0f, a01 = (float)(c01 >> 24) / 255.0f, a10 = (float)(c10 >> 24) / 255.0f, a11 = (float)(c11 >> 24) / 255.0f;
-	return tx_lerp(tx_lerp(a00, a01, ax), tx_lerp(a10, a11, ax), ay);
+	return SET::ok(*desc, in.extent);
 }
 
 // uv of an accepted triangle at the hit (shadow.comp.glsl:110-116); w0, w1, w2: the corners' packed texcoord bits tu | tv << 16
@@ -115,28 +99,13 @@ NV_RT RtUv rt_hit_uv(const RtHit& hit, uint32_t w0, uint32_t w1, uint32_t w2)
 	return RtUv{ u, v };
 }
 
-// the alpha of an accepted triangle at the hit (:117)
-NV_RT float rt_hit_alpha(const uint32_t* texels, const TxDesc& t, const RtHit& hit, uint32_t w0, uint32_t w1, uint32_t w2)
-{
-	const RtUv at = rt_hit_uv(hit, w0, w1, w2);
-	return rt_alpha_lod0(texels, t, at.u, at.v);
-}
-
-// what rt_occluded_alpha asks of its inputs, for the decoded set: the descriptor of "no texture yet" and the alpha at a hit.  The block set's
-// three (rt_alpha_texture, rt_alpha_none, rt_hit_alpha over RtAlphaBlockInputs) are shadowtrace_blocks.hip's.
-NV_RT TxDesc rt_alpha_none(const RtAlphaInputs&) { return TxDesc{ 0u, 1u, 1u, 1u }; }
-NV_RT float rt_hit_alpha(const RtAlphaInputs& in, const TxDesc& t, const RtHit& hit, uint32_t w0, uint32_t w1, uint32_t w2)
-{
-	return rt_hit_alpha(in.texels, t, hit, w0, w1, w2);
-}
-
 // rt_occluded(..., 1) whose hits are CONFIRMED: a triangle of a postPass == 0 instance always (FORCE_OPAQUE, src/scenert.cpp:516), one of a
 // postPass == 1 instance when its alpha is >= 0.5 (a NaN does not confirm).  The instance's texture is resolved once, where its BLAS is
 // entered; an instance without one confirms unconditionally and leaves at its first accepted triangle, as rt_occluded does.  The result is an OR
 // over the accepted triangles: it does not depend on the order of the walk.  The blob has passed nv_rt_scene_validate and carries
-// RT_FLAG_TEXCOORDS.  INPUTS = RtAlphaInputs or RtAlphaBlockInputs: one text for both residencies of the texture set.
-template <typename INPUTS>
-NV_RT bool rt_occluded_alpha(const unsigned char* blob, const INPUTS& in, rt3 o, rt3 d, float tmin, float tmax)
+// RT_FLAG_TEXCOORDS.  One text for both residencies of the texture set.
+template <typename SET>
+NV_RT bool rt_occluded_alpha(const unsigned char* blob, const RtAlphaInputs<SET>& in, rt3 o, rt3 d, float tmin, float tmax)
 {
 	if (!(rt_finite(o.x) && rt_finite(o.y) && rt_finite(o.z) && rt_finite(d.x) && rt_finite(d.y) && rt_finite(d.z)))
 		return false;
@@ -170,8 +139,8 @@ NV_RT bool rt_occluded_alpha(const unsigned char* blob, const INPUTS& in, rt3 o,
 		const uint32_t postPass = rt_bits(i2.y);
 		if (postPass > 1u)
 			continue;
-		auto tex = rt_alpha_none(in);
-		const bool tested = postPass == 1u && rt_alpha_texture(in, rt_bits(i2.x), &tex);
+		typename SET::Desc tex = SET::none();
+		const bool tested = postPass == 1u && rt_albedo_desc(in, rt_bits(i2.x), &tex);
 		const float position[3] = { i0.x, i0.y, i0.z }, orientation[4] = { i1.x, i1.y, i1.z, i1.w };
 		rt3 o2, d2;
 		rt_object_ray(o, d, position, orientation, i0.w, &o2, &d2);
@@ -209,7 +178,8 @@ NV_RT bool rt_occluded_alpha(const unsigned char* blob, const INPUTS& in, rt3 o,
 					continue;
 				if (!tested)
 					return true;
-				if (rt_hit_alpha(in, tex, hit, rt_bits(v0.w), rt_bits(v1.w), rt_bits(v2.w)) >= 0.5f) // :118; a NaN does not confirm
+				const RtUv at = rt_hit_uv(hit, rt_bits(v0.w), rt_bits(v1.w), rt_bits(v2.w));
+				if (SET::alpha_lod0(in.data, tex, at.u, at.v) >= 0.5f) // :117-118; a NaN does not confirm
 					return true;
 			}
 		}

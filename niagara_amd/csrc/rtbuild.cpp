@@ -569,9 +569,9 @@ int nv_rt_scene_trace_host_textured_rays(const void* blob, const float* origins,
 		return NV_EINVAL;
 	if (quality == 0)
 		return nv_rt_scene_trace_host_rays(blob, origins, dirs, count, tmin, tmax, 0, out);
-	RtAlphaInputs in;
-	in.draws = draws, in.materials = materials, in.textures = reinterpret_cast<const TxDesc*>(textures), in.texels = texels;
-	in.texelWords = texelWords, in.drawCount = drawCount, in.materialCount = materialCount, in.textureCount = textureCount;
+	RtAlphaInputs<TxDecoded> in;
+	in.draws = draws, in.materials = materials, in.textures = reinterpret_cast<const TxDesc*>(textures), in.data = texels;
+	in.extent = texelWords, in.drawCount = drawCount, in.materialCount = materialCount, in.textureCount = textureCount;
 	for (uint64_t i = 0; i < count; ++i)
 		out[i] = rt_occluded_alpha(static_cast<const unsigned char*>(blob), in, rt3{ origins[3 * i], origins[3 * i + 1], origins[3 * i + 2] },
 		                           rt3{ dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2] }, tmin, tmax)
@@ -591,7 +591,7 @@ int nv_rt_alpha_sample_host(const NvTextureDesc* desc, const uint32_t* texels, u
 		return NV_EINVAL;
 	for (uint64_t i = 0; i < count; ++i)
 	{
-		fourTap[i] = rt_alpha_lod0(texels, t, uv[2 * i], uv[2 * i + 1]);
+		fourTap[i] = TxDecoded::alpha_lod0(texels, t, uv[2 * i], uv[2 * i + 1]);
 		sampler[i] = tx_sample_lod0(texels, t, uv[2 * i], uv[2 * i + 1]).w;
 	}
 	return NV_OK;

@@ -26,27 +26,19 @@ struct rt3
 };
 
 // what the alpha test of rtalpha.h reads besides the blob: the caller's buffers, every index checked against its count before the load.  Here,
-// not there: it is a field of the alpha trace's kernel arguments (args.h), which do not need the test's text
-struct TxDesc; // texmath.h
+// not there: it is a field of the alpha trace's kernel arguments (args.h), which do not need the test's text.  SET is the residency of the
+// texture set, texmath.h's TxDecoded or TxBlocks (only named here: a translation unit that instantiates this has included texmath.h)
+struct TxDecoded;
+struct TxBlocks;
+template <typename SET>
 struct RtAlphaInputs
 {
+	typedef SET Set;
 	const NvMeshDraw* draws;
 	const NvMaterial* materials;
-	const TxDesc* textures; // == NvTextureDesc; entry 0 is "no texture"
-	const uint32_t* texels;
-	uint64_t texelWords;
-	uint32_t drawCount, materialCount, textureCount;
-};
-
-// the same over a block-resident texture set (shadowtrace_blocks.hip)
-struct TxBlockDesc; // texmath.h
-struct RtAlphaBlockInputs
-{
-	const NvMeshDraw* draws;
-	const NvMaterial* materials;
-	const TxBlockDesc* textures; // == NvTextureBlockDesc; entry 0 is "no texture"
-	const void* blocks;          // the DDS payloads, 16-byte aligned
-	uint64_t units16;
+	const typename SET::Desc* textures; // == NvTextureDesc / NvTextureBlockDesc; entry 0 is "no texture"
+	const typename SET::Unit* data;     // the decoded texels / the DDS payloads, 16-byte aligned
+	uint64_t extent;                    // texelWords / units16
 	uint32_t drawCount, materialCount, textureCount;
 };
 

@@ -1,7 +1,7 @@
 // shadowtrace.h — the tile walk of the two ray-traced shadow passes as ONE text: shadowtrace.hip instantiates it with
-// rtmath.h's rt_occluded (nv_shadow_trace), shadowtrace_alpha.hip with rtalpha.h's rt_occluded_alpha (nv_shadow_trace_textured at quality 1),
-// shadowtrace_blocks.hip with the same over a block-resident texture set (nv_shadow_trace_blocks, §4.21).  They
-// stay separate translation units: the opaque trace does not see the alpha test's text.
+// rtmath.h's rt_occluded (nv_shadow_trace), shadowtrace_alpha.h with rtalpha.h's rt_occluded_alpha over either residency of the texture set
+// (shadowtrace_alpha.hip: nv_shadow_trace_textured at quality 1; shadowtrace_blocks.hip: nv_shadow_trace_blocks, §4.21).  They stay separate
+// translation units: the opaque trace does not see the alpha test's text.
 //
 // Shape: one lane per invocation, a wave covers an 8 x 8 tile of invocations (the shader's workgroup: the rays of a wave start next to each
 // other and are parallel up to the jitter, so they walk the same nodes and their 16-byte node loads hit the same cache lines), four waves per
@@ -20,7 +20,7 @@ constexpr int ST_THREADS = 256;
 constexpr uint32_t ST_WAVES = ST_THREADS / 64;
 constexpr uint32_t ST_TILE = 8; // 8 x 8 invocations per wave (shadow.comp.glsl's local size)
 
-// ARGS = ShadowTraceArgs or ShadowTraceAlphaArgs (args.h); QUERY::occluded(a, origin, dir) is the ray query of shadow.comp.glsl:81
+// ARGS = ShadowTraceArgs or ShadowTraceSetArgs<SET> (args.h); QUERY::occluded(a, origin, dir) is the ray query of shadow.comp.glsl:81
 template <typename QUERY, typename ARGS>
 __global__ __launch_bounds__(ST_THREADS) void shadow_trace_kernel(ARGS a)
 {

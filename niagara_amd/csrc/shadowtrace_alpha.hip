@@ -4,23 +4,12 @@
 //
 // The kernel is shadowtrace.h's tile walk, shared with nv_shadow_trace, not copied.  The lanes of a wave walk the same nodes until the alpha
 // test, where they part: a lane whose candidate is transparent goes on while its neighbour has left.  A candidate's four alpha taps are issued
-// together and waited for once (rt_alpha_lod0).  Quality 0 has no alpha test: the entry point dispatches shadowtrace.hip's kernel.
-#include "shadowtrace.h"
-#include "rtalpha.h"
+// together and waited for once (TxDecoded::alpha_lod0).  Quality 0 has no alpha test: the entry point dispatches shadowtrace.hip's kernel.
+#include "shadowtrace_alpha.h"
 
 namespace nv
 {
 
-struct AlphaQuery
-{
-	static NV_DEV bool occluded(const ShadowTraceAlphaArgs& a, rt3 origin, rt3 dir) { return rt_occluded_alpha(a.scene, a.in, origin, dir, 1e-2f, 1e3f); } // :86-123
-};
-
-int launch_shadow_trace_alpha(hipStream_t stream, ShadowTraceAlphaArgs a, uint32_t maxBlocks)
-{
-	const uint32_t grid = shadow_trace_complete(a, maxBlocks);
-	hipLaunchKernelGGL((shadow_trace_kernel<AlphaQuery, ShadowTraceAlphaArgs>), dim3(grid), dim3(ST_THREADS), 0, stream, a);
-	return (int)hipGetLastError();
-}
+int launch_shadow_trace_alpha(hipStream_t stream, ShadowTraceAlphaArgs a, uint32_t maxBlocks) { return launch_shadow_trace_set(stream, a, maxBlocks); }
 
 } // namespace nv

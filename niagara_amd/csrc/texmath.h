@@ -390,6 +390,59 @@ NV_TX TxF4 tx_sample(const SRC& src, float u, float v, float dudx, float dvdx, f
 template <typename SRC>
 NV_TX TxF4 tx_sample_lod0(const SRC& src, float u, float v) { return tx_sample_lod(src, u, v, 0.0f); }
 
+// ---- what a texture set is.  A set is resident in one of two forms, TxDecoded here and TxBlocks below, and its three
+// consumers — the attribute pass (visattr.h), the alpha-tested raster (rasterdepth.h) and the alpha-tested shadow trace (rtalpha.h) — take the
+// form as a type and ask it for exactly this:
+//   Desc, Unit                one texture's descriptor (four words, the C ABI's) and what the set's buffer is an array of
+//   none()                    a well-formed descriptor that names nothing: what a consumer holds before it has looked a texture up
+//   ok(d, extent)             the check in front of every load through d; `extent` is the buffer's size as the entry point took it.  A consumer
+//                             compares the texture id with its table's count FIRST, loads the descriptor, then asks this (args.h TxTable::desc,
+//                             rtalpha.h rt_albedo_desc); it loads nothing from the buffer through a descriptor this refused
+//   sample(data, d, ...)      texture(sampler2D, uv) with explicit derivatives: the trilinear tx_sample, 8 taps
+//   texture(table, id, ...)   texture(SAMP(id), uv) over a table of the set (args.h TxTable): desc, then sample.  false: textures[id] was not
+//                             sampled and nothing was loaded from the buffer; the caller shades from the factors and counts the pixel
+//   alpha_lod0(data, d, u, v) textureLod(sampler2D, uv, 0).w from level 0's four taps alone (the shadow trace's, shadow.comp.glsl:117)
+// The two forms hand out the same RGBA8 codes and run the same operations on them in the same order, so a consumer's results are the same bits.
+struct TxDecoded
+{
+	typedef TxDesc Desc;
+	typedef uint32_t Unit; // RGBA8 words; extent = texelWords
+
+	static NV_TXM Desc none() { return Desc{ 0u, 1u, 1u, 1u }; }
+	static NV_TXM bool ok(const Desc& d, uint64_t extent) { return tx_desc_ok(d, extent); }
+	static NV_TXM TxF4 sample(const Unit* texels, const Desc& d, float u, float v, float dudx, float dvdx, float dudy, float dvdy)
+	{
+		return tx_sample(texels, d, u, v, dudx, dvdx, dudy, dvdy);
+	}
+	template <typename TABLE>
+	static NV_TXM bool texture(const TABLE& tx, uint32_t id, float u, float v, float dudx, float dvdx, float dudy, float dvdy, TxF4& c)
+	{
+		Desc d;
+		if (!tx.desc(id, d))
+			return false;
+		c = sample(tx.data, d, u, v, dudx, dvdx, dudy, dvdy);
+		return true;
+	}
+
+	// tx_sample_lod0(texels, t, u, v).w with the four alpha taps of level 0 alone.  tx_sample_lod at lambda = 0 blends level 0 with weight 1 - 0
+	// and level min(1, levels - 1) with weight 0: lo * 1 + hi * 0.  Every alpha is in [0, 1] or NaN, and a NaN comes from u, v alone (tx_axis), so
+	// hi is NaN only where lo is: for a finite lo the blend is lo + 0 = lo (lo >= 0, never -0), for a NaN lo it is NaN like lo.  The taps of the
+	// second level and the three colour channels change nothing and are left out; tests/test_shadow_alpha_cpu.py holds the two forms bit-identical
+	// (a NaN for a NaN: its sign and payload are no result, the test that follows is alpha >= 0.5).
+	// t has passed ok(): tx_axis keeps every index inside level 0 for EVERY bit pattern of u, v.
+	static NV_TXM float alpha_lod0(const Unit* texels, const Desc& t, float u, float v)
+	{
+		uint32_t x0, x1, y0, y1;
+		float ax, ay;
+		tx_axis(u, t.width, x0, x1, ax);
+		tx_axis(v, t.height, y0, y1, ay);
+		const uint64_t r0 = (uint64_t)t.offset + (uint64_t)y0 * t.width, r1 = (uint64_t)t.offset + (uint64_t)y1 * t.width;
+		const uint32_t c00 = texels[r0 + x0], c01 = texels[r0 + x1], c10 = texels[r1 + x0], c11 = texels[r1 + x1]; // the four loads together
+		const float a00 = (float)(c00 >> 24) / 255.0f, a01 = (float)(c01 >> 24) / 255.0f, a10 = (float)(c10 >> 24) / 255.0f, a11 = (float)(c11 >> 24) / 255.0f;
+		return tx_lerp(tx_lerp(a00, a01, ax), tx_lerp(a10, a11, ax), ay);
+	}
+};
+
 #ifndef NV_TX_SAMPLER_ONLY
 // ---- the block source (§4.21): the set's buffer holds the DDS payloads verbatim and a tap decodes its texel from its block.
 
@@ -661,6 +714,50 @@ NV_TX TxBlockSource tx_block_source(const void* blocks, const TxBlockDesc& d)
 {
 	return TxBlockSource{ blocks, (uint64_t)d.offset * 16u, d.width, d.height, d.levelsFormat & 255u, d.levelsFormat >> 8 & 255u };
 }
+
+// the block-resident form of a texture set: TxDecoded's interface over the DDS payloads.  Only a translation unit that includes this header in
+// full has it: one that defines NV_TX_SAMPLER_ONLY and names TxBlocks does not compile.
+struct TxBlocks
+{
+	typedef TxBlockDesc Desc;
+	typedef unsigned char Unit; // the payloads' bytes, 16-byte aligned; extent = units16
+
+	static NV_TXM Desc none() { return Desc{ 0u, 1u, 1u, 1u | TX_BC1 << 8 }; }
+	static NV_TXM bool ok(const Desc& d, uint64_t extent) { return tx_block_desc_ok(d, extent); }
+	static NV_TXM TxF4 sample(const Unit* blocks, const Desc& d, float u, float v, float dudx, float dvdx, float dudy, float dvdy)
+	{
+		return tx_sample(tx_block_source(blocks, d), u, v, dudx, dvdx, dudy, dvdy);
+	}
+	// (TxDecoded::texture with TABLE::desc's three statements written out: the text the block kernel of the attribute pass was compiled from.  Through
+	// the call the compiler lays the same operations out in another order, and the kernels keep their code: profiles/texture_set_refactor.md)
+	template <typename TABLE>
+	static NV_TXM bool texture(const TABLE& tx, uint32_t id, float u, float v, float dudx, float dvdx, float dudy, float dvdy, TxF4& c)
+	{
+		if (id >= tx.count)
+			return false;
+		const auto w = tx.descs[id];
+		const Desc d = { w.x, w.y, w.z, w.w };
+		if (!ok(d, tx.extent))
+			return false;
+		c = sample(tx.data, d, u, v, dudx, dvdx, dudy, dvdy);
+		return true;
+	}
+
+	// TxDecoded::alpha_lod0 with the four taps' alpha decoded from their blocks — alpha alone (tx_decode_alpha), a block loaded once per distinct
+	// block of the four taps (level 0 starts at the texture's first byte).  The alpha codes are the decoded chain's top bytes and the blend is the same
+	static NV_TXM float alpha_lod0(const Unit* blocks, const Desc& d, float u, float v)
+	{
+		const TxBlockSource src = tx_block_source(blocks, d);
+		uint32_t x0, x1, y0, y1;
+		float ax, ay;
+		tx_axis(u, src.width, x0, x1, ax);
+		tx_axis(v, src.height, y0, y1, ay);
+		uint32_t c00, c01, c10, c11;
+		src.walk<true>(src.byteBase, src.width, x0, x1, y0, y1, c00, c01, c10, c11);
+		const float a00 = (float)(c00 >> 24) / 255.0f, a01 = (float)(c01 >> 24) / 255.0f, a10 = (float)(c10 >> 24) / 255.0f, a11 = (float)(c11 >> 24) / 255.0f;
+		return tx_lerp(tx_lerp(a00, a01, ax), tx_lerp(a10, a11, ax), ay);
+	}
+};
 #endif // NV_TX_SAMPLER_ONLY
 
 } // namespace nv

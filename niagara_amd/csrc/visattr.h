@@ -1,8 +1,8 @@
 // visattr.h — the attribute pass of the visibility buffer as ONE text for its entry points: visattr.hip
 // instantiates visibility_attributes_kernel<RUNS> (nv_visibility_attributes: the fragment stage from the material's factors) and
-// visattr_tex.hip visibility_attributes_kernel<true, true, VisAttrTexArgs> (nv_visibility_attributes_textured: the complete fragment stage;
-// visattr_blocks.hip the same with VisAttrBlockArgs, over a block-resident texture set, §4.21); the
-// argument structs are args.h's.  Run detection, set-up, barycentrics and varyings are shared; TEX only adds statements under
+// visattr_tex.hip and visattr_blocks.hip visibility_attributes_kernel<true, true, VisAttrSetArgs<SET>> (nv_visibility_attributes_textured,
+// nv_visibility_attributes_blocks: the complete fragment stage over a texture set of residency SET, texmath.h's TxDecoded or TxBlocks, §4.21);
+// the argument structs are args.h's.  Run detection, set-up, barycentrics and varyings are shared; TEX only adds statements under
 // `if constexpr (TEX)`, so the untextured kernels keep their instruction streams.
 #pragma once
 #include "raster.h"
@@ -141,18 +141,7 @@ NV_DEV uint32_t va_unorm(float x, float scale)
 	return (uint32_t)__builtin_rintf(v * scale);
 }
 
-// texture(SAMP(id), uv) of the textured pass.  false: textures[id] was not sampled — id is past the table or its descriptor's chain does not
-// lie inside texelWords — and nothing was loaded from the texel buffer; the caller shades from the factors and counts the pixel.
-NV_DEV bool va_texture(const VaTextures& tx, uint32_t id, float u, float v, float dudx, float dvdx, float dudy, float dvdy, TxF4& c)
-{
-	TxDesc d;
-	if (!fa_texture_desc(tx, id, d))
-		return false;
-	c = tx_sample(tx.texels, d, u, v, dudx, dvdx, dudy, dvdy);
-	return true;
-}
-
-// ARGS = VisAttrArgs (TEX = false) or VisAttrTexArgs (TEX = true)
+// ARGS = VisAttrArgs (TEX = false) or VisAttrSetArgs<SET> (TEX = true)
 template <bool RUNS, bool TEX = false, typename ARGS = VisAttrArgs>
 __global__ __launch_bounds__(VA_THREADS) void visibility_attributes_kernel(ARGS a)
 {
@@ -244,28 +233,28 @@ __global__ __launch_bounds__(VA_THREADS) void visibility_attributes_kernel(ARGS 
 					TxF4 c;
 					if (tex.x != 0u)
 					{
-						if (va_texture(a.tx, tex.x, u, v, dudx, dvdx, dudy, dvdy, c))
+						if (ARGS::Set::texture(a.tx, tex.x, u, v, dudx, dvdx, dudy, dvdy, c))
 							albedo = make_float4(albedo.x * __builtin_powf(c.x, 2.2f), albedo.y * __builtin_powf(c.y, 2.2f), albedo.z * __builtin_powf(c.z, 2.2f), fa_alpha(albedo.w, c.w));
 						else
 							missing = true;
 					}
 					if (tex.y != 0u)
 					{
-						if (va_texture(a.tx, tex.y, u, v, dudx, dvdx, dudy, dvdy, c))
+						if (ARGS::Set::texture(a.tx, tex.y, u, v, dudx, dvdx, dudy, dvdy, c))
 							nmap = f3{ c.x * 2.0f - 1.0f, c.y * 2.0f - 1.0f, c.z * 2.0f - 1.0f };
 						else
 							missing = true;
 					}
 					if (tex.z != 0u)
 					{
-						if (va_texture(a.tx, tex.z, u, v, dudx, dvdx, dudy, dvdy, c))
+						if (ARGS::Set::texture(a.tx, tex.z, u, v, dudx, dvdx, dudy, dvdy, c))
 							gloss = gloss * c.w; // fromsrgb(vec4) leaves .a as it is
 						else
 							missing = true;
 					}
 					if (tex.w != 0u)
 					{
-						if (va_texture(a.tx, tex.w, u, v, dudx, dvdx, dudy, dvdy, c))
+						if (ARGS::Set::texture(a.tx, tex.w, u, v, dudx, dvdx, dudy, dvdy, c))
 							em = f3{ em.x * __builtin_powf(c.x, 2.2f), em.y * __builtin_powf(c.y, 2.2f), em.z * __builtin_powf(c.z, 2.2f) };
 						else
 							missing = true;
@@ -337,13 +326,22 @@ __global__ __launch_bounds__(VA_THREADS) void visibility_attributes_kernel(ARGS 
 	}
 }
 
-// the fields both launchers derive from the image size, and their grid
+// the fields every launcher derives from the image size, and their grid
 inline uint32_t va_complete(VisAttrArgs& a, uint32_t height, uint32_t maxBlocks)
 {
 	a.n = a.width * height;
 	a.fw = (float)a.width;
 	a.fh = (float)height;
 	return capped_grid(a.n, VA_THREADS, maxBlocks);
+}
+
+// the launch of the textured pass over either residency of the set
+template <typename ARGS>
+int launch_visibility_attributes_set(hipStream_t stream, ARGS a, uint32_t height, uint32_t maxBlocks)
+{
+	const uint32_t grid = va_complete(a, height, maxBlocks);
+	hipLaunchKernelGGL((visibility_attributes_kernel<true, true, ARGS>), dim3(grid), dim3(VA_THREADS), 0, stream, a);
+	return (int)hipGetLastError();
 }
 
 } // namespace nv

@@ -7,6 +7,8 @@
 // 8 taps each), one texture after the other so that only one texture's taps are live at a time, and enter mesh.frag.glsl:62-80.  Before any
 // texel load the index is checked against the table and the descriptor's whole chain against the texel buffer.  One launch, no scratch
 // memory, only enqueued work.
+// The kernel takes the set's residency as a type (VisAttrSetArgs<SET>::Set, texmath.h): this file instantiates it over the decoded set,
+// visattr_blocks.hip over the block-resident one.
 #include "visattr.h"
 
 namespace nv
@@ -14,9 +16,7 @@ namespace nv
 
 int launch_visibility_attributes_textured(hipStream_t stream, VisAttrTexArgs a, uint32_t height, uint32_t maxBlocks)
 {
-	const uint32_t grid = va_complete(a, height, maxBlocks);
-	hipLaunchKernelGGL((visibility_attributes_kernel<true, true, VisAttrTexArgs>), dim3(grid), dim3(VA_THREADS), 0, stream, a);
-	return (int)hipGetLastError();
+	return launch_visibility_attributes_set(stream, a, height, maxBlocks);
 }
 
 } // namespace nv

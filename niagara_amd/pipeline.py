@@ -204,10 +204,29 @@ class Context:
         test against the albedo texture (nv_rasterdepth_textured, mesh.frag.glsl:88): a sample with albedo.a < 0.5 touches neither target.
         materials = a device table of layouts.MATERIAL, textures / texels = texture_decode's set; totals4[3] counts the samples kept,
         alpha_totals2 (optional, accumulated): samples dropped, samples unevaluated"""
-        check(lib.nv_rasterdepth_textured(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(dcb), _ptr(db), _ptr(mlb), _ptr(meshlet_data),
-                                          _ptr(vertices), _ptr(cib), _ptr(ccb), _ptr(depth), int(width), int(height), _ptr(visibility), _ptr(totals4),
-                                          _ptr(materials), int(material_count), _ptr(textures), int(texture_count), _ptr(texels), int(texel_words),
-                                          _ptr(alpha_totals2)), "nv_rasterdepth_textured")
+        self._rasterdepth_set("nv_rasterdepth_textured", globals_, dcb, db, mlb, meshlet_data, vertices, cib, ccb, depth, width, height, visibility, totals4,
+                              materials, material_count, textures, texture_count, alpha_totals2, texels, texel_words)
+
+    # The three passes that read a texture set exist once per residency of the set (decoded RGBA8 words: *_textured; BC blocks: *_blocks) with
+    # one signature that differs in the set's last two values, its buffer and the buffer's size: each pair marshals through one helper
+    def _rasterdepth_set(self, entry, globals_, dcb, db, mlb, meshlet_data, vertices, cib, ccb, depth, width, height, visibility, totals4, materials,
+                         material_count, textures, texture_count, alpha_totals2, buffer, size):
+        check(getattr(lib, entry)(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(dcb), _ptr(db), _ptr(mlb), _ptr(meshlet_data), _ptr(vertices),
+                                  _ptr(cib), _ptr(ccb), _ptr(depth), int(width), int(height), _ptr(visibility), _ptr(totals4), _ptr(materials),
+                                  int(material_count), _ptr(textures), int(texture_count), _ptr(buffer), int(size), _ptr(alpha_totals2)), entry)
+
+    def _visibility_attributes_set(self, entry, globals_, records, width, height, db, draw_count, mlb, meshlet_count, meshlet_data, data_words, vertices,
+                                   vertex_count, materials, material_count, attributes, gbuffer0, gbuffer1, totals4, textures, texture_count, buffer, size):
+        check(getattr(lib, entry)(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(records), int(width), int(height), _ptr(db), int(draw_count),
+                                  _ptr(mlb), int(meshlet_count), _ptr(meshlet_data), int(data_words), _ptr(vertices), int(vertex_count), _ptr(materials),
+                                  int(material_count), _ptr(attributes), _ptr(gbuffer0), _ptr(gbuffer1), _ptr(totals4), _ptr(textures),
+                                  int(texture_count), _ptr(buffer), int(size)), entry)
+
+    def _shadow_trace_set(self, entry, shadow_data, depth, shadow, width, height, quality, draws, draw_count, materials, material_count, textures,
+                          texture_count, buffer, size):
+        check(getattr(lib, entry)(self.h, _stream(), C.c_void_p(shadow_data.ctypes.data) if shadow_data is not None else None, _ptr(depth), _ptr(shadow),
+                                  int(width), int(height), int(quality), _ptr(draws), int(draw_count), _ptr(materials), int(material_count),
+                                  _ptr(textures), int(texture_count), _ptr(buffer), int(size)), entry)
 
     def rasterdepth_indexed(self, globals_, dcb, dccb, db, draw_count, ib, index_capacity, vertices, vertex_capacity, depth, width, height,
                             totals4=None):
@@ -257,39 +276,31 @@ class Context:
         """visibility_attributes with the complete fragment stage (nv_visibility_attributes_textured): textures = a device table of
         layouts.TEXTUREDESC (entry 0 reserved), texels = the decoded set (texture_decode).  totals4[3] counts the pixels whose material names a
         texture the pass could not sample: 0 on a complete set"""
-        check(lib.nv_visibility_attributes_textured(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(records), int(width), int(height), _ptr(db),
-                                                    int(draw_count), _ptr(mlb), int(meshlet_count), _ptr(meshlet_data), int(data_words), _ptr(vertices),
-                                                    int(vertex_count), _ptr(materials), int(material_count), _ptr(attributes), _ptr(gbuffer0),
-                                                    _ptr(gbuffer1), _ptr(totals4), _ptr(textures), int(texture_count), _ptr(texels), int(texel_words)),
-              "nv_visibility_attributes_textured")
+        self._visibility_attributes_set("nv_visibility_attributes_textured", globals_, records, width, height, db, draw_count, mlb, meshlet_count,
+                                        meshlet_data, data_words, vertices, vertex_count, materials, material_count, attributes, gbuffer0, gbuffer1,
+                                        totals4, textures, texture_count, texels, texel_words)
 
     def rasterdepth_blocks(self, globals_, dcb, db, mlb, meshlet_data, vertices, cib, ccb, depth, width, height, visibility=None, totals4=None,
                            materials=None, material_count=0, textures=None, texture_count=0, blocks=None, units16=0, alpha_totals2=None):
         """rasterdepth_textured over a block-resident set (nv_rasterdepth_blocks): textures = a device table of
         layouts.TEXTUREBLOCKDESC, blocks = texture_blocks' buffer of units16 16-byte units.  The same targets and counters bit for bit"""
-        check(lib.nv_rasterdepth_blocks(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(dcb), _ptr(db), _ptr(mlb), _ptr(meshlet_data),
-                                        _ptr(vertices), _ptr(cib), _ptr(ccb), _ptr(depth), int(width), int(height), _ptr(visibility), _ptr(totals4),
-                                        _ptr(materials), int(material_count), _ptr(textures), int(texture_count), _ptr(blocks), int(units16),
-                                        _ptr(alpha_totals2)), "nv_rasterdepth_blocks")
+        self._rasterdepth_set("nv_rasterdepth_blocks", globals_, dcb, db, mlb, meshlet_data, vertices, cib, ccb, depth, width, height, visibility, totals4,
+                              materials, material_count, textures, texture_count, alpha_totals2, blocks, units16)
 
     def shadow_trace_blocks(self, shadow_data, depth, shadow, width, height, quality, draws, draw_count, materials, material_count, textures,
                             texture_count, blocks, units16):
         """shadow_trace_textured over a block-resident set (nv_shadow_trace_blocks): the same mask byte for byte"""
-        check(lib.nv_shadow_trace_blocks(self.h, _stream(), C.c_void_p(shadow_data.ctypes.data) if shadow_data is not None else None, _ptr(depth),
-                                         _ptr(shadow), int(width), int(height), int(quality), _ptr(draws), int(draw_count), _ptr(materials),
-                                         int(material_count), _ptr(textures), int(texture_count), _ptr(blocks), int(units16)),
-              "nv_shadow_trace_blocks")
+        self._shadow_trace_set("nv_shadow_trace_blocks", shadow_data, depth, shadow, width, height, quality, draws, draw_count, materials, material_count,
+                               textures, texture_count, blocks, units16)
 
     def visibility_attributes_blocks(self, globals_, records, width, height, db, draw_count, mlb, meshlet_count, meshlet_data, data_words, vertices,
                                      vertex_count, materials, material_count, attributes=None, gbuffer0=None, gbuffer1=None, totals4=None,
                                      textures=None, texture_count=0, blocks=None, units16=0):
         """visibility_attributes_textured over a block-resident set (nv_visibility_attributes_blocks): textures = a device table
         of layouts.TEXTUREBLOCKDESC (entry 0 reserved), blocks = texture_blocks' buffer of units16 16-byte units.  The same outputs bit for bit"""
-        check(lib.nv_visibility_attributes_blocks(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(records), int(width), int(height), _ptr(db),
-                                                  int(draw_count), _ptr(mlb), int(meshlet_count), _ptr(meshlet_data), int(data_words), _ptr(vertices),
-                                                  int(vertex_count), _ptr(materials), int(material_count), _ptr(attributes), _ptr(gbuffer0),
-                                                  _ptr(gbuffer1), _ptr(totals4), _ptr(textures), int(texture_count), _ptr(blocks), int(units16)),
-              "nv_visibility_attributes_blocks")
+        self._visibility_attributes_set("nv_visibility_attributes_blocks", globals_, records, width, height, db, draw_count, mlb, meshlet_count,
+                                        meshlet_data, data_words, vertices, vertex_count, materials, material_count, attributes, gbuffer0, gbuffer1,
+                                        totals4, textures, texture_count, blocks, units16)
 
     # ---- material textures (DESIGN.md §4.18); the three host functions need no device and are host.py's
     dds_parse = staticmethod(host.dds_parse)
@@ -368,10 +379,8 @@ class Context:
         counts only where its material's albedo texture has alpha >= 0.5.  The uploaded scene was built with texcoords=True; draws = the device
         draw array its instances index, materials = a device table of layouts.MATERIAL, textures / texels = texture_decode's set.  One launch,
         can be captured"""
-        check(lib.nv_shadow_trace_textured(self.h, _stream(), C.c_void_p(shadow_data.ctypes.data) if shadow_data is not None else None, _ptr(depth),
-                                           _ptr(shadow), int(width), int(height), int(quality), _ptr(draws), int(draw_count), _ptr(materials),
-                                           int(material_count), _ptr(textures), int(texture_count), _ptr(texels), int(texel_words)),
-              "nv_shadow_trace_textured")
+        self._shadow_trace_set("nv_shadow_trace_textured", shadow_data, depth, shadow, width, height, quality, draws, draw_count, materials,
+                               material_count, textures, texture_count, texels, texel_words)
 
     def shadow_trace(self, shadow_data, depth, shadow, width, height, quality=1):
         """shadow.comp.glsl (nv_shadow_trace): the u8 sun shadow mask (0 = in shadow, 255 = lit) of the depth target from the uploaded scene;
@@ -516,6 +525,7 @@ class VisibilityPipeline:
         self.rt_dynamic = False                    # build_rt_scene(dynamic=True): move_draws rebuilds the TLAS
         self.rt_texcoords = False                  # build_rt_scene(texcoords=True): shade(shadow="trace", textures=True) can run its alpha test
         self.rt_scene = self.shadow_image = None   # build_rt_scene's blob; shade(shadow="trace")'s mask, allocated on first use
+        self.texture_resident = None               # set_textures' residency: "decoded" or "blocks"
         self.index_count = self.vertex_count = 0
         if vertices is not None and (meshlet_data is not None or indices is not None):
             self.vertex_count = len(vertices)
@@ -573,19 +583,15 @@ class VisibilityPipeline:
         pass_data["postPass"] = post_pass
         g = synth.make_globals(pass_data, (self.depth_w, self.depth_h))
         if textures:
-            missing = [what for what, absent in (("set_textures()", getattr(self, "texture_table", None) is None),
+            missing = [what for what, absent in (("set_textures()", self.texture_resident is None),
                                                  ("a material table (materials=)", materials is None)) if absent]
             if missing:
                 raise NvError("render_depth(textures=True) needs " + ", ".join(missing))
             mat = to_device(np.ascontiguousarray(materials, L.MATERIAL), self.ctx.device) if isinstance(materials, np.ndarray) else materials
-            if getattr(self, "texture_resident", "decoded") == "blocks":
-                self.ctx.rasterdepth_blocks(g, self.dcb, self.db, self.mlb, self.mdb, self.vb, self.cib, self.ccb, self.depth, self.depth_w, self.depth_h,
-                                            visibility, totals4, mat, mat.numel() * mat.element_size() // L.MATERIAL.itemsize, self.texture_table,
-                                            len(self.texture_descs), self.texture_block_buffer, self.texture_block_buffer.numel() // 16, alpha_totals2)
-                return
-            self.ctx.rasterdepth_textured(g, self.dcb, self.db, self.mlb, self.mdb, self.vb, self.cib, self.ccb, self.depth, self.depth_w, self.depth_h,
-                                          visibility, totals4, mat, mat.numel() * mat.element_size() // L.MATERIAL.itemsize, self.texture_table,
-                                          len(self.texture_descs), self.texels, self.texels.numel(), alpha_totals2)
+            form, tset = self._texture_set()
+            getattr(self.ctx, "rasterdepth_" + form)(g, self.dcb, self.db, self.mlb, self.mdb, self.vb, self.cib, self.ccb, self.depth, self.depth_w,
+                                                     self.depth_h, visibility, totals4, mat, mat.numel() * mat.element_size() // L.MATERIAL.itemsize,
+                                                     *tset, alpha_totals2)
             return
         self.ctx.rasterdepth(g, self.dcb, self.db, self.mlb, self.mdb, self.vb, self.cib, self.ccb, self.depth, self.depth_w, self.depth_h,
                              visibility, totals4)
@@ -650,6 +656,13 @@ class VisibilityPipeline:
         self.texture_descs = descs
         self.texture_table = to_device(descs, self.ctx.device)
 
+    def _texture_set(self):
+        """what a pass over set_textures()'s set needs for the set's residency: the suffix of the Context method ("textured" or "blocks") and
+        that method's last four set arguments (the descriptor table, its entries, the set's buffer, the buffer's size in words or 16-byte units)"""
+        if self.texture_resident == "blocks":
+            return "blocks", (self.texture_table, len(self.texture_descs), self.texture_block_buffer, self.texture_block_buffer.numel() // 16)
+        return "textured", (self.texture_table, len(self.texture_descs), self.texels, self.texels.numel())
+
     def attributes(self, cull_data, records, materials=None, attributes=True, gbuffers=True, textures=False):
         """nv_visibility_attributes over resolve()'s "records" under the frame's CullData: a dict with "attributes" (uint8 tensor, height *
         width NvPixelAttributes), "gbuffer0" / "gbuffer1" (int32, height x width; only with `materials`, a host array of layouts.MATERIAL or a
@@ -675,21 +688,15 @@ class VisibilityPipeline:
         g = synth.make_globals(cull_data, (self.depth_w, self.depth_h))
         n_draws = getattr(self, "total_draws", self.draw_count)
         if textures:
-            if getattr(self, "texture_table", None) is None:
+            if self.texture_resident is None:
                 raise NvError("attributes(textures=True) samples set_textures()'s set: call set_textures first")
             if mat is None:
                 raise NvError("attributes(textures=True) needs the material table")
-            if getattr(self, "texture_resident", "decoded") == "blocks":
-                self.ctx.visibility_attributes_blocks(g, records, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws, self.mlb,
-                                                      self.meshlet_count, self.mdb, self.mdb.numel() * self.mdb.element_size() // 4, self.vb,
-                                                      self.vertex_count, mat, n_mat, out["attributes"], out["gbuffer0"], out["gbuffer1"], out["totals"],
-                                                      self.texture_table, len(self.texture_descs), self.texture_block_buffer,
-                                                      self.texture_block_buffer.numel() // 16)
-                return out
-            self.ctx.visibility_attributes_textured(g, records, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws, self.mlb,
-                                                    self.meshlet_count, self.mdb, self.mdb.numel() * self.mdb.element_size() // 4, self.vb,
-                                                    self.vertex_count, mat, n_mat, out["attributes"], out["gbuffer0"], out["gbuffer1"], out["totals"],
-                                                    self.texture_table, len(self.texture_descs), self.texels, self.texels.numel())
+            form, tset = self._texture_set()
+            getattr(self.ctx, "visibility_attributes_" + form)(g, records, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws, self.mlb,
+                                                               self.meshlet_count, self.mdb, self.mdb.numel() * self.mdb.element_size() // 4, self.vb,
+                                                               self.vertex_count, mat, n_mat, out["attributes"], out["gbuffer0"], out["gbuffer1"],
+                                                               out["totals"], *tset)
             return out
         self.ctx.visibility_attributes(g, records, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws, self.mlb, self.meshlet_count,
                                        self.mdb, self.mdb.numel() * self.mdb.element_size() // 4, self.vb, self.vertex_count, mat, n_mat,
@@ -789,21 +796,16 @@ class VisibilityPipeline:
             if textures:
                 if isinstance(self, ShardedVisibilityPipeline):
                     raise NvError("shade(shadow=\"trace\", textures=True) is not available on a sharded pipeline")
-                missing = [what for what, absent in (("set_textures()", getattr(self, "texture_table", None) is None),
+                missing = [what for what, absent in (("set_textures()", self.texture_resident is None),
                                                      ("a material table (materials=)", materials is None),
                                                      ("a scene with texcoords (build_rt_scene(..., texcoords=True))", not getattr(self, "rt_texcoords", False)))
                            if absent]
                 if missing:
                     raise NvError("shade(shadow=\"trace\", textures=True) needs " + ", ".join(missing))
                 mat = to_device(np.ascontiguousarray(materials, L.MATERIAL), dev) if isinstance(materials, np.ndarray) else materials
-                if getattr(self, "texture_resident", "decoded") == "blocks":
-                    self.ctx.shadow_trace_blocks(sh, self.depth, shadow, w, h, quality, self.db, self.draw_count, mat,
-                                                 mat.numel() * mat.element_size() // L.MATERIAL.itemsize, self.texture_table, len(self.texture_descs),
-                                                 self.texture_block_buffer, self.texture_block_buffer.numel() // 16)
-                else:
-                    self.ctx.shadow_trace_textured(sh, self.depth, shadow, w, h, quality, self.db, self.draw_count, mat,
-                                                   mat.numel() * mat.element_size() // L.MATERIAL.itemsize, self.texture_table,
-                                                   len(self.texture_descs), self.texels, self.texels.numel())
+                form, tset = self._texture_set()
+                getattr(self.ctx, "shadow_trace_" + form)(sh, self.depth, shadow, w, h, quality, self.db, self.draw_count, mat,
+                                                          mat.numel() * mat.element_size() // L.MATERIAL.itemsize, *tset)
             else:
                 self.ctx.shadow_trace(sh, self.depth, shadow, w, h, quality)
         if shadow is not None:

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import shadow_alpha_ref as SA
+import texture_ref as TR
 from niagara_amd import host, synth
 from niagara_amd import layouts as L
 from niagara_amd._lib import BloomDesc, PyramidDesc, TextureDesc, lib
@@ -79,6 +80,15 @@ class Env:
         assert t.data_ptr() % 256 == 0
         self.keep.append(t)
         return t.data_ptr()
+
+    def block_set(self):
+        """the block-resident set of the file's 4 x 4 BC1 texture (Context.texture_blocks): table address, entries, buffer address, units16"""
+        descs, blocks = self.ctx.texture_blocks([TR.dds_header(1, 4, 4, 1) + bytes(8)])
+        units16 = int(blocks.numel()) // 16
+        blocks = torch.cat([blocks, torch.zeros(SLACK, dtype=torch.uint8, device=self.ctx.device)])
+        assert blocks.data_ptr() % 256 == 0 and (len(descs), units16) == (2, 1)
+        self.keep.append(blocks)
+        return self.upload(descs), len(descs), blocks.data_ptr(), units16
 
 
 @pytest.fixture(scope="module")
@@ -177,6 +187,29 @@ def test_depth_passes(env):
     rows += sizes(fn, base, 11, 12)
     rows += [("screenWidth != width", fn, base, 2, e.globals_w, EINVAL), ("screenHeight != height", fn, base, 2, e.globals_h, EINVAL)]
 
+    # the alpha-tested pair: nv_rasterdepth's arguments, then the material table, the texture set and the alpha totals
+    materials, alpha = e.dev(MATERIALS * L.MATERIAL.itemsize), e.dev(16)
+    bdescs, bcount, blocks, units16 = e.block_set()
+    sets = (("nv_rasterdepth_textured", "texels", 3, [p(e.dev(2 * L.TEXTUREDESC.itemsize)), 2, p(e.dev(16 * 4)), 16]),
+            ("nv_rasterdepth_blocks", "blocks", 15, [p(bdescs), bcount, p(blocks), units16]))
+    for fn, buffer, mask, tset in sets:
+        base = [e.h, e.stream, e.globals, p(cmds), p(draws), p(meshlets), p(data), p(vertices), p(cib), p(ccb), p(depth), W, H, p(vis), p(totals),
+                p(materials), MATERIALS] + tset + [p(alpha)]
+        rows += null(fn, base, dict(context=0, globals=2, commands=3, draws=4, meshlets=5, meshletData=6, vertices=7, clusterIndices=8, clusterCount4=9,
+                                    depth=10))
+        rows += sizes(fn, base, 11, 12)
+        rows += [("screenWidth != width", fn, base, 2, e.globals_w, EINVAL), ("screenHeight != height", fn, base, 2, e.globals_h, EINVAL)]
+        masks = dict(commands=(3, 3), clusterIndices=(8, 3), clusterCount4=(9, 3), depth=(10, 3), meshlets=(5, 3), meshletData=(6, 3), visibility=(13, 7),
+                     totals4=(14, 7), alphaTotals2=(21, 7), draws=(4, 15), vertices=(7, 15), materials=(15, 15), textures=(17, 15))
+        masks[buffer] = (19, mask)
+        for name, (index, m) in masks.items():
+            rows += misaligned(fn, base, name, index, m)
+        # the table and its buffer come together or not at all; a count needs the table; a material table has entries
+        rows += [("textures NULL with %s" % buffer, fn, base, 17, None, EINVAL), ("%s NULL with textures" % buffer, fn, base, 19, None, EINVAL),
+                 ("materials with materialCount 0", fn, base, 16, 0, EINVAL)]
+        without = base[:17] + [None, 0, None, 0] + base[21:]
+        rows += [("textureCount without a table", fn, without, 18, 2, EINVAL)]
+
     fn = "nv_rasterdepth_indexed"
     base = [e.h, e.stream, e.globals, p(dcmds), p(count), p(draws), DRAWS, p(indices), 12, p(vertices), VERTICES, p(depth), W, H, p(totals)]
     rows += null(fn, base, dict(context=0, globals=2, commands=3, count=4, draws=5, indices=7, vertices=9, depth=11))
@@ -239,7 +272,9 @@ def test_visibility_passes(env):
 
     fn, base = "nv_visibility_attributes", attribute_args(p(materials), MATERIALS, p(gb0), p(gb1))
     tex = [p(descs), 2, p(texels), 16]
-    for fn, base in (("nv_visibility_attributes", base), ("nv_visibility_attributes_textured", base + tex)):
+    bdescs, bcount, blocks, units16 = e.block_set()
+    btex = [p(bdescs), bcount, p(blocks), units16]
+    for fn, base in (("nv_visibility_attributes", base), ("nv_visibility_attributes_textured", base + tex), ("nv_visibility_attributes_blocks", base + btex)):
         rows += null(fn, base, dict(context=0, **ATTR_NAMES, **ATTR_COUNTED, materials=14)) + sizes(fn, base, 4, 5)
         rows += [("screenWidth != width", fn, base, 2, e.globals_w, EINVAL), ("screenHeight != height", fn, base, 2, e.globals_h, EINVAL)]
         for name, (index, mask) in ATTR_MASKS.items():
@@ -252,6 +287,11 @@ def test_visibility_passes(env):
     rows += [("materials NULL with materialCount 0", fn, base, 14, None, EINVAL)]
     base = attribute_args(p(materials), MATERIALS, p(gb0), p(gb1)) + tex
     rows += null(fn, base, dict(textures=20, texels=22)) + misaligned(fn, base, "textures", 20, 15) + misaligned(fn, base, "texels", 22, 3)
+    # ... and so does the block-resident pass, over its table and its blocks
+    fn, base = "nv_visibility_attributes_blocks", attribute_args(p(materials), 0, None, None) + btex
+    rows += [("materials NULL with materialCount 0", fn, base, 14, None, EINVAL)]
+    base = attribute_args(p(materials), MATERIALS, p(gb0), p(gb1)) + btex
+    rows += null(fn, base, dict(textures=20, blocks=22)) + misaligned(fn, base, "textures", 20, 15) + misaligned(fn, base, "blocks", 22, 15)
     run(rows)
 
 
@@ -341,18 +381,23 @@ def test_shadow_trace(env):
     descs, texels = e.upload(np.ascontiguousarray(tset["descs"], L.TEXTUREDESC)), e.upload(np.ascontiguousarray(tset["texels"], np.uint32))
     trace = [e.h, e.stream, e.shadow_data, p(depth), p(shadow), W, H, 1]
     textured = trace + [p(draws), len(scene["draws"]), p(materials), len(scene["materials"]), p(descs), len(tset["descs"]), p(texels), len(tset["texels"])]
+    bdescs, bcount, bblocks, units16 = e.block_set()
+    blocks = trace + [p(draws), len(scene["draws"]), p(materials), len(scene["materials"]), p(bdescs), bcount, p(bblocks), units16]
     build = [e.h, e.stream, p(draws), len(scene["draws"])]
 
     # nothing uploaded: every argument is valid and the context has no scene (the context's first argument is repeated as the "change")
     run([("no scene uploaded", "nv_shadow_trace", trace, 0, e.h, EINVAL), ("no scene uploaded", "nv_shadow_trace_textured", textured, 0, e.h, EINVAL),
-         ("no scene uploaded, quality 0", "nv_shadow_trace_textured", textured, 7, 0, EINVAL), ("no scene uploaded", "nv_rt_tlas_build", build, 0, e.h, EINVAL)])
+         ("no scene uploaded, quality 0", "nv_shadow_trace_textured", textured, 7, 0, EINVAL), ("no scene uploaded", "nv_rt_tlas_build", build, 0, e.h, EINVAL),
+         ("no scene uploaded", "nv_shadow_trace_blocks", blocks, 0, e.h, EINVAL), ("no scene uploaded, quality 0", "nv_shadow_trace_blocks", blocks, 7, 0, EINVAL)])
 
     # a scene without texcoords
     e.ctx.rt_scene_upload(e.ctx.rt_scene_build(scene["meshes"], scene["indices"], scene["vertices"], scene["draws"]))
     fn = "nv_shadow_trace"
     rows = [("a scene built without texcoords", "nv_shadow_trace_textured", textured, 0, e.h, EINVAL),
             ("a scene built without texcoords, quality 0", "nv_shadow_trace_textured", textured, 7, 0, EINVAL),
-            ("before nv_rt_scene_reserve_dynamic", "nv_rt_tlas_build", build, 0, e.h, EINVAL)]
+            ("before nv_rt_scene_reserve_dynamic", "nv_rt_tlas_build", build, 0, e.h, EINVAL),
+            ("a scene built without texcoords", "nv_shadow_trace_blocks", blocks, 0, e.h, EINVAL),
+            ("a scene built without texcoords, quality 0", "nv_shadow_trace_blocks", blocks, 7, 0, EINVAL)]
     rows += null(fn, trace, dict(context=0, shadow_data=2, depth=3, shadow=4)) + sizes(fn, trace, 5, 6) + misaligned(fn, trace, "depth", 3, 3)
     rows += [("imageSize[0] != width", fn, trace, 2, e.shadow_data_w, EINVAL), ("imageSize[1] != height", fn, trace, 2, e.shadow_data_h, EINVAL),
              ("quality -1", fn, trace, 7, -1, EINVAL), ("quality 2", fn, trace, 7, 2, EINVAL)]
@@ -370,4 +415,10 @@ def test_shadow_trace(env):
              ("quality -1", fn, textured, 7, -1, EINVAL), ("quality 2", fn, textured, 7, 2, EINVAL)]
     for name, (index, mask) in dict(depth=(3, 3), draws=(8, 15), materials=(10, 15), textures=(12, 15), texels=(14, 3)).items():
         rows += misaligned(fn, textured, name, index, mask)
+    fn = "nv_shadow_trace_blocks"  # (a count or units16 without its table or buffer: the NULL rows)
+    rows += null(fn, blocks, dict(context=0, shadow_data=2, depth=3, shadow=4, draws=8, materials=10, textures=12, blocks=14)) + sizes(fn, blocks, 5, 6)
+    rows += [("imageSize[0] != width", fn, blocks, 2, e.shadow_data_w, EINVAL), ("imageSize[1] != height", fn, blocks, 2, e.shadow_data_h, EINVAL),
+             ("quality -1", fn, blocks, 7, -1, EINVAL), ("quality 2", fn, blocks, 7, 2, EINVAL)]
+    for name, (index, mask) in dict(depth=(3, 3), draws=(8, 15), materials=(10, 15), textures=(12, 15), blocks=(14, 15)).items():
+        rows += misaligned(fn, blocks, name, index, mask)
     run(rows)
