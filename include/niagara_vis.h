@@ -517,8 +517,7 @@ int nv_rasterdepth(nv_context* ctx, void* stream, const NvGlobals* globals, cons
  * Everything else is nv_rasterdepth's rule set, unchanged — the vertex stage, the snap, the near-plane / non-finite / guard-band rejection,
  * facing by globals->cullData.postPass, top-left coverage, the fixed-order fp32 depth and the atomic max — so the same triangle under the same
  * draw writes the same bits through either entry point, with NV_OPT_RASTER_NEAR_CLIP 1 as well (the same clip rule, totals word 2 then counts
- * pieces).  No visibility buffer (neither a 32-bit nor the stable form's 34-bit ID can name both a draw and a triangle of an arbitrary
- * indexed draw).
+ * pieces).  This entry point writes no visibility buffer; nv_rasterdepth_indexed_visibility (below) does.
  * d_totals4 (optional, accumulated: zero it first): commands drawn, triangles (sum of their indexCount / 3), triangles rasterised, samples
  * covered.  d_draws holds drawCount records and d_commands up to drawCount commands; a zero capacity is allowed (nothing is read then).
  * Scratch: 4 B per command slot (drawCount) + 20 KiB, sized by nv_create for 1 M and by nv_reserve(maxDraws); a larger drawCount returns
@@ -528,6 +527,54 @@ int nv_rasterdepth_indexed(nv_context* ctx, void* stream, const NvGlobals* globa
                            uint32_t drawCount /* = maxDrawCount, src/niagara.cpp:1693 */, const uint32_t* d_indices, uint32_t indexCapacity,
                            const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width, uint32_t height,
                            uint64_t* d_totals4 /* optional */);
+
+/* ---- the visibility buffer of the indexed draws ----
+ * A triangle t of draw d is named tri34 = offsets[d] + t, offsets being the prefix nv_assign_triangle_offsets (host helpers, below) takes over
+ * the draws' widest LODs: like the cluster path's meshlet-visibility index the name depends on the draw only, not on the pass, the LOD that
+ * was selected, the command slot or the rank of a sharded frame.
+ *
+ * nv_rasterdepth_indexed_visibility is nv_rasterdepth_indexed — the same arguments, rule set, skip rules, totals and NV_OPT_RASTER_NEAR_CLIP,
+ * the same depth bits — and every covered sample also takes the atomic maximum of bits(z) << 34 | (tri34 + 1) into d_visibility (width * height
+ * words, 8-byte aligned; the caller clears it; 0 = no sample), with tri34 = d_triangleOffsets[command.drawId] + t.  z is the clamped depth
+ * that was written, so ties in depth go to the larger id; both pieces of a clipped triangle carry the triangle's id.  A triangle with
+ * tri34 >= d_triangleOffsets[drawId + 1] or tri34 >= 2^34 - 1 writes depth as always and no word.  The word is always this stable form:
+ * NV_OPT_RASTER_VISIBILITY_ID is not read.  d_triangleOffsets holds drawCount + 1 entries (8-byte aligned).  On a rank of a sharded frame
+ * the commands' drawId is rank-local: pass the FULL array's pointer advanced by the rank's first draw — the values stay global, so every
+ * rank writes the same word for the same sample and nv_visibility_merge composites the targets.  NV_EINVAL as nv_rasterdepth_indexed, and
+ * for a NULL or misaligned d_triangleOffsets or d_visibility. */
+int nv_rasterdepth_indexed_visibility(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshDrawCommand* d_commands,
+                                      const uint32_t* d_count /* dccb: word 0 */, const NvMeshDraw* d_draws, uint32_t drawCount,
+                                      const uint32_t* d_indices, uint32_t indexCapacity, const NvVertex* d_vertices, uint32_t vertexCapacity,
+                                      float* d_depth, uint32_t width, uint32_t height, uint64_t* d_totals4 /* optional */,
+                                      const uint64_t* d_triangleOffsets /* drawCount + 1 */, uint64_t* d_visibility /* width*height */);
+
+/* One resolved pixel of nv_visibility_resolve_indexed.  No sample: {0xFFFFFFFF, 0, 0, 0}.  Unresolved: all four words 0xFFFFFFFF. */
+typedef struct NvVisIndexedRecord
+{
+	uint32_t drawId;        /* index into the d_draws the call was given (the full array: global ids in a sharded frame) */
+	uint32_t indexPosition; /* position of the triangle's first index in the index buffer: corners at indexPosition + 0 .. 2 */
+	uint32_t vertexOffset;  /* added to each index (mod 2^32), the mesh's vertexOffset */
+	uint32_t depthBits;     /* bits of the fp32 depth of the sample */
+} NvVisIndexedRecord;
+
+/* nv_visibility_resolve_indexed: per pixel with a non-zero word of nv_rasterdepth_indexed_visibility's width x height target
+ *   tri34 = (word & (2^34 - 1)) - 1, depthBits = word >> 34;
+ *   drawId = the largest d < drawCount with d_triangleOffsets[d] <= tri34 (non-decreasing in d; pass the FULL arrays, also on a rank);
+ *   t      = tri34 - d_triangleOffsets[drawId];
+ *   lod    = what nv_drawcull selects for that draw under `cull` (as nv_visibility_resolve: pass the CullData of the rasterised frame);
+ *   indexPosition = lods[lod].indexOffset + 3 t (in 64 bits), vertexOffset = mesh.vertexOffset: what drawcull.comp.glsl:145-150 puts into
+ *            the draw's command.
+ * The pixel is UNRESOLVED — its record all ones, counted, nothing else written — when the id field is 0, no draw has an offset <= tri34,
+ * draw.meshIndex >= meshCount, t >= lods[lod].indexCount / 3, tri34 >= d_triangleOffsets[drawCount], or indexPosition + 2 does not fit 32
+ * bits.  Outputs, each optional: d_records (width * height, 16-byte aligned), d_drawPixels (drawCount counters, += 1 per resolved pixel:
+ * zero it first), d_totals4 (accumulated: covered pixels, unresolved pixels, 0, 0).
+ * Enqueues one launch (no allocation, no synchronisation: it can be captured).  NV_EINVAL: a NULL ctx, cull, d_visibility or
+ * d_triangleOffsets, width or height 0 or above 16384, d_draws NULL with drawCount > 0, d_meshes NULL with meshCount > 0, a misaligned
+ * pointer (16 bytes: records, draws, meshes; 8: visibility, offsets, totals). */
+int nv_visibility_resolve_indexed(nv_context* ctx, void* stream, const NvCullData* cull, const uint64_t* d_visibility, uint32_t width,
+                                  uint32_t height, const NvMeshDraw* d_draws, uint32_t drawCount, const NvMesh* d_meshes, uint32_t meshCount,
+                                  const uint64_t* d_triangleOffsets /* drawCount + 1 */, NvVisIndexedRecord* d_records /* optional */,
+                                  uint32_t* d_drawPixels /* optional, drawCount */, uint64_t* d_totals4 /* optional */);
 
 /* depthreduce.comp.glsl:14-22 + the level loop at src/niagara.cpp:1703-1733.
  * d_depth is the width x height fp32 depth target (reverse-Z, far = 0). */
@@ -643,6 +690,21 @@ int nv_visibility_attributes(nv_context* ctx, void* stream, const NvGlobals* glo
                              const uint32_t* d_meshletData, uint32_t meshletDataWords, const NvVertex* d_vertices, uint32_t vertexCount,
                              const NvMaterial* d_materials /* optional */, uint32_t materialCount, NvPixelAttributes* d_attributes /* optional */,
                              uint32_t* d_gbuffer0 /* optional */, uint32_t* d_gbuffer1 /* optional */, uint64_t* d_totals4 /* optional */);
+
+/* nv_visibility_attributes_indexed: nv_visibility_attributes over nv_visibility_resolve_indexed's records — the classic
+ * path's vertex stage (mesh.vert.glsl:41-62) per corner, vi = d_indices[indexPosition + k] + vertexOffset (mod 2^32), k = 0 .. 2, then
+ * mesh.frag.glsl.  From the three fetched vertices on it is nv_visibility_attributes, word for word: the clip position, unpackTBN, the
+ * homogeneous barycentrics, the degenerate rule, the fragment stage from the material's factors (no texture is sampled; a material that
+ * names one is counted in totals word 3), the UNORM packs, the output structs and d_totals4.  A record is INVALID — counted, written like
+ * no sample — when drawId >= drawCount, indexPosition + 2 >= indexCapacity (in 64 bits), a corner >= vertexCapacity, or (with d_materials)
+ * materialIndex >= materialCount: every load stays inside the caller's buffers.  Alignment rules and NV_EINVAL as nv_visibility_attributes
+ * (d_indices: 4 bytes, NULL only with indexCapacity 0).  Enqueues one launch; it can be captured. */
+int nv_visibility_attributes_indexed(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisIndexedRecord* d_records, uint32_t width,
+                                     uint32_t height, const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices,
+                                     uint32_t indexCapacity, const NvVertex* d_vertices, uint32_t vertexCapacity,
+                                     const NvMaterial* d_materials /* optional */, uint32_t materialCount,
+                                     NvPixelAttributes* d_attributes /* optional */, uint32_t* d_gbuffer0 /* optional */,
+                                     uint32_t* d_gbuffer1 /* optional */, uint64_t* d_totals4 /* optional */);
 
 /* ---- material textures (replaces binding 8 `textureSampler` and set 1 `textures[]` of mesh.frag.glsl) ----
  * CDNA has no texture unit a HIP kernel can use: the library reads niagara's DDS files, decodes their BC blocks to RGBA8 once at load time
@@ -1142,6 +1204,12 @@ int nv_build_shadow_data(NvShadowData* out, const NvGlobals* globals, const floa
  * through out_slots (meshletVisibility bytes = (slots+31)/32*4) and the postPass mask. */
 int nv_assign_visibility_offsets(NvMeshDraw* draws, uint32_t drawCount, const NvMesh* meshes,
                                  uint32_t meshCount, uint32_t* out_slots, uint32_t* out_postPassMask);
+/* The names of the triangles of indexed draws (nv_rasterdepth_indexed_visibility): offsets[0] = 0, offsets[d + 1] =
+ * offsets[d] + span(d), span(d) = the maximum of lods[l].indexCount / 3 over l < min(lodCount, NV_MAX_LODS) of the draw's mesh, 0 when
+ * meshIndex >= meshCount.  `offsets` holds drawCount + 1 entries.  NV_EINVAL: a NULL array with a non-zero count, NULL offsets, or a total
+ * above 2^34 - 2 (the array is written all the same). */
+int nv_assign_triangle_offsets(const NvMeshDraw* draws, uint32_t drawCount, const NvMesh* meshes, uint32_t meshCount,
+                               uint64_t* offsets /* drawCount + 1 */);
 /* src/niagara.cpp:449-481,969-998: PCG32-seeded synthetic scene (state 0x42) */
 int nv_synth_draws(NvMeshDraw* draws, uint32_t drawCount, uint32_t meshCount, float sceneRadius);
 

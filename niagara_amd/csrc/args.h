@@ -275,6 +275,13 @@ struct RasterIndexedArgs
 	unsigned long long* __restrict__ partials; // library scratch: 4 counters per workgroup of the raster launch
 };
 
+// nv_rasterdepth_indexed_visibility (rasterindexed_vis.hip): the same, and where the visibility words come from and go
+struct RasterIndexedVisArgs : RasterIndexedArgs
+{
+	const unsigned long long* __restrict__ triangleOffsets; // drawCount + 1 (the caller's pointer: on a shard, advanced by its first draw)
+	unsigned long long* __restrict__ visibility;            // width x height (atomic max)
+};
+
 // nv_cluster_expand (submit.hip): the launch's arguments on the host; the kernel takes them one by one
 struct ClusterExpandArgs
 {
@@ -304,6 +311,22 @@ struct VisResolveArgs
 	unsigned long long* totals;         // optional
 };
 
+// nv_visibility_resolve_indexed (visresolve_indexed.hip)
+struct VisResolveIndexedArgs
+{
+	NvCullData cd;
+	const unsigned long long* __restrict__ visibility;
+	uint32_t n; // pixels, <= 16384 * 16384
+	const NvMeshDraw* __restrict__ draws;
+	uint32_t drawCount;
+	const NvMesh* __restrict__ meshes;
+	uint32_t meshCount;
+	const unsigned long long* __restrict__ triangleOffsets; // drawCount + 1
+	uint4* __restrict__ records;        // optional
+	uint32_t* drawPixels;               // optional
+	unsigned long long* totals;         // optional
+};
+
 // nv_visibility_attributes (visattr.h, visattr.hip)
 typedef uint32_t va_u4 __attribute__((ext_vector_type(4))); // (a native vector: what the non-temporal load builtin takes)
 
@@ -327,6 +350,13 @@ struct VisAttrArgs
 	uint32_t* __restrict__ gbuffer0;          // optional
 	uint32_t* __restrict__ gbuffer1;          // optional
 	unsigned long long* totals;               // optional
+};
+
+// nv_visibility_attributes_indexed (visattr_indexed.hip): the same pass over NvVisIndexedRecords; the meshlet fields stay unused
+struct VisAttrIndexedArgs : VisAttrArgs
+{
+	const uint32_t* __restrict__ indices;
+	uint32_t indexCapacity;
 };
 
 // The texture set of the attribute pass and of the alpha-tested raster: the descriptor table and the set's buffer.

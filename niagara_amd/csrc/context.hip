@@ -1265,17 +1265,16 @@ int nv_rasterdepth_blocks(nv_context* ctx, void* stream, const NvGlobals* global
 	return nv::launch_rasterdepth_blocks((hipStream_t)stream, a, persistent_grid(ctx, 8), ctx->rasterNearClip != 0, ctx->rasterStableIds != 0);
 }
 
-int nv_rasterdepth_indexed(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshDrawCommand* d_commands, const uint32_t* d_count,
-                           const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices, uint32_t indexCapacity,
-                           const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_totals4)
+// the arguments nv_rasterdepth_indexed and nv_rasterdepth_indexed_visibility share, checked (NV_EINVAL / NV_ENOMEM) and filled
+static int fill_rasterindexed_args(nv::RasterIndexedArgs& a, nv_context* ctx, const NvGlobals* globals, const NvMeshDrawCommand* d_commands,
+                                   const uint32_t* d_count, const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices, uint32_t indexCapacity,
+                                   const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_totals4)
 {
 	if (!ctx || !globals || !d_commands || !d_count || !d_draws || !d_indices || !d_vertices || !d_depth || !image_size_ok(width, height) ||
 	    globals->screenWidth != (float)width || globals->screenHeight != (float)height)
 		return NV_EINVAL;
 	if (drawCount > ctx->rasterScratchDraws)
 		return NV_ENOMEM; // nv_reserve(ctx, maxDraws, ...) first: a pass never allocates
-	DeviceGuard guard(ctx->device);
-	nv::RasterIndexedArgs a;
 	memset(&a, 0, sizeof(a));
 	a.globals = *globals;
 	a.commands = d_commands;
@@ -1292,7 +1291,38 @@ int nv_rasterdepth_indexed(nv_context* ctx, void* stream, const NvGlobals* globa
 	a.smallLimit = ctx->rasterSmallLimit;
 	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
 	a.partials = ctx->totalsPartials;
+	return NV_OK;
+}
+
+int nv_rasterdepth_indexed(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshDrawCommand* d_commands, const uint32_t* d_count,
+                           const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices, uint32_t indexCapacity,
+                           const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_totals4)
+{
+	nv::RasterIndexedArgs a;
+	const int rc = fill_rasterindexed_args(a, ctx, globals, d_commands, d_count, d_draws, drawCount, d_indices, indexCapacity, d_vertices, vertexCapacity,
+	                                       d_depth, width, height, d_totals4);
+	if (rc != NV_OK)
+		return rc;
+	DeviceGuard guard(ctx->device);
 	return nv::launch_rasterindexed((hipStream_t)stream, a, ctx->rasterScratch, persistent_grid(ctx, 8), ctx->rasterNearClip != 0);
+}
+
+int nv_rasterdepth_indexed_visibility(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshDrawCommand* d_commands,
+                                      const uint32_t* d_count, const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices,
+                                      uint32_t indexCapacity, const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width,
+                                      uint32_t height, uint64_t* d_totals4, const uint64_t* d_triangleOffsets, uint64_t* d_visibility)
+{
+	nv::RasterIndexedVisArgs a;
+	const int rc = fill_rasterindexed_args(a, ctx, globals, d_commands, d_count, d_draws, drawCount, d_indices, indexCapacity, d_vertices, vertexCapacity,
+	                                       d_depth, width, height, d_totals4);
+	if (rc != NV_OK)
+		return rc;
+	if (!d_triangleOffsets || !d_visibility || misaligned(d_triangleOffsets, 7u) || misaligned(d_visibility, 7u))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	a.triangleOffsets = reinterpret_cast<const unsigned long long*>(d_triangleOffsets);
+	a.visibility = reinterpret_cast<unsigned long long*>(d_visibility);
+	return nv::launch_rasterindexed_vis((hipStream_t)stream, a, ctx->rasterScratch, persistent_grid(ctx, 8), ctx->rasterNearClip != 0);
 }
 
 int nv_meshlet_bounds(nv_context* ctx, void* stream, const NvVertex* d_vertices, const uint32_t* d_meshletData, NvMeshlet* d_meshlets, uint32_t meshletCount,
@@ -1355,6 +1385,30 @@ int nv_visibility_resolve(nv_context* ctx, void* stream, const NvCullData* cull,
 	return nv::launch_visibility_resolve((hipStream_t)stream, a, persistent_grid(ctx, 8), ctx->resolvePerPixel != 0);
 }
 
+int nv_visibility_resolve_indexed(nv_context* ctx, void* stream, const NvCullData* cull, const uint64_t* d_visibility, uint32_t width, uint32_t height,
+                                  const NvMeshDraw* d_draws, uint32_t drawCount, const NvMesh* d_meshes, uint32_t meshCount,
+                                  const uint64_t* d_triangleOffsets, NvVisIndexedRecord* d_records, uint32_t* d_drawPixels, uint64_t* d_totals4)
+{
+	if (!ctx || !cull || !d_visibility || !d_triangleOffsets || !image_size_ok(width, height) || (drawCount && !d_draws) || (meshCount && !d_meshes) ||
+	    misaligned(d_visibility, 7u) || misaligned(d_triangleOffsets, 7u) || misaligned(d_records, 15u) || misaligned(d_totals4, 7u) ||
+	    misaligned(d_draws, 15u) || misaligned(d_meshes, 15u))
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	nv::VisResolveIndexedArgs a;
+	a.cd = *cull;
+	a.visibility = reinterpret_cast<const unsigned long long*>(d_visibility);
+	a.n = width * height;
+	a.draws = d_draws;
+	a.drawCount = drawCount;
+	a.meshes = d_meshes;
+	a.meshCount = meshCount;
+	a.triangleOffsets = reinterpret_cast<const unsigned long long*>(d_triangleOffsets);
+	a.records = reinterpret_cast<uint4*>(d_records);
+	a.drawPixels = d_drawPixels;
+	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
+	return nv::launch_visibility_resolve_indexed((hipStream_t)stream, a, persistent_grid(ctx, 8));
+}
+
 int nv_visibility_attributes(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisRecord* d_records, uint32_t width, uint32_t height,
                              const NvMeshDraw* d_draws, uint32_t drawCount, const NvMeshlet* d_meshlets, uint32_t meshletCount,
                              const uint32_t* d_meshletData, uint32_t meshletDataWords, const NvVertex* d_vertices, uint32_t vertexCount,
@@ -1368,6 +1422,22 @@ int nv_visibility_attributes(nv_context* ctx, void* stream, const NvGlobals* glo
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	return nv::launch_visibility_attributes((hipStream_t)stream, a, height, persistent_grid(ctx, 8), ctx->attributesPerPixel != 0);
+}
+
+int nv_visibility_attributes_indexed(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisIndexedRecord* d_records, uint32_t width,
+                                     uint32_t height, const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices, uint32_t indexCapacity,
+                                     const NvVertex* d_vertices, uint32_t vertexCapacity, const NvMaterial* d_materials, uint32_t materialCount,
+                                     NvPixelAttributes* d_attributes, uint32_t* d_gbuffer0, uint32_t* d_gbuffer1, uint64_t* d_totals4)
+{
+	nv::VisAttrIndexedArgs a;
+	if (fill_attribute_args(a, ctx, globals, reinterpret_cast<const NvVisRecord*>(d_records), width, height, d_draws, drawCount, nullptr, 0u, nullptr, 0u,
+	                        d_vertices, vertexCapacity, d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1, d_totals4) != NV_OK ||
+	    (materialCount && !d_materials) || ((d_gbuffer0 || d_gbuffer1) && !d_materials) || (indexCapacity && !d_indices) || misaligned(d_indices, 3u))
+		return NV_EINVAL;
+	a.indices = d_indices;
+	a.indexCapacity = indexCapacity;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_visibility_attributes_indexed((hipStream_t)stream, a, height, persistent_grid(ctx, 8));
 }
 
 // ---- material textures (texdecode.hip, visattr_tex.hip)

@@ -268,6 +268,29 @@ int nv_assign_visibility_offsets(NvMeshDraw* draws, uint32_t drawCount, const Nv
 	return NV_OK;
 }
 
+// the names of the triangles of indexed draws: the prefix of the draws' widest LODs, as the function above does for meshlets
+int nv_assign_triangle_offsets(const NvMeshDraw* draws, uint32_t drawCount, const NvMesh* meshes, uint32_t meshCount, uint64_t* offsets)
+{
+	if ((!draws && drawCount) || (!meshes && meshCount) || !offsets)
+		return NV_EINVAL;
+	uint64_t at = 0;
+	offsets[0] = 0;
+	for (uint32_t i = 0; i < drawCount; ++i)
+	{
+		uint32_t widest = 0;
+		if (draws[i].meshIndex < meshCount)
+		{
+			const NvMesh& mesh = meshes[draws[i].meshIndex];
+			for (uint32_t l = 0; l < mesh.lodCount && l < NV_MAX_LODS; ++l)
+				if (mesh.lods[l].indexCount / 3u > widest)
+					widest = mesh.lods[l].indexCount / 3u;
+		}
+		at += widest;
+		offsets[i + 1] = at;
+	}
+	return at > (1ull << 34) - 2ull ? NV_EINVAL : NV_OK;
+}
+
 namespace
 {
 // src/niagara.cpp:449-481

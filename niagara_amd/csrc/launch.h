@@ -73,6 +73,11 @@ int launch_rasterdepth_blocks(hipStream_t, const RasterBlockArgs& a, uint32_t gr
 int launch_raster_totals(hipStream_t, const unsigned long long* partials, uint32_t blocks, unsigned long long* totals, uint32_t counters); // (rasterindexed.hip's too)
 int launch_rasterindexed(hipStream_t, RasterIndexedArgs a, void* scratch, uint32_t gridBlocks, bool nearClip);
 size_t rasterindexed_scratch_bytes(uint32_t drawCount);
+// rasterindexed_vis.hip, visresolve_indexed.hip, visattr_indexed.hip (§4.23)
+void launch_rasterindexed_prepare(hipStream_t, RasterIndexedArgs& a, void* scratch); // (rasterindexed.hip's count and scan launches)
+int launch_rasterindexed_vis(hipStream_t, RasterIndexedVisArgs a, void* scratch, uint32_t gridBlocks, bool nearClip);
+int launch_visibility_resolve_indexed(hipStream_t, VisResolveIndexedArgs a, uint32_t maxBlocks);
+int launch_visibility_attributes_indexed(hipStream_t, VisAttrIndexedArgs a, uint32_t height, uint32_t maxBlocks);
 // depthmerge.hip
 int launch_depth_merge(hipStream_t, float* dst, const float* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks);
 int launch_visibility_merge(hipStream_t, unsigned long long* dst, const unsigned long long* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks);

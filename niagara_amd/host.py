@@ -183,6 +183,14 @@ def assign_visibility_offsets(draws, meshes):
     return slots.value, mask.value
 
 
+def assign_triangle_offsets(draws, meshes):
+    """the names of the triangles of indexed draws (nv_assign_triangle_offsets): len(draws) + 1 u64, the prefix of the draws' widest LODs'
+    triangle counts; NvError past 2^34 - 2 triangles"""
+    offsets = np.zeros(len(draws) + 1, np.uint64)
+    check(lib.nv_assign_triangle_offsets(_p(draws), len(draws), _p(meshes), len(meshes), _p(offsets)), "nv_assign_triangle_offsets")
+    return offsets
+
+
 def shard_range(total, rank, world):
     b, e = C.c_uint64(0), C.c_uint64(0)
     lib.nv_shard_range(total, rank, world, C.byref(b), C.byref(e))

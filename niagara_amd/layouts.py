@@ -39,6 +39,9 @@ assert (VERTEX.itemsize, GLOBALS.itemsize, TRIMASK.itemsize) == (16, 224, 16)
 # NvVisRecord: one pixel of nv_visibility_resolve (no sample: drawId = 0xFFFFFFFF, the rest 0; unresolved: all ones)
 VISRECORD = np.dtype([("drawId", "<u4"), ("meshletIndex", "<u4"), ("triangle", "<u4"), ("depthBits", "<u4")])
 assert VISRECORD.itemsize == 16
+# NvVisIndexedRecord: one pixel of nv_visibility_resolve_indexed (no sample: drawId = 0xFFFFFFFF, the rest 0; unresolved: all ones)
+VISINDEXEDRECORD = np.dtype([("drawId", "<u4"), ("indexPosition", "<u4"), ("vertexOffset", "<u4"), ("depthBits", "<u4")])
+assert VISINDEXEDRECORD.itemsize == 16
 # NvMaterial (src/scene.h:25-37, src/shaders/mesh.h:80-90) and NvPixelAttributes, one pixel of nv_visibility_attributes (no sample and invalid
 # records: all zero except drawId = 0xFFFFFFFF)
 MATERIAL = np.dtype([("albedoTexture", "<u4"), ("normalTexture", "<u4"), ("specularTexture", "<u4"), ("emissiveTexture", "<u4"),

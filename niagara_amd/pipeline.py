@@ -237,6 +237,35 @@ class Context:
                                          int(index_capacity), _ptr(vertices), int(vertex_capacity), _ptr(depth), int(width), int(height), _ptr(totals4)),
               "nv_rasterdepth_indexed")
 
+    def rasterdepth_indexed_visibility(self, globals_, dcb, dccb, db, draw_count, ib, index_capacity, vertices, vertex_capacity, depth, width, height,
+                                       triangle_offsets, visibility, totals4=None):
+        """rasterdepth_indexed, and per covered sample the atomic maximum of bits(z) << 34 | (triangle_offsets[drawId] + t + 1) into `visibility`
+        (u64 width x height: the caller clears it) — nv_rasterdepth_indexed_visibility.  triangle_offsets: draw_count + 1 u64 on the device
+        (host.assign_triangle_offsets); on a shard, the full array sliced at the rank's first draw"""
+        check(lib.nv_rasterdepth_indexed_visibility(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(dcb), _ptr(dccb), _ptr(db), int(draw_count),
+                                                    _ptr(ib), int(index_capacity), _ptr(vertices), int(vertex_capacity), _ptr(depth), int(width),
+                                                    int(height), _ptr(totals4), _ptr(triangle_offsets), _ptr(visibility)),
+              "nv_rasterdepth_indexed_visibility")
+
+    def visibility_resolve_indexed(self, cull, visibility, width, height, db, draw_count, mb, mesh_count, triangle_offsets, records=None,
+                                   draw_pixels=None, totals4=None):
+        """rasterdepth_indexed_visibility's target back to {draw, index position, vertex offset, depth bits} per pixel
+        (nv_visibility_resolve_indexed).  db / mb / triangle_offsets: the FULL arrays; cull: the CullData of the frame that was rasterised.
+        records (width * height layouts.VISINDEXEDRECORD), draw_pixels (draw_count u32, accumulated) and totals4 (u64: covered, unresolved, 0,
+        0, accumulated) are each optional"""
+        check(lib.nv_visibility_resolve_indexed(self.h, _stream(), C.c_void_p(cull.ctypes.data), _ptr(visibility), int(width), int(height), _ptr(db),
+                                                int(draw_count), _ptr(mb), int(mesh_count), _ptr(triangle_offsets), _ptr(records), _ptr(draw_pixels),
+                                                _ptr(totals4)), "nv_visibility_resolve_indexed")
+
+    def visibility_attributes_indexed(self, globals_, records, width, height, db, draw_count, ib, index_capacity, vertices, vertex_capacity,
+                                      materials=None, material_count=0, attributes=None, gbuffer0=None, gbuffer1=None, totals4=None):
+        """visibility_attributes over visibility_resolve_indexed's records (nv_visibility_attributes_indexed): the corners are
+        vertices[ib[indexPosition + k] + vertexOffset]; outputs, totals and the material rule as visibility_attributes"""
+        check(lib.nv_visibility_attributes_indexed(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(records), int(width), int(height), _ptr(db),
+                                                   int(draw_count), _ptr(ib), int(index_capacity), _ptr(vertices), int(vertex_capacity),
+                                                   _ptr(materials), int(material_count), _ptr(attributes), _ptr(gbuffer0), _ptr(gbuffer1),
+                                                   _ptr(totals4)), "nv_visibility_attributes_indexed")
+
     def depth_merge(self, dst, srcs, width, height):
         """dst = element-wise maximum of dst and every target of `srcs` on the bit patterns (nv_depth_merge): the depth composite of shards
         that live on one device, and the fold of a received target into the local one"""
@@ -541,6 +570,11 @@ class VisibilityPipeline:
                 if indices is not None:
                     ind = np.ascontiguousarray(indices, np.uint32)
                     self.ib = to_device(ind, dev) if len(ind) else torch.zeros(4, dtype=torch.uint8, device=dev)
+        # the names of the triangles of the classic path: with the index buffer and stable ids the indexed raster can write a
+        # visibility target too (render_draws / frame(task=False, visibility=)).  The prefix is the scene's, also on a shard; it is built and
+        # uploaded by the first call that needs it (_triangle_names), so a pipeline that never asks for it costs nothing and constructs as before
+        self.tob = self.triangle_offsets = None
+        self._meshes_host = meshes if self.ib is not None and self.stable_ids else None
 
     # src/niagara.cpp:1530-1574
     def cull(self, cull_data, late, task=True, post_pass=0):
@@ -596,16 +630,38 @@ class VisibilityPipeline:
         self.ctx.rasterdepth(g, self.dcb, self.db, self.mlb, self.mdb, self.vb, self.cib, self.ccb, self.depth, self.depth_w, self.depth_h,
                              visibility, totals4)
 
-    def render_draws(self, cull_data, late, post_pass=0, totals4=None):
+    def _triangle_names(self, what):
+        """the scene's triangle offsets on the device (nv_assign_triangle_offsets), built on first use; NvError when the pipeline has no index
+        buffer or no stable ids, or the scene holds more than 2^34 - 2 triangle names"""
+        if self.tob is None:
+            if self._meshes_host is None:
+                raise NvError(what + " names triangles by a frame-stable id: VisibilityPipeline(..., indices=, vertices=, stable_ids=True)")
+            self.triangle_offsets = host.assign_triangle_offsets(self.draws_host, self._meshes_host)
+            self.tob = to_device(self.triangle_offsets, self.ctx.device)
+        return self.tob
+
+    def _draw_triangle_offsets(self):
+        """the triangle offsets of the draws the passes run on (a shard: the scene's prefix from its first draw on)"""
+        return self._triangle_names("render_draws(visibility=)")
+
+    def render_draws(self, cull_data, late, post_pass=0, totals4=None, visibility=None):
         """the classic branch of render() (src/niagara.cpp:1680-1694): the MeshDrawCommands of the last cull(task=False) drawn from ib into
-        self.depth.  The early pass clears the target first, the late and post passes load it"""
+        self.depth.  The early pass clears the target first, the late and post passes load it.  visibility (stable_ids=True): a u64 target
+        that takes the stable-form word of nv_rasterdepth_indexed_visibility, cleared and loaded with the depth; resolve(classic=True) reads it"""
         if self.ib is None:
             raise NvError("render_draws needs the index buffer: VisibilityPipeline(..., indices=, vertices=)")
+        offsets = None if visibility is None else self._draw_triangle_offsets()  # (raises before anything is cleared)
         if not late:
             self.depth.zero_()
+            if visibility is not None:
+                visibility.zero_()
         pass_data = cull_data.copy()
         pass_data["postPass"] = post_pass
         g = synth.make_globals(pass_data, (self.depth_w, self.depth_h))
+        if visibility is not None:
+            self.ctx.rasterdepth_indexed_visibility(g, self.dcb, self.dccb, self.db, self.draw_count, self.ib, self.index_count, self.vb,
+                                                    self.vertex_count, self.depth, self.depth_w, self.depth_h, offsets, visibility, totals4)
+            return
         self.ctx.rasterdepth_indexed(g, self.dcb, self.dccb, self.db, self.draw_count, self.ib, self.index_count, self.vb, self.vertex_count,
                                      self.depth, self.depth_w, self.depth_h, totals4)
 
@@ -613,14 +669,24 @@ class VisibilityPipeline:
         """a cleared visibility target of the depth target's size (u64 words, held as int64)"""
         return torch.zeros((self.depth_h, self.depth_w), dtype=torch.int64, device=self.ctx.device)
 
-    def resolve(self, cull_data, visibility, records=True, meshlet_seen=True, draw_pixels=True):
+    def resolve(self, cull_data, visibility, records=True, meshlet_seen=True, draw_pixels=True, classic=False):
         """nv_visibility_resolve of a frame's stable-form visibility target under the frame's CullData: a dict with "records" (uint8 tensor,
         height * width NvVisRecord), "meshlet_seen" (int32, mvb's size and layout), "draw_pixels" (int32 per draw of the whole scene) and
-        "totals" (int64: covered, unresolved, 0, 0); an output switched off is None.  Draw ids are the scene's, also on a shard"""
+        "totals" (int64: covered, unresolved, 0, 0); an output switched off is None.  Draw ids are the scene's, also on a shard.
+        classic=True: the target is a classic frame's (frame(task=False, visibility=)): nv_visibility_resolve_indexed, "records" are
+        NvVisIndexedRecords and "meshlet_seen" is None (the classic path has no meshlets)"""
         if not self.stable_ids:
             raise NvError("resolve reads the stable form of the visibility word: VisibilityPipeline(..., stable_ids=True)")
         dev = self.ctx.device
         n_draws = getattr(self, "total_draws", self.draw_count)
+        if classic:
+            tob = self._triangle_names("resolve(classic=True)")
+            out = dict(records=torch.zeros(self.depth_w * self.depth_h * L.VISINDEXEDRECORD.itemsize, dtype=torch.uint8, device=dev) if records else None,
+                       meshlet_seen=None, draw_pixels=torch.zeros(max(1, n_draws), dtype=torch.int32, device=dev) if draw_pixels else None,
+                       totals=torch.zeros(4, dtype=torch.int64, device=dev))
+            self.ctx.visibility_resolve_indexed(cull_data, visibility, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws, self.mb,
+                                                self.mesh_count, tob, out["records"], out["draw_pixels"], out["totals"])
+            return out
         out = dict(records=torch.zeros(self.depth_w * self.depth_h * L.VISRECORD.itemsize, dtype=torch.uint8, device=dev) if records else None,
                    meshlet_seen=torch.zeros_like(self.mvb) if meshlet_seen else None,
                    draw_pixels=torch.zeros(max(1, n_draws), dtype=torch.int32, device=dev) if draw_pixels else None,
@@ -663,16 +729,21 @@ class VisibilityPipeline:
             return "blocks", (self.texture_table, len(self.texture_descs), self.texture_block_buffer, self.texture_block_buffer.numel() // 16)
         return "textured", (self.texture_table, len(self.texture_descs), self.texels, self.texels.numel())
 
-    def attributes(self, cull_data, records, materials=None, attributes=True, gbuffers=True, textures=False):
+    def attributes(self, cull_data, records, materials=None, attributes=True, gbuffers=True, textures=False, classic=False):
         """nv_visibility_attributes over resolve()'s "records" under the frame's CullData: a dict with "attributes" (uint8 tensor, height *
         width NvPixelAttributes), "gbuffer0" / "gbuffer1" (int32, height x width; only with `materials`, a host array of layouts.MATERIAL or a
         device tensor of them) and "totals" (int64: shaded, invalid, degenerate, textured); an output switched off is None.  The records are
         global (the scene's draw ids), so this works unchanged on any rank of a sharded frame after the composite.  textures=True runs
         nv_visibility_attributes_textured over set_textures()'s set: the complete fragment stage; totals[3] then counts only the pixels whose
-        material names a texture the set does not hold"""
+        material names a texture the set does not hold.  classic=True: `records` are resolve(classic=True)'s and the pass is
+        nv_visibility_attributes_indexed (no textured form)"""
         if not self.stable_ids:
             raise NvError("attributes reads resolve()'s records: VisibilityPipeline(..., stable_ids=True)")
-        if self.mdb is None:
+        if classic and textures:
+            raise NvError("attributes(classic=True, textures=True): the indexed attribute pass has no textured form")
+        if classic and self.ib is None:
+            raise NvError("attributes(classic=True) needs the index buffer: VisibilityPipeline(..., indices=, vertices=)")
+        if not classic and self.mdb is None:
             raise NvError("attributes needs the scene's geometry: VisibilityPipeline(..., meshlet_data=, vertices=)")
         dev = self.ctx.device
         n = self.depth_w * self.depth_h
@@ -697,6 +768,11 @@ class VisibilityPipeline:
                                                                self.meshlet_count, self.mdb, self.mdb.numel() * self.mdb.element_size() // 4, self.vb,
                                                                self.vertex_count, mat, n_mat, out["attributes"], out["gbuffer0"], out["gbuffer1"],
                                                                out["totals"], *tset)
+            return out
+        if classic:
+            self.ctx.visibility_attributes_indexed(g, records, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws, self.ib,
+                                                   self.index_count, self.vb, self.vertex_count, mat, n_mat, out["attributes"], out["gbuffer0"],
+                                                   out["gbuffer1"], out["totals"])
             return out
         self.ctx.visibility_attributes(g, records, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws, self.mlb, self.meshlet_count,
                                        self.mdb, self.mdb.numel() * self.mdb.element_size() // 4, self.vb, self.vertex_count, mat, n_mat,
@@ -836,13 +912,14 @@ class VisibilityPipeline:
         pyramid -> late cull -> clusters -> raster (-> post cull -> clusters -> raster).  task=False runs the classic path instead (no mesh
         shading): every cull writes MeshDrawCommands, render_draws rasterises them, and clusterOcclusionEnabled is 0 (src/niagara.cpp:1516).
         on_phase(name) is called after each phase's raster ("early", "late", "post").  visibility (stable_ids=True, task=True): a u64
-        target of the depth target's size that the three rasters share (cleared before the early one); resolve() reads it.  textures=True
+        target of the depth target's size that the three rasters share (cleared before the early one); resolve() reads it — with task=False
+        (and indices=) the indexed raster writes it and resolve(classic=True) / attributes(classic=True) read it.  textures=True
         (task=True, after set_textures, with `materials`): the post phase's raster is render_depth(textures=True), the alpha-tested one; the early
         and late phases stay on nv_rasterdepth (their bits are the same through either entry point)"""
         if textures and not task:
             raise NvError("frame(textures=True) needs the cluster path (task=True): nv_rasterdepth_indexed has no alpha-tested form")
-        if visibility is not None and not (self.stable_ids and task):
-            raise NvError("frame(visibility=) needs stable ids and the cluster path: VisibilityPipeline(..., stable_ids=True), task=True "
+        if visibility is not None and not self.stable_ids:
+            raise NvError("frame(visibility=) needs stable ids: VisibilityPipeline(..., stable_ids=True) "
                           "(the slot index of the default visibility word does not outlive a pass)")
         if not task:
             cull_data = cull_data.copy()
@@ -859,7 +936,7 @@ class VisibilityPipeline:
                 else:
                     self.render_depth(cull_data, late=late, post_pass=pp, visibility=visibility)
             else:
-                self.render_draws(cull_data, late=late, post_pass=pp)
+                self.render_draws(cull_data, late=late, post_pass=pp, visibility=visibility)
             if on_phase is not None:
                 on_phase(name)
 
@@ -954,16 +1031,19 @@ class ShardedVisibilityPipeline(VisibilityPipeline):
             raise NvError("a sharded frame has no visibility buffer: the slot index nv_rasterdepth writes is rank-local")
         super().render_depth(self._local(cull_data), late, post_pass, visibility, totals4)
 
-    def render_draws(self, cull_data, late, post_pass=0, totals4=None):
-        super().render_draws(self._local(cull_data), late, post_pass, totals4)
+    def _draw_triangle_offsets(self):
+        return self._triangle_names("render_draws(visibility=)")[self.begin * 8:]  # (a byte tensor of u64) global values, rank-local drawIds: every rank writes the same words
+
+    def render_draws(self, cull_data, late, post_pass=0, totals4=None, visibility=None):
+        super().render_draws(self._local(cull_data), late, post_pass, totals4, visibility)
 
     PHASES = (("early", False, 0), ("late", True, 0), ("post", True, 1))
 
     def phase(self, cull_data, name, task=True, totals4=None, visibility=None):
         """one phase of frame() up to and including its raster; the composite is the caller's next step"""
-        if visibility is not None and not (self.stable_ids and task):
+        if visibility is not None and not self.stable_ids:
             raise NvError("a sharded frame has no visibility buffer: the slot index nv_rasterdepth writes is rank-local "
-                          "(ShardedVisibilityPipeline(..., stable_ids=True) and task=True name clusters by a frame-stable id instead)")
+                          "(ShardedVisibilityPipeline(..., stable_ids=True) names clusters and triangles by a frame-stable id instead)")
         late, pp = {n: (l, p) for n, l, p in self.PHASES}[name]
         if not task:
             cull_data = cull_data.copy()
@@ -975,7 +1055,7 @@ class ShardedVisibilityPipeline(VisibilityPipeline):
             self.render_clusters(cull_data, late=late, post_pass=pp)
             self.render_depth(cull_data, late=late, post_pass=pp, totals4=totals4, visibility=visibility)
         else:
-            self.render_draws(cull_data, late=late, post_pass=pp, totals4=totals4)
+            self.render_draws(cull_data, late=late, post_pass=pp, totals4=totals4, visibility=visibility)
 
     def composite(self, visibility=None):
         """this rank's depth target (and stable-form visibility target) := the maximum over the ranks of the group (a no-op without a group)"""
@@ -990,9 +1070,9 @@ class ShardedVisibilityPipeline(VisibilityPipeline):
         the composite after the last phase: the rank's target then holds the earlier composites plus its own last raster"""
         if textures:
             raise NvError("frame(textures=True) is not available on a sharded pipeline")
-        if visibility is not None and not (self.stable_ids and task):
+        if visibility is not None and not self.stable_ids:
             raise NvError("a sharded frame has no visibility buffer: the slot index nv_rasterdepth writes is rank-local "
-                          "(ShardedVisibilityPipeline(..., stable_ids=True) and task=True name clusters by a frame-stable id instead)")
+                          "(ShardedVisibilityPipeline(..., stable_ids=True) names clusters and triangles by a frame-stable id instead)")
         names = ["early", "late"] + (["post"] if post_pass else [])
         for name in names:
             self.phase(cull_data, name, task=task, visibility=visibility)

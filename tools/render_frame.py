@@ -9,6 +9,7 @@
     python3 tools/render_frame.py --traced-shadows --animate 8          # 8 images, one box on a circle: its shadow follows (§4.17)
     python3 tools/render_frame.py --alpha-shadows                       # the wall is a cut-out in the post pass: its shadow has holes (§4.19)
     python3 tools/render_frame.py --alpha-coverage --alpha-shadows      # and so has the wall: the boxes behind it show through (§4.20)
+    python3 tools/render_frame.py --classic [--bloom]                   # the classic path's frame: indexed draws, their visibility buffer (§4.23)
 
 Writes a binary PPM (P6, R G B from the R8G8B8A8 colour words) and prints one JSON line with the passes' times by HIP events (one run
 each after a warm-up frame: launch gaps included, an upper bound of the kernel time; profiles/r13_shade.md has the kernel trace).
@@ -258,6 +259,8 @@ def main():
     ap.add_argument("--alpha-coverage", action="store_true", help="--textures with the wall in the post pass and a cut-out albedo: the post phase's raster runs the "
                     "fragment's alpha test (nv_rasterdepth_textured, DESIGN.md §4.20) and the boxes behind the wall's holes are in the image; alone or "
                     "with --alpha-shadows")
+    ap.add_argument("--classic", action="store_true", help="the classic path (no mesh shading): frame(task=False, visibility=) over the indexed draws, "
+                    "resolve(classic=True), attributes(classic=True), shade (DESIGN.md §4.23); the factor-only fragment stage: not with --textures")
     ap.add_argument("--quality", type=int, default=1, help="--traced-shadows: 0 = opaque draws cast, 1 = post-pass draws too")
     ap.add_argument("--animate", type=int, default=0, help="--traced-shadows: write N images (out_000.ppm ...) with one draw displaced along a circle "
                     "per frame through move_draws, which rebuilds the TLAS on the device")
@@ -271,6 +274,8 @@ def main():
     if args.alpha_coverage or args.block_textures:
         args.textures = True
     cutout = args.alpha_shadows or args.alpha_coverage
+    if args.classic and args.textures:
+        ap.error("--classic shades from the materials' factors: the indexed attribute pass and raster have no textured form")
     if args.passes == "shadow_trace":
         if not args.traced_shadows:
             ap.error("--passes shadow_trace times the ray-traced pass: give --traced-shadows")
@@ -285,7 +290,7 @@ def main():
     from niagara_amd import layouts as L
     from niagara_amd import pipeline as P
 
-    s = _scene(args, args.traced_shadows)  # the traced mask needs the index buffer of the classic path
+    s = _scene(args, args.traced_shadows or args.classic)  # the traced mask and the classic frame need the index buffer of the classic path
     w, h = s["viewport"]
     # attributes for the vertices and a material per draw: unit normals from the positions, colours by draw
     rng = np.random.default_rng(7)
@@ -310,7 +315,8 @@ def main():
         v, materials, textures = t["vertices"], t["materials"], t["textures"]
     if cutout:
         draws["postPass"][s["wall"]] = 1  # both alpha tests see post-pass draws only (src/scenert.cpp:516, mesh.frag.glsl:88)
-    pipe = P.VisibilityPipeline(s["meshes"], s["meshlets"], draws, (w, h), fused=True, vertices=v, meshlet_data=s["data"], stable_ids=True)
+    pipe = P.VisibilityPipeline(s["meshes"], s["meshlets"], draws, (w, h), fused=True, vertices=v, meshlet_data=s["data"], stable_ids=True,
+                                indices=s["indices"] if args.classic else None)
     if textures:
         pipe.set_textures(textures, resident="blocks" if args.block_textures else "decoded")
     x, y = np.meshgrid(np.arange(w), np.arange(h))
@@ -323,9 +329,11 @@ def main():
 
     def frame(events):
         vis = pipe.new_visibility()
-        _timed(events, "frame", lambda: pipe.frame(s["cull"], post_pass=True, visibility=vis, textures=args.alpha_coverage, materials=mat))
-        res = _timed(events, "resolve", lambda: pipe.resolve(s["cull"], vis))
-        att = _timed(events, "attributes", lambda: pipe.attributes(s["cull"], res["records"], mat, attributes=False, textures=args.textures))
+        _timed(events, "frame", lambda: pipe.frame(s["cull"], post_pass=True, visibility=vis, textures=args.alpha_coverage, materials=mat,
+                                                   task=not args.classic))
+        res = _timed(events, "resolve", lambda: pipe.resolve(s["cull"], vis, classic=args.classic))
+        att = _timed(events, "attributes", lambda: pipe.attributes(s["cull"], res["records"], mat, attributes=False, textures=args.textures,
+                                                                   classic=args.classic))
         shadow = None if args.no_shadow else "trace" if args.traced_shadows else torch.from_numpy(mask.copy()).to(pipe.ctx.device)
         return _timed(events, "shade", lambda: pipe.shade(s["cull"], att["gbuffer0"], att["gbuffer1"], (0.0, 0.0, 0.0), sun, shadow=shadow,
                                                           checkerboard=args.checkerboard, bloom=args.bloom, quality=args.quality,
@@ -336,7 +344,7 @@ def main():
         with open(path, "wb") as f:
             f.write(b"P6\n%d %d\n255\n" % (w, h))
             f.write(rgb.tobytes())
-        print(json.dumps(dict(out=path, viewport=[w, h], shadow=not args.no_shadow, traced=bool(args.traced_shadows and not args.no_shadow), bloom=args.bloom,
+        print(json.dumps(dict(out=path, viewport=[w, h], shadow=not args.no_shadow, traced=bool(args.traced_shadows and not args.no_shadow), bloom=args.bloom, classic=bool(args.classic),
                               covered=int((pipe.depth > 0).sum().item()), alpha_coverage=bool(args.alpha_coverage), mean_rgb=[round(float(c), 2) for c in rgb.reshape(-1, 3).mean(0)],
                               us={name: round(a.elapsed_time(b) * 1e3, 1) for name, a, b in events}, **extra)))
     frame([])  # warm-up (and the visibility bits of the closed loop)

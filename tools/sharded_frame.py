@@ -7,12 +7,13 @@
     python3 tools/sharded_frame.py --local-shards 8                           # 8 shards in ONE process, composite = nv_depth_merge
     python3 tools/sharded_frame.py --as-rank 0/8                              # one rank's share alone (no exchange): the per-rank frame cost
     python3 tools/sharded_frame.py --local-shards 4 --visibility              # + the stable-ID visibility buffer, composited and resolved
+    python3 tools/sharded_frame.py --local-shards 2 --scene occluder_indexed --visibility --attributes   # the classic path's
 
 Like bench.py --gpus N it starts its own ranks under torch.distributed.run when no launcher did.  Prints ONE JSON line (rank 0): the
 per-phase counts of the last frame summed over the ranks, the frame time (MAX over the ranks; the shortest of three timed loops of
 --frames frames) and the time of one depth composite.  --dump DIR writes rank_<r>.npz per rank: for every frame f and phase p the
 commands, cluster ids, dvb (the rank's draws), mvb, counts and depth, and the pyramid per frame (the frames start from cleared
-visibility; nothing is timed then).  --visibility (cluster scenes) runs the frame with stable ids and a visibility target per rank,
+visibility; nothing is timed then).  --visibility runs the frame with stable ids (on an indexed scene: the classic path, its triangle names and indexed records) and a visibility target per rank,
 composited with the depth; the JSON line gains the resolve totals of the last frame and the dump "f<f>_visibility" and "f<f>_records".
 --attributes (with --visibility) runs the attribute pass on every rank after the last frame (a fixed four-entry material table; the
 vertices' packed fields as the scene has them): the JSON line gains its totals and one digest of the outputs per rank of this process
@@ -128,8 +129,7 @@ def main():
 
     s, task, near_clip = make_scene(args)
     geometry = dict(vertices=s["vertices"], meshlet_data=s["data"]) if task else dict(vertices=s["vertices"], indices=s["indices"])
-    if args.visibility and not task:
-        raise SystemExit("--visibility needs a cluster scene: the indexed path has no visibility buffer")
+    classic = not task  # an indexed scene: the classic path's visibility buffer, resolve and attribute pass
     if args.attributes and not args.visibility:
         raise SystemExit("--attributes reads the resolved visibility buffer: add --visibility")
     kw = dict(task_capacity=4096 if len(s["draws"]) < 256 else None, cluster_capacity=4096 * 64 if len(s["draws"]) < 256 else None,
@@ -182,7 +182,8 @@ def main():
                 d["f%d_pyramid" % f] = p.pyramid.data.cpu().numpy().copy()
                 if vis is not None:
                     d["f%d_visibility" % f] = vis_of(k).cpu().numpy().view(np.uint64).copy()
-                    d["f%d_records" % f] = P.from_device(p.resolve(s["cull"], vis_of(k))["records"], L.VISRECORD).copy()
+                    d["f%d_records" % f] = P.from_device(p.resolve(s["cull"], vis_of(k), classic=classic)["records"],
+                                                          L.VISINDEXEDRECORD if classic else L.VISRECORD).copy()
         for p, d in zip(pipes, dumps):
             np.savez(os.path.join(args.dump, "rank_%d.npz" % (p.rank if shards or args.as_rank else rank)), **d)
         result.update(frame_ms=None, composite_ms=None, timed=False)
@@ -213,7 +214,7 @@ def main():
         runner.frame(s["cull"], on_phase=lambda name: last_counts.__setitem__(name, counts_now()), **frame_kw)
         result.update(frame_ms=float(t[0]), composite_ms=float(t[1]), timed=True)
     if vis is not None:  # every rank holds the frame's buffer after the composite: rank 0's resolve is the frame's
-        tot = pipes[0].resolve(s["cull"], vis_of(0), records=False)["totals"].cpu().numpy()
+        tot = pipes[0].resolve(s["cull"], vis_of(0), records=False, classic=classic)["totals"].cpu().numpy()
         result.update(visibility=True, covered_pixels=int(tot[0]), unresolved_pixels=int(tot[1]), visibility_payload_bytes=w * h * 8)
     if args.attributes:  # the records are global after the composite: every rank shades the whole frame, and all of them the same bytes
         import hashlib
@@ -222,7 +223,7 @@ def main():
         mats["diffuseFactor"][:, 0] = np.linspace(0.2, 1.0, 4)
         digests, tot = [], None
         for k, p in enumerate(pipes):
-            out = p.attributes(s["cull"], p.resolve(s["cull"], vis_of(k))["records"], mats)
+            out = p.attributes(s["cull"], p.resolve(s["cull"], vis_of(k), classic=classic)["records"], mats, classic=classic)
             tot = out["totals"].cpu().numpy()
             hsh = hashlib.sha256()
             for name in ("attributes", "gbuffer0", "gbuffer1"):
