@@ -228,8 +228,10 @@ inline vec4 imageLoad(image2D t, ivec2 p)
 	shim_stats[0] += !shim_inside(p, t.width, t.height);
 	return shim_inside(p, t.width, t.height) ? shim_decode(t.data, t.format, (size_t)p.y * t.width + (size_t)p.x) : vec4(0);
 }
+static ivec2 shim_last_store; /* where the running invocation's last imageStore went, inside the image or not (ref_shadow files its log there) */
 inline void imageStore(image2D t, ivec2 p, vec4 v)
 {
+	shim_last_store = p;
 	if (!shim_inside(p, t.width, t.height))
 	{
 		shim_stats[1]++;

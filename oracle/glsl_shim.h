@@ -50,6 +50,7 @@ struct uvec2
 	uvec2() : x(0), y(0) {}
 	uvec2(uint x_, uint y_) : x(x_), y(y_) {}
 };
+struct ivec2;
 struct vec2
 {
 	float x, y;
@@ -57,6 +58,7 @@ struct vec2
 	explicit vec2(float s) : x(s), y(s) {}
 	vec2(float x_, float y_) : x(x_), y(y_) {}
 	explicit vec2(uvec2 v) : x((float)v.x), y((float)v.y) {}
+	explicit inline vec2(ivec2 v); /* shadow.comp.glsl:136, :147-148 */
 	vec2 xy() const { return *this; }
 	vec2 yx() const { return vec2(y, x); }
 };
@@ -68,7 +70,10 @@ struct ivec2
 	explicit ivec2(int s) : x(s), y(s) {}
 	explicit ivec2(uint s) : x((int)s), y((int)s) {}
 	explicit ivec2(uvec2 v) : x((int)v.x), y((int)v.y) {}
+	ivec2 xy() const { return *this; }
+	ivec2 yx() const { return ivec2(y, x); }
 };
+inline vec2::vec2(ivec2 v) : x((float)v.x), y((float)v.y) {}
 struct uvec3
 {
 	uint x, y, z;
@@ -239,6 +244,9 @@ inline uint atomicAnd(uint& mem, uint v)
 #ifdef REF_SHADING
 } // namespace glsl
 #include "glsl_shade_shim.h"
+#ifdef REF_SHADOW /* shadow.comp.glsl: a CPU rayQueryEXT and the material sampler's textureLod */
+#include "glsl_rayquery_shim.h"
+#endif
 namespace glsl
 {
 #else

@@ -181,6 +181,55 @@ def final(sd, gbuffer0, gbuffer1, depth, shadow=None, bloom0=None):
     return out, handed
 
 
+RAY_INFO = ("queries", "flags", "opaque_commits", "candidates", "confirmed", "committed_instance")
+
+
+def has_shadow():
+    """True when the built library holds shadow.comp.glsl.  One built before that shader was translated does not: an out-of-date build, which
+    tests/test_shadow_vs_ref.py reports as a failure that names `make -C oracle ref`, not as a skip"""
+    return available() and hasattr(lib(), "ref_shadow")
+
+
+def shadow(sd, depth, meshes, indices, vertices, draws, materials=None, textures=None, quality=0, prefill=0):
+    """shadow.comp.glsl over its dispatch (src/niagara.cpp:1797-1817) against the CPU ray query of oracle/glsl_rayquery_shim.h.  sd: the 96-byte
+    ShadowData record; meshes / draws / vertices / materials in the C ABI's layouts (208 / 48 / 16 / 64 bytes); textures: None, or a dict with
+    "descs" (four words per texture: offset, width, height, levels; entry 0 reserved) and "texels" (uint32, decoded RGBA8).  Returns a dict:
+      mask    (h, w) u8      texels no invocation stored to keep the prefill byte
+      handed  (h, w, 4) f32  the vec4 given to each store (zeros where nothing was stored)
+      rays    (h, w, 8) f32  origin, direction, tmin, tmax of the storing invocation's query
+      queries, flags, opaque_commits, candidates, confirmed, committed_instance  (h, w) u32 each; rejected = candidates - confirmed;
+              queries == 0 where no invocation stored; committed_instance is 0xffffffff where nothing was committed
+      samples (n, 8) f32     id, u, v, the alpha returned, and the candidate's instance, primitive and barycentrics, of every textureLod call in
+              order
+      dropped, dropped_at_width  stores outside the image, and those of them with x == width inside the rows"""
+    h, w = depth.shape
+    sdw = np.frombuffer(np.ascontiguousarray(sd).tobytes(), np.float32).copy()
+    assert sdw.size == 24
+    m, i, v, d = (np.ascontiguousarray(a) for a in (meshes, indices, vertices, draws))
+    assert m.dtype.itemsize == 208 and v.dtype.itemsize == 16 and d.dtype.itemsize == 48 and i.dtype == np.uint32
+    mt = np.zeros(0, np.dtype([("w", np.uint32, 16)])) if materials is None else np.ascontiguousarray(materials)
+    assert mt.dtype.itemsize == 64
+    descs = np.zeros(0, np.uint32) if textures is None else np.ascontiguousarray(textures["descs"]).view(np.uint32).reshape(-1, 4)
+    texels = np.zeros(0, np.uint32) if textures is None else np.ascontiguousarray(textures["texels"], np.uint32)
+    mask = np.full((h, w), prefill, np.uint8)
+    handed, rays, info = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 8), np.float32), np.zeros((h, w, 6), np.uint32)
+    room = 1 << 16
+    while True:
+        stats("shadow")  # reset the shim's counters
+        samples, count = np.zeros((room, 8), np.float32), C.c_uint64(0)
+        mask[...] = prefill
+        lib().ref_shadow(_p(sdw), _p(_f32(depth)), C.c_uint32(w), C.c_uint32(h), _p(m), C.c_uint32(len(m)), _p(i), C.c_uint32(len(i)), _p(v), C.c_uint32(len(v)),
+                         _p(d), C.c_uint32(len(d)), _p(mt), C.c_uint32(len(mt)), _p(descs), C.c_uint32(len(descs)), _p(texels), C.c_uint64(len(texels)),
+                         C.c_int(quality), _p(mask), _p(handed), _p(rays), _p(info), _p(samples), C.c_uint64(room), C.byref(count))
+        if count.value <= room:
+            break
+        room = int(count.value)
+    st = stats("shadow")
+    out = dict(mask=mask, handed=handed, rays=rays, samples=samples[:count.value], dropped=st["dropped"], dropped_at_width=st["dropped_at_width"])
+    out.update({name: info[..., k] for k, name in enumerate(RAY_INFO)})
+    return out
+
+
 def bloom_pass(which, src, dst_shape, radius=0.0, dst=None):
     """one dispatch of bloom.comp.glsl: which 0 (src = gbuffer0 words), 1, 2 (src = a bloom level; dst = the level accumulated into)
     -> (level (h, w) u32, handed (h, w, 4) f32)"""

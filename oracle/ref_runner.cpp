@@ -664,3 +664,157 @@ extern "C" void ref_mesh_frag(const void* records, uint32_t n, uint32_t width, c
 	}
 }
 #endif
+
+#ifdef REF_SHADOW
+#include <vector>
+/* src/niagara.cpp:1797-1817: dispatch(shadowWidthCB, height) of shadow.comp.glsl, shadowWidthCB = checkerboard ? (width + 1) / 2 : width, into
+ * shadowTarget (R8_UNORM); QUALITY 0 is shadowlqPipeline, 1 shadowhqPipeline (:1803).  sd: the 96-byte ShadowData as the host lays it out (vec3,
+ * float, mat4, vec2, int).  The bindings of :1808 are the caller's arrays in the C ABI's layouts (Mesh 208 bytes, MeshDraw 48, Vertex 16,
+ * Material 64, texture descriptors of four words {offset, width, height, levels} over one buffer of decoded RGBA8 words, entry 0 reserved).
+ * The acceleration structure is built here from the draws as glsl_rayquery_shim.h's model states (fillInstanceRT, src/scenert.cpp:504-518).
+ * mask: w * h bytes, prefilled by the caller; texels no invocation stores to keep their byte.  Per texel an invocation stored to: handed (4
+ * floats: the vec4 given to imageStore), rays (8 floats: origin, direction, tmin, tmax of its last rayQueryInitializeEXT) and info (6 words:
+ * queries initialised, ray flags, opaque commits, non-opaque candidates, confirmed candidates, the committed instance or ~0).  samples: up to
+ * sampleRoom x 8 floats {id, u, v, alpha, instance, primitive, bary.x, bary.y} of the textureLod calls, in order; *sampleCount is how many there were. */
+extern "C" void ref_shadow(const float* sd, const float* depth, uint32_t w, uint32_t h, const void* meshes_, uint32_t meshCount, const uint32_t* indices_,
+                           uint32_t indexCapacity, const void* vertices_, uint32_t vertexCapacity, const void* draws_, uint32_t drawCount, const void* materials_,
+                           uint32_t materialCount, const uint32_t* descs, uint32_t textureCount, const uint32_t* texels, uint64_t texelWords, int quality,
+                           uint8_t* mask, float* handed, float* rays, uint32_t* info, float* samples, uint64_t sampleRoom, uint64_t* sampleCount)
+{
+	static_assert(sizeof(Mesh) == 208 && sizeof(MeshDraw) == 48 && sizeof(Vertex) == 16, "the translated structs have the C ABI's layouts");
+	struct MaterialIn
+	{
+		uint32_t tex[4];
+		float diffuse[4], specular[4], emissive[3];
+		uint32_t padding;
+	};
+	const MaterialIn* min_ = (const MaterialIn*)materials_;
+	int cb;
+	memcpy(&cb, sd + 22, 4);
+	shadowData.sunDirection = vec3(sd[0], sd[1], sd[2]);
+	shadowData.sunJitter = sd[3];
+	for (int c = 0; c < 4; ++c)
+		shadowData.inverseViewProjection[c] = vec4(sd[4 + 4 * c], sd[5 + 4 * c], sd[6 + 4 * c], sd[7 + 4 * c]);
+	shadowData.imageSize = vec2(sd[20], sd[21]);
+	shadowData.checkerboard = cb;
+	QUALITY = quality;
+
+	/* materials: one entry behind the table stands for every material index at or past it — "no texture" (the shader's own
+	 * load there is out of bounds) */
+	std::vector<Material> table(materialCount + 1u);
+	for (uint32_t m = 0; m < materialCount; ++m)
+	{
+		table[m].albedoTexture = min_[m].tex[0], table[m].normalTexture = min_[m].tex[1];
+		table[m].specularTexture = min_[m].tex[2], table[m].emissiveTexture = min_[m].tex[3];
+	}
+	table[materialCount].albedoTexture = 0;
+	std::vector<MeshDraw> drawTable(drawCount ? drawCount : 1u);
+	if (drawCount)
+		memcpy(drawTable.data(), draws_, (size_t)drawCount * sizeof(MeshDraw));
+	for (uint32_t i = 0; i < drawCount; ++i)
+		if (drawTable[i].materialIndex >= materialCount)
+			drawTable[i].materialIndex = materialCount;
+	draws = drawTable.data();
+	meshes = (Mesh*)meshes_;
+	materials = table.data();
+	vertices = (Vertex*)vertices_;
+	indices = (uint*)indices_;
+
+	/* textures: level 0 of every descriptor the set holds whole (DESIGN.md §4.18's descriptor check); the others are "no texture" */
+	std::vector<ShimLevel0> levels(textureCount ? textureCount : 1u);
+	for (uint32_t t = 0; t < textureCount; ++t)
+	{
+		const uint32_t offset = descs[4 * t], tw = descs[4 * t + 1], th = descs[4 * t + 2], tl = descs[4 * t + 3];
+		uint64_t words = 0;
+		bool ok = t != 0 && tw != 0 && th != 0 && tw <= 16384u && th <= 16384u && tl != 0 && tl <= 15u;
+		for (uint32_t l = 0; ok && l < tl; ++l)
+			words += (uint64_t)((tw >> l) ? (tw >> l) : 1u) * ((th >> l) ? (th >> l) : 1u);
+		ok = ok && (uint64_t)offset + words <= texelWords;
+		levels[t].texels = ok ? texels + offset : 0;
+		levels[t].width = tw, levels[t].height = th;
+	}
+	shim_rq_textures = levels.data();
+	shim_rq_texture_count = textureCount;
+	shim_rq_samples.clear();
+
+	/* the acceleration structure: the triangles of every mesh's lods[lodRT] once, an instance per draw */
+	const Mesh* meshIn = (const Mesh*)meshes_;
+	const Vertex* vertexIn = (const Vertex*)vertices_;
+	std::vector<std::vector<nv::rt3>> corners(meshCount);
+	std::vector<std::vector<uint8_t>> kept(meshCount);
+	for (uint32_t m = 0; m < meshCount; ++m)
+	{
+		const Mesh& mesh = meshIn[m];
+		if (mesh.lodRT >= 8u || mesh.lodRT >= mesh.lodCount)
+			continue;
+		const MeshLod& lod = mesh.lods[mesh.lodRT];
+		const uint32_t count = lod.indexCount / 3u;
+		corners[m].resize((size_t)count * 3u);
+		kept[m].assign(count, 1);
+		for (uint32_t t = 0; t < count; ++t)
+			for (uint32_t k = 0; k < 3u; ++k)
+			{
+				const uint64_t at = (uint64_t)lod.indexOffset + 3ull * t + k;
+				const uint64_t corner = at < indexCapacity ? (uint64_t)mesh.vertexOffset + indices_[at] : ~0ull;
+				if (at >= indexCapacity || corner >= vertexCapacity)
+				{
+					kept[m][t] = 0;
+					continue;
+				}
+				corners[m][3 * (size_t)t + k] = nv::rt3{ (float)vertexIn[corner].vx, (float)vertexIn[corner].vy, (float)vertexIn[corner].vz };
+			}
+	}
+	std::vector<ShimRtInstance> instances(drawCount ? drawCount : 1u);
+	const MeshDraw* drawIn = (const MeshDraw*)draws_;
+	for (uint32_t i = 0; i < drawCount; ++i)
+	{
+		const MeshDraw& d = drawIn[i];
+		ShimRtInstance& in = instances[i];
+		in.position[0] = d.position.x, in.position[1] = d.position.y, in.position[2] = d.position.z;
+		in.scale = d.scale;
+		in.orientation[0] = d.orientation.x, in.orientation[1] = d.orientation.y, in.orientation[2] = d.orientation.z, in.orientation[3] = d.orientation.w;
+		in.mask = d.postPass < 32u ? (1u << d.postPass) & 0xffu : 0u; /* src/scenert.cpp:515 */
+		in.opaque = d.postPass == 0u;                                   /* :516 */
+		bool finite = nv::rt_finite(d.scale);
+		for (int k = 0; k < 3; ++k)
+			finite = finite && nv::rt_finite(in.position[k]);
+		for (int k = 0; k < 4; ++k)
+			finite = finite && nv::rt_finite(in.orientation[k]);
+		const bool geometry = d.postPass <= 1u /* :517 */ && d.meshIndex < meshCount && finite && d.scale > 0.0f && !kept[d.meshIndex < meshCount ? d.meshIndex : 0].empty();
+		in.corners = geometry ? corners[d.meshIndex].data() : 0;
+		in.kept = geometry ? kept[d.meshIndex].data() : 0;
+		in.triangles = geometry ? (uint)kept[d.meshIndex].size() : 0u;
+	}
+	tlas.instances = instances.data();
+	tlas.count = drawCount;
+
+	outImage = bind_image(mask, w, h, FORMAT_R8_UNORM, handed);
+	depthImage = bind_texture(depth, w, h, FORMAT_R32_SFLOAT);
+	run_grid(cb ? (w + 1) / 2 : w, h, [&] {
+		ShimRayLog log;
+		memset(&log, 0, sizeof(log));
+		log.committedInstance = ~0u;
+		shim_rq_log = &log;
+		shim_last_store = ivec2(-1, -1);
+		shader_main();
+		shim_rq_log = &shim_rq_scratch;
+		if (!shim_inside(shim_last_store, w, h))
+			return;
+		const size_t at = (size_t)shim_last_store.y * w + (size_t)shim_last_store.x;
+		memcpy(rays + at * 8, log.origin, 8 * sizeof(float));
+		const uint32_t words[6] = { log.queries, log.flags, log.opaqueCommits, log.candidates, log.confirmed, log.committedInstance };
+		memcpy(info + at * 6, words, sizeof(words));
+	});
+	*sampleCount = shim_rq_samples.size();
+	for (size_t i = 0; i < shim_rq_samples.size() && i < sampleRoom; ++i)
+	{
+		const ShimSample& s = shim_rq_samples[i];
+		float* o = samples + 8 * i;
+		o[0] = (float)s.id, o[1] = s.u, o[2] = s.v, o[3] = s.alpha;
+		o[4] = (float)s.instance, o[5] = (float)s.primitive, o[6] = s.baryX, o[7] = s.baryY;
+	}
+	shim_rq_textures = 0;
+	shim_rq_texture_count = 0;
+	tlas.instances = 0, tlas.count = 0;
+}
+#endif

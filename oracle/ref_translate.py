@@ -21,7 +21,7 @@ Rewrites (nothing semantic):
   * `void main()` -> `void shader_main()`.
   * mesh-shader declarations (meshlet.mesh.glsl): `layout(triangles, ...) out;` dropped, `layout(location=N) out [flat] T
     name[];` -> `T name[256];`, `taskPayloadSharedEXT` / `shared` qualifiers dropped (the runner serialises a workgroup).
-`--shading` adds the rewrites the shading shaders need (shadowfill, shadowblur, final, bloom, mesh.frag), still purely syntactic; the cull
+`--shading` adds the rewrites the shading shaders need (shadowfill, shadowblur, final, bloom, mesh.frag, shadow), still purely syntactic; the cull
 shaders are translated without it, so their generated text does not depend on any of these:
   * literals with an exponent and no point (`1e-2`) get the `f` suffix too;
   * the colour swizzles: `.rgb` -> `.xyz()`, `.rg` -> `.xy()`, `.r .g .b .a` -> `.x .y .z .w`; `.yx` -> `.yx()`;
@@ -29,7 +29,11 @@ shaders are translated without it, so their generated text does not depend on an
   * fragment-stage declarations: `layout(location=N) in [flat] T name;` -> `T name;`, `layout(location=N) out vec4 gbuffer[2];` ->
     `vec4 gbuffer[2];`, `layout(constant_id=N) const int X = v;` -> `int X = v;`, `uniform texture2D textures[];` -> the shim's table
     (`nonuniformEXT` is a function of the shim);
-  * `discard;` -> `{ ref_discard = true; return; }` (the runner reads the flag back).
+  * `discard;` -> `{ ref_discard = true; return; }` (the runner reads the flag back);
+  * `layout(binding=N) uniform accelerationStructureEXT name;` (shadow.comp.glsl:45) -> `accelerationStructureEXT name;`, a global of the
+    type oracle/glsl_rayquery_shim.h defines.  It is the only rewrite shadow.comp.glsl adds: `rayQueryEXT rq;` (:80, :88) is already a C++
+    declaration of the shim's struct, and the `sampler2D(textures[nonuniformEXT(id)], textureSampler)` of its SAMP macro (:76) is the
+    constructor call mesh.frag.glsl's SAMP already makes (glsl_shade_shim.h's sampler2D and ShimTextureTable), so neither is touched.
 `--limit math.h:49` keeps only the first 49 lines of that include (the cull helpers; the rest is shading).
 `--define NAME=V` flips one of the reference's own `#define NAME ...` configuration switches (MESH_CULL, src/config.h:10-11).
 `--once "stmt;"` guards ONE statement with `if (gl_LocalInvocationID.x == 0u)`: a workgroup-shared variable that every
@@ -77,6 +81,7 @@ def translate(src):
         src = re.sub(r"layout\s*\(\s*location\s*=\s*\d+\s*\)\s*in\s+(?:flat\s+)?(\w+)\s+(\w+)\s*;", r"\1 \2;", src)
         src = re.sub(r"layout\s*\([^)]*\)\s*uniform\s+texture2D\s+(\w+)\s*\[\s*\]\s*;", r"ShimTextureTable \1;", src)
         src = re.sub(r"\bdiscard\s*;", "{ ref_discard = true; return; }", src)
+        src = re.sub(r"layout\s*\([^)]*\)\s*uniform\s+accelerationStructureEXT\s+(\w+)\s*;", r"accelerationStructureEXT \1;", src)
     src = re.sub(r"layout\s*\(\s*local_size_x[^)]*\)\s*in\s*;", "", src)
     src = re.sub(r"layout\s*\(\s*triangles[^)]*\)\s*out\s*;", "", src)
     src = re.sub(r"layout\s*\(\s*location\s*=\s*\d+\s*\)\s*out\s+(?:flat\s+)?(\w+)\s+(\w+)\s*\[\s*\]\s*;", r"\1 \2[256];", src)

@@ -7,6 +7,10 @@ mounted; the fixtures travel with the repository, the reference does not.
 
 Each fixture stores the inputs (meshes, meshlets, draws, CullData, depth target, flags) and every buffer the
 reference's passes leave behind over two frames of the early -> pyramid -> late protocol (src/niagara.cpp:1765-1788).
+
+Sections of their own, each in a directory of its own: `--shade` (tests/golden/shade: the shading passes) and `--shadow`
+(tests/golden/shadow: shadow.comp.glsl against a CPU ray query — masks per quality, the textured mask and the ray log; see
+shadow_fixtures).  Without an argument everything is written.
 """
 import os
 import sys
@@ -151,6 +155,52 @@ def shade_fixtures():
     assert total <= kitten, "the shade fixtures (%d bytes) outgrow the largest committed fixture (%d)" % (total, kitten)
 
 
+def shadow_fixtures():
+    """tests/golden/shadow/<w>x<h>.npz and range.npz: the inputs of the shadow pass at three image sizes, and of the four rays that hold tmin
+    and tmax from both sides exactly (tests/shadow_cases.py, range_case: one launch, its own one-mesh scene), and what the REFERENCE'S
+    shadow.comp.glsl, translated and run on the CPU against the ray query of oracle/glsl_rayquery_shim.h, makes of them.  Data only.
+      inputs   sd (one 96-byte NvShadowData record per launch of shadow_cases.FIXTURE_LAUNCHES), depth, meshes, indices, vertices, the draws
+               with the opaque scene's postPass (draws_opaque) and with the textured scene's (draws_textured), materials, the decoded set
+               (descs, texels) and the DDS file images it was decoded from (dds, dds_sizes)
+      outputs  per launch k: mask_q0_k, mask_q1_k (untextured, draws_opaque), mask_tex_k (quality 1 with the alpha test, draws_textured), each
+               over a mask prefilled with shadow_cases.PREFILL, and rays_k (origin, direction, tmin, tmax of every storing invocation)"""
+    import shadow_cases as SC
+    os.makedirs(SC.GOLDEN, exist_ok=True)
+
+    def record(launches, opaque, textured, tset, files):
+        depth = launches[0][1]
+        assert opaque["meshes"].tobytes() == textured["meshes"].tobytes() and opaque["indices"].tobytes() == textured["indices"].tobytes()
+        f = dict(sd=np.stack([np.frombuffer(sd.tobytes(), np.uint8) for sd, _ in launches]), depth=depth, meshes=textured["meshes"], indices=textured["indices"],
+                 vertices=textured["vertices"], draws_opaque=opaque["draws"], draws_textured=textured["draws"], materials=textured["materials"],
+                 descs=tset["descs"], texels=tset["texels"], dds=np.frombuffer(b"".join(files), np.uint8), dds_sizes=np.array([len(t) for t in files], np.uint32))
+        for k, (sd, d) in enumerate(launches):
+            assert d.tobytes() == depth.tobytes()
+            for q in (0, 1):
+                r = R.shadow(sd, d, textured["meshes"], textured["indices"], textured["vertices"], opaque["draws"], None, None, q, SC.PREFILL)
+                f["mask_q%d_%d" % (q, k)] = r["mask"]
+            f["rays_%d" % k] = r["rays"]
+            r = R.shadow(sd, d, textured["meshes"], textured["indices"], textured["vertices"], textured["draws"], textured["materials"], tset, 1, SC.PREFILL)
+            f["mask_tex_%d" % k] = r["mask"]
+        return f
+
+    opaque, (textured, tset) = SC.opaque_scene(), SC.textured_scene()
+    records = [("%dx%d" % (w, h), record([SC.inputs(w, h, jitter, cb) for cb, jitter in SC.FIXTURE_LAUNCHES], opaque, textured, tset, textured["textures"]))
+               for w, h in SC.SIZES]
+    # the four rays that hold tmin and tmax from both sides (shadow_cases.range_case): one launch
+    sd, depth, opaque, textured, tset, files = SC.range_case()
+    records.append(("range", record([(sd, depth)], opaque, textured, tset, files)))
+    assert (records[-1][1]["mask_q0_0"] == SC.RANGE_MASK).all() and (records[-1][1]["mask_tex_0"] == SC.RANGE_MASK).all()
+    total = 0
+    for name, f in records:
+        path = os.path.join(SC.GOLDEN, name + ".npz")
+        np.savez_compressed(path, **f)
+        total += os.path.getsize(path)
+        print("%-28s %6d bytes, %d arrays" % ("shadow/%s.npz" % name, os.path.getsize(path), len(f)))
+    kitten = os.path.getsize(os.path.join(HERE, "mesh", "kitten.npz"))
+    print("tests/golden/shadow: %d bytes" % total)
+    assert total <= kitten, "the shadow fixtures (%d bytes) outgrow the largest committed fixture (%d)" % (total, kitten)
+
+
 def kitten_fixture(obj):
     """tests/golden/mesh/kitten.npz: the reference's data/kitten.obj as arrays (the text file is too large to commit): positions and normals as
     float32 exactly as float() + np.float32 parse them, and every face corner as 0-based (position, normal) indices, three corners per triangle
@@ -180,7 +230,11 @@ if __name__ == "__main__":
     if len(sys.argv) == 2 and sys.argv[1] == "--shade":
         shade_fixtures()
         raise SystemExit(0)
+    if len(sys.argv) == 2 and sys.argv[1] == "--shadow":
+        shadow_fixtures()
+        raise SystemExit(0)
     main()
     mesh_fixture()
     task_fixture()
     shade_fixtures()
+    shadow_fixtures()

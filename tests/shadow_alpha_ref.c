@@ -95,6 +95,22 @@ static float alpha_lod0(const uint32_t* texels, const TextureDesc* d, float u, f
 	return mix1(mix1(a00, a01, ax), mix1(a10, a11, ax), ay);
 }
 
+/* shadow.comp.glsl:113: uv = uva (1 - bary.x - bary.y) + uvb bary.x + uvc bary.y, the operators left to right */
+static void interpolate_uv(float b1, float b2, const float* tu, const float* tv, float* u, float* v)
+{
+	float w0 = (1.0f - b1) - b2;
+	*u = (tu[0] * w0 + tu[1] * b1) + tu[2] * b2;
+	*v = (tv[0] * w0 + tv[1] * b1) + tv[2] * b2;
+}
+
+/* the same for n hits (test infrastructure: tests/test_shadow_vs_ref.py holds the reference's uv against it).  bary: n x 2, tu / tv: n x 3 */
+void sar_interpolate_uv(const float* bary, const float* tu, const float* tv, uint64_t n, float* uv)
+{
+	uint64_t i;
+	for (i = 0; i < n; ++i)
+		interpolate_uv(bary[2 * i], bary[2 * i + 1], tu + 3 * i, tv + 3 * i, &uv[2 * i], &uv[2 * i + 1]);
+}
+
 typedef struct
 {
 	const Material* materials;
@@ -169,10 +185,9 @@ static int occluded_alpha(const Mesh* meshes, uint32_t meshCount, const uint32_t
 			if (tex)
 			{
 				float b1 = uvwd[1] / uvwd[3], b2 = uvwd[2] / uvwd[3];
-				float w0 = (1.0f - b1) - b2;
-				float u = (tu[0] * w0 + tu[1] * b1) + tu[2] * b2;
-				float w = (tv[0] * w0 + tv[1] * b1) + tv[2] * b2;
-				float alpha = alpha_lod0(in->texels, tex, u, w);
+				float u, w, alpha;
+				interpolate_uv(b1, b2, tu, tv, &u, &w);
+				alpha = alpha_lod0(in->texels, tex, u, w);
 				if (!(alpha >= 0.5f)) /* a NaN does not confirm */
 				{
 					++*rejected;

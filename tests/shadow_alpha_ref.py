@@ -29,7 +29,7 @@ def _alpha_args(scene, tset, texel_words=None):
 class ShadowAlphaRef:
     def __init__(self, so):
         self.lib = C.CDLL(so)
-        for f in ("sar_trace", "sar_shadow_trace"):
+        for f in ("sar_trace", "sar_shadow_trace", "sar_interpolate_uv"):
             getattr(self.lib, f).restype = None
         assert self.lib.sar_sizes_ok() == 1
 
@@ -43,6 +43,13 @@ class ShadowAlphaRef:
         self.lib.sar_trace(*args, *alpha, _p(o), _p(r), C.c_uint64(len(o)), C.c_float(tmin), C.c_float(tmax), C.c_int(quality), _p(out), _p(rejected))
         del keep, keep2
         return out, rejected
+
+    def interpolate_uv(self, bary, tu, tv):
+        """shadow.comp.glsl:113 for n hits: bary (n, 2), the corners' texcoords tu, tv (n, 3) -> uv (n, 2), all float32"""
+        b, u, v = (np.ascontiguousarray(a, np.float32) for a in (bary, tu, tv))
+        out = np.zeros((len(b), 2), np.float32)
+        self.lib.sar_interpolate_uv(_p(b), _p(u), _p(v), C.c_uint64(len(b)), _p(out))
+        return out
 
     def shadow_trace(self, sd, scene, tset, depth, shadow, quality=1):
         """(mask, rejected): the pass over a copy of `shadow` (h, w) u8 — texels no invocation owns keep their bytes, and a rejected count of 0"""
