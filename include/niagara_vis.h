@@ -879,6 +879,64 @@ int nv_rasterdepth_textured(nv_context* ctx, void* stream, const NvGlobals* glob
                             const NvTextureDesc* d_textures /* optional */, uint32_t textureCount,
                             const uint32_t* d_texels /* optional */, uint64_t texelWords, uint64_t* d_alphaTotals2 /* optional */);
 
+/* ---- the classic path with textures: the complete fragment stage and the POST alpha discard for the indexed draws ----
+ * nv_visibility_attributes_indexed_textured: nv_visibility_attributes_indexed with the complete fragment stage.  The records, the corner
+ * validity, the run key, d_totals4 words 0-2 and the output of an invalid record are nv_visibility_attributes_indexed's; the descriptor rule
+ * (an id past textureCount or a descriptor that does not describe a chain inside texelWords: the texture is treated as absent), the
+ * d_totals4[3] rule (pixels whose material names a texture the pass could not sample) and the sampler are nv_visibility_attributes_textured's.
+ * NV_EINVAL, nothing launched: the union of the two parents' refusals (d_materials is required).  One launch, capturable. */
+int nv_visibility_attributes_indexed_textured(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisIndexedRecord* d_records, uint32_t width,
+                                              uint32_t height, const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices,
+                                              uint32_t indexCapacity, const NvVertex* d_vertices, uint32_t vertexCapacity, const NvMaterial* d_materials,
+                                              uint32_t materialCount, NvPixelAttributes* d_attributes /* optional */, uint32_t* d_gbuffer0 /* optional */,
+                                              uint32_t* d_gbuffer1 /* optional */, uint64_t* d_totals4 /* optional */, const NvTextureDesc* d_textures,
+                                              uint32_t textureCount, const uint32_t* d_texels, uint64_t texelWords);
+
+/* the same pass over a block-resident set (NvTextureBlockDesc, d_blocks 16-byte aligned, units16): the same outputs bit for bit */
+int nv_visibility_attributes_indexed_blocks(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisIndexedRecord* d_records, uint32_t width,
+                                            uint32_t height, const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices,
+                                            uint32_t indexCapacity, const NvVertex* d_vertices, uint32_t vertexCapacity, const NvMaterial* d_materials,
+                                            uint32_t materialCount, NvPixelAttributes* d_attributes /* optional */, uint32_t* d_gbuffer0 /* optional */,
+                                            uint32_t* d_gbuffer1 /* optional */, uint64_t* d_totals4 /* optional */, const NvTextureBlockDesc* d_textures,
+                                            uint32_t textureCount, const void* d_blocks, uint64_t units16);
+
+/* nv_rasterdepth_indexed_textured: nv_rasterdepth_indexed_visibility whose covered samples of a post-pass launch also pass the fragment's alpha
+ * test before they touch d_depth or d_visibility.  d_triangleOffsets / d_visibility are optional as a pair: both NULL is depth only.  The
+ * options, smallLimit, both faces in the post pass, the skip rules and the count / scan launches are nv_rasterdepth_indexed's.
+ * The test is nv_rasterdepth_textured's, stated per command where that states it per slot.  It applies only when
+ * globals->cullData.postPass != 0 and d_materials is given; otherwise the call writes nv_rasterdepth_indexed_visibility's bits and totals (with
+ * both visibility pointers NULL nv_rasterdepth_indexed's) and both alpha totals stay as they are.  The command's draw gives materialIndex:
+ *   - materialIndex >= materialCount: the command is opaque; its covered samples are counted as unevaluated;
+ *   - albedoTexture == 0: albedo.a = diffuseFactor.a for every sample of the command;
+ *   - albedoTexture >= textureCount or a refused descriptor: the texture is absent, albedo.a = diffuseFactor.a, the samples are unevaluated;
+ *   - otherwise albedo.a = diffuseFactor.a * texture(albedo, uv).a per covered sample, uv and its per-pixel steps from the ORIGINAL triangle's
+ *     corners (with NV_OPT_RASTER_NEAR_CLIP 1 too) exactly as nv_visibility_attributes_indexed_textured takes them for that triangle and pixel.
+ * A covered sample with albedo.a < 0.5 is dropped: no load, no atomic on either target.  A NaN albedo.a keeps the sample.  The depth bias of
+ * the post pass stays unmodelled.  d_totals4 words 0-2 are nv_rasterdepth_indexed's; word 3 counts the samples KEPT.  d_alphaTotals2
+ * (optional, accumulated: zero it first): samples dropped, samples unevaluated.  Word 3 + dropped = nv_rasterdepth_indexed's word 3 on the
+ * same inputs; every total is independent of the order of the GPU's work.
+ * NV_EINVAL, nothing launched: nv_rasterdepth_indexed's refusals; one of d_triangleOffsets / d_visibility without the other; d_commands /
+ * d_count / d_indices / d_depth / d_texels not 4-byte aligned, d_triangleOffsets / d_visibility / d_totals4 / d_alphaTotals2 not 8-byte aligned,
+ * d_draws / d_vertices / d_materials / d_textures not 16-byte aligned; d_textures without d_texels or the reverse; textureCount != 0 without
+ * d_textures; d_materials with materialCount == 0.  NV_ENOMEM: nv_rasterdepth_indexed's, and d_alphaTotals2 while the context holds no
+ * partial sums for it (nv_create reserves them).  Capturable: the launches only enqueue work. */
+int nv_rasterdepth_indexed_textured(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshDrawCommand* d_commands, const uint32_t* d_count,
+                                    const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices, uint32_t indexCapacity,
+                                    const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width, uint32_t height,
+                                    uint64_t* d_totals4 /* optional */, const uint64_t* d_triangleOffsets /* optional */,
+                                    uint64_t* d_visibility /* optional */, const NvMaterial* d_materials /* optional */, uint32_t materialCount,
+                                    const NvTextureDesc* d_textures /* optional */, uint32_t textureCount, const uint32_t* d_texels /* optional */,
+                                    uint64_t texelWords, uint64_t* d_alphaTotals2 /* optional */);
+
+/* the same pass over a block-resident set (NvTextureBlockDesc, d_blocks 16-byte aligned, units16): targets and counters bit for bit */
+int nv_rasterdepth_indexed_blocks(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshDrawCommand* d_commands, const uint32_t* d_count,
+                                  const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices, uint32_t indexCapacity,
+                                  const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width, uint32_t height,
+                                  uint64_t* d_totals4 /* optional */, const uint64_t* d_triangleOffsets /* optional */,
+                                  uint64_t* d_visibility /* optional */, const NvMaterial* d_materials /* optional */, uint32_t materialCount,
+                                  const NvTextureBlockDesc* d_textures /* optional */, uint32_t textureCount, const void* d_blocks /* optional */,
+                                  uint64_t units16, uint64_t* d_alphaTotals2 /* optional */);
+
 /* ---- the shading end of the frame (replaces shadowfill.comp.glsl, shadowblur.comp.glsl and final.comp.glsl) ----
  * Three of niagara's compute passes behind the G-buffer.  All images are linear buffers with row 0 at the top, as the raster target is:
  *   depth               width * height fp32, the raster target as it stands: reverse-Z, 0 = no sample;

@@ -104,6 +104,14 @@ _SIGS = {
     "nv_rasterdepth_indexed_visibility": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
     "nv_visibility_resolve_indexed": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
     "nv_visibility_attributes_indexed": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "nv_rasterdepth_indexed_textured": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _u32,
+                                             _vp, C.c_uint64, _vp]),
+    "nv_rasterdepth_indexed_blocks": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _u32,
+                                           _vp, C.c_uint64, _vp]),
+    "nv_visibility_attributes_indexed_textured": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp,
+                                                       _vp, _u32, _vp, C.c_uint64]),
+    "nv_visibility_attributes_indexed_blocks": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp,
+                                                     _vp, _u32, _vp, C.c_uint64]),
     "nv_assign_triangle_offsets": (_i, [_vp, _u32, _vp, _u32, _vp]),
     "nv_depthreduce": (_i, [_vp, _vp, _vp, _u32, _u32, C.POINTER(PyramidDesc)]),
     "nv_depth_merge": (_i, [_vp, _vp, _vp, C.POINTER(_vp), _u32, _u32, _u32]),

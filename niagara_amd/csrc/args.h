@@ -407,6 +407,32 @@ struct VisAttrSetArgs : VisAttrArgs
 typedef VisAttrSetArgs<TxDecoded> VisAttrTexArgs;
 typedef VisAttrSetArgs<TxBlocks> VisAttrBlockArgs;
 
+// nv_visibility_attributes_indexed_textured, nv_visibility_attributes_indexed_blocks (visattr_indexed.h, visattr_indexed_tex.hip, §4.24):
+// VisAttrIndexedArgs plus the texture set
+template <typename SET>
+struct VisAttrIndexedSetArgs : VisAttrIndexedArgs
+{
+	typedef SET Set;
+	TxTable<SET> tx;
+};
+typedef VisAttrIndexedSetArgs<TxDecoded> VisAttrIndexedTexArgs;
+typedef VisAttrIndexedSetArgs<TxBlocks> VisAttrIndexedBlockArgs;
+
+// nv_rasterdepth_indexed_textured, nv_rasterdepth_indexed_blocks (rasterindexed.h, rasterindexed_alpha.hip, §4.24): RasterIndexedVisArgs —
+// whose triangleOffsets / visibility are optional as a pair here — plus the material table, the texture set and the alpha totals
+template <typename SET>
+struct RasterIndexedSetArgs : RasterIndexedVisArgs
+{
+	typedef SET Set;
+	const NvMaterial* __restrict__ materials; // optional
+	uint32_t materialCount;
+	TxTable<SET> tx;
+	unsigned long long* __restrict__ alphaTotals;   // optional: {dropped, unevaluated}
+	unsigned long long* __restrict__ alphaPartials; // library scratch: 2 counters per workgroup of the launch (set whenever alphaTotals is)
+};
+typedef RasterIndexedSetArgs<TxDecoded> RasterIndexedAlphaArgs;
+typedef RasterIndexedSetArgs<TxBlocks> RasterIndexedBlockArgs;
+
 // nv_shade_final (shade.hip)
 struct ShadeFinalArgs
 {

@@ -519,6 +519,95 @@ static int fill_attribute_set_args(nv::VisAttrSetArgs<SET>& a, nv_context* ctx, 
 	return NV_OK;
 }
 
+// the arguments nv_rasterdepth_indexed and nv_rasterdepth_indexed_visibility share, checked (NV_EINVAL / NV_ENOMEM) and filled
+static int fill_rasterindexed_args(nv::RasterIndexedArgs& a, nv_context* ctx, const NvGlobals* globals, const NvMeshDrawCommand* d_commands,
+                                   const uint32_t* d_count, const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices, uint32_t indexCapacity,
+                                   const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_totals4)
+{
+	if (!ctx || !globals || !d_commands || !d_count || !d_draws || !d_indices || !d_vertices || !d_depth || !image_size_ok(width, height) ||
+	    globals->screenWidth != (float)width || globals->screenHeight != (float)height)
+		return NV_EINVAL;
+	if (drawCount > ctx->rasterScratchDraws)
+		return NV_ENOMEM; // nv_reserve(ctx, maxDraws, ...) first: a pass never allocates
+	memset(&a, 0, sizeof(a));
+	a.globals = *globals;
+	a.commands = d_commands;
+	a.count = d_count;
+	a.draws = d_draws;
+	a.drawCount = drawCount;
+	a.indices = d_indices;
+	a.indexCapacity = indexCapacity;
+	a.vertices = d_vertices;
+	a.vertexCapacity = vertexCapacity;
+	a.depth = reinterpret_cast<uint32_t*>(d_depth);
+	a.width = width;
+	a.height = height;
+	a.smallLimit = ctx->rasterSmallLimit;
+	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
+	a.partials = ctx->totalsPartials;
+	return NV_OK;
+}
+
+// What nv_rasterdepth_indexed_textured and nv_rasterdepth_indexed_blocks add to fill_rasterindexed_args (rasterindexed_alpha.hip, DESIGN.md
+// §4.24): the visibility pair, optional here as a pair, then fill_raster_set_args' alignments and rules for the material table, the texture set
+// and the alpha totals.  d_buffer, bufferMask and extent as fill_raster_set_args'
+template <typename SET>
+static int fill_rasterindexed_set_args(nv::RasterIndexedSetArgs<SET>& a, nv_context* ctx, const NvGlobals* globals, const NvMeshDrawCommand* d_commands,
+                                       const uint32_t* d_count, const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices,
+                                       uint32_t indexCapacity, const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width,
+                                       uint32_t height, uint64_t* d_totals4, const uint64_t* d_triangleOffsets, uint64_t* d_visibility,
+                                       const NvMaterial* d_materials, uint32_t materialCount, const void* d_textures, uint32_t textureCount,
+                                       const void* d_buffer, uintptr_t bufferMask, uint64_t extent, uint64_t* d_alphaTotals2)
+{
+	const int rc = fill_rasterindexed_args(a, ctx, globals, d_commands, d_count, d_draws, drawCount, d_indices, indexCapacity, d_vertices, vertexCapacity,
+	                                       d_depth, width, height, d_totals4);
+	if (rc != NV_OK)
+		return rc;
+	if ((d_triangleOffsets != nullptr) != (d_visibility != nullptr) || misaligned(d_triangleOffsets, 7u) || misaligned(d_visibility, 7u) ||
+	    misaligned(d_commands, 3u) || misaligned(d_count, 3u) || misaligned(d_indices, 3u) || misaligned(d_depth, 3u) || misaligned(d_buffer, bufferMask) ||
+	    misaligned(d_totals4, 7u) || misaligned(d_alphaTotals2, 7u) || misaligned(d_draws, 15u) || misaligned(d_vertices, 15u) ||
+	    misaligned(d_materials, 15u) || misaligned(d_textures, 15u) || (d_textures != nullptr) != (d_buffer != nullptr) || (textureCount && !d_textures) ||
+	    (d_materials && materialCount == 0))
+		return NV_EINVAL;
+	if (d_alphaTotals2 && !ctx->alphaPartials)
+		return NV_ENOMEM; // (nv_create reserves them: a pass never allocates)
+	a.triangleOffsets = reinterpret_cast<const unsigned long long*>(d_triangleOffsets);
+	a.visibility = reinterpret_cast<unsigned long long*>(d_visibility);
+	a.materials = d_materials;
+	a.materialCount = d_materials ? materialCount : 0u;
+	a.tx.descs = static_cast<const uint4*>(d_textures);
+	a.tx.count = d_textures ? textureCount : 0u;
+	a.tx.data = static_cast<const typename SET::Unit*>(d_buffer);
+	a.tx.extent = d_buffer ? extent : 0u;
+	a.alphaTotals = reinterpret_cast<unsigned long long*>(d_alphaTotals2);
+	a.alphaPartials = d_alphaTotals2 ? ctx->alphaPartials : nullptr;
+	return NV_OK;
+}
+
+// The indexed pair (visattr_indexed_tex.hip): nv_visibility_attributes_indexed's refusals and fields, then
+// fill_attribute_set_args' rule for the material table and the texture set — the union of the two parents' refusals
+template <typename SET>
+static int fill_attribute_indexed_set_args(nv::VisAttrIndexedSetArgs<SET>& a, nv_context* ctx, const NvGlobals* globals, const NvVisIndexedRecord* d_records,
+                                           uint32_t width, uint32_t height, const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices,
+                                           uint32_t indexCapacity, const NvVertex* d_vertices, uint32_t vertexCapacity, const NvMaterial* d_materials,
+                                           uint32_t materialCount, NvPixelAttributes* d_attributes, uint32_t* d_gbuffer0, uint32_t* d_gbuffer1,
+                                           uint64_t* d_totals4, const void* d_textures, uint32_t textureCount, const void* d_buffer, uintptr_t bufferMask,
+                                           uint64_t extent)
+{
+	if (fill_attribute_args(a, ctx, globals, reinterpret_cast<const NvVisRecord*>(d_records), width, height, d_draws, drawCount, nullptr, 0u, nullptr, 0u,
+	                        d_vertices, vertexCapacity, d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1, d_totals4) != NV_OK ||
+	    (indexCapacity && !d_indices) || misaligned(d_indices, 3u) || !d_materials || (textureCount && (!d_textures || !d_buffer)) ||
+	    misaligned(d_textures, 15u) || misaligned(d_buffer, bufferMask))
+		return NV_EINVAL;
+	a.indices = d_indices;
+	a.indexCapacity = indexCapacity;
+	a.tx.descs = static_cast<const uint4*>(d_textures);
+	a.tx.count = d_textures ? textureCount : 0u;
+	a.tx.data = static_cast<const typename SET::Unit*>(d_buffer);
+	a.tx.extent = extent;
+	return NV_OK;
+}
+
 // what the three trace entry points share: the refusals, then the caller-facing fields of the opaque launch
 static int fill_trace_args(nv::ShadowTraceArgs& a, nv_context* ctx, const NvShadowData* shadow, const float* d_depth, uint8_t* d_shadow, uint32_t width,
                            uint32_t height, int quality)
@@ -1265,35 +1354,6 @@ int nv_rasterdepth_blocks(nv_context* ctx, void* stream, const NvGlobals* global
 	return nv::launch_rasterdepth_blocks((hipStream_t)stream, a, persistent_grid(ctx, 8), ctx->rasterNearClip != 0, ctx->rasterStableIds != 0);
 }
 
-// the arguments nv_rasterdepth_indexed and nv_rasterdepth_indexed_visibility share, checked (NV_EINVAL / NV_ENOMEM) and filled
-static int fill_rasterindexed_args(nv::RasterIndexedArgs& a, nv_context* ctx, const NvGlobals* globals, const NvMeshDrawCommand* d_commands,
-                                   const uint32_t* d_count, const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices, uint32_t indexCapacity,
-                                   const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_totals4)
-{
-	if (!ctx || !globals || !d_commands || !d_count || !d_draws || !d_indices || !d_vertices || !d_depth || !image_size_ok(width, height) ||
-	    globals->screenWidth != (float)width || globals->screenHeight != (float)height)
-		return NV_EINVAL;
-	if (drawCount > ctx->rasterScratchDraws)
-		return NV_ENOMEM; // nv_reserve(ctx, maxDraws, ...) first: a pass never allocates
-	memset(&a, 0, sizeof(a));
-	a.globals = *globals;
-	a.commands = d_commands;
-	a.count = d_count;
-	a.draws = d_draws;
-	a.drawCount = drawCount;
-	a.indices = d_indices;
-	a.indexCapacity = indexCapacity;
-	a.vertices = d_vertices;
-	a.vertexCapacity = vertexCapacity;
-	a.depth = reinterpret_cast<uint32_t*>(d_depth);
-	a.width = width;
-	a.height = height;
-	a.smallLimit = ctx->rasterSmallLimit;
-	a.totals = reinterpret_cast<unsigned long long*>(d_totals4);
-	a.partials = ctx->totalsPartials;
-	return NV_OK;
-}
-
 int nv_rasterdepth_indexed(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshDrawCommand* d_commands, const uint32_t* d_count,
                            const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices, uint32_t indexCapacity,
                            const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width, uint32_t height, uint64_t* d_totals4)
@@ -1323,6 +1383,41 @@ int nv_rasterdepth_indexed_visibility(nv_context* ctx, void* stream, const NvGlo
 	a.triangleOffsets = reinterpret_cast<const unsigned long long*>(d_triangleOffsets);
 	a.visibility = reinterpret_cast<unsigned long long*>(d_visibility);
 	return nv::launch_rasterindexed_vis((hipStream_t)stream, a, ctx->rasterScratch, persistent_grid(ctx, 8), ctx->rasterNearClip != 0);
+}
+
+int nv_rasterdepth_indexed_textured(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshDrawCommand* d_commands, const uint32_t* d_count,
+                                    const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices, uint32_t indexCapacity,
+                                    const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width, uint32_t height,
+                                    uint64_t* d_totals4, const uint64_t* d_triangleOffsets, uint64_t* d_visibility, const NvMaterial* d_materials,
+                                    uint32_t materialCount, const NvTextureDesc* d_textures, uint32_t textureCount, const uint32_t* d_texels,
+                                    uint64_t texelWords, uint64_t* d_alphaTotals2)
+{
+	nv::RasterIndexedAlphaArgs a;
+	const int rc = fill_rasterindexed_set_args(a, ctx, globals, d_commands, d_count, d_draws, drawCount, d_indices, indexCapacity, d_vertices, vertexCapacity,
+	                                           d_depth, width, height, d_totals4, d_triangleOffsets, d_visibility, d_materials, materialCount, d_textures,
+	                                           textureCount, d_texels, 3u, texelWords, d_alphaTotals2);
+	if (rc != NV_OK)
+		return rc;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_rasterindexed_alpha((hipStream_t)stream, a, ctx->rasterScratch, persistent_grid(ctx, 8), ctx->rasterNearClip != 0);
+}
+
+// the same pass over a block-resident set
+int nv_rasterdepth_indexed_blocks(nv_context* ctx, void* stream, const NvGlobals* globals, const NvMeshDrawCommand* d_commands, const uint32_t* d_count,
+                                  const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices, uint32_t indexCapacity,
+                                  const NvVertex* d_vertices, uint32_t vertexCapacity, float* d_depth, uint32_t width, uint32_t height,
+                                  uint64_t* d_totals4, const uint64_t* d_triangleOffsets, uint64_t* d_visibility, const NvMaterial* d_materials,
+                                  uint32_t materialCount, const NvTextureBlockDesc* d_textures, uint32_t textureCount, const void* d_blocks,
+                                  uint64_t units16, uint64_t* d_alphaTotals2)
+{
+	nv::RasterIndexedBlockArgs a;
+	const int rc = fill_rasterindexed_set_args(a, ctx, globals, d_commands, d_count, d_draws, drawCount, d_indices, indexCapacity, d_vertices, vertexCapacity,
+	                                           d_depth, width, height, d_totals4, d_triangleOffsets, d_visibility, d_materials, materialCount, d_textures,
+	                                           textureCount, d_blocks, 15u, units16, d_alphaTotals2);
+	if (rc != NV_OK)
+		return rc;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_rasterindexed_blocks((hipStream_t)stream, a, ctx->rasterScratch, persistent_grid(ctx, 8), ctx->rasterNearClip != 0);
 }
 
 int nv_meshlet_bounds(nv_context* ctx, void* stream, const NvVertex* d_vertices, const uint32_t* d_meshletData, NvMeshlet* d_meshlets, uint32_t meshletCount,
@@ -1472,6 +1567,39 @@ int nv_visibility_attributes_blocks(nv_context* ctx, void* stream, const NvGloba
 		return NV_EINVAL;
 	DeviceGuard guard(ctx->device);
 	return nv::launch_visibility_attributes_blocks((hipStream_t)stream, a, height, persistent_grid(ctx, 8));
+}
+
+int nv_visibility_attributes_indexed_textured(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisIndexedRecord* d_records, uint32_t width,
+                                              uint32_t height, const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices,
+                                              uint32_t indexCapacity, const NvVertex* d_vertices, uint32_t vertexCapacity, const NvMaterial* d_materials,
+                                              uint32_t materialCount, NvPixelAttributes* d_attributes, uint32_t* d_gbuffer0, uint32_t* d_gbuffer1,
+                                              uint64_t* d_totals4, const NvTextureDesc* d_textures, uint32_t textureCount, const uint32_t* d_texels,
+                                              uint64_t texelWords)
+{
+	nv::VisAttrIndexedTexArgs a;
+	if (fill_attribute_indexed_set_args(a, ctx, globals, d_records, width, height, d_draws, drawCount, d_indices, indexCapacity, d_vertices, vertexCapacity,
+	                                    d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1, d_totals4, d_textures, textureCount, d_texels, 3u,
+	                                    texelWords) != NV_OK)
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_visibility_attributes_indexed_textured((hipStream_t)stream, a, height, persistent_grid(ctx, 8));
+}
+
+// the same pass over a block-resident set
+int nv_visibility_attributes_indexed_blocks(nv_context* ctx, void* stream, const NvGlobals* globals, const NvVisIndexedRecord* d_records, uint32_t width,
+                                            uint32_t height, const NvMeshDraw* d_draws, uint32_t drawCount, const uint32_t* d_indices,
+                                            uint32_t indexCapacity, const NvVertex* d_vertices, uint32_t vertexCapacity, const NvMaterial* d_materials,
+                                            uint32_t materialCount, NvPixelAttributes* d_attributes, uint32_t* d_gbuffer0, uint32_t* d_gbuffer1,
+                                            uint64_t* d_totals4, const NvTextureBlockDesc* d_textures, uint32_t textureCount, const void* d_blocks,
+                                            uint64_t units16)
+{
+	nv::VisAttrIndexedBlockArgs a;
+	if (fill_attribute_indexed_set_args(a, ctx, globals, d_records, width, height, d_draws, drawCount, d_indices, indexCapacity, d_vertices, vertexCapacity,
+	                                    d_materials, materialCount, d_attributes, d_gbuffer0, d_gbuffer1, d_totals4, d_textures, textureCount, d_blocks, 15u,
+	                                    units16) != NV_OK)
+		return NV_EINVAL;
+	DeviceGuard guard(ctx->device);
+	return nv::launch_visibility_attributes_indexed_blocks((hipStream_t)stream, a, height, persistent_grid(ctx, 8));
 }
 
 int nv_texture_decode(nv_context* ctx, void* stream, const void* d_blocks, uint32_t format, uint32_t width, uint32_t height, uint32_t levels,

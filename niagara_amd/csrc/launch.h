@@ -78,6 +78,11 @@ void launch_rasterindexed_prepare(hipStream_t, RasterIndexedArgs& a, void* scrat
 int launch_rasterindexed_vis(hipStream_t, RasterIndexedVisArgs a, void* scratch, uint32_t gridBlocks, bool nearClip);
 int launch_visibility_resolve_indexed(hipStream_t, VisResolveIndexedArgs a, uint32_t maxBlocks);
 int launch_visibility_attributes_indexed(hipStream_t, VisAttrIndexedArgs a, uint32_t height, uint32_t maxBlocks);
+// rasterindexed_alpha.hip, rasterindexed_blocks.hip, visattr_indexed_tex.hip, visattr_indexed_blocks.hip (§4.24)
+int launch_rasterindexed_alpha(hipStream_t, RasterIndexedAlphaArgs a, void* scratch, uint32_t gridBlocks, bool nearClip);
+int launch_rasterindexed_blocks(hipStream_t, RasterIndexedBlockArgs a, void* scratch, uint32_t gridBlocks, bool nearClip);
+int launch_visibility_attributes_indexed_textured(hipStream_t, VisAttrIndexedTexArgs a, uint32_t height, uint32_t maxBlocks);
+int launch_visibility_attributes_indexed_blocks(hipStream_t, VisAttrIndexedBlockArgs a, uint32_t height, uint32_t maxBlocks);
 // depthmerge.hip
 int launch_depth_merge(hipStream_t, float* dst, const float* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks);
 int launch_visibility_merge(hipStream_t, unsigned long long* dst, const unsigned long long* const* srcs, uint32_t sources, uint32_t n, uint32_t maxBlocks);

@@ -1,10 +1,14 @@
 // rasterindexed.h — the text nv_rasterdepth_indexed (rasterindexed.hip) and nv_rasterdepth_indexed_visibility (rasterindexed_vis.hip) share
 // (DESIGN.md §4.11, §4.23): the chunk arithmetic, the command search and the raster kernel, rasterindexed_kernel<CLIP, ARGS>.  Without a visibility target
 // it is the depth-only kernel, statement for statement what rasterindexed.hip held before the header existed; with one (VIS) it adds the stable-form
-// visibility word of §4.23 and nothing else (every addition sits under `if constexpr (VIS)`).
+// visibility word of §4.23 and nothing else (every addition sits under `if constexpr (VIS)`).  rasterindexed_alpha.hip and rasterindexed_blocks.hip
+// instantiate it on RasterIndexedSetArgs<SET> (nv_rasterdepth_indexed_textured, nv_rasterdepth_indexed_blocks, §4.24): VIS with an optional target,
+// and the covered samples of a post-pass launch also pass the fragment's alpha test (ALPHA: every addition sits under `if constexpr (ALPHA)`, so
+// the four kernels of the two untextured entry points keep their instruction streams).
 #pragma once
 
 #include "raster.h"
+#include "rasterdepth.h" // ALPHA: the record of a material (rd_alpha_slot) and the alpha-tested sample (rd_sample_alpha), §4.20's, not restated
 
 namespace nv
 {
@@ -89,16 +93,57 @@ struct ri_writes_visibility<RasterIndexedVisArgs>
 	static constexpr bool value = true;
 };
 
+// ARGS = RasterIndexedSetArgs<SET> (ALPHA, §4.24): VIS with an optional target, and the covered samples of a post-pass launch also pass the
+// fragment's alpha test against a texture set of residency SET.  Every addition sits under `if constexpr (ALPHA)`.
+template <class ARGS>
+struct ri_tests_alpha
+{
+	static constexpr bool value = false;
+};
+template <class SET>
+struct ri_tests_alpha<RasterIndexedSetArgs<SET>>
+{
+	static constexpr bool value = true;
+};
+template <class SET>
+struct ri_writes_visibility<RasterIndexedSetArgs<SET>>
+{
+	static constexpr bool value = true;
+};
+
+// ALPHA: one corner of the ORIGINAL triangle as fragalpha.h takes it: rd_clip_position's clip x, y, w (the statements rd_vertex starts with:
+// the bits both stages share) and the record's fourth word, the packed texcoord
+NV_DEV FaCorner ri_corner(const NvGlobals& g, const NvVertex* v, f3 q, float qw, float scale, float px, float py, float pz)
+{
+	const uint4 r = *reinterpret_cast<const uint4*>(v);
+	float clip[4];
+	rd_clip_position(g, make_uint2(r.x, r.y), q, qw, scale, px, py, pz, clip);
+	return FaCorner{ clip[0], clip[1], clip[3], r.w };
+}
+NV_DEV float4 ri_corner_word(const FaCorner& c) { return make_float4(c.cx, c.cy, c.cw, __uint_as_float(c.uv)); }
+
+// One covered-or-not pixel centre of the ALPHA instantiations: §4.20's sample (coverage, the alpha test, then the atomics) with the indexed word
+template <class ARGS>
+NV_DEV void ri_sample_alpha(const ARGS& a, const RdTri& t, const RdAlphaSlot& m, const FaCorner& ca, const FaCorner& cb, const FaCorner& cc, int32_t x, int32_t y,
+                            float fw, float fh, unsigned long long* __restrict__ vis, unsigned long long id, unsigned long long& kept,
+                            unsigned long long& dropped, unsigned long long& unevaluated)
+{
+	rd_sample_alpha<true, typename ARGS::Set>(t, m, a.tx.data, ca, cb, cc, x, y, a.width, fw, fh, a.depth, id ? vis : nullptr, id, kept, dropped, unevaluated);
+}
+
 template <bool CLIP, class ARGS>
 __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 {
 	constexpr bool VIS = ri_writes_visibility<ARGS>::value;
+	constexpr bool ALPHA = ri_tests_alpha<ARGS>::value;
 	unsigned long long* vis = nullptr;
 	if constexpr (VIS)
 		vis = a.visibility;
 	__shared__ int4 s_queue[RI_WAVES][RI_CHUNK][3]; // large pieces of the current chunk (one piece number at a time): their snapped corners
 	// VIS: the id34 of each queued piece, next to its corners (a named array of its own: the corners' entry keeps its layout)
 	__shared__ unsigned long long s_ids[VIS ? RI_WAVES : 1][VIS ? RI_CHUNK : 1];
+	// ALPHA: the three corners of the ORIGINAL triangle of each queued piece (clip x, y, w, packed texcoord), a named array of its own as well
+	__shared__ float4 s_corners[ALPHA ? RI_WAVES : 1][ALPHA ? RI_CHUNK : 1][3];
 
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -114,6 +159,18 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 	const bool bothFaces = a.globals.cullData.postPass != 0;
 	int4(*queue)[3] = s_queue[wave];
 	unsigned long long* queueIds = s_ids[VIS ? wave : 0u];
+	// ALPHA: the test applies in a post-pass launch that has a material table; otherwise every command's mode is 0 and the kernel writes
+	// nv_rasterdepth_indexed_visibility's bits (without a target: nv_rasterdepth_indexed's)
+	float4(*queueCorners)[3] = s_corners[ALPHA ? wave : 0u];
+	bool alphaOn = false, textured = false;
+	float fw = 0.0f, fh = 0.0f;
+	unsigned long long dropped = 0, unevaluated = 0;           // per lane
+	RdAlphaSlot mat = { 0u, 0.0f, TxDesc{ 0u, 0u, 0u, 0u } }; // the record of the current command's material (wave-uniform)
+	if constexpr (ALPHA)
+	{
+		alphaOn = bothFaces && a.materials != nullptr;
+		fw = (float)a.width, fh = (float)a.height;
+	}
 
 	uint32_t drawn = 0;             // per lane
 	unsigned long long samples = 0; // per lane
@@ -136,10 +193,29 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 			firstIndex = __builtin_amdgcn_readfirstlane(c.firstIndex);
 			vertexOffset = __builtin_amdgcn_readfirstlane(c.vertexOffset);
 			const float4* dp = reinterpret_cast<const float4*>(a.draws + __builtin_amdgcn_readfirstlane(c.drawId));
-			if constexpr (VIS)
+			if constexpr (VIS && !ALPHA)
 			{
 				const unsigned long long* op = a.triangleOffsets + __builtin_amdgcn_readfirstlane(c.drawId); // (drawId < drawCount: [drawId + 1] exists)
 				triFirst = op[0], triEnd = op[1];
+			}
+			if constexpr (ALPHA)
+			{
+				triFirst = triEnd = 0; // (without a visibility target every id is 0: depth only)
+				if (a.triangleOffsets)
+				{
+					const unsigned long long* op = a.triangleOffsets + __builtin_amdgcn_readfirstlane(c.drawId);
+					triFirst = op[0], triEnd = op[1];
+				}
+				// the command's material, where its transform is loaded: word 11 of the draw, then rd_alpha_slot's guarded loads
+				uint32_t mode = 0u;
+				float factor = 0.0f;
+				uint4 desc = make_uint4(0u, 0u, 0u, 0u);
+				if (alphaOn)
+					rd_alpha_slot(a, reinterpret_cast<const uint32_t*>(dp + 2)[3], mode, factor, desc);
+				mat = RdAlphaSlot{ (uint32_t)__builtin_amdgcn_readfirstlane(mode), __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(factor))),
+					                TxDesc{ (uint32_t)__builtin_amdgcn_readfirstlane(desc.x), (uint32_t)__builtin_amdgcn_readfirstlane(desc.y),
+					                        (uint32_t)__builtin_amdgcn_readfirstlane(desc.z), (uint32_t)__builtin_amdgcn_readfirstlane(desc.w) } };
+				textured = (mat.mode & RD_A_TEXTURED) != 0u;
 			}
 			const float4 d0 = dp[0], d1 = dp[1];
 			q = { d1.x, d1.y, d1.z };
@@ -151,6 +227,7 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 		unsigned long long id = 0;
 		if constexpr (VIS)
 			id = ri_id34(triFirst, triEnd, t);
+		FaCorner fa = { 0.0f, 0.0f, 0.0f, 0u }, fb = fa, fc = fa; // ALPHA: the lane's ORIGINAL triangle, in registers
 		// The two branches repeat each other's text on purpose: written as one loop over pieces, the CLIP = false instantiation compiles to other
 		// code than the kernel had before the option (other registers, other schedule); kept apart, it is that kernel instruction for instruction.
 		if constexpr (!CLIP)
@@ -168,6 +245,13 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 					cb = rd_vertex(a.globals, *reinterpret_cast<const uint2*>(a.vertices + vb), q, qw, scale, px, py, pz, H);
 					cc = rd_vertex(a.globals, *reinterpret_cast<const uint2*>(a.vertices + vc), q, qw, scale, px, py, pz, H);
 					live = rd_setup_corners(ca, cb, cc, bothFaces, W, H, tri);
+					if constexpr (ALPHA)
+						if (textured)
+						{
+							fa = ri_corner(a.globals, a.vertices + va, q, qw, scale, px, py, pz);
+							fb = ri_corner(a.globals, a.vertices + vb, q, qw, scale, px, py, pz);
+							fc = ri_corner(a.globals, a.vertices + vc, q, qw, scale, px, py, pz);
+						}
 				}
 			}
 			if (live)
@@ -180,7 +264,12 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 					if (!large)
 						for (int32_t y = tri.y0; y <= tri.y1; ++y)
 							for (int32_t x = tri.x0; x <= tri.x1; ++x)
-								samples += ri_sample<VIS>(tri, x, y, a.width, a.depth, vis, id) ? 1u : 0u;
+							{
+								if constexpr (ALPHA)
+									ri_sample_alpha(a, tri, mat, fa, fb, fc, x, y, fw, fh, vis, id, samples, dropped, unevaluated);
+								else
+									samples += ri_sample<VIS>(tri, x, y, a.width, a.depth, vis, id) ? 1u : 0u;
+							}
 				}
 			}
 			const uint64_t qb = __ballot(large);
@@ -193,6 +282,9 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 				queue[slot][2] = cc;
 				if constexpr (VIS)
 					queueIds[slot] = id;
+				if constexpr (ALPHA)
+					if (textured)
+						queueCorners[slot][0] = ri_corner_word(fa), queueCorners[slot][1] = ri_corner_word(fb), queueCorners[slot][2] = ri_corner_word(fc);
 			}
 			rd_lds_order();
 
@@ -204,6 +296,10 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 				unsigned long long idq = 0;
 				if constexpr (VIS)
 					idq = queueIds[e];
+				FaCorner ea = { 0.0f, 0.0f, 0.0f, 0u }, eb = ea, ec = ea; // ALPHA: the queued triangle's corners
+				if constexpr (ALPHA)
+					if (textured)
+						ea = rd_corner(queueCorners[e][0]), eb = rd_corner(queueCorners[e][1]), ec = rd_corner(queueCorners[e][2]);
 				rd_setup_corners(queue[e][0], queue[e][1], queue[e][2], bothFaces, W, H, tq); // (true: it was queued; same inputs, same bits)
 				const uint32_t sw = (uint32_t)(tq.x1 - tq.x0) / 8u + 1u, sh = (uint32_t)(tq.y1 - tq.y0) / 8u + 1u;
 				const int32_t lx = (int32_t)(lane & 7u), ly = (int32_t)(lane >> 3);
@@ -213,7 +309,12 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 					for (uint32_t sx = 0; sx < sw; ++sx)
 					{
 						const int32_t x = tq.x0 + (int32_t)sx * 8 + lx;
-						if (x <= tq.x1 && y <= tq.y1)
+						if constexpr (ALPHA)
+						{
+							if (x <= tq.x1 && y <= tq.y1)
+								ri_sample_alpha(a, tq, mat, ea, eb, ec, x, y, fw, fh, vis, idq, samples, dropped, unevaluated);
+						}
+						else if (x <= tq.x1 && y <= tq.y1)
 							samples += ri_sample<VIS>(tq, x, y, a.width, a.depth, vis, idq) ? 1u : 0u;
 					}
 				}
@@ -236,6 +337,13 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 					const int4 cb = rd_vertex_clip(a.globals, rb, q, qw, scale, px, py, pz, H, kb);
 					const int4 cc = rd_vertex_clip(a.globals, rc, q, qw, scale, px, py, pz, H, kc);
 					pieces = rd_clip(a.globals, ca, cb, cc, ka, kb, kc, H, p0, p1, p2, p3);
+					if constexpr (ALPHA)
+						if (textured) // (the ORIGINAL triangle's corners, not a piece's: the visibility word names that triangle)
+						{
+							fa = ri_corner(a.globals, a.vertices + va, q, qw, scale, px, py, pz);
+							fb = ri_corner(a.globals, a.vertices + vb, q, qw, scale, px, py, pz);
+							fc = ri_corner(a.globals, a.vertices + vc, q, qw, scale, px, py, pz);
+						}
 				}
 			}
 			for (uint32_t p = 0; p < 2u; ++p)
@@ -256,7 +364,12 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 						if (!large)
 							for (int32_t y = tri.y0; y <= tri.y1; ++y)
 								for (int32_t x = tri.x0; x <= tri.x1; ++x)
-									samples += ri_sample<VIS>(tri, x, y, a.width, a.depth, vis, id) ? 1u : 0u;
+								{
+									if constexpr (ALPHA)
+										ri_sample_alpha(a, tri, mat, fa, fb, fc, x, y, fw, fh, vis, id, samples, dropped, unevaluated);
+									else
+										samples += ri_sample<VIS>(tri, x, y, a.width, a.depth, vis, id) ? 1u : 0u;
+								}
 					}
 				}
 				const uint64_t qb = __ballot(large);
@@ -269,6 +382,9 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 					queue[slot][2] = cc;
 					if constexpr (VIS)
 						queueIds[slot] = id;
+					if constexpr (ALPHA)
+						if (textured)
+							queueCorners[slot][0] = ri_corner_word(fa), queueCorners[slot][1] = ri_corner_word(fb), queueCorners[slot][2] = ri_corner_word(fc);
 				}
 				rd_lds_order();
 
@@ -280,6 +396,10 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 					unsigned long long idq = 0;
 					if constexpr (VIS)
 						idq = queueIds[e];
+					FaCorner ea = { 0.0f, 0.0f, 0.0f, 0u }, eb = ea, ec = ea; // ALPHA: the corners of the ORIGINAL triangle of the queued piece
+					if constexpr (ALPHA)
+						if (textured)
+							ea = rd_corner(queueCorners[e][0]), eb = rd_corner(queueCorners[e][1]), ec = rd_corner(queueCorners[e][2]);
 					rd_setup_corners(queue[e][0], queue[e][1], queue[e][2], bothFaces, W, H, tq); // (true: it was queued; same inputs, same bits)
 					const uint32_t sw = (uint32_t)(tq.x1 - tq.x0) / 8u + 1u, sh = (uint32_t)(tq.y1 - tq.y0) / 8u + 1u;
 					const int32_t lx = (int32_t)(lane & 7u), ly = (int32_t)(lane >> 3);
@@ -289,7 +409,12 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 						for (uint32_t sx = 0; sx < sw; ++sx)
 						{
 							const int32_t x = tq.x0 + (int32_t)sx * 8 + lx;
-							if (x <= tq.x1 && y <= tq.y1)
+							if constexpr (ALPHA)
+							{
+								if (x <= tq.x1 && y <= tq.y1)
+									ri_sample_alpha(a, tq, mat, ea, eb, ec, x, y, fw, fh, vis, idq, samples, dropped, unevaluated);
+							}
+							else if (x <= tq.x1 && y <= tq.y1)
 								samples += ri_sample<VIS>(tq, x, y, a.width, a.depth, vis, idq) ? 1u : 0u;
 						}
 					}
@@ -299,19 +424,39 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 	}
 
 	// totals 2-3: per-workgroup partial sums, plain stores (0 in slots 0-1: the scan launch added those); launch_raster_totals adds them up
-	__shared__ unsigned long long s_tot[RI_WAVES][2];
+	__shared__ unsigned long long s_tot[RI_WAVES][ALPHA ? 4 : 2];
 	unsigned long long d = drawn, smp = samples;
 	for (int o = 32; o > 0; o >>= 1)
 	{
 		d += __shfl_xor(d, o, 64);
 		smp += __shfl_xor(smp, o, 64);
+		if constexpr (ALPHA)
+		{
+			dropped += __shfl_xor(dropped, o, 64);
+			unevaluated += __shfl_xor(unevaluated, o, 64);
+		}
 	}
 	if (lane == 0)
 	{
 		s_tot[wave][0] = d;
 		s_tot[wave][1] = smp;
+		if constexpr (ALPHA)
+		{
+			s_tot[wave][2] = dropped;
+			s_tot[wave][3] = unevaluated;
+		}
 	}
 	__syncthreads();
+	// ALPHA: two more partial sums, {dropped, unevaluated}, from threads 4 and 5 (the four below keep their statements)
+	if constexpr (ALPHA)
+		if (threadIdx.x >= 4 && threadIdx.x < 6 && a.alphaPartials)
+		{
+			unsigned long long t = 0;
+#pragma unroll
+			for (int k = 0; k < RI_WAVES; ++k)
+				t += s_tot[k][threadIdx.x - 2];
+			a.alphaPartials[(size_t)blockIdx.x * 2 + (threadIdx.x - 4)] = t;
+		}
 	if (threadIdx.x < 4)
 	{
 		unsigned long long t = 0;
@@ -321,6 +466,25 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 				t += s_tot[k][threadIdx.x - 2];
 		a.partials[(size_t)blockIdx.x * 4 + threadIdx.x] = t;
 	}
+}
+
+// The launches of an ALPHA entry point: the count and scan launches every indexed raster starts with, the kernel by near clip, then the totals
+// launches the caller asked for
+template <typename ARGS>
+int launch_rasterindexed_set(hipStream_t stream, ARGS a, void* scratch, uint32_t gridBlocks, bool nearClip)
+{
+	launch_rasterindexed_prepare(stream, a, scratch);
+	gridBlocks = gridBlocks / 8 * RI_BLOCKS_PER_CU; // the caller passes 8 workgroups per CU, the size of `partials` and `alphaPartials`
+	if (nearClip)
+		hipLaunchKernelGGL((rasterindexed_kernel<true, ARGS>), dim3(gridBlocks), dim3(RI_THREADS), 0, stream, a);
+	else
+		hipLaunchKernelGGL((rasterindexed_kernel<false, ARGS>), dim3(gridBlocks), dim3(RI_THREADS), 0, stream, a);
+	hipError_t e = hipGetLastError();
+	if (e == hipSuccess && a.totals)
+		e = (hipError_t)launch_raster_totals(stream, a.partials, gridBlocks, a.totals, 4);
+	if (e == hipSuccess && a.alphaTotals)
+		e = (hipError_t)launch_raster_totals(stream, a.alphaPartials, gridBlocks, a.alphaTotals, 2);
+	return (int)e;
 }
 
 } // namespace nv

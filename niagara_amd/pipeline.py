@@ -266,6 +266,57 @@ class Context:
                                                    _ptr(materials), int(material_count), _ptr(attributes), _ptr(gbuffer0), _ptr(gbuffer1),
                                                    _ptr(totals4)), "nv_visibility_attributes_indexed")
 
+    # ---- the classic path over a texture set: one pair per pass, marshalled like the cluster path's pairs above
+    def _rasterdepth_indexed_set(self, entry, globals_, dcb, dccb, db, draw_count, ib, index_capacity, vertices, vertex_capacity, depth, width, height,
+                                 totals4, triangle_offsets, visibility, materials, material_count, textures, texture_count, alpha_totals2, buffer, size):
+        check(getattr(lib, entry)(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(dcb), _ptr(dccb), _ptr(db), int(draw_count), _ptr(ib),
+                                  int(index_capacity), _ptr(vertices), int(vertex_capacity), _ptr(depth), int(width), int(height), _ptr(totals4),
+                                  _ptr(triangle_offsets), _ptr(visibility), _ptr(materials), int(material_count), _ptr(textures), int(texture_count),
+                                  _ptr(buffer), int(size), _ptr(alpha_totals2)), entry)
+
+    def rasterdepth_indexed_textured(self, globals_, dcb, dccb, db, draw_count, ib, index_capacity, vertices, vertex_capacity, depth, width, height,
+                                     triangle_offsets=None, visibility=None, totals4=None, materials=None, material_count=0, textures=None,
+                                     texture_count=0, texels=None, texel_words=0, alpha_totals2=None):
+        """rasterdepth_indexed_visibility (triangle_offsets / visibility optional as a pair: without them rasterdepth_indexed) whose covered
+        samples of a post-pass launch (globals' postPass != 0, with `materials`) also pass the fragment's alpha test against the albedo
+        texture (nv_rasterdepth_indexed_textured): a sample with albedo.a < 0.5 touches neither target.  totals4[3] counts the samples kept,
+        alpha_totals2 (optional, accumulated): samples dropped, samples unevaluated"""
+        self._rasterdepth_indexed_set("nv_rasterdepth_indexed_textured", globals_, dcb, dccb, db, draw_count, ib, index_capacity, vertices,
+                                      vertex_capacity, depth, width, height, totals4, triangle_offsets, visibility, materials, material_count, textures,
+                                      texture_count, alpha_totals2, texels, texel_words)
+
+    def rasterdepth_indexed_blocks(self, globals_, dcb, dccb, db, draw_count, ib, index_capacity, vertices, vertex_capacity, depth, width, height,
+                                   triangle_offsets=None, visibility=None, totals4=None, materials=None, material_count=0, textures=None,
+                                   texture_count=0, blocks=None, units16=0, alpha_totals2=None):
+        """rasterdepth_indexed_textured over a block-resident set (nv_rasterdepth_indexed_blocks): the same targets and counters bit for bit"""
+        self._rasterdepth_indexed_set("nv_rasterdepth_indexed_blocks", globals_, dcb, dccb, db, draw_count, ib, index_capacity, vertices,
+                                      vertex_capacity, depth, width, height, totals4, triangle_offsets, visibility, materials, material_count, textures,
+                                      texture_count, alpha_totals2, blocks, units16)
+
+    def _visibility_attributes_indexed_set(self, entry, globals_, records, width, height, db, draw_count, ib, index_capacity, vertices, vertex_capacity,
+                                           materials, material_count, attributes, gbuffer0, gbuffer1, totals4, textures, texture_count, buffer, size):
+        check(getattr(lib, entry)(self.h, _stream(), C.c_void_p(globals_.ctypes.data), _ptr(records), int(width), int(height), _ptr(db), int(draw_count),
+                                  _ptr(ib), int(index_capacity), _ptr(vertices), int(vertex_capacity), _ptr(materials), int(material_count),
+                                  _ptr(attributes), _ptr(gbuffer0), _ptr(gbuffer1), _ptr(totals4), _ptr(textures), int(texture_count), _ptr(buffer),
+                                  int(size)), entry)
+
+    def visibility_attributes_indexed_textured(self, globals_, records, width, height, db, draw_count, ib, index_capacity, vertices, vertex_capacity,
+                                               materials, material_count, attributes=None, gbuffer0=None, gbuffer1=None, totals4=None, textures=None,
+                                               texture_count=0, texels=None, texel_words=0):
+        """visibility_attributes_indexed with the complete fragment stage (nv_visibility_attributes_indexed_textured): the set as
+        visibility_attributes_textured takes it; totals4[3] counts the pixels whose material names a texture the pass could not sample"""
+        self._visibility_attributes_indexed_set("nv_visibility_attributes_indexed_textured", globals_, records, width, height, db, draw_count, ib,
+                                                index_capacity, vertices, vertex_capacity, materials, material_count, attributes, gbuffer0, gbuffer1,
+                                                totals4, textures, texture_count, texels, texel_words)
+
+    def visibility_attributes_indexed_blocks(self, globals_, records, width, height, db, draw_count, ib, index_capacity, vertices, vertex_capacity,
+                                             materials, material_count, attributes=None, gbuffer0=None, gbuffer1=None, totals4=None, textures=None,
+                                             texture_count=0, blocks=None, units16=0):
+        """visibility_attributes_indexed_textured over a block-resident set (nv_visibility_attributes_indexed_blocks): the same outputs bit for bit"""
+        self._visibility_attributes_indexed_set("nv_visibility_attributes_indexed_blocks", globals_, records, width, height, db, draw_count, ib,
+                                                index_capacity, vertices, vertex_capacity, materials, material_count, attributes, gbuffer0, gbuffer1,
+                                                totals4, textures, texture_count, blocks, units16)
+
     def depth_merge(self, dst, srcs, width, height):
         """dst = element-wise maximum of dst and every target of `srcs` on the bit patterns (nv_depth_merge): the depth composite of shards
         that live on one device, and the fold of a received target into the local one"""
@@ -644,12 +695,20 @@ class VisibilityPipeline:
         """the triangle offsets of the draws the passes run on (a shard: the scene's prefix from its first draw on)"""
         return self._triangle_names("render_draws(visibility=)")
 
-    def render_draws(self, cull_data, late, post_pass=0, totals4=None, visibility=None):
+    def render_draws(self, cull_data, late, post_pass=0, totals4=None, visibility=None, textures=False, materials=None, alpha_totals2=None):
         """the classic branch of render() (src/niagara.cpp:1680-1694): the MeshDrawCommands of the last cull(task=False) drawn from ib into
         self.depth.  The early pass clears the target first, the late and post passes load it.  visibility (stable_ids=True): a u64 target
-        that takes the stable-form word of nv_rasterdepth_indexed_visibility, cleared and loaded with the depth; resolve(classic=True) reads it"""
+        that takes the stable-form word of nv_rasterdepth_indexed_visibility, cleared and loaded with the depth; resolve(classic=True) reads it.
+        textures=True: the raster is nv_rasterdepth_indexed_textured (or _blocks, by set_textures()'s residency) over `materials` (a host array
+        of layouts.MATERIAL or a device tensor of them): the covered samples of a post pass also pass the alpha test of mesh.frag.glsl:88 (a
+        pass with post_pass = 0 writes the same bits either way); alpha_totals2 (optional): samples dropped, samples unevaluated"""
         if self.ib is None:
             raise NvError("render_draws needs the index buffer: VisibilityPipeline(..., indices=, vertices=)")
+        if textures:
+            missing = [what for what, absent in (("set_textures()", self.texture_resident is None),
+                                                 ("a material table (materials=)", materials is None)) if absent]
+            if missing:
+                raise NvError("render_draws(textures=True) needs " + ", ".join(missing))
         offsets = None if visibility is None else self._draw_triangle_offsets()  # (raises before anything is cleared)
         if not late:
             self.depth.zero_()
@@ -658,6 +717,13 @@ class VisibilityPipeline:
         pass_data = cull_data.copy()
         pass_data["postPass"] = post_pass
         g = synth.make_globals(pass_data, (self.depth_w, self.depth_h))
+        if textures:
+            mat = to_device(np.ascontiguousarray(materials, L.MATERIAL), self.ctx.device) if isinstance(materials, np.ndarray) else materials
+            form, tset = self._texture_set()
+            getattr(self.ctx, "rasterdepth_indexed_" + form)(g, self.dcb, self.dccb, self.db, self.draw_count, self.ib, self.index_count, self.vb,
+                                                             self.vertex_count, self.depth, self.depth_w, self.depth_h, offsets, visibility, totals4, mat,
+                                                             mat.numel() * mat.element_size() // L.MATERIAL.itemsize, *tset, alpha_totals2)
+            return
         if visibility is not None:
             self.ctx.rasterdepth_indexed_visibility(g, self.dcb, self.dccb, self.db, self.draw_count, self.ib, self.index_count, self.vb,
                                                     self.vertex_count, self.depth, self.depth_w, self.depth_h, offsets, visibility, totals4)
@@ -736,11 +802,9 @@ class VisibilityPipeline:
         global (the scene's draw ids), so this works unchanged on any rank of a sharded frame after the composite.  textures=True runs
         nv_visibility_attributes_textured over set_textures()'s set: the complete fragment stage; totals[3] then counts only the pixels whose
         material names a texture the set does not hold.  classic=True: `records` are resolve(classic=True)'s and the pass is
-        nv_visibility_attributes_indexed (no textured form)"""
+        nv_visibility_attributes_indexed, with textures=True nv_visibility_attributes_indexed_textured (or _blocks)"""
         if not self.stable_ids:
             raise NvError("attributes reads resolve()'s records: VisibilityPipeline(..., stable_ids=True)")
-        if classic and textures:
-            raise NvError("attributes(classic=True, textures=True): the indexed attribute pass has no textured form")
         if classic and self.ib is None:
             raise NvError("attributes(classic=True) needs the index buffer: VisibilityPipeline(..., indices=, vertices=)")
         if not classic and self.mdb is None:
@@ -764,6 +828,11 @@ class VisibilityPipeline:
             if mat is None:
                 raise NvError("attributes(textures=True) needs the material table")
             form, tset = self._texture_set()
+            if classic:
+                getattr(self.ctx, "visibility_attributes_indexed_" + form)(g, records, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws,
+                                                                           self.ib, self.index_count, self.vb, self.vertex_count, mat, n_mat,
+                                                                           out["attributes"], out["gbuffer0"], out["gbuffer1"], out["totals"], *tset)
+                return out
             getattr(self.ctx, "visibility_attributes_" + form)(g, records, self.depth_w, self.depth_h, getattr(self, "db_all", self.db), n_draws, self.mlb,
                                                                self.meshlet_count, self.mdb, self.mdb.numel() * self.mdb.element_size() // 4, self.vb,
                                                                self.vertex_count, mat, n_mat, out["attributes"], out["gbuffer0"], out["gbuffer1"],
@@ -914,10 +983,13 @@ class VisibilityPipeline:
         on_phase(name) is called after each phase's raster ("early", "late", "post").  visibility (stable_ids=True, task=True): a u64
         target of the depth target's size that the three rasters share (cleared before the early one); resolve() reads it — with task=False
         (and indices=) the indexed raster writes it and resolve(classic=True) / attributes(classic=True) read it.  textures=True
-        (task=True, after set_textures, with `materials`): the post phase's raster is render_depth(textures=True), the alpha-tested one; the early
-        and late phases stay on nv_rasterdepth (their bits are the same through either entry point)"""
+        (after set_textures, with `materials`): the post phase's raster is the alpha-tested one, render_depth(textures=True) or with task=False
+        render_draws(textures=True); the early and late phases stay on the plain entry points (their bits are the same through either)"""
         if textures and not task:
-            raise NvError("frame(textures=True) needs the cluster path (task=True): nv_rasterdepth_indexed has no alpha-tested form")
+            missing = [what for what, absent in (("the index buffer (indices=)", self.ib is None), ("set_textures()", self.texture_resident is None),
+                                                 ("a material table (materials=)", materials is None)) if absent]
+            if missing:  # (before the early phase clears or launches anything)
+                raise NvError("frame(task=False, textures=True) needs " + ", ".join(missing))
         if visibility is not None and not self.stable_ids:
             raise NvError("frame(visibility=) needs stable ids: VisibilityPipeline(..., stable_ids=True) "
                           "(the slot index of the default visibility word does not outlive a pass)")
@@ -935,6 +1007,8 @@ class VisibilityPipeline:
                     self.render_depth(cull_data, late=late, post_pass=pp, visibility=visibility, textures=True, materials=materials)
                 else:
                     self.render_depth(cull_data, late=late, post_pass=pp, visibility=visibility)
+            elif textures and pp:
+                self.render_draws(cull_data, late=late, post_pass=pp, visibility=visibility, textures=True, materials=materials)
             else:
                 self.render_draws(cull_data, late=late, post_pass=pp, visibility=visibility)
             if on_phase is not None:

@@ -10,6 +10,7 @@
     python3 tools/render_frame.py --alpha-shadows                       # the wall is a cut-out in the post pass: its shadow has holes (§4.19)
     python3 tools/render_frame.py --alpha-coverage --alpha-shadows      # and so has the wall: the boxes behind it show through (§4.20)
     python3 tools/render_frame.py --classic [--bloom]                   # the classic path's frame: indexed draws, their visibility buffer (§4.23)
+    python3 tools/render_frame.py --classic --alpha-coverage            # the same frame textured, the wall a cut-out in the post pass (§4.24)
 
 Writes a binary PPM (P6, R G B from the R8G8B8A8 colour words) and prints one JSON line with the passes' times by HIP events (one run
 each after a warm-up frame: launch gaps included, an upper bound of the kernel time; profiles/r13_shade.md has the kernel trace).
@@ -260,7 +261,8 @@ def main():
                     "fragment's alpha test (nv_rasterdepth_textured, DESIGN.md §4.20) and the boxes behind the wall's holes are in the image; alone or "
                     "with --alpha-shadows")
     ap.add_argument("--classic", action="store_true", help="the classic path (no mesh shading): frame(task=False, visibility=) over the indexed draws, "
-                    "resolve(classic=True), attributes(classic=True), shade (DESIGN.md §4.23); the factor-only fragment stage: not with --textures")
+                    "resolve(classic=True), attributes(classic=True), shade (DESIGN.md §4.23); with --textures / --block-textures the complete fragment "
+                    "stage and with --alpha-coverage the alpha-tested indexed raster in the post phase (§4.24)")
     ap.add_argument("--quality", type=int, default=1, help="--traced-shadows: 0 = opaque draws cast, 1 = post-pass draws too")
     ap.add_argument("--animate", type=int, default=0, help="--traced-shadows: write N images (out_000.ppm ...) with one draw displaced along a circle "
                     "per frame through move_draws, which rebuilds the TLAS on the device")
@@ -274,8 +276,6 @@ def main():
     if args.alpha_coverage or args.block_textures:
         args.textures = True
     cutout = args.alpha_shadows or args.alpha_coverage
-    if args.classic and args.textures:
-        ap.error("--classic shades from the materials' factors: the indexed attribute pass and raster have no textured form")
     if args.passes == "shadow_trace":
         if not args.traced_shadows:
             ap.error("--passes shadow_trace times the ray-traced pass: give --traced-shadows")
