@@ -253,6 +253,7 @@ struct RasterArgs
 // nv_rasterdepth_indexed (rasterindexed.hip)
 struct RasterIndexedArgs
 {
+	static constexpr bool VIS = false, ALPHA = false; // what rasterindexed_kernel compiles for these arguments: restated by every struct derived from this one
 	NvGlobals globals;
 	const NvMeshDrawCommand* __restrict__ commands;
 	const uint32_t* __restrict__ count; // dccb word 0
@@ -278,6 +279,7 @@ struct RasterIndexedArgs
 // nv_rasterdepth_indexed_visibility (rasterindexed_vis.hip): the same, and where the visibility words come from and go
 struct RasterIndexedVisArgs : RasterIndexedArgs
 {
+	static constexpr bool VIS = true, ALPHA = false;
 	const unsigned long long* __restrict__ triangleOffsets; // drawCount + 1 (the caller's pointer: on a shard, advanced by its first draw)
 	unsigned long long* __restrict__ visibility;            // width x height (atomic max)
 };
@@ -423,6 +425,7 @@ typedef VisAttrIndexedSetArgs<TxBlocks> VisAttrIndexedBlockArgs;
 template <typename SET>
 struct RasterIndexedSetArgs : RasterIndexedVisArgs
 {
+	static constexpr bool VIS = true, ALPHA = true;
 	typedef SET Set;
 	const NvMaterial* __restrict__ materials; // optional
 	uint32_t materialCount;

@@ -30,62 +30,36 @@
 namespace nv
 {
 
-// adds the per-workgroup partial sums of a launch to the caller's four totals (one workgroup)
+// adds the K per-workgroup partial sums of a launch to the caller's K totals (one workgroup)
+template <int K>
 __global__ __launch_bounds__(256) void rasterdepth_totals_kernel(const unsigned long long* __restrict__ partials, uint32_t blocks,
                                                                  unsigned long long* __restrict__ totals)
 {
-	__shared__ unsigned long long s_part[4][4];
-	unsigned long long t[4] = { 0, 0, 0, 0 };
+	__shared__ unsigned long long s_part[4][K];
+	unsigned long long t[K] = {};
 	for (uint32_t i = threadIdx.x; i < blocks; i += 256)
 #pragma unroll
-		for (int k = 0; k < 4; ++k)
-			t[k] += partials[(size_t)i * 4 + k];
+		for (int k = 0; k < K; ++k)
+			t[k] += partials[(size_t)i * K + k];
 #pragma unroll
-	for (int k = 0; k < 4; ++k)
+	for (int k = 0; k < K; ++k)
 		for (int o = 32; o > 0; o >>= 1)
 			t[k] += __shfl_xor(t[k], o, 64);
 	if ((threadIdx.x & 63u) == 0)
-		for (int k = 0; k < 4; ++k)
+		for (int k = 0; k < K; ++k)
 			s_part[threadIdx.x >> 6][k] = t[k];
 	__syncthreads();
-	if (threadIdx.x < 4)
+	if (threadIdx.x < K)
 		totals[threadIdx.x] += s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
 }
 
-// The same for the two alpha totals {dropped, unevaluated} of an ALPHA launch.  Not the kernel above as a template over the number of counters: its
-// instantiation for two allocates other registers than this text does, and the kernels keep their code (profiles/texture_set_refactor.md)
-__global__ __launch_bounds__(256) void rasterdepth_alpha_totals_kernel(const unsigned long long* __restrict__ partials, uint32_t blocks,
-                                                                       unsigned long long* __restrict__ totals)
-{
-	__shared__ unsigned long long s_part[4][2];
-	unsigned long long t0 = 0, t1 = 0;
-	for (uint32_t i = threadIdx.x; i < blocks; i += 256)
-	{
-		t0 += partials[(size_t)i * 2];
-		t1 += partials[(size_t)i * 2 + 1];
-	}
-	for (int o = 32; o > 0; o >>= 1)
-	{
-		t0 += __shfl_xor(t0, o, 64);
-		t1 += __shfl_xor(t1, o, 64);
-	}
-	if ((threadIdx.x & 63u) == 0)
-	{
-		s_part[threadIdx.x >> 6][0] = t0;
-		s_part[threadIdx.x >> 6][1] = t1;
-	}
-	__syncthreads();
-	if (threadIdx.x < 2)
-		totals[threadIdx.x] += s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
-}
-
-// counters = 4 (the raster totals) or 2 (the alpha totals)
+// counters = 4 (the raster totals) or 2 (the alpha totals {dropped, unevaluated} of an ALPHA launch)
 int launch_raster_totals(hipStream_t stream, const unsigned long long* partials, uint32_t blocks, unsigned long long* totals, uint32_t counters)
 {
 	if (counters == 4u)
-		hipLaunchKernelGGL(rasterdepth_totals_kernel, dim3(1), dim3(256), 0, stream, partials, blocks, totals);
+		hipLaunchKernelGGL(rasterdepth_totals_kernel<4>, dim3(1), dim3(256), 0, stream, partials, blocks, totals);
 	else
-		hipLaunchKernelGGL(rasterdepth_alpha_totals_kernel, dim3(1), dim3(256), 0, stream, partials, blocks, totals);
+		hipLaunchKernelGGL(rasterdepth_totals_kernel<2>, dim3(1), dim3(256), 0, stream, partials, blocks, totals);
 	return (int)hipGetLastError();
 }
 

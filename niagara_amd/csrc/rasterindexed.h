@@ -1,10 +1,11 @@
 // rasterindexed.h — the text nv_rasterdepth_indexed (rasterindexed.hip) and nv_rasterdepth_indexed_visibility (rasterindexed_vis.hip) share
-// (DESIGN.md §4.11, §4.23): the chunk arithmetic, the command search and the raster kernel, rasterindexed_kernel<CLIP, ARGS>.  Without a visibility target
-// it is the depth-only kernel, statement for statement what rasterindexed.hip held before the header existed; with one (VIS) it adds the stable-form
-// visibility word of §4.23 and nothing else (every addition sits under `if constexpr (VIS)`).  rasterindexed_alpha.hip and rasterindexed_blocks.hip
-// instantiate it on RasterIndexedSetArgs<SET> (nv_rasterdepth_indexed_textured, nv_rasterdepth_indexed_blocks, §4.24): VIS with an optional target,
-// and the covered samples of a post-pass launch also pass the fragment's alpha test (ALPHA: every addition sits under `if constexpr (ALPHA)`, so
-// the four kernels of the two untextured entry points keep their instruction streams).
+// (DESIGN.md §4.11, §4.23): the chunk arithmetic, the command search and the raster kernel, rasterindexed_kernel<CLIP, ARGS>, and its
+// launch, launch_rasterindexed_as<ARGS>.  The argument struct states what the kernel is (args.h: VIS, ALPHA): depth only; with the stable-form
+// visibility word of §4.23 (VIS); or, on RasterIndexedSetArgs<SET> (rasterindexed_alpha.hip, rasterindexed_blocks.hip:
+// nv_rasterdepth_indexed_textured, nv_rasterdepth_indexed_blocks, §4.24), VIS with an optional target and the covered samples of a post-pass
+// launch also passing the fragment's alpha test (ALPHA).  Every instantiation is held to its bits by the GPU tests of its entry point
+// (test_raster_indexed_gpu.py, test_raster_clip_gpu.py, test_visindexed_gpu.py, test_visindexed_textured_gpu.py: lane and wave path, near
+// clip on and off).  The kernel repeats its walks per CLIP branch and per ALPHA arm: profiles/raster_fold.md has what one text for them costs.
 #pragma once
 
 #include "raster.h"
@@ -80,37 +81,6 @@ NV_DEV bool ri_sample(const RdTri& t, int32_t x, int32_t y, uint32_t W, uint32_t
 		return rd_sample(t, x, y, W, depth, nullptr, 0u);
 }
 
-// The raster kernel.  ARGS = RasterIndexedArgs: nv_rasterdepth_indexed's, depth only.  ARGS = RasterIndexedVisArgs (VIS): the same with the
-// visibility word; a.triangleOffsets (drawCount + 1 non-decreasing 64-bit prefixes, the caller's) and a.visibility are read then.
-template <class ARGS>
-struct ri_writes_visibility
-{
-	static constexpr bool value = false;
-};
-template <>
-struct ri_writes_visibility<RasterIndexedVisArgs>
-{
-	static constexpr bool value = true;
-};
-
-// ARGS = RasterIndexedSetArgs<SET> (ALPHA, §4.24): VIS with an optional target, and the covered samples of a post-pass launch also pass the
-// fragment's alpha test against a texture set of residency SET.  Every addition sits under `if constexpr (ALPHA)`.
-template <class ARGS>
-struct ri_tests_alpha
-{
-	static constexpr bool value = false;
-};
-template <class SET>
-struct ri_tests_alpha<RasterIndexedSetArgs<SET>>
-{
-	static constexpr bool value = true;
-};
-template <class SET>
-struct ri_writes_visibility<RasterIndexedSetArgs<SET>>
-{
-	static constexpr bool value = true;
-};
-
 // ALPHA: one corner of the ORIGINAL triangle as fragalpha.h takes it: rd_clip_position's clip x, y, w (the statements rd_vertex starts with:
 // the bits both stages share) and the record's fourth word, the packed texcoord
 NV_DEV FaCorner ri_corner(const NvGlobals& g, const NvVertex* v, f3 q, float qw, float scale, float px, float py, float pz)
@@ -131,11 +101,14 @@ NV_DEV void ri_sample_alpha(const ARGS& a, const RdTri& t, const RdAlphaSlot& m,
 	rd_sample_alpha<true, typename ARGS::Set>(t, m, a.tx.data, ca, cb, cc, x, y, a.width, fw, fh, a.depth, id ? vis : nullptr, id, kept, dropped, unevaluated);
 }
 
+// The raster kernel.  ARGS = RasterIndexedArgs: nv_rasterdepth_indexed's, depth only.  ARGS = RasterIndexedVisArgs (ARGS::VIS): the same with the
+// visibility word; a.triangleOffsets (drawCount + 1 non-decreasing 64-bit prefixes, the caller's) and a.visibility are read then.
+// ARGS = RasterIndexedSetArgs<SET> (ARGS::ALPHA, §4.24): VIS with an optional target, and the covered samples of a post-pass launch also pass the
+// fragment's alpha test against a texture set of residency SET.  Every addition sits under `if constexpr (VIS)` or `if constexpr (ALPHA)`.
 template <bool CLIP, class ARGS>
 __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 {
-	constexpr bool VIS = ri_writes_visibility<ARGS>::value;
-	constexpr bool ALPHA = ri_tests_alpha<ARGS>::value;
+	constexpr bool VIS = ARGS::VIS, ALPHA = ARGS::ALPHA;
 	unsigned long long* vis = nullptr;
 	if constexpr (VIS)
 		vis = a.visibility;
@@ -468,10 +441,10 @@ __global__ __launch_bounds__(RI_THREADS) void rasterindexed_kernel(ARGS a)
 	}
 }
 
-// The launches of an ALPHA entry point: the count and scan launches every indexed raster starts with, the kernel by near clip, then the totals
-// launches the caller asked for
+// The launches of one pass, for every ARGS: the count and scan launches every indexed raster starts with, the kernel by near clip, then the
+// totals launches the caller asked for
 template <typename ARGS>
-int launch_rasterindexed_set(hipStream_t stream, ARGS a, void* scratch, uint32_t gridBlocks, bool nearClip)
+int launch_rasterindexed_as(hipStream_t stream, ARGS a, void* scratch, uint32_t gridBlocks, bool nearClip)
 {
 	launch_rasterindexed_prepare(stream, a, scratch);
 	gridBlocks = gridBlocks / 8 * RI_BLOCKS_PER_CU; // the caller passes 8 workgroups per CU, the size of `partials` and `alphaPartials`
@@ -482,8 +455,9 @@ int launch_rasterindexed_set(hipStream_t stream, ARGS a, void* scratch, uint32_t
 	hipError_t e = hipGetLastError();
 	if (e == hipSuccess && a.totals)
 		e = (hipError_t)launch_raster_totals(stream, a.partials, gridBlocks, a.totals, 4);
-	if (e == hipSuccess && a.alphaTotals)
-		e = (hipError_t)launch_raster_totals(stream, a.alphaPartials, gridBlocks, a.alphaTotals, 2);
+	if constexpr (ARGS::ALPHA)
+		if (e == hipSuccess && a.alphaTotals)
+			e = (hipError_t)launch_raster_totals(stream, a.alphaPartials, gridBlocks, a.alphaTotals, 2);
 	return (int)e;
 }
 

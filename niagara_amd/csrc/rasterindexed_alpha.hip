@@ -17,7 +17,7 @@ namespace nv
 
 int launch_rasterindexed_alpha(hipStream_t stream, RasterIndexedAlphaArgs a, void* scratch, uint32_t gridBlocks, bool nearClip)
 {
-	return launch_rasterindexed_set(stream, a, scratch, gridBlocks, nearClip);
+	return launch_rasterindexed_as(stream, a, scratch, gridBlocks, nearClip);
 }
 
 } // namespace nv

@@ -11,7 +11,7 @@ namespace nv
 
 int launch_rasterindexed_blocks(hipStream_t stream, RasterIndexedBlockArgs a, void* scratch, uint32_t gridBlocks, bool nearClip)
 {
-	return launch_rasterindexed_set(stream, a, scratch, gridBlocks, nearClip);
+	return launch_rasterindexed_as(stream, a, scratch, gridBlocks, nearClip);
 }
 
 } // namespace nv

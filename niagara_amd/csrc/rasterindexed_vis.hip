@@ -12,16 +12,7 @@ namespace nv
 
 int launch_rasterindexed_vis(hipStream_t stream, RasterIndexedVisArgs a, void* scratch, uint32_t gridBlocks, bool nearClip)
 {
-	launch_rasterindexed_prepare(stream, a, scratch);
-	gridBlocks = gridBlocks / 8 * RI_BLOCKS_PER_CU; // the caller passes 8 workgroups per CU, the size of `partials`
-	if (nearClip)
-		hipLaunchKernelGGL((rasterindexed_kernel<true, RasterIndexedVisArgs>), dim3(gridBlocks), dim3(RI_THREADS), 0, stream, a);
-	else
-		hipLaunchKernelGGL((rasterindexed_kernel<false, RasterIndexedVisArgs>), dim3(gridBlocks), dim3(RI_THREADS), 0, stream, a);
-	hipError_t e = hipGetLastError();
-	if (e != hipSuccess || !a.totals)
-		return (int)e;
-	return launch_raster_totals(stream, a.partials, gridBlocks, a.totals, 4);
+	return launch_rasterindexed_as(stream, a, scratch, gridBlocks, nearClip);
 }
 
 } // namespace nv

@@ -245,9 +245,11 @@ def test_the_wall_keeps_and_drops_samples_and_a_draw_behind_it_shows(viewport, r
 
 @pytest.mark.parametrize("source,kernel,count", [("rasterindexed_alpha", "rasterindexed_kernel", 2), ("rasterindexed_blocks", "rasterindexed_kernel", 2),
                                                  ("visattr_indexed_tex", "visibility_attributes_kernel", 1),
-                                                 ("visattr_indexed_blocks", "visibility_attributes_kernel", 1)])
+                                                 ("visattr_indexed_blocks", "visibility_attributes_kernel", 1),
+                                                 ("rasterdepth", "rasterdepth_kernel", 4), ("rasterdepth_alpha", "rasterdepth_kernel", 4),
+                                                 ("rasterindexed", "rasterindexed_kernel", 2), ("rasterindexed_vis", "rasterindexed_kernel", 2)])
 def test_new_kernels_use_no_scratch_memory(source, kernel, count, tmp_path):
-    """the six new instantiations, compiled with the Makefile's flags: 0 bytes of private segment, no spilled vector register"""
+    """the classic path's textured instantiations and the raster kernels of both paths, compiled with the Makefile's flags: 0 bytes of private segment, no spilled vector register"""
     import subprocess
     csrc = os.path.join(ROOT, "niagara_amd", "csrc")
     asm = str(tmp_path / (source + ".s"))
