@@ -469,7 +469,13 @@ typedef struct NvTriangleMask
  * (optional) receives the unquantised {center.xyz, radius, axis.xyz, cutoff} per meshlet.  Call nv_upload_meshlets
  * afterwards (a mirror built from these records before is dropped).
  * PARITY UNPINNED: the arithmetic is meshoptimizer's, which the reference does not vendor; the library's published
- * algorithm is restated with defined fp32 semantics here and in the CPU oracle (orc_meshlet_bounds), and the two agree bit for bit. */
+ * algorithm is restated with defined fp32 semantics here and in the CPU oracle (orc_meshlet_bounds), and the two agree bit for bit.
+ * Defined for any input: vertexCount / triangleCount above 64 / 96 are clamped, and the index bytes start where the
+ * clamped vertex count puts them; an index byte is masked with 63, a slot at or above vertexCount is the point (0, 0, 0); shortRefs == 1
+ * means 16-bit references, every other value 32-bit ones; x < NaN is false, so a NaN coordinate is never an extreme (unless it is the
+ * first point) and never outside the sphere; cone_cutoff = q < 127 ? (int)q : 127 with q = 127 (cutoff + e) + 1, so a NaN (non-finite
+ * vertices) gives 127, no cone culling; a NaN among the eight results is the quiet NaN 0x7fc00000 in d_bounds8 and 0x7e00 in the record.
+ * The caller keeps every reference (baseVertex + reference < vertices, dataOffset and the payload inside d_meshletData) in bounds. */
 int nv_meshlet_bounds(nv_context* ctx, void* stream, const NvVertex* d_vertices, const uint32_t* d_meshletData, NvMeshlet* d_meshlets,
                       uint32_t meshletCount, float* d_bounds8);
 

@@ -6,7 +6,9 @@
 // cone_cutoff_s8).  PARITY UNPINNED: the arithmetic is meshoptimizer's (an un-vendored submodule of the reference, no
 // pinned commit); this file and the CPU oracle (orc_meshlet_bounds) restate the library's published algorithm —
 // meshopt_computeClusterBounds with the three-axis Ritter sphere — with defined semantics (fp32, one IEEE operation per
-// source operation, sums left to right, points in triangle order), and the two agree bit for bit.
+// source operation, sums left to right, points in triangle order), and the two agree bit for bit.  What is defined for any
+// input (count clamps, the index mask, shortRefs != 1, NaN never an extreme, the s8 cutoff of a NaN, the canonical NaN of the
+// results) is listed in DESIGN.md §4.9 and pinned by tests/test_meshlet_bounds_edges_gpu.py.
 //
 // Mapping to CDNA4: one wavefront per meshlet (<= 64 vertices, <= 96 triangles).  Vertices, the compacted triangle list
 // and its normals live in a 2.3 KiB LDS slice per wave.  The algorithm's sequential loops are kept exact without being
@@ -180,6 +182,11 @@ NV_DEV uint32_t quantize_half(float v)
 	return (uint32_t)(s | h) & 0xffffu;
 }
 
+NV_DEV float canonical_nan(float v)
+{
+	return v != v ? __uint_as_float(0x7fc00000u) : v;
+}
+
 // meshopt_quantizeSnorm(v, 8)
 NV_DEV int quantize_snorm8(float v)
 {
@@ -301,10 +308,14 @@ __global__ __launch_bounds__(MB_WAVES * 64) void meshlet_bounds_kernel(const NvV
 					a8[k] = quantize_snorm8(ax[k]);
 					e += __builtin_fabsf((float)a8[k] / 127.0f - ax[k]);
 				}
-				const int q = (int)(127.0f * (cutoff + e) + 1.0f);
-				c8 = q > 127 ? 127 : q;
+				const float q = 127.0f * (cutoff + e) + 1.0f; // never negative; a NaN takes the clamp (no cone culling)
+				c8 = q < 127.0f ? (int)q : 127;
 			}
 		}
+		// a NaN among the eight results is the canonical quiet NaN (sign and payload of a computed NaN differ between instruction sets)
+		center = f3{ canonical_nan(center.x), canonical_nan(center.y), canonical_nan(center.z) };
+		axis = f3{ canonical_nan(axis.x), canonical_nan(axis.y), canonical_nan(axis.z) };
+		radius = canonical_nan(radius), cutoff = canonical_nan(cutoff);
 		if (lane == 0)
 		{
 			uint32_t* out = reinterpret_cast<uint32_t*>(meshlets + mi);

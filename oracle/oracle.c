@@ -977,7 +977,11 @@ void orc_drawcull_mt(const OrcCullData* cd, int late, int task, const OrcMeshDra
  * library: the HIP kernel equals this function bit for bit, every vertex lies inside the sphere and every triangle normal
  * inside the cone (up to the fp16 / s8 rounding that niagara's own call sites accept), and culling real geometry with the
  * generated bounds never removes a meshlet whose triangles a per-triangle test keeps (tests/test_meshlet_bounds.py).
- * Input positions are the fp16 vertex positions, dequantised, exactly like src/scene.cpp:193-198 feeds the library. */
+ * Input positions are the fp16 vertex positions, dequantised, exactly like src/scene.cpp:193-198 feeds the library.
+ * Defined for any input: counts clamp to 64 / 96, index bytes are masked with 63, shortRefs != 1 means 32-bit
+ * references, a NaN is never an extreme (x < NaN is false) unless it is point 0, the s8 cutoff of a NaN is 127, a NaN among the
+ * results is the canonical quiet NaN.  A second restatement (tests/bounds_ref.py) holds this one to the letter on the edge cases of
+ * tests/bounds_cases.py, and tools/bounds_check.c runs it under the host sanitizers. */
 static uint16_t orc_quantize_half(float v)
 {
 	/* meshopt_quantizeHalf: round to nearest (ties away in the mantissa sum), flush below 2^-14, saturate to inf */
@@ -990,6 +994,11 @@ static uint16_t orc_quantize_half(float v)
 	h = (em >= (143 << 23)) ? 0x7c00 : h;
 	h = (em > (255 << 23)) ? 0x7e00 : h;
 	return (uint16_t)(s | h);
+}
+
+static float orc_canonical_nan(float v)
+{
+	return v != v ? u2f(0x7fc00000u) : v;
 }
 
 static int orc_quantize_snorm8(float v)
@@ -1127,10 +1136,15 @@ void orc_meshlet_bounds(const OrcVertex* vertices, const uint32_t* meshletData, 
 					e += fabsf((float)axis_s8[k] / 127.0f - axis[k]);
 				}
 				/* rounded up so that the 8-bit test stays conservative */
-				int c8 = (int)(127 * (cutoff + e) + 1);
-				cutoff_s8 = c8 > 127 ? 127 : c8;
+				/* q is never negative; a NaN (non-finite vertices) takes the clamp: 127 = no cone culling */
+				float q = 127 * (cutoff + e) + 1;
+				cutoff_s8 = q < 127.0f ? (int)q : 127;
 			}
 		}
+		/* a NaN among the eight results is the canonical quiet NaN: sign and payload of a computed NaN differ between instruction sets */
+		for (int k = 0; k < 3; ++k)
+			center[k] = orc_canonical_nan(center[k]), axis[k] = orc_canonical_nan(axis[k]);
+		radius = orc_canonical_nan(radius), cutoff = orc_canonical_nan(cutoff);
 		m->center[0] = orc_quantize_half(center[0]);
 		m->center[1] = orc_quantize_half(center[1]);
 		m->center[2] = orc_quantize_half(center[2]);
